@@ -10,7 +10,11 @@ bs=12, 192x640, synthetic KITTI-shaped batches, random-init weigh
 backward (+ RCCL all-reduce of the flat gradient for N>1) + fused AdamW, exactly what projects/Supervised/train.py:L99-128 does.
 Inputs are resident in HBM when the timed region starts.  Rank 0 prints ONE JSON line.
 
-Extra objects on that line (tier contract):
+A plain run only sets up, warms up, times the --steps steps and prints the line.  --dump-outputs DIR also writes what the last timed step
+computed (the loss values, a fixed seeded sample of the updated parameters and of the step's gradient) as DIR/<name>.npy; the inputs and the
+initial weights are seeded, so two builds run with the same arguments can be compared output for output.
+
+Extra objects on that line, with --full only (they take passes of their own after the timed region):
   roofline     -- dominant kernel family by device time (the implicit-GEMM convolution kernel), algorithmic FLOPs / measured
                   duration, from an event-instrumented pass of the same step inside this process (events on the launch stream).
   cpu_baseline -- the CPU oracle (torch-CPU restatement of the reference, "port") timed on this host on a bounded sample.
@@ -307,6 +311,25 @@ def cpu_baseline(args):
     return out
 
 
+DUMP_SAMPLE = 1 << 22          # elements of the flat parameter / gradient buffers written by --dump-outputs (16 MB each in float32)
+
+
+def dump_outputs(out_dir, trainer, losses):
+    """What the last timed step computed, as float32 / float64 .npy files: every loss, and the flat parameter buffer after the optimizer
+    update and the flat gradient of that step -- whole when small, else the same seeded sample of element indices for both."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in losses.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), v.detach().double().cpu().numpy())
+    n = trainer.numel
+    idx = None
+    if n > DUMP_SAMPLE:
+        idx = torch.from_numpy(np.sort(np.random.default_rng(0).integers(0, n, DUMP_SAMPLE))).to(trainer.pflat.device)
+    for name, buf in (("params", trainer.pflat), ("grads", trainer.gflat)):
+        x = buf if idx is None else buf[idx]
+        np.save(os.path.join(out_dir, f"{name}.npy"), x.detach().float().cpu().numpy())
+
+
 def self_launch(args):
     """`python bench.py --gpus N` without a launcher (the shape of the reference's `--num-gpus N`, detectron2/engine/launch.py:L24-92): the
     parent -- which has not touched the GPU -- starts N fresh rank processes with the torch.distributed environment, relays rank 0's JSON
@@ -364,12 +387,14 @@ def main():
     ap.add_argument("--height", type=int, default=192)
     ap.add_argument("--width", type=int, default=640)
     ap.add_argument("--no-graph", action="store_true", help="launch every kernel eagerly instead of replaying the captured hipGraph")
-    ap.add_argument("--profile-steps", type=int, default=5, help="instrumented eager steps for the roofline object (0 = skip; at least 4 are run)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed to DIR/<name>.npy (losses, sampled parameters and gradients)")
+    ap.add_argument("--full", action="store_true", help="after the timed region also measure the roofline object and the CPU baseline")
+    ap.add_argument("--profile-steps", type=int, default=5, help="--full: instrumented eager steps for the roofline object (0 = skip; at least 4 are run)")
     ap.add_argument("--cpu-steps", type=int, default=10)
     ap.add_argument("--cpu-warmup", type=int, default=3)
     ap.add_argument("--cpu-threads", type=int, default=0, help="0 = physical cores of one socket (SURVEY.md 8d)")
     ap.add_argument("--cpu-batch", type=int, default=2)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: leave the CPU baseline out")
     ap.add_argument("--with-loader", action="store_true", help="feed every step from pinned uint8 host frames through DevicePrefetcher + the device resize / "
                     "colour-jitter kernels (the input side inside the timed region) instead of device-resident inputs")
     ap.add_argument("--aug-on-copy-stream", action="store_true", help="--with-loader: run the resize / jitter kernels on the prefetcher's copy stream (then copied "
@@ -383,6 +408,8 @@ def main():
     ap.add_argument("--opt", action="append", default=[], metavar="KEY=VALUE", help="sde_conv_set_option(KEY, VALUE) before the model is built (A/B measurements)")
     ap.add_argument("--no-pgemm", action="store_true", help="register-staged GEMM kernels only (A/B against the persistent LDS-DMA GEMM)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return self_launch(args)                    # before anything in this process touches the GPU
@@ -490,6 +517,8 @@ def main():
         elapsed = float(t.item())
     final = {k: float(v.item()) for k, v in losses.items()}
     assert all(x == x and abs(x) != float("inf") for x in final.values()), f"non-finite loss {final}"
+    if args.dump_outputs and rank == 0:              # before --full's passes: they run more steps on the same buffers
+        dump_outputs(args.dump_outputs, trainer, losses)
 
     if rank == 0:
         ms = elapsed / args.steps * 1e3
@@ -511,11 +540,11 @@ def main():
         if args.with_loader:
             out["data"] = "synthetic uint8 frames at 375x1242 fed per step through the pinned host -> device prefetcher and the device resize + colour-jitter kernels"
             out["input_side"] = {"h2d_bytes_per_step": h2d_bytes, "in_timed_region": True, "copy_stream": getattr(prefetcher, "picked", None)}
-        if args.profile_steps > 0:
+        if args.full and args.profile_steps > 0:
             hbm, out["roofline"] = roofline_pass(trainer, batch, args.profile_steps, args.dtype, args.workload, step_ms=ms)
             if hbm is not None:
                 out["roofline_photometric"] = hbm        # MonoDepth2 workloads: the HBM-bound warp+SSIM kernel next to the dominant GEMM
-        if not args.no_cpu_baseline and world == 1:          # reported at N=1 only
+        if args.full and not args.no_cpu_baseline and world == 1:          # reported at N=1 only
             out["cpu_baseline"] = cpu_baseline(args)
         print(json.dumps(out), flush=True)
     if world > 1:

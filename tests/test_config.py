@@ -1,17 +1,30 @@
 """Config surface (detectron2/config/defaults.py, utils/setup.py:L17-20): defaults equal the reference's for the keys it defines, the
 embedded project bases equal projects/*/configs/Base.yaml, and every YAML of the two projects on the path merges unchanged.
 
-The YAML files exist only where /root/reference does (the build container): those tests skip elsewhere."""
-import glob
+The reference's YAML files are stored as parsed mappings in tests/golden/configs.json (oracle/gen_golden_config.py); the tests write them
+back out as files (``_BASE_`` entries included) and load those."""
+import json
 import os
 
 import pytest
+import yaml
 
 from simpledepthestimation_amd.config import get_cfg, get_project_cfg
 from simpledepthestimation_amd.config.defaults import PROJECT_BASE
 
-REF = "/root/reference"
-needs_ref = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "projects")), reason="reference checkout not present (GPU box)")
+with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "configs.json")) as _f:
+    CONFIGS = json.load(_f)           # "<project>/<file name>" -> the file's mapping
+
+
+@pytest.fixture
+def ref_root(tmp_path):
+    """A directory laid out like the reference's projects/<project>/configs/*.yaml, written from tests/golden/configs.json."""
+    for key, content in CONFIGS.items():
+        project, name = key.split("/")
+        d = tmp_path / "projects" / project / "configs"
+        d.mkdir(parents=True, exist_ok=True)
+        (d / name).write_text(yaml.safe_dump(content, sort_keys=False))
+    return str(tmp_path)
 
 
 def test_defaults_are_the_references():
@@ -32,12 +45,11 @@ def _flat(d, prefix=""):
     return out
 
 
-@needs_ref
 @pytest.mark.parametrize("project", ["MonoDepth2", "Supervised"])
-def test_embedded_project_base_equals_the_yaml(project):
+def test_embedded_project_base_equals_the_yaml(project, ref_root):
     """Every key of PROJECT_BASE[project] has the value projects/<project>/configs/Base.yaml gives it."""
     cfg = get_cfg()
-    cfg.merge_from_file(os.path.join(REF, "projects", project, "configs", "Base.yaml"))
+    cfg.merge_from_file(os.path.join(ref_root, "projects", project, "configs", "Base.yaml"))
     want = _flat(cfg)
     for k, v in _flat(PROJECT_BASE[project]).items():
         if k == "DATASETS.TEST.PREPROCESS":
@@ -51,12 +63,11 @@ def test_embedded_project_base_equals_the_yaml(project):
         assert emb[k] == want[k], k
 
 
-@needs_ref
-@pytest.mark.parametrize("path", sorted(glob.glob(os.path.join(REF, "projects", "Supervised", "configs", "*.yaml")) +
-                                        glob.glob(os.path.join(REF, "projects", "MonoDepth2", "configs", "*.yaml"))),
-                         ids=lambda p: "/".join(p.split("/")[-3::2]))
-def test_reference_yaml_merges_unchanged(path):
-    """the reference's YAMLs load as they are (``_BASE_`` inheritance, anchors, tuple strings, new keys) and CLI-style overrides apply."""
+@pytest.mark.parametrize("key", sorted(CONFIGS), ids=str)
+def test_reference_yaml_merges_unchanged(key, ref_root):
+    """the reference's YAMLs load as they are (``_BASE_`` inheritance, tuple strings, new keys) and CLI-style overrides apply."""
+    project, name = key.split("/")
+    path = os.path.join(ref_root, "projects", project, "configs", name)
     cfg = get_cfg()
     cfg.set_new_allowed(True)                       # utils/setup.py:L18
     cfg.merge_from_file(path)
@@ -67,11 +78,11 @@ def test_reference_yaml_merges_unchanged(path):
     names = [s["NAME"] for s in cfg.DATASETS.TEST.PREPROCESS]
     assert names[0] == "LoadImg" and names[-1] == "ToTensor" and ("Resize" in names or "KBCrop" in names or "CropTopTo" in names)
     assert isinstance(cfg.EVALUATORS, tuple) and cfg.EVALUATORS[0] == "kitti_evaluator"
-    if "MonoDepth2" in path:
+    if project == "MonoDepth2":
         assert isinstance(cfg.SOLVER.LR_STEPS, tuple) and cfg.LOSS.SSIM_WEIGHT == 0.85 and cfg.SOLVER.GAMMA == 0.1
-        if "waymo" not in path:
+        if "waymo" not in name:
             assert cfg.SOLVER.LR_STEPS == (15,) and cfg.SOLVER.DEPTH_LR == 2e-4 and cfg.TEST.GT_SCALE is True
-        if "Base" not in os.path.basename(path):
+        if "Base" not in name:
             assert cfg.MODEL.POSE_NET.NUM_CONTEXTS == 2 and cfg.MODEL.POSE_NET.NAME == "PoseNet"
     cfg.freeze()
     with pytest.raises(AttributeError):
