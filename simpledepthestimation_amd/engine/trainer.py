@@ -169,7 +169,7 @@ class HipTrainer:
         self._packer = None            # built lazily after the first eager step (needs the operand shapes seen in forward)
         self._one = None
         self.batch_pack = adam_fn is None
-        # one weight-gradient slab reduction launch per backward phase
+        # one weight-gradient slab reduction launch per backward phase (None: immediate mode, every layer reduces and joins at once)
         self._wreduce = HN.WGradReducer() if adam_fn is None else None
 
     # ------------------------------------------------------------------------------------------------------------
@@ -273,8 +273,6 @@ class HipTrainer:
             losses = losses + t
         if self.amp:
             losses = losses * self.scale_state[0]       # GradScaler.scale(loss): a device scalar, so the multiply is part of the captured graph
-        if self._packer is not None:
-            self._packer.join_dgrad()
         if self._one is None or self._one.dtype != losses.dtype or self._one.device != losses.device or self._one.shape != losses.shape:
             self._one = torch.ones_like(losses)         # d loss / d loss, kept: backward() would launch a fill for it every step
         L.mark("loss_fwd_end")
@@ -289,45 +287,24 @@ class HipTrainer:
 
     def _backward(self, run, first_of_two=False):
         """One backward phase with the convolutions' weight-gradient reductions deferred to a single launch at its end."""
-        HN.WGRAD_DEFER = self._wreduce
-        # the fork / lagging-join bookkeeping of the weight-gradient side stream (hip/nn.py) is written against ONE main stream: every
-        # convolution's backward must run on the stream this phase started on
-        HN.MAIN_STREAM = torch.cuda.current_stream() if self.device.type == "cuda" else None
         tag = "" if self._cut is None else ("A_" if first_of_two else "B_")       # (marker names per phase of a two-phase backward)
-        if self._wreduce is not None:
-            self._wreduce.first_group = L.FIRST_GROUP_B if (self._cut is not None and not first_of_two) else None
         try:
-            L.mark(tag + "bwd_start")
-            run()
-            if L.MARKS is not None:                  # diagnostic timeline (bench.py --marks): the last work of each stream of the phase
-                L.mark(tag + "bwd_main_end")
-                capturing = torch.cuda.is_current_stream_capturing()
-                for name, st_ in [(tag + "bwd_side_end", L.side_stream())] + ([(tag + "bwd_aux_end", L.aux_stream())] if L.AUX_USED else []):
-                    with torch.cuda.stream(st_):
-                        if torch.cuda.is_current_stream_capturing() == capturing:      # (a helper stream this phase never forked is not part of the capture)
-                            L.mark(name)
-                            joined = True
-                        else:
-                            joined = False
-                    if joined:
-                        torch.cuda.current_stream().wait_stream(st_)                   # the marker is the stream's last node: join it
-            L.join_aux()            # a network that ran on the auxiliary stream (PoseNet): its backward ran there as well
-            if self._wreduce is not None:
-                self._wreduce.flush()
+            with (self._wreduce or HN.WGradReducer(defer=False)).phase(self.device, phase_b=self._cut is not None and not first_of_two):
+                L.mark(tag + "bwd_start")
+                run()
+                if L.MARKS is not None:                  # diagnostic timeline (bench.py --marks): the last work of each stream of the phase
+                    L.mark(tag + "bwd_main_end")
+                    capturing = torch.cuda.is_current_stream_capturing()
+                    for name, st_ in [(tag + "bwd_side_end", L.side_stream())] + ([(tag + "bwd_aux_end", L.aux_stream())] if L.AUX_USED else []):
+                        with torch.cuda.stream(st_):
+                            joined = torch.cuda.is_current_stream_capturing() == capturing      # (a helper stream this phase never forked is not part of the capture)
+                            if joined:
+                                L.mark(name)
+                        if joined:
+                            torch.cuda.current_stream().wait_stream(st_)                   # the marker is the stream's last node: join it
+                L.join_aux()            # a network that ran on the auxiliary stream (PoseNet): its backward ran there as well
         finally:
-            HN.WGRAD_DEFER = None
-            HN.MAIN_STREAM = None
-            HN._RES_GRAD.clear(); HN._BN_PART.clear()      # hand-over entries between backward nodes: nothing outlives the phase
-            L.join_aux()            # (backward raised before the join above)
-            if self._wreduce is not None:
-                self._wreduce.join_pending()
-                if self._wreduce.forked:                                  # backward raised before the flush: still join the side stream
-                    for st_ in HN.L.all_side_streams():
-                        torch.cuda.current_stream().wait_stream(st_)
-                    self._wreduce.forked = False
-                self._wreduce.jobs, self._wreduce._seen = [], set()       # nothing left registered if backward raised
-                self._wreduce.bias_jobs, self._wreduce._seen_bias = [], set()
-                self._wreduce.queue, self._wreduce.groups_done = [], 0
+            L.join_aux()                # (backward raised before the join above)
             L.mark(tag + "bwd_end")
 
     def _backward_rest(self):

@@ -131,10 +131,10 @@ def stream():
 
 
 _side = {}
-# Weight-gradient GEMMs run on ONE side stream, forked in groups and joined late (hip/nn.py: _Conv2d.backward, WGradReducer).  The values below
+# Weight-gradient GEMMs run on ONE side stream, forked in groups and joined late (hip/nn.py: WGradReducer, wgrad_group_rule).  The values below
 # were each decided by an A/B run inside one gpurun call in round 1 (DESIGN.md 6.1 keeps the measurements); the environment switches that
 # selected the losing variants (late join per phase, several side streams, packing on the side stream) were removed with those variants.
-SIDE_STREAM = True      # HipTrainer(side_stream=False) / hip.lib.SIDE_STREAM = False: single-stream backward (profiling, debugging)
+SIDE_STREAM = True      # hip.lib.SIDE_STREAM = False (bench.py --no-side-stream): single-stream backward (profiling, debugging)
 JOIN_LAG = 1            # the main stream joins all but the newest JOIN_LAG - 1 groups before it forks the next one
 WGRAD_GROUP = 6         # weight-gradient GEMMs of that many consecutive layers behind one fork
 # The two constants are set per network family when a HipTrainer is built (apply_schedule), from A/B runs inside one gpurun call each:
@@ -169,13 +169,13 @@ FORK_MIN_BYTES = 0              # layers with fewer operand bytes keep their wei
                                 # 10 / 25 / 50 / 100 MB -> 7.52 / 7.93 / 8.77 / 7.78 ms/step against 7.26-7.28 at 0: bench.py --const FORK_MIN_BYTES=...)
 
 
-def side_stream(rotate=True):
+def side_stream():
     """Per-device helper stream: weight-gradient GEMMs run there concurrently with the data-gradient GEMM of the same layers (fork / join with
     stream / event waits, so they are captured into the step's hipGraph as a parallel branch)."""
     d = torch.cuda.current_device()
     if d not in _side:
-        _side[d] = [torch.cuda.Stream(device=d)]
-    return _side[d][0]
+        _side[d] = torch.cuda.Stream(device=d)
+    return _side[d]
 
 
 _aux = {}
@@ -203,11 +203,6 @@ def join_aux():
     if AUX_USED:
         torch.cuda.current_stream().wait_stream(aux_stream())
         AUX_USED = False
-
-
-def all_side_streams():
-    d = torch.cuda.current_device()
-    return list(_side.get(d, [])) + ([_aux[d]] if d in _aux else [])
 
 
 # Timeline markers (bench.py --marks): mark(name) enqueues one sde_mark_time launch on the current stream; under graph capture it becomes a node of the

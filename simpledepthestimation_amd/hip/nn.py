@@ -3,9 +3,12 @@
 Tensor convention: activations are NHWC torch tensors [B, H, W, C] (float32, bfloat16 or float16), C padded to 16 bytes;
 parameters stay fp32 in the reference's layouts (conv weight OIHW) so state dicts are interchangeable.
 """
+import contextlib
 import ctypes
-import weakref
+import functools
 import os
+import weakref
+from collections import namedtuple
 from ctypes import POINTER, Structure, c_float, c_int, c_int32, c_long, c_void_p
 
 import torch
@@ -185,6 +188,107 @@ def conv_raw(d, x_dtype, w_packed, bias, act, Cout, ldy, want_stats, device, kin
     return y, stats
 
 
+class _Handovers:
+    """What one autograd node leaves for a later one, keyed by the data_ptr of the tensor that links the two (size-capped: _put)."""
+
+    def __init__(self):
+        self.bn_out = {}        # residual-free BatchNorm+ReLU output -> (weakref, y, bnp): _BatchNormAct.forward -> the one _Conv2d.forward consuming it
+        self.bn_out_res = {}    # the same of a residual BatchNorm+ReLU with two consumers; it stays until that BatchNorm's backward drops it
+        self.bn_part = {}       # gradient a fused data-gradient GEMM returned -> (y.data_ptr(), partials, rows[, skip gradient's data_ptr]) for _BatchNormAct.backward
+        self.res_grad = {}      # block input -> the gradient that arrived over the skip path: _BatchNormAct.backward -> the block's first _Conv2d.backward
+        self.head_slot = {}     # one-channel bias convolution's output -> (weakref, its bias): _Conv2d.forward -> _DepthHead.forward
+        self.head_done = {}     # logit gradient _DepthHead.backward returned -> id(the bias whose gradient it accumulated): -> _Conv2d.backward
+
+    @staticmethod
+    def _put(d, cap, t, ent):
+        if len(d) > cap:
+            d.clear()
+        d[t.data_ptr()] = ent
+
+    @staticmethod
+    def _live(ent, t):
+        # the weak reference pins the entry to THIS tensor object (Function.apply returns it as is): an address reused by another never matches
+        return ent[1:] if (ent is not None and ent[0]() is t) else None
+
+    def put_bn_out(self, out, y, bnp, res=False):
+        (self.res_grad if res else self.bn_part).clear()      # (the backward side's entries live from one backward node to the next only)
+        self._put(self.bn_out_res if res else self.bn_out, 64, out, (weakref.ref(out), y, bnp))
+
+    def take_bn_out(self, x, res=False):
+        return self._live(self.bn_out_res.get(x.data_ptr()) if res else self.bn_out.pop(x.data_ptr(), None), x)
+
+    def drop_bn_out_res(self, ptr):
+        self.bn_out_res.pop(ptr, None)
+
+    def put_bn_part(self, g, ent):
+        self._put(self.bn_part, 16, g, ent)
+
+    def take_bn_part(self, g, res=False):
+        """The partials left under gradient g; the residual form (four fields) is only taken when it is asked for."""
+        ent = self.bn_part.get(g.data_ptr())
+        return self.bn_part.pop(g.data_ptr()) if (ent is not None and (not res or len(ent) == 4)) else None
+
+    def put_res_grad(self, ptr, g, if_expected=False):
+        """if_expected: only while a residual BatchNorm+ReLU output is registered (some convolution may take the gradient)."""
+        if self.bn_out_res or not if_expected:
+            self.res_grad[ptr] = g
+
+    def take_res_grad(self, x):
+        return self.res_grad.pop(x.data_ptr(), None)
+
+    def put_head_slot(self, y, bias):
+        self.head_done.clear()                    # (entries live from a head's backward to its convolution's backward only)
+        self._put(self.head_slot, 64, y, (weakref.ref(y), bias))
+
+    def take_head_slot(self, y):
+        return (self._live(self.head_slot.pop(y.data_ptr(), None), y) or (None,))[0]
+
+    def put_head_done(self, dy, bias):
+        self.head_done[dy.data_ptr()] = id(bias)
+
+    def take_head_done(self, dy, bias):
+        return self.head_done.pop(dy.data_ptr(), None) == id(bias)
+
+    def drop_head_done(self, bias):
+        """Drop every entry of this bias; True when there was one."""
+        n = len(self.head_done)
+        self.head_done = {k: v for k, v in self.head_done.items() if v != id(bias)}
+        return len(self.head_done) < n
+
+    def end_phase(self):
+        self.res_grad.clear()
+        self.bn_part.clear()
+
+
+_HANDOVER = _Handovers()
+
+
+def _dgrad_bnbwd(dd, wd, dz, x0, Cv, bn, flops, res):
+    """Data gradient of a stride-1 convolution of x0 = relu(BatchNorm(y_bn)) (+ identity: `res`, adding the skip path's gradient) that masks it with
+    relu'(x0) and leaves BatchNorm's partials under its address: _BatchNormAct.backward then skips its reduce pass.  None: no fused form here."""
+    lib = L.lib()
+    g_other = _HANDOVER.take_res_grad(x0) if res else None
+    if res and (g_other is None or not (g_other.shape == x0.shape and g_other.dtype == x0.dtype and g_other.is_contiguous())):
+        return None
+    name = "sde_conv_dgrad_bnbwd_res" if res else "sde_conv_dgrad_bnbwd"
+    rows = getattr(lib, name + "_rows")(ctypes.byref(dd), Cv, Cv)
+    if rows <= 0:
+        if res:
+            _HANDOVER.put_res_grad(x0.data_ptr(), g_other)            # (no fused form for this layer after all: nothing consumed)
+        return None
+    y_bn, bnp = bn
+    part = torch.empty(rows + REDUCE_ROWS, Cv, 2, device=x0.device, dtype=torch.float32)
+    dx0 = torch.empty(x0.shape[:3] + (Cv,), device=x0.device, dtype=x0.dtype)
+    variant = lib.sde_conv_fwd_variant(ctypes.byref(dd), Cv) if L.PROFILE is not None else 0
+    meta = dict(M=dx0.numel() // Cv, N=Cv, K=dd.KH * dd.KW * dd.C0, k=dd.KH, s=1, mode=0,
+                bytes=2 * (dz.numel() + (4 if res else 2) * dx0.numel())) if L.PROFILE is not None else None
+    extra = (L.ptr(g_other), L.ptr(x0)) if res else ()
+    _timed("igemm_dgrad", flops, variant, lambda: L.check(getattr(lib, name)(ctypes.byref(dd), L.ptr(wd), L.ptr(dx0), Cv, Cv, L.ptr(y_bn), L.ptr(bnp),
+                                                                             L.ptr(part), *extra, L.stream()), name), meta)
+    _HANDOVER.put_bn_part(dx0, (y_bn.data_ptr(), part, rows) + ((g_other.data_ptr(),) if res else ()))
+    return dx0
+
+
 # ---------------------------------------------------------------------------------------------------------------
 # Convolution (+bias, +ELU, optional BatchNorm statistics) with every input mode of the path
 # ---------------------------------------------------------------------------------------------------------------
@@ -219,25 +323,21 @@ class _Conv2d(torch.autograd.Function):
                 owner._pack_shapes = (dt, C0 + C1, ldy)            # lets WeightPacker build its job table after a first step
         b32 = _f32(bias) if bias is not None else None
         flops = 2.0 * B * OH * OW * Cout * KH * KW * Cin          # algorithmic (real channels)
+        plain = x1 is None and not upcat and not reflect and stride == 1
         # x0 = relu(BatchNorm(y_bn)) with this convolution as its only consumer: the data gradient below can carry BatchNorm's backward reduction
-        ent = _BN_OUT.pop(x0.data_ptr(), None) if _BN_OUT else None
-        ctx.bn_in = (ent[1], ent[2]) if (ent is not None and ent[0]() is x0 and x1 is None and not upcat and not reflect and stride == 1) else None
+        ent = _HANDOVER.take_bn_out(x0)
+        ctx.bn_in = ent if plain else None
         # x0 = relu(BatchNorm(y_bn) + identity) with this convolution and the next block's skip path as its two consumers: the data gradient below can take over
-        # that BatchNorm's whole backward reduce pass, once the skip path's gradient has arrived (_RES_GRAD)
-        entr = _BN_OUT_RES.get(x0.data_ptr()) if (_BN_OUT_RES and RESBN_FUSED) else None
-        ctx.bn_in_res = (entr[1], entr[2]) if (entr is not None and entr[0]() is x0 and x1 is None and not upcat and not reflect and stride == 1 and ctx.bn_in is None) else None
+        # that BatchNorm's whole backward reduce pass, once the skip path's gradient has arrived
+        ent = _HANDOVER.take_bn_out(x0, res=True) if RESBN_FUSED else None
+        ctx.bn_in_res = ent if (plain and ctx.bn_in is None) else None
         y, stats = conv_raw(d, dt, wp, b32, act, Cout, ldy, want_stats, x0.device, "igemm_fwd", flops)
         ctx.save_for_backward(x0, x1, weight, y if act != ACT_NONE else None)
         ctx.params = (weight, bias)
         ctx.cfg = (stride, pad, reflect, act, upcat, bias is not None, IH, IW, OH, OW)
         ctx.want_stats = want_stats
         if HEAD_BIAS_FUSED and bias is not None and act == ACT_NONE and Cout == 1 and not want_stats and n_out == 1:
-            if len(_HEAD_SLOT) > 64:
-                _HEAD_SLOT.clear()
-            _HEAD_DONE.clear()                        # (entries live from a head's backward to its convolution's backward only: none survives into a new forward)
-            # a disparity head: depth_head's backward can produce this layer's bias gradient on its way.  The weak reference pins the entry to THIS
-            # output tensor object (Function.apply hands the same object to the caller), so an address reused by another tensor never matches
-            _HEAD_SLOT[y.data_ptr()] = (bias, weakref.ref(y))
+            _HANDOVER.put_head_slot(y, bias)          # a disparity head: depth_head's backward can produce this layer's bias gradient on its way
         if want_stats:
             ctx.mark_non_differentiable(stats)
             return y, stats
@@ -281,13 +381,11 @@ class _Conv2d(torch.autograd.Function):
         dbias = None
         dz = dy
         # (the depth head's backward already summed this one-channel layer's bias gradient into its slot: nothing left to do in this step)
-        head_did_bias = has_bias and act == ACT_NONE and dy1 is None and _HEAD_DONE.pop(dy.data_ptr(), None) == id(ctx.params[1])
-        if has_bias and not head_did_bias and id(ctx.params[1]) in _HEAD_DONE.values():
+        head_did_bias = has_bias and act == ACT_NONE and dy1 is None and _HANDOVER.take_head_done(dy, ctx.params[1])
+        if has_bias and not head_did_bias and _HANDOVER.drop_head_done(ctx.params[1]):
             # depth_head's backward already accumulated its share of this bias gradient, but the gradient arriving here is not the tensor it
             # returned: the logit has a second consumer and autograd summed the two -- adding the full column sum on top would count the
             # head's share twice (the slot call accumulates)
-            for k in [k for k, v in _HEAD_DONE.items() if v == id(ctx.params[1])]:
-                del _HEAD_DONE[k]
             raise L.SdeHipError("conv2d backward: the one-channel output feeding depth_head has a second consumer; the fused disparity-head bias "
                                 "gradient supports exactly one (set hip.nn.HEAD_BIAS_FUSED = False for such a graph)")
         if (act != ACT_NONE or has_bias or dy1 is not None) and not head_did_bias:
@@ -297,196 +395,58 @@ class _Conv2d(torch.autograd.Function):
             dbias = (bslot if bslot is not None else torch.empty(Cout, device=dev)) if has_bias else None
             dz = torch.empty_like(dy) if (act != ACT_NONE or dy1 is not None) else None
             # the column partials' final sum is nothing the chain waits for: into a gradient slot it rides in the phase's ONE batched finalize (flush)
-            later = bslot is not None and WGRAD_DEFER is not None and BIAS_DEFER and L.PROFILE is None and WGRAD_DEFER.accepts_bias(bslot)
+            later = bslot is not None and WGRAD_DEFER.add_bias(part, nblk, ldy, Cout, bslot)
             L.check(lib.sde_act_bwd_bias_sum(L.ptr(dy), L.ptr(dy1), L.ptr(y), act, M, ldy, dtype_code(dt), L.ptr(dz), L.ptr(part), None if later else L.ptr(dbias), Cout,
                                              int(bslot is not None), L.stream()), "sde_act_bwd_bias_sum")
-            if later:
-                WGRAD_DEFER.add_bias(part, nblk, ldy, Cout, bslot)
             if bslot is not None:
                 dbias = None
             if dz is None:
                 dz = dy
-        st = {"dw": None, "forked": False, "side": None, "dx0": None, "dx1": None}
         need_dx = ctx.needs_input_grad[0] or (x1 is not None and ctx.needs_input_grad[1])
-        def do_wgrad():
-            # 2. weight gradient -- on the side stream when a data gradient follows, so the two independent GEMMs overlap
-            dw = None
-            forked = False
-            side = None
-            if ctx.needs_input_grad[2]:
-                if not need_dx and WGRAD_DEFER is not None and WGRAD_DEFER.queue and not off_main and EARLY_TAIL:
-                    # a layer without a data gradient (the stem) ends the chain: its weight gradient runs on the main stream, so the group still queued goes
-                    # to the side stream NOW, underneath it, instead of after it at the phase's flush
-                    WGRAD_DEFER.run_queue()
-                d = _desc(x0, x1, SRC_UPCAT if upcat else SRC_PLAIN, KH, KW, stride, pad, reflect, IH, IW, OH, OW)
-                splits = lib.sde_conv_wgrad_splits(ctypes.byref(d), Cout)
-                wslot = _grad_slot(ctx.params[0])
-                meta = None
-                if L.PROFILE is not None:
-                    esz = 4 if dt == torch.float32 else 2
-                    meta = dict(M=M, N=Cout, K=KH * KW * (C0 + C1), k=KH, s=stride, mode=int(upcat), splits=splits,
-                                bytes=esz * (B * H0 * W0 * C0 + B * IH * IW * C1 + M * ldy) + 8 * splits * Cout * KH * KW * (C0 + C1))
-                forked = need_dx and L.SIDE_STREAM and L.PROFILE is None and not off_main
-                if forked and L.FORK_MIN_BYTES:      # (A/B aid, default 0: every layer forks)
-                    forked = (dz.numel() + x0.numel() + (x1.numel() if x1 is not None else 0)) * dz.element_size() >= L.FORK_MIN_BYTES
-                # layers with very large operands (PackNet's full-resolution 64-channel maps: 190 MB each) fork on their own: holding three of
-                # them alive for a group pushes the working set out of the Infinity Cache (PackNet-1A: 60.2 vs 58.4 ms/step when grouped)
-                op_bytes = (dz.numel() + x0.numel() + (x1.numel() if x1 is not None else 0)) * dz.element_size()
-                grouped = forked and L.WGRAD_GROUP > 1 and WGRAD_DEFER is not None and op_bytes <= L.GROUP_MAX_BYTES
-                if forked and not grouped and WGRAD_DEFER is not None:
-                    WGRAD_DEFER.run_queue()              # keep the side stream in layer order
-                cur = torch.cuda.current_stream()
-                if grouped:
-                    import contextlib
-                    wctx = contextlib.nullcontext()      # the launch happens later, inside WGradReducer.run_queue's side-stream context
-                elif forked:
-                    side = L.side_stream()
-                    if WGRAD_DEFER is not None:
-                        WGRAD_DEFER.join_pending(keep=L.JOIN_LAG - 1)      # lagging joins of earlier layers
-                    side.wait_stream(cur)
-                    wctx = torch.cuda.stream(side)
-                else:
-                    import contextlib
-                    wctx = contextlib.nullcontext()
-                dw = wslot if wslot is not None else torch.empty(weight.shape, device=dev)      # a fresh gradient tensor is plain OIHW
-                wflags = (1 if wslot is not None else 0) | (2 if is_ohwi(dw) else 0)                # SDE_WREDUCE_ACCUMULATE | SDE_WREDUCE_OHWI
-                # small slab stacks wait for the phase's one batched reduction; big ones (ResNet-50's 20-40 MB stacks add up to ~1 GB per step)
-                # are summed at once on the side stream while they are still in the Infinity Cache and their block can be recycled
-                slab_bytes = 4 * splits * Cout * KH * KW * (C0 + C1)
-                defer = WGRAD_DEFER if (wslot is not None and WGRAD_DEFER is not None and slab_bytes <= L.DEFER_MAX_BYTES and WGRAD_DEFER.accepts(wslot)) else None
-                # one pixel range and a channels-last slot without channel padding: the GEMM's only "slab" IS the gradient row block -- it writes
-                # straight into the (zeroed) flat gradient, nothing to reduce.  (A second use of the same weight in the phase accumulates normally.)
-                direct = (splits == 1 and wslot is not None and WGRAD_DEFER is not None and WGRAD_DEFER.accepts(wslot) and (C0 + C1) == Cin
-                          and (KH * KW == 1 or is_ohwi(wslot)) and wslot.data_ptr() % 16 == 0 and L.PROFILE is None)
-                if direct:
-                    WGRAD_DEFER._seen.add(wslot.data_ptr())
-                    slab, slab_p, defer = wslot, _wptr(wslot), None
-                else:
-                    slab = torch.empty(splits, Cout, KH * KW * (C0 + C1), device=dev)
-                    slab_p = L.ptr(slab)
-                if grouped:
-                    side_g = L.side_stream(rotate=False)
-                    if direct:
-                        def launch(d=d):
-                            L.check(lib.sde_conv_wgrad_partial(ctypes.byref(d), L.ptr(dz), Cout, ldy, slab_p, 1, L.stream()), "sde_conv_wgrad_partial")
-                    elif defer is not None:
-                        defer.add(slab, slab.data_ptr(), splits, wslot, Cout, KH * KW, C0 + C1, Cin, wflags)
-                        def launch(d=d, slab=slab):
-                            L.check(lib.sde_conv_wgrad_partial(ctypes.byref(d), L.ptr(dz), Cout, ldy, L.ptr(slab), splits, L.stream()), "sde_conv_wgrad_partial")
-                            slab.record_stream(side_g)
-                    else:
-                        def launch(d=d, slab=slab, dw=dw):
-                            L.check(lib.sde_conv_wgrad(ctypes.byref(d), L.ptr(dz), Cout, ldy, Cin, L.ptr(slab), splits, _wptr(dw), wflags, L.stream()),
-                                    "sde_conv_wgrad")
-                            slab.record_stream(side_g)
-                    WGRAD_DEFER.queue.append((launch, (dz, x0, x1, slab, dw)))
-                    WGRAD_DEFER.queue_bytes += op_bytes
-                    # a group closes after WGRAD_GROUP layers or once its operands (kept alive until the group's GEMMs ran) exceed the byte budget
-                    fg = WGRAD_DEFER.first_group if WGRAD_DEFER.first_group is not None else L.FIRST_GROUP      # (the second phase of a two-phase backward has its own)
-                    prefix = str(fg) if fg else ""      # decimal digits = sizes of the first groups of the phase (33: 3 then 3)
-                    limit = int(prefix[WGRAD_DEFER.groups_done]) if WGRAD_DEFER.groups_done < len(prefix) else L.WGRAD_GROUP
-                    if len(WGRAD_DEFER.queue) >= limit or WGRAD_DEFER.queue_bytes >= L.GROUP_BUDGET_BYTES:
-                        WGRAD_DEFER.run_queue()
-                    st["dw"], st["forked"], st["side"] = (None if wslot is not None else dw), False, None
-                    return
-                with wctx:
-                    if direct:
-                        L.check(lib.sde_conv_wgrad_partial(ctypes.byref(d), L.ptr(dz), Cout, ldy, slab_p, 1, L.stream()), "sde_conv_wgrad_partial")
-                    elif defer is not None:
-                        _timed("wgrad", flops, 0, lambda: L.check(lib.sde_conv_wgrad_partial(ctypes.byref(d), L.ptr(dz), Cout, ldy, L.ptr(slab), splits, L.stream()),
-                                                                  "sde_conv_wgrad_partial"), meta)
-                        defer.add(slab, slab.data_ptr(), splits, wslot, Cout, KH * KW, C0 + C1, Cin, wflags)
-                    else:
-                        if L.PROFILE is None:
-                            L.check(lib.sde_conv_wgrad(ctypes.byref(d), L.ptr(dz), Cout, ldy, Cin, L.ptr(slab), splits, _wptr(dw), wflags, L.stream()),
-                                    "sde_conv_wgrad")
-                        else:       # the same two launches, timed separately (bench.py's roofline pass: GEMM FLOPs against GEMM time)
-                            _timed("wgrad", flops, 0, lambda: L.check(lib.sde_conv_wgrad_partial(ctypes.byref(d), L.ptr(dz), Cout, ldy, L.ptr(slab), splits,
-                                                                                                 L.stream()), "sde_conv_wgrad_partial"), meta)
-                            one = (WReduceItem * 1)(WReduceItem(slab.data_ptr(), dw.data_ptr(), splits, Cout, KH * KW, C0 + C1, Cin, wflags))
-                            _timed("wgrad_reduce", 0.0, 0, lambda: L.check(lib.sde_wgrad_reduce_batched(one, 1, L.stream()), "sde_wgrad_reduce_batched"),
-                                   dict(jobs=1))
-                    if forked and not direct:
-                        slab.record_stream(side)
-                if wslot is not None:
-                    dw = None
-            st["dw"], st["forked"], st["side"] = dw, forked, side
-
-        def do_dgrad():
-            # 3. data gradient
-            dx0 = dx1 = None
-            if ctx.needs_input_grad[0] or (x1 is not None and ctx.needs_input_grad[1]):
-                Cv = C0 + C1
-                wd = ctx.wd_pre if ctx.wd_pre is not None else pack_weight(weight, dt, Cv, ldy, for_dgrad=True)   # [Cv][KH][KW][ldy], taps flipped
-                if reflect:
-                    dd = _desc(dz, None, SRC_PLAIN, KH, KW, 1, KH - 1, False, OH, OW, IH + 2, IW + 2)
-                    dxp, _ = conv_raw(dd, dt, wd, None, ACT_NONE, Cv, Cv, False, dev, "igemm_dgrad", flops)
-                    dx0 = torch.empty_like(x0)
-                    dx1 = torch.empty_like(x1) if x1 is not None else None
-                    L.check(lib.sde_refl_fold(L.ptr(dxp), B, IH, IW, Cv, C0, int(upcat), dtype_code(dt), L.ptr(dx0), L.ptr(dx1), L.stream()), "sde_refl_fold")
-                else:
-                    if upcat:
-                        raise L.SdeHipError("upsample+concat source is only supported with reflection padding (decoder)")
-                    if stride == 1:
-                        dd = _desc(dz, None, SRC_PLAIN, KH, KW, 1, KH - 1 - pad, False, OH, OW, IH, IW)
-                        g_other = _RES_GRAD.pop(x0.data_ptr(), None) if (ctx.bn_in_res is not None and _RES_GRAD) else None
-                        if g_other is not None and not (g_other.shape == x0.shape and g_other.dtype == dt and g_other.is_contiguous()):
-                            g_other = None
-                        rows = lib.sde_conv_dgrad_bnbwd_res_rows(ctypes.byref(dd), Cv, Cv) if g_other is not None else 0
-                        if rows > 0:
-                            # gm = (this data gradient + the skip path's gradient) * relu'(x0), with the partials of the BatchNorm behind x0: that BatchNorm's
-                            # backward finds both under the gradient's address, skips its reduce pass and does not add the skip gradient again
-                            y_bn, bnp = ctx.bn_in_res
-                            part = torch.empty(rows + REDUCE_ROWS, Cv, 2, device=dev, dtype=torch.float32)
-                            dx0 = torch.empty(B, IH, IW, Cv, device=dev, dtype=dt)
-                            variant = lib.sde_conv_fwd_variant(ctypes.byref(dd), Cv) if L.PROFILE is not None else 0
-                            meta = dict(M=B * IH * IW, N=Cv, K=KH * KW * ldy, k=KH, s=1, mode=0, bytes=2 * (dz.numel() + 4 * dx0.numel())) if L.PROFILE is not None else None
-                            _timed("igemm_dgrad", flops, variant, lambda: L.check(lib.sde_conv_dgrad_bnbwd_res(ctypes.byref(dd), L.ptr(wd), L.ptr(dx0), Cv, Cv, L.ptr(y_bn),
-                                                                                                           L.ptr(bnp), L.ptr(part), L.ptr(g_other), L.ptr(x0), L.stream()),
-                                                                                  "sde_conv_dgrad_bnbwd_res"), meta)
-                            if len(_BN_PART) > 16:
-                                _BN_PART.clear()
-                            _BN_PART[dx0.data_ptr()] = (y_bn.data_ptr(), part, rows, g_other.data_ptr())
-                            st["dx0"], st["dx1"] = dx0, None
-                            return
-                        if g_other is not None:
-                            _RES_GRAD[x0.data_ptr()] = g_other                # (no fused form for this layer after all: nothing consumed)
-                        rows = lib.sde_conv_dgrad_bnbwd_rows(ctypes.byref(dd), Cv, Cv) if (ctx.bn_in is not None and BNBWD_FUSED) else 0
-                        if rows > 0:
-                            # the GEMM's epilogue masks the gradient with relu'(bn(y_bn)) and leaves BatchNorm's (sum gm, sum gm * xhat) partials:
-                            # _BatchNormAct.backward finds them under the gradient's address and skips its reduce pass
-                            y_bn, bnp = ctx.bn_in
-                            part = torch.empty(rows + REDUCE_ROWS, Cv, 2, device=dev, dtype=torch.float32)
-                            dx0 = torch.empty(B, IH, IW, Cv, device=dev, dtype=dt)
-                            variant = lib.sde_conv_fwd_variant(ctypes.byref(dd), Cv) if L.PROFILE is not None else 0
-                            meta = dict(M=B * IH * IW, N=Cv, K=KH * KW * ldy, k=KH, s=1, mode=0, bytes=2 * (dz.numel() + 2 * dx0.numel())) if L.PROFILE is not None else None
-                            _timed("igemm_dgrad", flops, variant, lambda: L.check(lib.sde_conv_dgrad_bnbwd(ctypes.byref(dd), L.ptr(wd), L.ptr(dx0), Cv, Cv, L.ptr(y_bn),
-                                                                                                       L.ptr(bnp), L.ptr(part), L.stream()), "sde_conv_dgrad_bnbwd"), meta)
-                            if len(_BN_PART) > 16:
-                                _BN_PART.clear()
-                            _BN_PART[dx0.data_ptr()] = (y_bn.data_ptr(), part, rows)
-                            st["dx0"], st["dx1"] = dx0, None
-                            return
-                    elif stride == 2:
-                        # virtual zero-inserted gradient image: Z[2i, 2j] = dz[i, j]
-                        dd = _desc(dz, None, SRC_ZEROINS, KH, KW, 1, KH - 1 - pad, False, 2 * OH - 1, 2 * OW - 1, IH, IW)
-                    else:
-                        raise L.SdeHipError(f"stride {stride} not supported")
-                    dx0, _ = conv_raw(dd, dt, wd, None, ACT_NONE, Cv, Cv, False, dev, "igemm_dgrad", flops)
-            st["dx0"], st["dx1"] = dx0, dx1
-
-        do_wgrad()       # first: launching the data-gradient GEMM ahead of the fork measured 10 % slower end to end
-        do_dgrad()
-        dw, forked, side, dx0, dx1 = st["dw"], st["forked"], st["side"], st["dx0"], st["dx1"]
-        if forked:
-            if L.JOIN_LAG > 0 and WGRAD_DEFER is not None:
-                # lagging join: the main stream goes on with the next layers' backward and joins this layer's weight-gradient GEMM
-                # SDE_JOIN_LAG convolutions later (or at the reducer's flush); the operands are kept alive until then
-                ev = torch.cuda.Event()
-                ev.record(side)
-                WGRAD_DEFER.pending.append((ev, (dz, x0, x1)))
+        # 2. weight gradient -- the phase's reducer places it (side stream when a data gradient follows, so the two independent GEMMs overlap).
+        # It goes first: launching the data-gradient GEMM ahead of the fork measured 10 % slower end to end
+        dw = side = None
+        if ctx.needs_input_grad[2]:
+            d = _desc(x0, x1, SRC_UPCAT if upcat else SRC_PLAIN, KH, KW, stride, pad, reflect, IH, IW, OH, OW)
+            splits = lib.sde_conv_wgrad_splits(ctypes.byref(d), Cout)
+            wslot = _grad_slot(ctx.params[0])
+            esz = 4 if dt == torch.float32 else 2
+            meta = dict(M=M, N=Cout, K=KH * KW * (C0 + C1), k=KH, s=stride, mode=int(upcat), splits=splits,
+                        bytes=esz * (B * H0 * W0 * C0 + B * IH * IW * C1 + M * ldy) + 8 * splits * Cout * KH * KW * (C0 + C1)) if L.PROFILE is not None else None
+            dw = wslot if wslot is not None else torch.empty(weight.shape, device=dev)      # a fresh gradient tensor is plain OIHW
+            wflags = (1 if wslot is not None else 0) | (2 if is_ohwi(dw) else 0)                # SDE_WREDUCE_ACCUMULATE | SDE_WREDUCE_OHWI
+            op_bytes = (dz.numel() + x0.numel() + (x1.numel() if x1 is not None else 0)) * dz.element_size()
+            dw, side = WGRAD_DEFER.weight_grad(WGradJob(d, dz, x0, x1, Cout, ldy, Cin, C0 + C1, KH * KW, splits, wslot, dw, wflags,
+                                                        4 * splits * Cout * KH * KW * (C0 + C1), op_bytes, need_dx, off_main, flops, meta))
+        # 3. data gradient
+        dx0 = dx1 = None
+        if need_dx:
+            Cv = C0 + C1
+            wd = ctx.wd_pre if ctx.wd_pre is not None else pack_weight(weight, dt, Cv, ldy, for_dgrad=True)   # [Cv][KH][KW][ldy], taps flipped
+            if reflect:
+                dd = _desc(dz, None, SRC_PLAIN, KH, KW, 1, KH - 1, False, OH, OW, IH + 2, IW + 2)
+                dxp, _ = conv_raw(dd, dt, wd, None, ACT_NONE, Cv, Cv, False, dev, "igemm_dgrad", flops)
+                dx0 = torch.empty_like(x0)
+                dx1 = torch.empty_like(x1) if x1 is not None else None
+                L.check(lib.sde_refl_fold(L.ptr(dxp), B, IH, IW, Cv, C0, int(upcat), dtype_code(dt), L.ptr(dx0), L.ptr(dx1), L.stream()), "sde_refl_fold")
             else:
-                torch.cuda.current_stream().wait_stream(side)       # join: dz / x0 / x1 stay alive until both GEMMs are done
+                if upcat:
+                    raise L.SdeHipError("upsample+concat source is only supported with reflection padding (decoder)")
+                if stride == 1:
+                    dd = _desc(dz, None, SRC_PLAIN, KH, KW, 1, KH - 1 - pad, False, OH, OW, IH, IW)
+                    if ctx.bn_in_res is not None:
+                        dx0 = _dgrad_bnbwd(dd, wd, dz, x0, Cv, ctx.bn_in_res, flops, res=True)
+                    elif ctx.bn_in is not None and BNBWD_FUSED:
+                        dx0 = _dgrad_bnbwd(dd, wd, dz, x0, Cv, ctx.bn_in, flops, res=False)
+                elif stride == 2:
+                    # virtual zero-inserted gradient image: Z[2i, 2j] = dz[i, j]
+                    dd = _desc(dz, None, SRC_ZEROINS, KH, KW, 1, KH - 1 - pad, False, 2 * OH - 1, 2 * OW - 1, IH, IW)
+                else:
+                    raise L.SdeHipError(f"stride {stride} not supported")
+                if dx0 is None:
+                    dx0, _ = conv_raw(dd, dt, wd, None, ACT_NONE, Cv, Cv, False, dev, "igemm_dgrad", flops)
+        # 4. join a weight-gradient GEMM that forked alone (now or SDE_JOIN_LAG layers later); dz / x0 / x1 stay alive until then
+        WGRAD_DEFER.join(side, (dz, x0, x1))
         return dx0, dx1, dw, dbias, None, None, None, None, None, None, None, None
 
 
@@ -510,80 +470,165 @@ class WReduceItem(Structure):
                 ("Cin_real", c_int32), ("accumulate", c_int32)]
 
 
+# One convolution's weight-gradient GEMM as _Conv2d.backward hands it to the phase's reducer (dw: the gradient slot wslot, or a fresh OIHW tensor)
+WGradJob = namedtuple("WGradJob", "d dz x0 x1 Cout ldy Cin Cin_pad KHW splits wslot dw flags slab_bytes op_bytes need_dx off_main flops meta")
+
+
+def wgrad_group_rule(queued, queued_bytes, groups_done, op_bytes, need_dx, fork, first_group, group, max_bytes, budget_bytes, early_tail):
+    """Side-stream group boundaries for one layer of a backward phase on the main stream, from plain numbers (the open group, the layer, the
+    schedule knobs).  Returns (fork the open group first, "group" / "alone" (a fork of its own) / "inline", fork the group once this layer is queued)."""
+    if not fork:
+        # a layer without a data gradient (the stem) ends the chain: its GEMM runs on the main stream, so the open group goes to the side stream
+        # NOW, underneath it, instead of after it at the phase's flush
+        return queued > 0 and not need_dx and early_tail, "inline", False
+    if group <= 1 or op_bytes > max_bytes:
+        # layers with very large operands (PackNet's full-resolution 64-channel maps: 190 MB each) fork on their own, after the open group (layer
+        # order): holding three of them alive for a group pushes the working set out of the Infinity Cache (PackNet-1A: 60.2 vs 58.4 ms/step)
+        return queued > 0, "alone", False
+    digits = str(first_group) if first_group else ""      # decimal digits = sizes of the first groups of the phase (33: 3 then 3)
+    limit = int(digits[groups_done]) if groups_done < len(digits) else group
+    # a group closes after `limit` layers or once its operands (kept alive until the group's GEMMs ran) reach the byte budget
+    return False, "group", queued + 1 >= limit or queued_bytes + op_bytes >= budget_bytes
+
+
 class WGradReducer:
-    """Defers the final slab reduction of every convolution's weight gradient to ONE launch per backward phase.
+    """Owns where each convolution's weight gradient of a backward phase runs (weight_grad, join) and its reduction: ONE batched launch at the end of
+    the phase (phase, flush).  Nothing persists across steps: slabs come from the caching allocator (the graph pool under capture) and are released
+    at flush.  defer=False, immediate mode (substitute optimizers, a backward outside any phase): every weight gradient is reduced and joined at once."""
 
-    While installed (`WGRAD_DEFER = reducer`, done by HipTrainer around backward) each _Conv2d.backward runs only the GEMM (+fold) and
-    registers its slabs here; flush() sums them all into the flat gradient.  Nothing persists across steps: slabs come from the caching
-    allocator (the graph pool under capture) and are released at flush; the item table is a host array that the C side copies into the
-    kernel arguments, so there is no device table to upload, keep alive or re-fill after graph capture."""
+    def __init__(self, defer=True):
+        self.defer = defer
+        self._drop()
 
-    def __init__(self):
-        self.jobs, self._seen = [], set()
+    def _drop(self):
+        self.first_group = None    # this phase's first-group digits when they differ from hip.lib.FIRST_GROUP (second phase of a two-phase backward)
+        self.jobs, self._seen = [], set()                # (slab, gradient slot, WReduceItem fields) of the deferred slab reductions
         self.bias_jobs, self._seen_bias = [], set()      # (partial slab, rows, ld, C, gradient slot) of convolutions whose bias-gradient finalize is deferred
-        self.forked = False        # some GEMM of this phase still runs on the side stream (late join)
-        self.pending = []          # (event behind a layer's side-stream work, its operands) of convolutions whose join is lagging (SDE_JOIN_LAG)
-        self.queue = []            # SDE_WGRAD_GROUP > 1: (launch closure, operands) of layers whose weight-gradient GEMM waits for its group's fork
+        self.pending = []          # (event behind side-stream work, its operands) whose join is lagging (SDE_JOIN_LAG)
+        self.queue = []            # (launch, operands) of layers whose weight-gradient GEMM waits for its group's fork
         self.queue_bytes = 0       # operand bytes held by the queued layers
-        self.groups_done = 0       # groups forked so far in this backward phase (the first one may be shorter: hip.lib.FIRST_GROUP)
-        self.first_group = None    # this phase's first-group digits when they differ from hip.lib.FIRST_GROUP (HipTrainer: second phase of a two-phase backward)
+        self.groups_done = 0       # groups forked so far in this backward phase
+
+    @contextlib.contextmanager
+    def phase(self, device, phase_b=False):
+        """One backward phase on ONE main stream: flushes on normal exit; after an exception it still joins the side stream and drops the rest."""
+        global WGRAD_DEFER, MAIN_STREAM
+        WGRAD_DEFER, MAIN_STREAM = self, (torch.cuda.current_stream() if device.type == "cuda" else None)
+        self.first_group = L.FIRST_GROUP_B if phase_b else None
+        try:
+            yield
+            self.flush()
+        finally:
+            WGRAD_DEFER, MAIN_STREAM = _NO_PHASE, None
+            _HANDOVER.end_phase()           # no hand-over between backward nodes outlives the phase
+            self.join_pending()
+            self._drop()
+
+    def weight_grad(self, j):
+        """Launch or queue the GEMM of one WGradJob: straight into the gradient slot, slabs for the phase's batched reduction, or GEMM + reduction
+        at once; queued into a group, forked alone or inline.  Returns (the weight gradient for autograd, the side stream to join() or None)."""
+        fork = j.need_dx and L.SIDE_STREAM and L.PROFILE is None and not j.off_main
+        if fork and L.FORK_MIN_BYTES:      # (A/B aid, default 0: every layer forks)
+            fork = j.op_bytes >= L.FORK_MIN_BYTES
+        run_first, place, close = False, ("alone" if fork else "inline"), False
+        if self.defer and not j.off_main:
+            run_first, place, close = wgrad_group_rule(len(self.queue), self.queue_bytes, self.groups_done, j.op_bytes, j.need_dx, fork,
+                                                       L.FIRST_GROUP if self.first_group is None else self.first_group,
+                                                       L.WGRAD_GROUP, L.GROUP_MAX_BYTES, L.GROUP_BUDGET_BYTES, EARLY_TAIL)
+        if run_first:
+            self.run_queue()
+        side = L.side_stream() if place != "inline" else None
+        if place == "alone":
+            self.join_pending(keep=L.JOIN_LAG - 1)      # lagging joins of earlier layers
+            side.wait_stream(torch.cuda.current_stream())
+        # (a weight used twice in one phase reduces at once: two blocks of one batched launch must not accumulate into the same slot)
+        ok = self.defer and j.wslot is not None and j.wslot.data_ptr() not in self._seen
+        # one pixel range and a channels-last slot without channel padding: the GEMM's only "slab" IS the gradient row block -- it writes
+        # straight into the (zeroed) flat gradient, nothing to reduce
+        direct = (ok and j.splits == 1 and j.Cin_pad == j.Cin and (j.KHW == 1 or is_ohwi(j.wslot)) and j.wslot.data_ptr() % 16 == 0
+                  and L.PROFILE is None)
+        # small slab stacks wait for the phase's one batched reduction; big ones (ResNet-50's 20-40 MB stacks add up to ~1 GB per step)
+        # are summed at once while they are still in the Infinity Cache and their block can be recycled
+        deferred = ok and not direct and j.slab_bytes <= L.DEFER_MAX_BYTES
+        slab = j.wslot if direct else torch.empty(j.splits, j.Cout, j.KHW * j.Cin_pad, device=j.x0.device)
+        if direct or deferred:
+            self._seen.add(j.wslot.data_ptr())
+        if deferred:
+            self.jobs.append((slab, j.wslot, (slab.data_ptr(), j.wslot.data_ptr(), j.splits, j.Cout, j.KHW, j.Cin_pad, j.Cin, j.flags)))
+        launch = functools.partial(self._launch, j, slab, "direct" if direct else "deferred" if deferred else "reduce", side)
+        if place == "group":      # launched by run_queue, in the group's side-stream context
+            self.queue.append((launch, (j.dz, j.x0, j.x1, slab, j.dw)))
+            self.queue_bytes += j.op_bytes
+            if close:
+                self.run_queue()
+        else:
+            with torch.cuda.stream(side) if side is not None else contextlib.nullcontext():
+                launch()
+        return (None if j.wslot is not None else j.dw), (side if place == "alone" else None)
+
+    @staticmethod
+    def _launch(j, slab, target, side):
+        lib = L.lib()
+        if target == "reduce" and L.PROFILE is None:
+            L.check(lib.sde_conv_wgrad(ctypes.byref(j.d), L.ptr(j.dz), j.Cout, j.ldy, j.Cin, L.ptr(slab), j.splits, _wptr(j.dw), j.flags, L.stream()),
+                    "sde_conv_wgrad")
+        else:
+            rows = 1 if target == "direct" else j.splits
+            _timed("wgrad", j.flops, 0, lambda: L.check(lib.sde_conv_wgrad_partial(ctypes.byref(j.d), L.ptr(j.dz), j.Cout, j.ldy, _wptr(slab), rows,
+                                                                                   L.stream()), "sde_conv_wgrad_partial"), j.meta)
+            if target == "reduce":      # the same two launches, timed separately (bench.py's roofline pass: GEMM FLOPs against GEMM time)
+                one = (WReduceItem * 1)(WReduceItem(slab.data_ptr(), j.dw.data_ptr(), j.splits, j.Cout, j.KHW, j.Cin_pad, j.Cin, j.flags))
+                _timed("wgrad_reduce", 0.0, 0, lambda: L.check(lib.sde_wgrad_reduce_batched(one, 1, L.stream()), "sde_wgrad_reduce_batched"),
+                       dict(jobs=1))
+        if side is not None and target != "direct":
+            slab.record_stream(side)
+
+    def join(self, side, operands):
+        """After the layer's data gradient: wait for a GEMM that forked alone onto `side`, SDE_JOIN_LAG layers later (lagging join: the main
+        stream goes on with the next layers' backward; the operands stay alive until then) or at once."""
+        if side is not None and L.JOIN_LAG > 0 and self.defer:
+            self.pending.append((side.record_event(), operands))
+        elif side is not None:
+            torch.cuda.current_stream().wait_stream(side)
 
     def run_queue(self):
-        """SDE_WGRAD_GROUP > 1: launch the queued weight-gradient GEMMs of the last few layers behind ONE fork of the side stream (one
-        cross-stream edge per group in the captured graph instead of one per layer) and leave one lagging join for the whole group."""
+        """Launch the queued weight-gradient GEMMs of the last few layers behind ONE fork of the side stream (one cross-stream edge per group in
+        the captured graph instead of one per layer) and leave one lagging join for the whole group."""
         if not self.queue:
             return
         side = L.side_stream()
-        self.join_pending(keep=max(0, L.JOIN_LAG - 1))
+        self.join_pending(keep=L.JOIN_LAG - 1)
         side.wait_stream(torch.cuda.current_stream())
-        refs = []
         with torch.cuda.stream(side):
-            for launch, operands in self.queue:
+            for launch, _ in self.queue:
                 launch()
-                refs.append(operands)
-        ev = torch.cuda.Event()
-        ev.record(side)
-        self.pending.append((ev, refs))
+        self.pending.append((side.record_event(), [operands for _, operands in self.queue]))
         self.queue, self.queue_bytes = [], 0
         self.groups_done += 1
 
     def join_pending(self, keep=0):
         """Make the current stream wait for all but the newest `keep` lagging weight-gradient GEMMs and release their operands."""
         while len(self.pending) > max(0, keep):
-            ev, _refs = self.pending.pop(0)
-            torch.cuda.current_stream().wait_event(ev)
-
-    def accepts(self, wslot):
-        # a weight used twice in one phase (shared modules) must not be accumulated by two blocks of one launch: the second use reduces at once
-        return wslot.data_ptr() not in self._seen
-
-    def accepts_bias(self, bslot):
-        # (a bias used twice in one phase must not be accumulated by two blocks of one launch)
-        return bslot.data_ptr() not in self._seen_bias
+            torch.cuda.current_stream().wait_event(self.pending.pop(0)[0])
 
     def add_bias(self, part, rows, ld, C, bslot):
+        """Leave a bias gradient's column partials to the phase's batched finalize (True), unless that is off or the bias was seen in this phase
+        (two blocks of one launch must not accumulate into the same slot)."""
+        if not (self.defer and BIAS_DEFER and L.PROFILE is None and bslot.data_ptr() not in self._seen_bias):
+            return False
         self._seen_bias.add(bslot.data_ptr())
         self.bias_jobs.append((part, rows, ld, C, bslot))
+        return True
 
-    def flush_bias(self):
+    def flush(self):
+        """End of a phase: the last group, every join, and the deferred bias and slab sums in one launch each."""
+        self.run_queue()
+        self.groups_done = 0
+        self.join_pending()
         if self.bias_jobs:
             arr = (ColsumItem * len(self.bias_jobs))(*[ColsumItem(p.data_ptr(), b.data_ptr(), r, ld, C, 1) for p, r, ld, C, b in self.bias_jobs])
             L.check(L.lib().sde_colsum_finalize_batched(arr, len(self.bias_jobs), L.stream()), "sde_colsum_finalize_batched")
         self.bias_jobs, self._seen_bias = [], set()
-
-    def add(self, slab, src_ptr, rows, wslot, Cout, KHW, Cin_pad, Cin_real, flags=1):
-        self._seen.add(wslot.data_ptr())
-        self.jobs.append((slab, wslot, (src_ptr, wslot.data_ptr(), rows, Cout, KHW, Cin_pad, Cin_real, flags)))
-
-    def flush(self):
-        self.run_queue()
-        self.groups_done = 0
-        self.join_pending()
-        if self.forked:
-            for st_ in L.all_side_streams():
-                torch.cuda.current_stream().wait_stream(st_)
-            self.forked = False
-        self.flush_bias()
         if not self.jobs:
             return
         items = []
@@ -607,12 +652,9 @@ BNBWD_FUSED = True      # BatchNorm's backward reduce pass in the epilogue of th
 BNBWD_HITS = 0          # times the fused path ran (tests)
 RESBN_FUSED = os.environ.get("SDE_RESBN", "1") != "0"      # ... and the whole reduce pass of a residual BatchNorm in the data gradient of the next block's first convolution (A/B, tests: False)
 RESBN_HITS = 0
-_BN_OUT_RES = {}        # data_ptr of a residual BatchNorm+ReLU output with two consumers -> (weakref to it, y, bnp)
-_RES_GRAD = {}          # data_ptr of a block input -> the gradient that arrived over the block's skip path (set by the block's last BatchNorm backward)
-_BN_OUT = {}            # data_ptr of a residual-free BatchNorm+ReLU output -> (weakref to it, y, bnp): set by _BatchNormAct.forward, taken by _Conv2d.forward
-_BN_PART = {}           # data_ptr of the masked gradient a fused data-gradient GEMM returned -> (y.data_ptr(), partial slab, rows)
-WGRAD_DEFER = None      # HipTrainer installs a WGradReducer around backward
-MAIN_STREAM = None      # ... and the stream the backward phase runs on: the side-stream fork / lagging-join bookkeeping assumes ONE main stream
+_NO_PHASE = WGradReducer(defer=False)
+WGRAD_DEFER = _NO_PHASE  # the reducer of the running backward phase (WGradReducer.phase)
+MAIN_STREAM = None      # ... and the stream it runs on (None: no phase)
 FOLD_ROWS = 16          # SDE_WGRAD_FOLD_ROWS
 
 
@@ -666,9 +708,6 @@ class WeightPacker:
             raise L.SdeHipError("WeightPacker: a weight tensor moved (e.g. flattened after the packer was built); rebuild the packer")
         L.check(L.lib().sde_pack_weights_batched(L.ptr(self.items), self.n, self.total, dtype_code(self.dtype), L.stream()), "sde_pack_weights_batched")
 
-    def join_dgrad(self):
-        """Kept for the trainer's call order (the data-gradient operands are packed by the same launch as the forward ones)."""
-
 
 def conv2d(x, weight, bias=None, stride=1, pad=0, reflect=False, act=ACT_NONE, skip=None, upsample=False, bn_stats=False, owner=None, n_out=1):
     """y = act(conv(x) + bias) on NHWC tensors.
@@ -720,18 +759,12 @@ class _BatchNormAct(torch.autograd.Function):
         ctx.cfg = (relu, residual is not None, training)
         if training and relu and residual is None and n_out == 1 and dt != torch.float32 and C % 64 == 0 and ctx.needs_input_grad[0] and BNBWD_FUSED:
             # candidates for the fused backward reduction: the convolution that consumes `out` (and nothing else does: n_out == 1) picks this up
-            if len(_BN_OUT) > 64:
-                _BN_OUT.clear()
-            _BN_PART.clear()                          # (entries live from a convolution's backward to this BatchNorm's backward only)
-            _BN_OUT[out.data_ptr()] = (weakref.ref(out), y, bnp)
+            _HANDOVER.put_bn_out(out, y, bnp)
         ctx.res_ptr = residual.data_ptr() if residual is not None else None
         if training and relu and residual is not None and n_out == 2 and dt != torch.float32 and C % 64 == 0 and ctx.needs_input_grad[0] and BNBWD_FUSED and RESBN_FUSED:
             # residual BatchNorm + ReLU with two consumers (torchvision's blocks: the next block's first convolution and its skip path): that convolution's
             # data gradient can carry this BatchNorm's backward reduce pass (residual form), see _Conv2d.backward
-            if len(_BN_OUT_RES) > 64:
-                _BN_OUT_RES.clear()
-            _RES_GRAD.clear()                         # (entries live from a block's last BatchNorm backward to its first convolution's backward only)
-            _BN_OUT_RES[out.data_ptr()] = (weakref.ref(out), y, bnp)
+            _HANDOVER.put_bn_out(out, y, bnp, res=True)
             ctx.res_tag = out.data_ptr()              # (this BatchNorm's backward drops the entry: the consuming convolution took its references in forward)
         if n_out == 1:
             return out
@@ -742,7 +775,7 @@ class _BatchNormAct(torch.autograd.Function):
         y, out, bnp, gamma = ctx.saved_tensors
         relu, has_res, training = ctx.cfg
         if getattr(ctx, "res_tag", None) is not None:
-            _BN_OUT_RES.pop(ctx.res_tag, None)
+            _HANDOVER.drop_bn_out_res(ctx.res_tag)
         if not training:
             raise L.SdeHipError("BatchNorm backward in eval mode is not on the path")
         grads = [d.contiguous() for d in douts if d is not None]
@@ -764,33 +797,25 @@ class _BatchNormAct(torch.autograd.Function):
         dgamma = gs if direct else torch.empty(C, device=dev)
         dbeta = bs if direct else torch.empty(C, device=dev)
         dy = torch.empty_like(y)
-        ent = _BN_PART.pop(grads[0].data_ptr(), None) if (_BN_PART and len(grads) == 1 and relu and not has_res) else None
-        if ent is not None and ent[0] == y.data_ptr() and grads[0].shape == y.shape and grads[0].dtype == dt:
-            # the data-gradient GEMM that produced this gradient already masked it and reduced it (sde_conv_dgrad_bnbwd): finalize + apply only
-            global BNBWD_HITS
-            BNBWD_HITS += 1
-            L.check(lib.sde_bn_bwd_from_part(L.ptr(ent[1]), ent[2], L.ptr(grads[0]), L.ptr(y), L.ptr(bnp), M, C, dtype_code(dt), L.ptr(coef), L.ptr(dgamma),
-                                             L.ptr(dbeta), int(direct), L.ptr(dy), L.stream()), "sde_bn_bwd_from_part")
-            if direct:
-                dgamma = dbeta = None
-            return dy, None, dgamma, dbeta, None, None, None, None, None, None, None, None
-        entr = _BN_PART.get(grads[0].data_ptr()) if (_BN_PART and len(grads) == 2 and relu and has_res) else None
-        if entr is not None and len(entr) == 4:
-            # residual form: the next block's first convolution already formed gm = (its data gradient + the skip gradient) * relu'(out) and reduced it
-            del _BN_PART[grads[0].data_ptr()]
-            if not (entr[0] == y.data_ptr() and entr[3] == grads[1].data_ptr() and grads[0].shape == y.shape and grads[0].dtype == dt):
-                raise L.SdeHipError("BatchNorm backward: a data gradient that already contains the skip path's gradient arrived at a BatchNorm it was not "
-                                    "formed for (hip.nn.RESBN_FUSED = False selects the separate reduce pass)")
-            global RESBN_HITS
-            RESBN_HITS += 1
+        # the data-gradient GEMM that produced this gradient already masked and reduced it (sde_conv_dgrad_bnbwd; residual form: the next block's first
+        # convolution formed gm = (its data gradient + the skip gradient) * relu'(out) and reduced it): finalize + apply only
+        ent = _HANDOVER.take_bn_part(grads[0], res=has_res) if (relu and len(grads) == 1 + has_res) else None
+        fits = ent is not None and ent[0] == y.data_ptr() and grads[0].shape == y.shape and grads[0].dtype == dt
+        if has_res and ent is not None and not (fits and ent[3] == grads[1].data_ptr()):
+            raise L.SdeHipError("BatchNorm backward: a data gradient that already contains the skip path's gradient arrived at a BatchNorm it was not "
+                                "formed for (hip.nn.RESBN_FUSED = False selects the separate reduce pass)")
+        if fits:
+            global BNBWD_HITS, RESBN_HITS
+            RESBN_HITS += has_res
+            BNBWD_HITS += not has_res
             gm = grads[0]
-            L.check(lib.sde_bn_bwd_from_part(L.ptr(entr[1]), entr[2], L.ptr(gm), L.ptr(y), L.ptr(bnp), M, C, dtype_code(dt), L.ptr(coef), L.ptr(dgamma),
+            L.check(lib.sde_bn_bwd_from_part(L.ptr(ent[1]), ent[2], L.ptr(gm), L.ptr(y), L.ptr(bnp), M, C, dtype_code(dt), L.ptr(coef), L.ptr(dgamma),
                                              L.ptr(dbeta), int(direct), L.ptr(dy), L.stream()), "sde_bn_bwd_from_part")
-            if ctx.res_ptr is not None:
-                _RES_GRAD[ctx.res_ptr] = gm
+            if has_res and ctx.res_ptr is not None:
+                _HANDOVER.put_res_grad(ctx.res_ptr, gm)
             if direct:
                 dgamma = dbeta = None
-            return dy, None, dgamma, dbeta, None, None, gm, None, None, None, None, None
+            return dy, None, dgamma, dbeta, None, None, (gm if has_res else None), None, None, None, None, None
         part = torch.empty(lib.sde_reduce_num_blocks(M, C) + REDUCE_ROWS, C, 2, device=dev)
         # gm = relu'(out) * (sum of the incoming gradients): needed when there is anything to mask or to sum; it is also the residual's gradient
         gm = torch.empty_like(y) if (relu or len(grads) > 1) else None
@@ -798,8 +823,8 @@ class _BatchNormAct(torch.autograd.Function):
         L.check(lib.sde_bn_bwd(L.ptr(d0), L.ptr(d1), L.ptr(d2), L.ptr(out), L.ptr(y), L.ptr(bnp), L.ptr(gamma), int(relu), M, C, dtype_code(dt), L.ptr(part),
                                L.ptr(coef), L.ptr(dgamma), L.ptr(dbeta), int(direct), L.ptr(gm), L.ptr(dy), L.stream()), "sde_bn_bwd")
         dres = (gm if gm is not None else d0) if has_res else None
-        if dres is not None and ctx.res_ptr is not None and RESBN_FUSED and _BN_OUT_RES:
-            _RES_GRAD[ctx.res_ptr] = dres          # the skip path's gradient, for the data gradient of the convolution that shares the block input (residual form)
+        if dres is not None and ctx.res_ptr is not None and RESBN_FUSED:
+            _HANDOVER.put_res_grad(ctx.res_ptr, dres, if_expected=True)         # the skip path's gradient, for the data gradient of the convolution that shares the block input (residual form)
         if direct:
             dgamma = dbeta = None
         return dy, None, dgamma, dbeta, None, None, dres, None, None, None, None, None
@@ -868,15 +893,12 @@ def prep_input(img, mean, std, dtype, flip=False):
 
 HEAD_BIAS_HITS = 0       # times the fused path below ran (tests)
 HEAD_BIAS_FUSED = True   # the bias gradient of a one-channel convolution feeding depth_head comes out of depth_head's backward (False: separate pass; tests)
-_HEAD_SLOT = {}     # data_ptr of a one-channel bias convolution's output -> its bias parameter (set by _Conv2d.forward, taken by _DepthHead.forward)
-_HEAD_DONE = {}     # data_ptr of the logit gradient _DepthHead.backward returned -> id(bias parameter) whose gradient it accumulated
 
 
 class _DepthHead(torch.autograd.Function):
     @staticmethod
     def forward(ctx, y, min_depth, max_depth, flip):
-        ent = _HEAD_SLOT.pop(y.data_ptr(), None)
-        ctx.bias_param = ent[0] if (ent is not None and ent[1]() is y) else None
+        ctx.bias_param = _HANDOVER.take_head_slot(y)
         B, H, W, ld = y.shape
         depth = torch.empty(B, 1, H, W, device=y.device, dtype=torch.float32)
         L.check(L.lib().sde_depth_head_fwd(L.ptr(y.contiguous()), B, H, W, ld, min_depth, max_depth, int(flip), dtype_code(y.dtype), L.ptr(depth), L.stream()),
@@ -901,7 +923,7 @@ class _DepthHead(torch.autograd.Function):
                                                 L.ptr(dy), L.ptr(part), L.ptr(bslot), 1, L.stream()), "sde_depth_head_bwd_bias")
             global HEAD_BIAS_HITS
             HEAD_BIAS_HITS += 1
-            _HEAD_DONE[dy.data_ptr()] = id(ctx.bias_param)
+            _HANDOVER.put_head_done(dy, ctx.bias_param)
         else:
             L.check(lib.sde_depth_head_bwd(L.ptr(y), L.ptr(ddepth.contiguous().float()), B, H, W, ld, min_depth, max_depth, int(flip), dtype_code(y.dtype),
                                            L.ptr(dy), L.stream()), "sde_depth_head_bwd")
