@@ -379,6 +379,50 @@ int sde_gn_relu_res_bwd(const void* dout, const void* out, const void* x, const 
                         int dtype, float* part, float* coef, float* dgamma, float* dbeta, int accumulate_params, void* dx, sde_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * BTS decoder operators (csrc/bts.hip; detectron2/modeling/depth_net/BTSNet.py:L39-275), NHWC activations in `dtype`, 16-byte channel groups
+ * ------------------------------------------------------------------------------------------------- */
+/* Dilated 3x3 convolution (atrous_conv, L39-64: stride 1, pad = dilation d) as space-to-batch around the conv engine:
+ * split: x [B,H,W,C] -> sub [B*d*d, Hs, Ws, C], Hs = ceil(H/d), Ws = ceil(W/d), sub[(b*d+ph)*d+pw, i, j] = x[b, i*d+ph, j*d+pw] (zero beyond the map);
+ * a 3x3 pad-1 convolution of sub (sde_conv_fwd, and its data and weight gradients) is then the dilated convolution of x, and
+ * merge: sub [B*d*d, Hs, Ws, C] -> out [B,H,W,C] crops it back.  Each is the other's backward. */
+int sde_dilate_split(const void* x, int B, int H, int W, int C, int d, int dtype, void* out, sde_stream_t stream);
+int sde_dilate_merge(const void* sub, int B, int H, int W, int C, int d, int dtype, void* out, sde_stream_t stream);
+/* F.interpolate(scale_factor=2, mode='nearest') of `upconv` (L67-79): x [B,H,W,C] -> out [B,2H,2W,C]; backward: dx [B,H,W,C] = 2x2 block sums of dout */
+int sde_upsample2_fwd(const void* x, int B, int H, int W, int C, int dtype, void* out, sde_stream_t stream);
+int sde_upsample2_bwd(const void* dout, int B, int H, int W, int C, int dtype, void* dx, sde_stream_t stream);
+/* torch.cat(pieces, dim=1) of bts.forward (L208-268): P pixels, pieces in channel order; an activation piece is [P][ld] in `dtype` with C real channels,
+ * an f32map piece a planar [B,1,H,W] fp32 map (C = 1, ld ignored).  out [P][Ct], Ct = the real channels rounded up to the 16-byte group, zero filled.
+ * Backward: the same piece list names the destinations; activation destinations get zeros in channels [C, ld).  The list is copied by value. */
+#define SDE_CAT_MAX 6
+typedef struct sde_cat_piece {
+    void* p;
+    int32_t C, ld, f32map, reserved;
+} sde_cat_piece;
+int sde_cat_fwd(const sde_cat_piece* pieces, int n, long P, int Ct, int dtype, void* out, sde_stream_t stream);
+int sde_cat_bwd(const void* dout, long P, int Ct, int dtype, const sde_cat_piece* grads, int n, sde_stream_t stream);
+/* Batch statistics of a stored tensor x [M][C] (first_bn over a concatenation, L44-47): part [sde_channel_stats_tiles(M) + SDE_REDUCE_ROWS][C][2]
+ * receives per-tile (sum, sum of squares) over SDE_STATS_ROWS rows each -- the slab sde_bn_finalize reads. */
+#define SDE_STATS_ROWS 256
+int sde_channel_stats_tiles(long M);
+int sde_channel_stats(const void* x, long M, int C, int dtype, float* part, sde_stream_t stream);
+/* nn.ReLU (L53): y = max(x, 0) over n elements (backward: sde_act_bwd_bias with SDE_ACT_RELU) */
+int sde_relu_fwd(const void* x, long n, int dtype, void* y, sde_stream_t stream);
+/* reduction_1x1's plane head (L110-122) + F.normalize + local_planar_guidance (L126-148) + / max_depth (+ nearest down-sampling by ds), fused:
+ * y [B,h,w,ld] = the plane_params convolution's output (channels 0..2 the logits) -> full [B,1,h*r,w*r] fp32, and with ds > 0
+ * down [B,1,h*r/ds,w*r/ds] = full[:, :, ds*i, ds*j] (F.interpolate(scale_factor=1/ds, mode='nearest')).  No clamp on the plane denominator.
+ * Backward: dfull and / or ddown (either may be NULL; the two consumers' gradients add) -> dy [B,h,w,ld] (channels >= 3 zero). */
+int sde_lpg_fwd(const void* y, int B, int h, int w, int ld, int r, float max_depth, int ds, int dtype, float* full, float* down, sde_stream_t stream);
+int sde_lpg_bwd(const void* y, const float* dfull, const float* ddown, int B, int h, int w, int ld, int r, float max_depth, int ds, int dtype, void* dy,
+                sde_stream_t stream);
+/* Sigmoid depth heads (reduc1x1 `final`, L88-95; get_depth, L195-196,L272-274): out [B,1,H,W] fp32 = sigmoid(y[...,0]) * scale, then
+ * (* focal[b]) / focal_div when focal (device [B]) is given; flip mirrors the output along x.  Backward writes dy [B,H,W,ld] (channels > 0 zero). */
+int sde_sigmoid_head_fwd(const void* y, int B, int H, int W, int ld, float scale, const float* focal, float focal_div, int flip, int dtype, float* out,
+                         sde_stream_t stream);
+int sde_sigmoid_head_bwd(const void* y, const float* dout, int B, int H, int W, int ld, float scale, const float* focal, float focal_div, int flip, int dtype,
+                         void* dy, sde_stream_t stream);
+
+
+/* ---------------------------------------------------------------------------------------------------
  * PackNet's 3-D convolution (layers01.py:L223-298): x.unsqueeze(1) -> nn.Conv3d(1, 8, 3, padding=1) -> view(b, 8*D, h, w) on NHWC data:
  * y[b,h,w,f*D+ch] = bias[f] + sum w[f][kd][kh][kw] x[b,h+kh-1,w+kw-1,ch+kd-1].  w: [8][3][3][3] fp32 (torch's [8,1,3,3,3]), D % (16 B) == 0.
  * wgrad: part = workspace [sde_conv3d_wgrad_num_blocks()][224] floats; dw [8*27], dbias [8] (may be NULL). */

@@ -15,11 +15,17 @@ _C.MODEL.MAX_DEPTH = 80
 _C.MODEL.PIXEL_MEAN = [0.485, 0.456, 0.406]
 _C.MODEL.PIXEL_STD = [0.229, 0.224, 0.225]
 _C.MODEL.COMPUTE_DTYPE = "fp32"
+_C.MODEL.DATASET = ""                      # BtsModel: "kitti" scales the final depth by focal / 715.0873
 _C.MODEL.DEPTH_NET = CN()
 _C.MODEL.DEPTH_NET.NAME = "DepthResNet"
 _C.MODEL.DEPTH_NET.ENCODER_NAME = "18"
 _C.MODEL.DEPTH_NET.UPSAMPLE_DEPTH = False
 _C.MODEL.DEPTH_NET.VERSION = "1A"          # PackNet01 only (packnet_1a.yaml)
+# --- BtsModel only (projects/Supervised/configs/bts_r50.yaml; BTSNet.py:L337-413) ---
+_C.MODEL.DEPTH_NET.BTS_SIZE = 512          # decoder width (num_features)
+_C.MODEL.DEPTH_NET.BN_NO_TRACK = False     # bn_init_as_tf: m.eval() at build time, undone by the training loop's model.train()
+_C.MODEL.DEPTH_NET.FIX_1ST_CONV = False    # also freeze layer1.0 of the encoder
+_C.MODEL.DEPTH_NET.FIX_1ST_CONVS = False   # also freeze layer1.0 and layer1.1
 _C.MODEL.POSE_NET = CN()
 _C.MODEL.POSE_NET.NAME = "PoseNet"
 _C.MODEL.POSE_NET.NUM_CONTEXTS = 2

@@ -54,6 +54,20 @@ _PROTOS = {
     "sde_silog_multi_num_blocks": ([_I, _P, _P, _I], c_int),
     "sde_silog_multi_fwd": ([_P, _P, _I, _P, _P, _P, _I, _I, _I, _F, _P, _P, _P, _P], c_int),
     "sde_silog_multi_bwd": ([_P, _P, _P, _P, _F, _F, _I, _P, _P, _P, _I, _I, _I, _P, _P], c_int),
+    # BTS decoder operators (csrc/bts.hip; autograd wrappers in hip/bts.py)
+    "sde_dilate_split": ([_P, _I, _I, _I, _I, _I, _I, _P, _P], c_int),
+    "sde_dilate_merge": ([_P, _I, _I, _I, _I, _I, _I, _P, _P], c_int),
+    "sde_upsample2_fwd": ([_P, _I, _I, _I, _I, _I, _P, _P], c_int),
+    "sde_upsample2_bwd": ([_P, _I, _I, _I, _I, _I, _P, _P], c_int),
+    "sde_cat_fwd": ([_P, _I, ctypes.c_long, _I, _I, _P, _P], c_int),
+    "sde_cat_bwd": ([_P, ctypes.c_long, _I, _I, _P, _I, _P], c_int),
+    "sde_channel_stats_tiles": ([ctypes.c_long], c_int),
+    "sde_channel_stats": ([_P, ctypes.c_long, _I, _I, _P, _P], c_int),
+    "sde_relu_fwd": ([_P, ctypes.c_long, _I, _P, _P], c_int),
+    "sde_lpg_fwd": ([_P, _I, _I, _I, _I, _I, _F, _I, _I, _P, _P, _P], c_int),
+    "sde_lpg_bwd": ([_P, _P, _P, _I, _I, _I, _I, _I, _F, _I, _I, _P, _P], c_int),
+    "sde_sigmoid_head_fwd": ([_P, _I, _I, _I, _I, _F, _P, _F, _I, _I, _P, _P], c_int),
+    "sde_sigmoid_head_bwd": ([_P, _P, _I, _I, _I, _I, _F, _P, _F, _I, _I, _P, _P], c_int),
 }
 
 _lib = None
