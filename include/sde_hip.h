@@ -423,6 +423,33 @@ int sde_sigmoid_head_bwd(const void* y, const float* dout, int B, int H, int W, 
 
 
 /* ---------------------------------------------------------------------------------------------------
+ * GoogleResNet operators (csrc/google.hip; detectron2/modeling/depth_net/GoogleResNet.py, detectron2/layers/layer_norm.py), NHWC activations
+ * in fp32 or bf16 (SDE_F16 is refused), 16-byte channel groups.  No atomics: repeated runs give identical bits.
+ * ------------------------------------------------------------------------------------------------- */
+/* RandLayerNorm (layer_norm.py:L7-33) of y [B,HW,C] (C <= 2048 channels, the first Cr real): per-(sample, channel) mean and unbiased variance
+ * over HW >= 2 pixels; in training (train = 1) both are multiplied by 1 + fmod(z * s, 2s) with z [2][B][Cr] (mean draws, then variance draws) and
+ * s = *stddev read from device memory (s == 0: factor 1 exactly); out = gamma * (y - mean) * rsqrt(var + eps) + beta [+ res] [-> ReLU], pad
+ * channels zero.  part: [B][SDE_RLN_CHUNKS][C][2] workspace; rlnp [B][C][2] = (mean, rstd) as used, saved for backward.  Two launches.
+ * sde_randln_chunks(HW): pixel chunks per sample (workgroups per sample of every launch). */
+#define SDE_RLN_CHUNKS 32
+int sde_randln_chunks(int HW);
+int sde_randln_fwd(const void* y, const void* res, const float* gamma, const float* beta, const float* z, const float* stddev, int train, int B, int HW,
+                   int C, int Cr, float eps, int relu, int dtype, float* part, float* rlnp, void* out, sde_stream_t stream);
+/* Backward (mean and variance are detached): g = (d0 [+ d1 [+ d2]]) * relu'(out) (out needed when relu), stored in gm when gm != NULL (the
+ * residual's gradient); dx = g * gamma * rstd; dgamma [Cr] (+)= sum g * xhat, dbeta [Cr] (+)= sum g (accumulate).  part as in forward.
+ * Two launches. */
+int sde_randln_bwd(const void* d0, const void* d1, const void* d2, const void* out, const void* y, const float* rlnp, const float* gamma, int relu, int B,
+                   int HW, int C, int Cr, int dtype, float* part, float* dgamma, float* dbeta, int accumulate, void* gm, void* dx, sde_stream_t stream);
+/* F.interpolate(scale_factor=2, mode='bilinear', align_corners=True) of UpsampleBlock (L107-112): x [B,H,W,C] -> out [B,2H,2W,C] with torch's
+ * source index scale = (H-1)/(2H-1).  Backward: dx [B,H,W,C], every input pixel gathers the output taps that read it. */
+int sde_bilinear2_fwd(const void* x, int B, int H, int W, int C, int dtype, void* out, sde_stream_t stream);
+int sde_bilinear2_bwd(const void* dout, int B, int H, int W, int C, int dtype, void* dx, sde_stream_t stream);
+/* F.softplus(out_conv(x)) (L103; beta 1, threshold 20): channel 0 of y [B,H,W,ld] -> out [B,1,H,W] fp32, mirrored along x when flip.
+ * Backward: dy [B,H,W,ld] = dout * sigmoid(y) (dout where y > 20) in channel 0, zero in the others. */
+int sde_softplus_head_fwd(const void* y, int B, int H, int W, int ld, int flip, int dtype, float* out, sde_stream_t stream);
+int sde_softplus_head_bwd(const void* y, const float* dout, int B, int H, int W, int ld, int flip, int dtype, void* dy, sde_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * PackNet's 3-D convolution (layers01.py:L223-298): x.unsqueeze(1) -> nn.Conv3d(1, 8, 3, padding=1) -> view(b, 8*D, h, w) on NHWC data:
  * y[b,h,w,f*D+ch] = bias[f] + sum w[f][kd][kh][kw] x[b,h+kh-1,w+kw-1,ch+kd-1].  w: [8][3][3][3] fp32 (torch's [8,1,3,3,3]), D % (16 B) == 0.
  * wgrad: part = workspace [sde_conv3d_wgrad_num_blocks()][224] floats; dw [8*27], dbias [8] (may be NULL). */

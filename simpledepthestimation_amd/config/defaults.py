@@ -26,6 +26,11 @@ _C.MODEL.DEPTH_NET.BTS_SIZE = 512          # decoder width (num_features)
 _C.MODEL.DEPTH_NET.BN_NO_TRACK = False     # bn_init_as_tf: m.eval() at build time, undone by the training loop's model.train()
 _C.MODEL.DEPTH_NET.FIX_1ST_CONV = False    # also freeze layer1.0 of the encoder
 _C.MODEL.DEPTH_NET.FIX_1ST_CONVS = False   # also freeze layer1.0 and layer1.1
+# --- GoogleResNet only (projects/MotionLearning/configs/resnet18.yaml; GoogleResNet.py:L126-155) ---
+_C.MODEL.DEPTH_NET.NORM = "randLN"         # encoder norm layer: "randLN" (RandLayerNorm), "BN" or None (BN)
+_C.MODEL.DEPTH_NET.NOISE_STDDEV = 0.5      # RandLayerNorm noise reached at the end of the ramp
+_C.MODEL.DEPTH_NET.RAMPUP_ITERS = 0        # > 0: the noise ramps as NOISE_STDDEV * min(step / RAMPUP_ITERS, 1)^2 (0: the modules keep stddev 0.5)
+_C.MODEL.DEPTH_NET.LEARN_SCALE = False     # adds decoder.scale (ones(1)), which the forward pass never reads
 _C.MODEL.POSE_NET = CN()
 _C.MODEL.POSE_NET.NAME = "PoseNet"
 _C.MODEL.POSE_NET.NUM_CONTEXTS = 2

@@ -20,6 +20,7 @@ import torch.distributed as dist
 
 from ..checkpoint import DetectionCheckpointer, PeriodicCheckpointer
 from ..evaluation import build_evaluator, inference_on_dataset
+from ..modeling.depth_net.GoogleResNet import noise_ramp
 from . import trainer as T
 
 log = logging.getLogger(__name__)
@@ -116,20 +117,31 @@ def do_train(cfg, model, data_loader, data_loader_test=None, resume=False, use_g
             log.info("epoch %d iter %d: %s", epoch, global_step, {k: (round(v, 5) if isinstance(v, float) else v) for k, v in rec.items()})
         records.append(rec)
 
+    # GoogleResNet's RandLayerNorm noise (projects/MotionLearning/train.py:L57-58,L101-105): ramped before every step when RAMPUP_ITERS > 0,
+    # zero for evaluation; every other depth net runs as before
+    depth_net = getattr(core, "depth_net", None)
+    noisy = depth_net if hasattr(depth_net, "set_stddev") else None
+    ramp = noisy is not None and cfg.MODEL.DEPTH_NET.get("RAMPUP_ITERS", 0) > 0
+    noise = {}
     log.info("Starting training from iteration %d", start_epoch)
     for epoch in range(start_epoch, cfg.SOLVER.MAX_EPOCHS):
         for epoch_iter, data in enumerate(data_loader):
             global_step += 1
             if supervised:      # polynomial decay (Supervised/train.py:L125-128): the reference sets it AFTER step g from g, so step g runs on f(g - 1)
                 tr.set_lr([T.poly_lr(cfg, global_step - 1, max_iter)] * len(tr.groups))
+            if ramp:
+                noise["noise_stddev"] = noise_ramp(cfg.MODEL.DEPTH_NET.NOISE_STDDEV, cfg.MODEL.DEPTH_NET.RAMPUP_ITERS, global_step)
+                noisy.set_stddev(noise["noise_stddev"])
             meter.add(tr.step(data))
             if (epoch_iter + 1) % cfg.LOG_PERIOD == 0:
-                write()
+                write(noise)
         if not supervised:
             tr.set_lr(epoch_lrs(epoch + 1))                      # scheduler.step() at the end of the epoch (MonoDepth2/train.py:L109)
         sched.last_epoch, sched.global_step = epoch + 1, global_step
         periodic.step(epoch)
         if cfg.TEST.EVAL_PERIOD > 0 and (epoch + 1) % cfg.TEST.EVAL_PERIOD == 0 and data_loader_test is not None:
+            if noisy is not None:
+                noisy.set_stddev(0.0)
             results = do_test(cfg, core, data_loader_test)
             core.train()
             write({f"{tag}/{k}": v for tag, table in results.items() for k, v in table.items()})

@@ -68,6 +68,14 @@ _PROTOS = {
     "sde_lpg_bwd": ([_P, _P, _P, _I, _I, _I, _I, _I, _F, _I, _I, _P, _P], c_int),
     "sde_sigmoid_head_fwd": ([_P, _I, _I, _I, _I, _F, _P, _F, _I, _I, _P, _P], c_int),
     "sde_sigmoid_head_bwd": ([_P, _P, _I, _I, _I, _I, _F, _P, _F, _I, _I, _P, _P], c_int),
+    # GoogleResNet operators (csrc/google.hip; autograd wrappers in hip/google.py)
+    "sde_randln_chunks": ([_I], c_int),
+    "sde_randln_fwd": ([_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _I, _I, _P, _P, _P, _P], c_int),
+    "sde_randln_bwd": ([_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P], c_int),
+    "sde_bilinear2_fwd": ([_P, _I, _I, _I, _I, _I, _P, _P], c_int),
+    "sde_bilinear2_bwd": ([_P, _I, _I, _I, _I, _I, _P, _P], c_int),
+    "sde_softplus_head_fwd": ([_P, _I, _I, _I, _I, _I, _I, _P, _P], c_int),
+    "sde_softplus_head_bwd": ([_P, _P, _I, _I, _I, _I, _I, _I, _P, _P], c_int),
 }
 
 _lib = None

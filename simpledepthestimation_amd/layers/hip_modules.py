@@ -8,6 +8,7 @@ import math
 import torch
 import torch.nn as nn
 
+from ..hip import google as HG
 from ..hip import nn as HN
 
 
@@ -91,3 +92,50 @@ def conv_bn(conv, bn, x, residual=None, relu=True, n_out=1):
     else:
         y, stats = conv(x), None
     return bn(y, stats, residual, relu, n_out)
+
+
+class HipRandLayerNorm(nn.Module):
+    """RandLayerNorm (detectron2/layers/layer_norm.py:L7-33) on NHWC activations: per-sample statistics, noise-scaled in training.
+
+    Same forward contract as HipBatchNorm2d minus the statistics slab: norm(y, residual, relu, n_out).  ``stddev`` lives in a one-element
+    device buffer (not in the state dict, which holds weight and bias only, as the reference's) that the kernel reads, so a captured graph
+    follows later set_stddev values.  z: [2,B,C] draws (mean, variance) for the next training forward -- the owning network hands each norm a
+    slice of one draw per forward (``_z``); ``inject_z`` overrides them for one forward (tests)."""
+
+    def __init__(self, num_channels, eps=1e-3):
+        super().__init__()
+        self.num_channels, self.eps = int(num_channels), eps
+        self.weight = nn.Parameter(torch.ones(num_channels))
+        self.bias = nn.Parameter(torch.zeros(num_channels))
+        self.register_buffer("noise_stddev", torch.full((1,), 0.5), persistent=False)
+        self._stddev = 0.5
+        self._z = None
+        self._injected = None
+
+    @property
+    def stddev(self):
+        return self._stddev
+
+    @stddev.setter
+    def stddev(self, value):
+        self._stddev = float(value)
+        self.noise_stddev.fill_(self._stddev)
+
+    def inject_z(self, z_mean, z_var):
+        """Use these [B,C] draws (the reference's randn_like(mean) and randn_like(var)) in the next training forward."""
+        self._injected = torch.stack([torch.as_tensor(z_mean).reshape(-1), torch.as_tensor(z_var).reshape(-1)])
+
+    def forward(self, y, residual=None, relu=True, n_out=1):
+        z = None
+        if self.training:
+            B, C = y.shape[0], self.num_channels
+            if self._injected is not None:
+                z, self._injected = self._injected.to(device=y.device, dtype=torch.float32).reshape(2, B, C), None
+            elif self._z is not None:
+                z, self._z = self._z, None
+            else:
+                z = torch.randn(2, B, C, device=y.device)
+        return HG.rand_layer_norm(y, self.weight, self.bias, z, self.noise_stddev, self.eps, self.training, residual, relu, n_out)
+
+    def extra_repr(self):
+        return f"{self.num_channels}, eps={self.eps}, stddev={self._stddev}"
