@@ -450,6 +450,41 @@ int sde_softplus_head_fwd(const void* y, int B, int H, int W, int ld, int flip, 
 int sde_softplus_head_bwd(const void* y, const float* dout, int B, int H, int W, int ld, int flip, int dtype, void* dy, sde_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * GoogleMotionNet / GooglePoseNet operators (csrc/motion.hip; detectron2/modeling/pose_net/GooglePoseNet.py), NHWC activations in fp32 or bf16
+ * (SDE_F16 is refused), 16-byte channel groups.  The 3-channel motion field is fp32 [B,h,w,4] (channel 3 zero) in both modes.  No atomics:
+ * repeated runs give identical bits.  No call synchronises.
+ * ------------------------------------------------------------------------------------------------- */
+/* MotionRefiner's input (L91-94): F.interpolate(field, (H, W), mode='bilinear', align_corners=True) for any size pair (source index
+ * o * (h-1)/(H-1), 0 when H == 1) and cat([resized, skip], 1) in one pass.  skip [B,H,W,Cs], its first Cr channels real; X [B,H,W,Cx] in
+ * `dtype`, Cx >= 3 + Cr, channels [resized (3), skip (Cr), zeros]; up [B,H,W,4] fp32 = the resized field.
+ * Backward: g = dX0 [+ dX1] (either may be NULL); dfield [B,h,w,4] = the gather of g[..., 0:3] + dup (dup may be NULL) over the output
+ * positions that read each field pixel; dskip [B,H,W,Cs] = g[..., 3:3+Cr], pad channels zero (NULL: not written). */
+int sde_motion_resize_cat_fwd(const float* field, int h, int w, const void* skip, int B, int H, int W, int Cs, int Cr, int Cx, int dtype, void* X,
+                              float* up, sde_stream_t stream);
+int sde_motion_resize_cat_bwd(const void* dX0, const void* dX1, const float* dup, int B, int H, int W, int Cx, int Cr, int Cs, int h, int w, int dtype,
+                              float* dfield, void* dskip, sde_stream_t stream);
+/* MotionRefiner's tail (L95-99): out [P,4] fp32 = up [P,4] + w3 . cat[o1, o2] per pixel; o1, o2 [P,ld] with `mid` real channels each,
+ * w3 [3][2*mid] fp32 (the bias-free 1x1 conv3, OIHW).  Backward: do1, do2 [P,ld] (pad channels zero), dw3 [3][2*mid] (overwritten) through
+ * part [sde_motion_tail_blocks(P, ld, dtype)][3][2*mid] partial sums and a fixed-order final sum (two launches); d up = dout. */
+int sde_motion_tail_fwd(const void* o1, const void* o2, const float* w3, const float* up, long P, int ld, int mid, int dtype, float* out,
+                        sde_stream_t stream);
+int sde_motion_tail_blocks(long P, int ld, int dtype);
+int sde_motion_tail_bwd(const float* dout, const void* o1, const void* o2, const float* w3, long P, int ld, int mid, int dtype, void* do1, void* do2,
+                        float* part, float* dw3, sde_stream_t stream);
+/* GoogleMotionNet's head (L190-205): r = field * *scale; mask = 1: n = |r|_2 over the 3 channels, r *= (n > mean of n over all B*H*W pixels);
+ * out [B,3,H,W] fp32 planar = r * *weight.  scale and weight are one-element device buffers (a captured graph follows later values).
+ * part: [sde_motion_head_blocks(B*H*W)] floats; keep [B*H*W] bytes, the mask (both unused when mask = 0).  One launch, two with the mask.
+ * Backward: g = dout * *weight * keep (keep NULL: all ones); dfield [B,H,W,4] = g * *scale; part[blk] = partial sums of sum g * field, whose
+ * total is the gradient of *scale (the mask carries no gradient). */
+int sde_motion_head_blocks(long P);
+int sde_motion_head_fwd(const float* field, const float* scale, const float* weight, int mask, int B, int H, int W, float* part, unsigned char* keep,
+                        float* out, sde_stream_t stream);
+int sde_motion_head_bwd(const float* dout, const float* field, const float* scale, const float* weight, const unsigned char* keep, int B, int H, int W,
+                        float* dfield, float* part, sde_stream_t stream);
+/* Gradient of sde_prep_input without mean / std / flip: d0 [+ d1] [B,H,W,Cp] in `dtype` -> dimg [B,C,H,W] fp32 (d1 may be NULL). */
+int sde_prep_input_bwd(const void* d0, const void* d1, int B, int C, int H, int W, int Cp, int dtype, float* dimg, sde_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * PackNet's 3-D convolution (layers01.py:L223-298): x.unsqueeze(1) -> nn.Conv3d(1, 8, 3, padding=1) -> view(b, 8*D, h, w) on NHWC data:
  * y[b,h,w,f*D+ch] = bias[f] + sum w[f][kd][kh][kw] x[b,h+kh-1,w+kw-1,ch+kd-1].  w: [8][3][3][3] fp32 (torch's [8,1,3,3,3]), D % (16 B) == 0.
  * wgrad: part = workspace [sde_conv3d_wgrad_num_blocks()][224] floats; dw [8*27], dbias [8] (may be NULL). */

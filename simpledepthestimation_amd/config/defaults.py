@@ -34,6 +34,13 @@ _C.MODEL.DEPTH_NET.LEARN_SCALE = False     # adds decoder.scale (ones(1)), which
 _C.MODEL.POSE_NET = CN()
 _C.MODEL.POSE_NET.NAME = "PoseNet"
 _C.MODEL.POSE_NET.NUM_CONTEXTS = 2
+# GooglePoseNet / GoogleMotionNet (projects/MotionLearning/configs/Base.yaml); PoseNet reads none of these
+_C.MODEL.POSE_NET.USE_DEPTH = True           # pose_net_input carries 2 x (RGB + depth) = 8 channels (False: 6)
+_C.MODEL.POSE_NET.GROUP_NORM = False         # GroupNorm(16) between every convolution and its ReLU (never in refiner0)
+_C.MODEL.POSE_NET.MASK_MOTION = True         # keep the motion field only where its norm exceeds the batch mean
+_C.MODEL.POSE_NET.LEARN_SCALE = True         # rot_scale / trans_scale parameters (False: the constant 0.01)
+_C.MODEL.POSE_NET.SCALE_CONSTRAIN = "clip"   # "clip", "clip_ste" or "softplus" (GoogleMotionNet; anything else raises NotImplementedError)
+_C.MODEL.POSE_NET.BURN_IN_ITERS = 20000      # stored only: the MotionLearning training loop reads it
 _C.LOSS = CN()
 _C.LOSS.SSIM_WEIGHT = 0.85
 _C.LOSS.C1 = 1e-4

@@ -76,6 +76,16 @@ _PROTOS = {
     "sde_bilinear2_bwd": ([_P, _I, _I, _I, _I, _I, _P, _P], c_int),
     "sde_softplus_head_fwd": ([_P, _I, _I, _I, _I, _I, _I, _P, _P], c_int),
     "sde_softplus_head_bwd": ([_P, _P, _I, _I, _I, _I, _I, _I, _P, _P], c_int),
+    # GoogleMotionNet / GooglePoseNet operators (csrc/motion.hip; autograd wrappers in hip/motion.py)
+    "sde_motion_resize_cat_fwd": ([_P, _I, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P], c_int),
+    "sde_motion_resize_cat_bwd": ([_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P], c_int),
+    "sde_motion_tail_fwd": ([_P, _P, _P, _P, ctypes.c_long, _I, _I, _I, _P, _P], c_int),
+    "sde_motion_tail_blocks": ([ctypes.c_long, _I, _I], c_int),
+    "sde_motion_tail_bwd": ([_P, _P, _P, _P, ctypes.c_long, _I, _I, _I, _P, _P, _P, _P, _P], c_int),
+    "sde_motion_head_blocks": ([ctypes.c_long], c_int),
+    "sde_motion_head_fwd": ([_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P], c_int),
+    "sde_motion_head_bwd": ([_P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P], c_int),
+    "sde_prep_input_bwd": ([_P, _P, _I, _I, _I, _I, _I, _I, _P, _P], c_int),
 }
 
 _lib = None
