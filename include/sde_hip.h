@@ -573,6 +573,63 @@ int sde_depth_metrics(const float* pred, int ph, int pw, const float* gt, int gh
                       int x0, int x1, float min_depth, float max_depth, int gt_scale, double* part, float* med, unsigned* keys, double* out,
                       sde_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------------
+ * MotionLearning loss stack (csrc/motion_loss.hip; autograd wrappers in hip/motion_loss.py).  fp32, planar NCHW, no host synchronisation.
+ *
+ * sde_view_synthesis_pp: detectron2/geometry/camera.py:L166-202 with a per-pixel translation t [B,3,H,W] and a 3x3 rotation R [B,3,3]; the
+ * outputs of sde_view_synthesis (Z, grid, valid optional).  The projection keeps that entry point's fp32 operation order; K @ t is formed per pixel.
+ *
+ * sde_rgbd_fwd / sde_rgbd_bwd: detectron2/modeling/meta_arch/MotionLearning.py:L248-291 for N samples (both directions of a pair stack along N).
+ * frame_* [N,3,H,W], depth_* [N,1,H,W], K, R [N,3,3], t [N,3,H,W]; ssim != 0 adds the WeightedSSIM term (C1 or C2 may be +inf: that factor is
+ * dropped, ssim_loss.py:L99-104).  Forward, three launches: sampled [N,3,H,W] (warped frame_B), grid [N,H,W,2] (coords_A_in_B), occ [N,1,H,W]
+ * (occlusion mask), err [N,1,H,W] (depth_in_B - sampled depth_B), valid [N,1,H,W] (projection mask), dpw [N,1,H,W] (depth_proximity_weight),
+ * part1 [sde_rgbd_num_blocks][4] and part2 [sde_rgbd_num_blocks] workspaces, stats [4][N] = per-sample sum |sampled - frame_A| occ,
+ * sum ssim_map avg_w, sum |err| occ / normalizer, normalizer.  Backward, three launches: g_l1 / g_ssim / g_dl1 [N] are the upstream gradients
+ * of stats rows 0 / 1 / 2 (NULL: zero; the SSIM row's is multiplied by gscale_ssim), coef [N,3,H,W,4] workspace (16-byte aligned),
+ * d_depth [N,1,H,W], d_t [N,3,H,W], dR_partial [sde_rgbd_num_blocks][9] workspace, dR [N,3,3].  frame_*, K and depth_B receive no gradient.
+ *
+ * sde_wssim_fwd / sde_wssim_bwd: ssim_loss.py:L56-111, (x, y [N,C,H,W], w [N,1,H,W]) -> (map [N,C,H,W], avg_w [N,1,H,W]); gradients of the map
+ * to x and y (either may be NULL), coef [N,C,H,W,4] workspace.
+ *
+ * sde_motion_consistency_fwd / _bwd: detectron2/modeling/losses/motion_loss.py:L7-48.  grid [N,H,W,2] (a constant), mask [N,1,H,W], R_* [N,3,3],
+ * t_* [N,3,H,W]; out[2] = rot_error, trans_error; partial [sde_rgbd_num_blocks] workspace.  Backward: g_rot / g_trans device scalars (NULL: zero),
+ * d_tB_zeroed [N,3,H,W] must be zero on entry (the bilinear taps are scattered into it with fp32 atomic adds: the one sum of this stack whose
+ * order is not fixed), dR_partial [sde_rgbd_num_blocks][9] workspace.
+ *
+ * sde_motion_smooth_* / sde_motion_sparsity_*: motion_loss.py:L51-64 over planes = B * C maps; one launch each way.  partial: workspace of
+ * sde_motion_smooth_num_blocks / planes floats; ticket: one device int, zero between launches; mean [planes]: the per-plane mean |f| (kept for
+ * the backward).  out / gout: device scalars.
+ *
+ * sde_avgpool_fwd / _bwd: F.adaptive_avg_pool2d (camera.py:L49-54), [planes,H,W] <-> [planes,h,w]. */
+typedef struct sde_rgbd_desc {
+    const float *frame_A, *frame_B, *depth_A, *depth_B, *K, *R, *t;
+    int32_t N, H, W, ssim;
+    float C1, C2;
+} sde_rgbd_desc;
+int sde_view_synthesis_pp(const float* img, const float* depth, const float* K, const float* R, const float* t, int B, int C, int H, int W, float* sampled,
+                          float* Z, float* grid, uint8_t* valid, sde_stream_t stream);
+int sde_rgbd_num_blocks(int N, int H, int W);
+int sde_rgbd_fwd(const sde_rgbd_desc* d, float* sampled, float* grid, float* occ, float* err, uint8_t* valid, float* dpw, float* part1, float* part2,
+                 float* stats, sde_stream_t stream);
+int sde_rgbd_bwd(const sde_rgbd_desc* d, const float* sampled, const float* occ, const float* err, const float* dpw, const float* stats, const float* g_l1,
+                 const float* g_ssim, const float* g_dl1, float gscale_ssim, float* coef, float* d_depth, float* d_t, float* dR_partial, float* dR,
+                 sde_stream_t stream);
+int sde_wssim_fwd(const float* x, const float* y, const float* w, int N, int C, int H, int W, float C1, float C2, float* map, float* avg_w, sde_stream_t stream);
+int sde_wssim_bwd(const float* x, const float* y, const float* w, const float* gout, int N, int C, int H, int W, float C1, float C2, float* coef, float* dx,
+                  float* dy, sde_stream_t stream);
+int sde_motion_consistency_fwd(const float* grid, const float* mask, const float* R_A2B, const float* R_B2A, const float* t_A2B, const float* t_B2A, int N, int H,
+                               int W, float* partial, float* out, sde_stream_t stream);
+int sde_motion_consistency_bwd(const float* grid, const float* mask, const float* R_A2B, const float* R_B2A, const float* t_A2B, const float* t_B2A,
+                               const float* g_rot, const float* g_trans, int N, int H, int W, float* d_tA, float* d_tB_zeroed, float* dR_partial, float* dR_A2B,
+                               float* dR_B2A, sde_stream_t stream);
+int sde_motion_smooth_num_blocks(int planes, int H, int W);
+int sde_motion_smooth_fwd(const float* f, int planes, int H, int W, float* partial, float* out, int* ticket, sde_stream_t stream);
+int sde_motion_smooth_bwd(const float* f, const float* gout, int planes, int H, int W, float* df, sde_stream_t stream);
+int sde_motion_sparsity_fwd(const float* f, int planes, long hw, float* mean, float* partial, float* out, int* ticket, sde_stream_t stream);
+int sde_motion_sparsity_bwd(const float* f, const float* mean, const float* gout, int planes, long hw, float* df, sde_stream_t stream);
+int sde_avgpool_fwd(const float* src, float* dst, int planes, int H, int W, int h, int w, sde_stream_t stream);
+int sde_avgpool_bwd(const float* dout, float* din, int planes, int H, int W, int h, int w, sde_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,900 @@
+// MotionLearning loss stack for gfx950 (MI355X): view synthesis with a per-pixel translation, the RGB-D consistency loss (warp + 4-channel
+// gather + per-sample reductions + weighted SSIM), the stand-alone WeightedSSIM, the motion consistency / smoothness / sparsity terms and the
+// adaptive average pool of the image pyramid.
+//
+// Replaces (reference, read-only): detectron2/geometry/camera.py:L49-54,L166-202 with t [B,3,H,W], detectron2/modeling/losses/ssim_loss.py:L56-111,
+// detectron2/modeling/losses/motion_loss.py:L7-64 and detectron2/modeling/meta_arch/MotionLearning.py:L248-291.
+//
+// Numerics: fp32, planar NCHW.  Compiled with -ffp-contract=off like photometric.hip: the projection keeps that file's operation order (projection.h),
+// the only difference being K @ t evaluated per pixel.  One workgroup = 4 rows of 64 pixels of one sample (a wave reads one contiguous 256 B row
+// segment per plane); the 3x3 neighbourhoods of the SSIM kernels are re-read through L1 / L2.  Per-sample camera values live in scalar registers.
+// Reductions: per-workgroup partials in a fixed order, then a finalize; the only float atomics are the bilinear scatter of mc_bwd_kernel.
+#include "common.h"
+#include "projection.h"
+#include "sde_hip.h"
+
+namespace {
+
+constexpr int PB_N = 256;     // 64 x 4 pixels per workgroup
+
+// K, K^-1 and K @ R of one sample (make_cam with unit scale factors and a 3x3 rotation); kt is set per pixel
+__device__ __forceinline__ void make_cam_rt(const float* __restrict__ K, const float* __restrict__ R, Cam& c) {
+#pragma unroll
+    for (int i = 0; i < 9; ++i) { c.k[i] = K[i]; c.ki[i] = K[i]; }
+    c.ki[0] = 1.0f / c.k[0];
+    c.ki[4] = 1.0f / c.k[4];
+    c.ki[2] = (-1.0f * c.k[2]) / c.k[0];
+    c.ki[5] = (-1.0f * c.k[5]) / c.k[4];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+#pragma unroll
+        for (int j = 0; j < 3; ++j) c.kr[3 * i + j] = (c.k[3 * i] * R[j] + c.k[3 * i + 1] * R[3 + j]) + c.k[3 * i + 2] * R[6 + j];
+        c.kt[i] = 0.f;
+    }
+    c = cam_uniform(c);
+}
+
+// K @ t of this pixel: the chain of make_cam's kt
+__device__ __forceinline__ void set_kt(Cam& c, float t0, float t1, float t2) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i) c.kt[i] = fmaf(c.k[3 * i + 2], t2, fmaf(c.k[3 * i + 1], t1, c.k[3 * i] * t0));
+}
+
+__device__ __forceinline__ bool proj_valid(const Proj& pr, int W, int H) {
+    const bool fin = (pr.X == pr.X) && fabsf(pr.X) <= kFltMax && (pr.Y == pr.Y) && fabsf(pr.Y) <= kFltMax;
+    return fin && pr.X >= 0.f && pr.X < (float)(W - 1) && pr.Y >= 0.f && pr.Y < (float)(H - 1) && pr.q[2] > 0.f;
+}
+
+__device__ __forceinline__ void store_grid(const Proj& pr, int W, int H, float* __restrict__ g) {
+    const float wm1 = (float)(W - 1), hm1 = (float)(H - 1);
+    const float xs = fminf(fmaxf(nan_to_num(pr.X), 0.f), wm1), ys = fminf(fmaxf(nan_to_num(pr.Y), 0.f), hm1);
+    g[0] = (2.0f * xs) / wm1 - 1.0f;
+    g[1] = (2.0f * ys) / hm1 - 1.0f;
+}
+
+// Sums of NV values over a 256-thread workgroup, written by threads 0..NV-1 to out[0..NV) (waves added in order: deterministic)
+template <int NV>
+__device__ __forceinline__ void block_sums(float (&v)[NV], float* red /*[4 * NV]*/, float* __restrict__ out) {
+#pragma unroll
+    for (int i = 0; i < NV; ++i) v[i] = sde_wave_sum(v[i]);
+    const int tid = threadIdx.x;
+    if ((tid & 63) == 0)
+#pragma unroll
+        for (int i = 0; i < NV; ++i) red[(tid >> 6) * NV + i] = v[i];
+    __syncthreads();
+    if (tid < NV) out[tid] = ((red[tid] + red[NV + tid]) + red[2 * NV + tid]) + red[3 * NV + tid];
+}
+
+// ------------------------------------------------------------------------------------------------
+// view_synthesis with t [B,3,H,W] (camera.py:L166-202): the outputs of view_synthesis_kernel
+// ------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(PB_N) view_synthesis_pp_kernel(const float* __restrict__ img, const float* __restrict__ depth, const float* __restrict__ K,
+                                                                 const float* __restrict__ R, const float* __restrict__ t, int C, int H, int W,
+                                                                 float* __restrict__ sampled, float* __restrict__ Zout, float* __restrict__ grid,
+                                                                 uint8_t* __restrict__ valid) {
+    const int b = blockIdx.z;
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63);
+    const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (x >= W || y >= H) return;
+    Cam cam;
+    make_cam_rt(K + 9 * b, R + 9 * b, cam);
+    const long pix = (long)y * W + x;
+    const long hw = (long)H * W;
+    const float* tp = t + (long)b * 3 * hw + pix;
+    set_kt(cam, tp[0], tp[hw], tp[2 * hw]);
+    Proj pr;
+    project(cam, x, y, depth[b * hw + pix], W, H, pr);
+    Taps tp4;
+    make_taps(pr.ix, pr.iy, W, H, tp4);
+    for (int c = 0; c < C; ++c) sampled[((long)b * C + c) * hw + pix] = bilinear(img + ((long)b * C + c) * hw, W, tp4, nullptr);
+    if (Zout) Zout[b * hw + pix] = fmaxf(pr.q[2], 1e-5f);
+    if (grid) store_grid(pr, W, H, grid + (b * hw + pix) * 2);
+    if (valid) valid[b * hw + pix] = proj_valid(pr, W, H) ? 1 : 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// RGB-D consistency (MotionLearning.py:L248-291), pass 1: warp, gather frame_B + depth_B, masks, per-workgroup partial sums
+// ------------------------------------------------------------------------------------------------
+struct RgbdArgs {
+    const float *fA, *fB, *dA, *dB, *K, *R, *t;
+    int N, H, W;
+    float* sampled;   // [N,3,H,W] warped frame_B
+    float* grid;      // [N,H,W,2]
+    float* occ;       // [N,1,H,W] occlusion mask (0 / 1)
+    float* err;       // [N,1,H,W] depth_in_B - sampled_depth_B (signed; the SSIM weight squares it, the backward takes its sign)
+    uint8_t* valid;   // [N,1,H,W] projection mask
+    float* partial;   // [workgroups][4]: sum occ, sum err^2 occ, sum |sampled - frame_A| occ, sum |err| occ
+};
+
+__global__ void __launch_bounds__(PB_N) rgbd_warp_kernel(const RgbdArgs a) {
+    __shared__ float red[16];
+    const int n = blockIdx.z, H = a.H, W = a.W;
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    const bool act = x < W && y < H;
+    const long hw = (long)H * W, pix = act ? (long)y * W + x : 0;
+    Cam cam;
+    make_cam_rt(a.K + 9 * n, a.R + 9 * n, cam);
+    float v[4] = {0.f, 0.f, 0.f, 0.f};
+    if (act) {
+        const float* tp = a.t + (long)n * 3 * hw + pix;
+        set_kt(cam, tp[0], tp[hw], tp[2 * hw]);
+        Proj pr;
+        project(cam, x, y, a.dA[n * hw + pix], W, H, pr);
+        Taps t4;
+        make_taps(pr.ix, pr.iy, W, H, t4);
+        const float Z = fmaxf(pr.q[2], 1e-5f);
+        const float sD = bilinear(a.dB + n * hw, W, t4, nullptr);
+        const bool ok = proj_valid(pr, W, H);
+        const float occ = (Z < sD && ok) ? 1.f : 0.f;
+        const float e = Z - sD;
+        float l1 = 0.f;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const long o = ((long)n * 3 + c) * hw;
+            const float s = bilinear(a.fB + o, W, t4, nullptr);
+            a.sampled[o + pix] = s;
+            l1 += fabsf(s - a.fA[o + pix]) * occ;
+        }
+        store_grid(pr, W, H, a.grid + (n * hw + pix) * 2);
+        a.occ[n * hw + pix] = occ;
+        a.err[n * hw + pix] = e;
+        a.valid[n * hw + pix] = ok ? 1 : 0;
+        v[0] = occ; v[1] = (e * e) * occ; v[2] = l1; v[3] = fabsf(sD - Z) * occ;
+    }
+    const int blk = (n * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
+    block_sums<4>(v, red, a.partial + 4 * (long)blk);
+}
+
+// ------------------------------------------------------------------------------------------------
+// WeightedSSIM (ssim_loss.py:L56-111).  mode 0: both factors, 1: C1 == inf (structure term only), 2: C2 == inf (luminance term only).
+// The weight comes from a map (stand-alone operator, backward) or is formed on the fly from pass 1's depth error (RGB-D pass 2):
+// w = m2 / (err^2 + m2) * valid with m2 = sum(err^2 occ) / (sum(occ) + 1) + 1e-4 of the sample.
+// ------------------------------------------------------------------------------------------------
+struct WssimArgs {
+    const float *x, *y;
+    const float* w;            // [N,1,H,W] or null
+    const float* err;          // w == null: pass 1's outputs
+    const uint8_t* valid;
+    const float* part1;        // [N * bps][4]
+    int N, C, H, W, mode;
+    float C1, C2;
+    float* map;                // [N,C,H,W] or null
+    float* avg_w;              // [N,1,H,W] or null
+    float* wout;               // [N,1,H,W] or null: the weight itself (depth_proximity_weight)
+    float* partial;            // [workgroups] or null: sum over channels and pixels of map * avg_w
+};
+
+struct Win {
+    int off[9];
+    float wp[9];     // w + 1e-2 at the reflected taps
+    float aw;        // avg_pool2d(w, 3, 1, padding=1): zeros outside, divided by 9
+    float wc;        // w at the centre
+};
+
+__device__ __forceinline__ float wssim_weight(const WssimArgs& a, long idx, float m2) {
+    if (a.w) return a.w[idx];
+    const float e = a.err[idx];
+    return (m2 / (e * e + m2)) * (a.valid[idx] ? 1.f : 0.f);
+}
+
+__device__ __forceinline__ void make_win(const WssimArgs& a, int n, int x, int y, float m2, Win& w) {
+    const long hw = (long)a.H * a.W;
+    float aw = 0.f;
+#pragma unroll
+    for (int dy = -1; dy <= 1; ++dy) {
+        const int ry = reflect_idx(y + dy, a.H);
+#pragma unroll
+        for (int dx = -1; dx <= 1; ++dx) {
+            const int rx = reflect_idx(x + dx, a.W), k = (dy + 1) * 3 + dx + 1;
+            w.off[k] = ry * a.W + rx;
+            const float wv = wssim_weight(a, n * hw + w.off[k], m2);
+            if (y + dy >= 0 && y + dy < a.H && x + dx >= 0 && x + dx < a.W) aw += wv;
+            if (k == 4) w.wc = wv;
+            w.wp[k] = wv + 1e-2f;
+        }
+    }
+    w.aw = aw / 9.0f;
+}
+
+struct Mom { float mx, my, n1, n2, d1, d2, n, d, inv; };
+
+__device__ __forceinline__ float wssim_value(const float* __restrict__ xs, const float* __restrict__ ys, const Win& w, int mode, float C1, float C2, Mom& m) {
+    float sx = 0.f, sy = 0.f, sxx = 0.f, syy = 0.f, sxy = 0.f;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) {
+        const float xv = xs[w.off[k]], yv = ys[w.off[k]], wp = w.wp[k];
+        sx += xv * wp; sy += yv * wp; sxx += (xv * xv) * wp; syy += (yv * yv) * wp; sxy += (xv * yv) * wp;
+    }
+    const float inv9 = 1.0f / 9.0f;
+    m.inv = 1.0f / (w.aw + 1e-2f);
+    m.mx = (sx * inv9) * m.inv; m.my = (sy * inv9) * m.inv;
+    const float vx = (sxx * inv9) * m.inv - m.mx * m.mx, vy = (syy * inv9) * m.inv - m.my * m.my, vxy = (sxy * inv9) * m.inv - m.mx * m.my;
+    m.n1 = mode == 1 ? 1.f : 2.0f * m.mx * m.my + C1;
+    m.d1 = mode == 1 ? 1.f : m.mx * m.mx + m.my * m.my + C1;
+    m.n2 = mode == 2 ? 1.f : 2.0f * vxy + C2;
+    m.d2 = mode == 2 ? 1.f : vx + vy + C2;
+    m.n = m.n1 * m.n2; m.d = m.d1 * m.d2;
+    return (1.0f - m.n / m.d) * 0.5f;
+}
+
+// normalizer - 1 and the depth error's second moment of sample n from pass 1's partials: every workgroup of the sample adds them in the same order
+__device__ __forceinline__ float sample_m2(const float* __restrict__ part1, int n, int bps, float* red) {
+    float so = 0.f, se = 0.f;
+    for (int i = threadIdx.x; i < bps; i += PB_N) { so += part1[((long)n * bps + i) * 4]; se += part1[((long)n * bps + i) * 4 + 1]; }
+    so = sde_block_sum(so, red);
+    __syncthreads();
+    se = sde_block_sum(se, red);
+    __shared__ float m2s;
+    if (threadIdx.x == 0) m2s = se / (so + 1.0f) + 1e-4f;
+    __syncthreads();
+    return m2s;
+}
+
+__global__ void __launch_bounds__(PB_N) wssim_fwd_kernel(const WssimArgs a) {
+    __shared__ float red[16];
+    const int n = blockIdx.z, H = a.H, W = a.W;
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    const bool act = x < W && y < H;
+    const long hw = (long)H * W, pix = act ? (long)y * W + x : 0;
+    const float m2 = a.w ? 0.f : sample_m2(a.part1, n, gridDim.x * gridDim.y, red);
+    float acc = 0.f;
+    if (act) {
+        Win w;
+        make_win(a, n, x, y, m2, w);
+        for (int c = 0; c < a.C; ++c) {
+            const long o = ((long)n * a.C + c) * hw;
+            Mom m;
+            const float l = fminf(fmaxf(wssim_value(a.x + o, a.y + o, w, a.mode, a.C1, a.C2, m), 0.f), 1.f);
+            if (a.map) a.map[o + pix] = l;
+            acc += l * w.aw;
+        }
+        if (a.avg_w) a.avg_w[n * hw + pix] = w.aw;
+        if (a.wout) a.wout[n * hw + pix] = w.wc;
+    }
+    if (a.partial) {
+        __syncthreads();
+        const float s = sde_block_sum(acc, red);
+        if (threadIdx.x == 0) a.partial[(n * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = s;
+    }
+}
+
+// Backward, step 1: per window and channel the four coefficients of d(loss)/d(weighted window sums): (sum x wp, sum y wp, sum x^2 wp = sum y^2 wp, sum xy wp),
+// the 1/9 of the pool folded in.  Upstream: gmap [N,C,H,W] (d loss / d map), or gvec[n] * gscale * avg_w (the RGB-D loss: mean of map * avg_w).
+__global__ void __launch_bounds__(PB_N) wssim_coef_kernel(const WssimArgs a, const float* __restrict__ gmap, const float* __restrict__ gvec, float gscale,
+                                                          float* __restrict__ coef) {
+    const int n = blockIdx.z, H = a.H, W = a.W;
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (x >= W || y >= H) return;
+    const long hw = (long)H * W, pix = (long)y * W + x;
+    Win w;
+    make_win(a, n, x, y, 0.f, w);
+    for (int c = 0; c < a.C; ++c) {
+        const long o = ((long)n * a.C + c) * hw;
+        Mom m;
+        const float l = wssim_value(a.x + o, a.y + o, w, a.mode, a.C1, a.C2, m);
+        float4 k = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (l >= 0.f && l <= 1.f) {                       // clamp passes the gradient on [0, 1] only
+            const float g = gmap ? gmap[o + pix] : gvec[n] * gscale * w.aw;
+            const float f = -0.5f * g * (1.0f / 9.0f);
+            const float rd = 1.0f / m.d;
+            const float an1 = a.mode == 1 ? 0.f : m.n2 * rd, an2 = a.mode == 2 ? 0.f : m.n1 * rd;
+            const float ad1 = a.mode == 1 ? 0.f : -m.n * m.d2 * rd * rd, ad2 = a.mode == 2 ? 0.f : -m.n * m.d1 * rd * rd;
+            // means enter n1 / d1 directly and the (co)variances through - mu^2, - mu_x mu_y
+            const float dmx = (an1 * 2.0f * m.my + ad1 * 2.0f * m.mx) - 2.0f * m.mx * ad2 - m.my * 2.0f * an2;
+            const float dmy = (an1 * 2.0f * m.mx + ad1 * 2.0f * m.my) - 2.0f * m.my * ad2 - m.mx * 2.0f * an2;
+            k = make_float4(f * dmx * m.inv, f * dmy * m.inv, f * ad2 * m.inv, f * 2.0f * an2 * m.inv);
+        }
+        reinterpret_cast<float4*>(coef)[o + pix] = k;
+    }
+}
+
+// sum over the (up to nine) windows that contain pixel (px, py) of the window coefficients applied to it, with the multiplicity reflection gives border taps
+__device__ __forceinline__ void wssim_gather(const float* __restrict__ coef, long plane, int H, int W, int px, int py, float xv, float yv, float& gx, float& gy) {
+    gx = 0.f; gy = 0.f;
+#pragma unroll
+    for (int ey = -1; ey <= 1; ++ey) {
+        const int wy = py + ey;
+        if (wy < 0 || wy >= H) continue;
+        const float my_ = ((py == 1 && ey == -1) || (py == H - 2 && ey == 1)) ? 2.f : 1.f;
+#pragma unroll
+        for (int ex = -1; ex <= 1; ++ex) {
+            const int wx = px + ex;
+            if (wx < 0 || wx >= W) continue;
+            const float mx_ = ((px == 1 && ex == -1) || (px == W - 2 && ex == 1)) ? 2.f : 1.f;
+            const float4 c = reinterpret_cast<const float4*>(coef)[plane + (long)wy * W + wx];
+            const float m = my_ * mx_;
+            gx += m * (c.x + 2.0f * xv * c.z + yv * c.w);
+            gy += m * (c.y + 2.0f * yv * c.z + xv * c.w);
+        }
+    }
+}
+
+__global__ void __launch_bounds__(PB_N) wssim_gather_kernel(const float* __restrict__ xs, const float* __restrict__ ys, const float* __restrict__ w,
+                                                            const float* __restrict__ coef, int C, int H, int W, float* __restrict__ dx, float* __restrict__ dy) {
+    const int n = blockIdx.z;
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (x >= W || y >= H) return;
+    const long hw = (long)H * W, pix = (long)y * W + x;
+    const float wp = w[n * hw + pix] + 1e-2f;
+    for (int c = 0; c < C; ++c) {
+        const long o = ((long)n * C + c) * hw;
+        float gx, gy;
+        wssim_gather(coef, o, H, W, x, y, xs[o + pix], ys[o + pix], gx, gy);
+        if (dx) dx[o + pix] = wp * gx;
+        if (dy) dy[o + pix] = wp * gy;
+    }
+}
+
+// per-sample results of the RGB-D forward: stats [4][N] = sum |sampled - frame_A| occ, sum map * avg_w, sum |err| occ / normalizer, normalizer
+__global__ void __launch_bounds__(PB_N) rgbd_finalize_kernel(const float* __restrict__ part1, const float* __restrict__ part2, int bps, int N, float* __restrict__ stats) {
+    __shared__ float red[20];
+    const int n = blockIdx.x;
+    float v[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+    for (int i = threadIdx.x; i < bps; i += PB_N) {
+        const float* p = part1 + ((long)n * bps + i) * 4;
+        v[0] += p[0]; v[1] += p[1]; v[2] += p[2]; v[3] += p[3];
+        if (part2) v[4] += part2[(long)n * bps + i];
+    }
+    __shared__ float tot[5];
+    block_sums<5>(v, red, tot);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const float nrm = tot[0] + 1.0f;
+        stats[n] = tot[2];
+        stats[N + n] = tot[4];
+        stats[2 * N + n] = tot[3] / nrm;
+        stats[3 * N + n] = nrm;
+    }
+}
+
+// RGB-D backward, step 2: SSIM gather + L1 terms -> d sampled -> bilinear sample -> projection: d depth_A, d t per pixel, d R per workgroup
+struct RgbdBwdArgs {
+    const float *fA, *fB, *dA, *K, *R, *t;
+    const float *sampled, *occ, *err, *dpw, *coef /* null: no SSIM term */, *stats;
+    const float *g_l1, *g_dl1;                   // [N] upstream gradients of stats rows 0 and 2 (null: zero)
+    int N, H, W;
+    float *d_depth, *d_t, *dR_partial;           // [N,1,H,W], [N,3,H,W], [workgroups][9]
+};
+
+__global__ void __launch_bounds__(PB_N) rgbd_bwd_kernel(const RgbdBwdArgs a) {
+    __shared__ float red[36];
+    const int n = blockIdx.z, H = a.H, W = a.W;
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    const bool act = x < W && y < H;
+    const long hw = (long)H * W, pix = act ? (long)y * W + x : 0;
+    Cam cam;
+    make_cam_rt(a.K + 9 * n, a.R + 9 * n, cam);
+    const float gl1 = a.g_l1 ? sde_uniform(a.g_l1[n]) : 0.f;
+    const float gdl = a.g_dl1 ? sde_uniform(a.g_dl1[n]) / sde_uniform(a.stats[3 * a.N + n]) : 0.f;
+    float acc9[9];
+#pragma unroll
+    for (int i = 0; i < 9; ++i) acc9[i] = 0.f;
+    if (act) {
+        const float occ = a.occ[n * hw + pix];
+        const float wp = a.coef ? a.dpw[n * hw + pix] + 1e-2f : 0.f;
+        float ds[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const long o = ((long)n * 3 + c) * hw;
+            const float xv = a.sampled[o + pix], yv = a.fA[o + pix];
+            float gx = 0.f, gy = 0.f;
+            if (a.coef) wssim_gather(a.coef, o, H, W, x, y, xv, yv, gx, gy);
+            const float df = xv - yv;
+            const float sg = df > 0.f ? 1.f : (df < 0.f ? -1.f : 0.f);
+            ds[c] = wp * gx + gl1 * occ * sg;
+        }
+        const float* tp = a.t + (long)n * 3 * hw + pix;
+        set_kt(cam, tp[0], tp[hw], tp[2 * hw]);
+        Proj pr;
+        project(cam, x, y, a.dA[n * hw + pix], W, H, pr);
+        Taps t4;
+        make_taps(pr.ix, pr.iy, W, H, t4);
+        float dix = 0.f, diy = 0.f;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            float v4[4];
+            bilinear(a.fB + ((long)n * 3 + c) * hw, W, t4, v4);
+            dix += ds[c] * ((v4[1] - v4[0]) * t4.sy + (v4[3] - v4[2]) * t4.ny);
+            diy += ds[c] * ((v4[2] - v4[0]) * t4.ex + (v4[3] - v4[1]) * t4.wx);
+        }
+        const float dX = pr.passx ? dix : 0.f, dY = pr.passy ? diy : 0.f;
+        // depth L1: |sampled_depth_B.detach() - Z| occ / normalizer; Z = clamp(q2, min=1e-5) passes the gradient where q2 >= 1e-5
+        const float e = a.err[n * hw + pix];
+        const float dZ = (occ != 0.f && pr.q[2] >= 1e-5f) ? gdl * (e > 0.f ? 1.f : (e < 0.f ? -1.f : 0.f)) : 0.f;
+        const float rden = 1.0f / (pr.q[2] + kEps);
+        float dq[3];
+        dq[0] = dX * rden; dq[1] = dY * rden;
+        dq[2] = -(dX * pr.X + dY * pr.Y) * rden + dZ;
+        const float fxp = (float)x, fyp = (float)y;
+        float dd = 0.f;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const float dp = dq[0] * cam.kr[k] + dq[1] * cam.kr[3 + k] + dq[2] * cam.kr[6 + k];
+            dd += dp * (cam.ki[3 * k] * fxp + cam.ki[3 * k + 1] * fyp + cam.ki[3 * k + 2]);
+        }
+        a.d_depth[n * hw + pix] = dd;
+        // q = (K R) p + K t  ->  d t_m = sum_i K_im dq_i ; d R_mk = (sum_i K_im dq_i) p_k
+#pragma unroll
+        for (int m = 0; m < 3; ++m) {
+            const float kq = cam.k[m] * dq[0] + cam.k[3 + m] * dq[1] + cam.k[6 + m] * dq[2];
+            a.d_t[((long)n * 3 + m) * hw + pix] = kq;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) acc9[3 * m + k] = kq * pr.p[k];
+        }
+    }
+    const int blk = (n * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
+    block_sums<9>(acc9, red, a.dR_partial + 9 * (long)blk);
+}
+
+// d R [N,3,3] (+ optional second destination) from the per-workgroup partials: one wave per sample, lanes split the partials, fixed butterfly
+__global__ void __launch_bounds__(64) sum9_finalize_kernel(const float* __restrict__ partial, int bps, float* __restrict__ dR) {
+    const int n = blockIdx.x, lane = threadIdx.x;
+    float acc[9];
+#pragma unroll
+    for (int i = 0; i < 9; ++i) acc[i] = 0.f;
+    for (int k = lane; k < bps; k += 64) {
+        const float* p = partial + ((long)n * bps + k) * 9;
+#pragma unroll
+        for (int i = 0; i < 9; ++i) acc[i] += p[i];
+    }
+#pragma unroll
+    for (int i = 0; i < 9; ++i) acc[i] = sde_wave_sum(acc[i]);
+    if (lane < 9) {
+        float s = 0.f;
+#pragma unroll
+        for (int i = 0; i < 9; ++i) s = lane == i ? acc[i] : s;
+        dR[n * 9 + lane] = s;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// motion_consistency_loss (motion_loss.py:L7-48)
+// ------------------------------------------------------------------------------------------------
+struct McPix { float s[3], e[3], tA[3], E, den; Taps t4; };
+
+__device__ __forceinline__ void mc_pixel(const float* __restrict__ grid, const float* __restrict__ R, const float* __restrict__ tA, const float* __restrict__ tB,
+                                         int n, long pix, int H, int W, McPix& o) {
+    const long hw = (long)H * W;
+    const float gx = grid[(n * hw + pix) * 2], gy = grid[(n * hw + pix) * 2 + 1];
+    const float ix = (gx + 1.0f) * ((float)(W - 1) / 2.0f), iy = (gy + 1.0f) * ((float)(H - 1) / 2.0f);      // grid_sample, align_corners=True
+    make_taps(ix, iy, W, H, o.t4);
+    float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        o.s[c] = bilinear(tB + ((long)n * 3 + c) * hw, W, o.t4, nullptr);
+        o.tA[c] = tA[((long)n * 3 + c) * hw + pix];
+        s1 += o.tA[c] * o.tA[c]; s2 += o.s[c] * o.s[c];
+    }
+    o.E = 0.f;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        o.e[i] = (R[3 * i] * o.s[0] + R[3 * i + 1] * o.s[1] + R[3 * i + 2] * o.s[2]) + o.tA[i];
+        o.E += o.e[i] * o.e[i];
+    }
+    o.den = s1 + s2 + 1e-24f;
+}
+
+__global__ void __launch_bounds__(PB_N) mc_fwd_kernel(const float* __restrict__ grid, const float* __restrict__ mask, const float* __restrict__ R1,
+                                                      const float* __restrict__ tA, const float* __restrict__ tB, int H, int W, float* __restrict__ partial) {
+    __shared__ float red[16];
+    const int n = blockIdx.z;
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    float v = 0.f;
+    if (x < W && y < H) {
+        const long pix = (long)y * W + x;
+        float R[9];
+#pragma unroll
+        for (int i = 0; i < 9; ++i) R[i] = sde_uniform(R1[n * 9 + i]);
+        McPix p;
+        mc_pixel(grid, R, tA, tB, n, pix, H, W, p);
+        v = mask[(long)n * H * W + pix] * (p.E / p.den);
+    }
+    const float s = sde_block_sum(v, red);
+    if (threadIdx.x == 0) partial[(n * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = s;
+}
+
+// rotation part of one sample: r = mean((R1 R2 - I)^2) / (mean((R1 - I)^2) + mean((R2 - I)^2) + 1e-24); optionally its gradient * g
+__device__ __forceinline__ float mc_rot(const float* __restrict__ R1, const float* __restrict__ R2, float g, float* dR1, float* dR2) {
+    float M[9], A[9], B[9], re = 0.f, a = 0.f, b = 0.f;
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            const float id = i == j ? 1.f : 0.f;
+            M[3 * i + j] = ((R1[3 * i] * R2[j] + R1[3 * i + 1] * R2[3 + j]) + R1[3 * i + 2] * R2[6 + j]) - id;
+            A[3 * i + j] = R1[3 * i + j] - id; B[3 * i + j] = R2[3 * i + j] - id;
+            re += M[3 * i + j] * M[3 * i + j]; a += A[3 * i + j] * A[3 * i + j]; b += B[3 * i + j] * B[3 * i + j];
+        }
+    re = re / 9.0f; a = a / 9.0f; b = b / 9.0f;
+    const float den = a + b + 1e-24f;
+    if (dR1) {
+        const float gm = g / den * (2.0f / 9.0f), gs = -g * re / (den * den) * (2.0f / 9.0f);
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                // d R1 = dM R2^T, d R2 = R1^T dM
+                dR1[3 * i + j] = gm * (M[3 * i] * R2[3 * j] + M[3 * i + 1] * R2[3 * j + 1] + M[3 * i + 2] * R2[3 * j + 2]) + gs * A[3 * i + j];
+                dR2[3 * i + j] = gm * (R1[i] * M[j] + R1[3 + i] * M[3 + j] + R1[6 + i] * M[6 + j]) + gs * B[3 * i + j];
+            }
+    }
+    return re / den;
+}
+
+// out[0] = rot_error, out[1] = trans_error (one workgroup)
+__global__ void __launch_bounds__(PB_N) mc_finalize_kernel(const float* __restrict__ partial, int nblk, const float* __restrict__ R1, const float* __restrict__ R2,
+                                                           int N, float inv_pixels, float* __restrict__ out) {
+    __shared__ float red[16];
+    float s = 0.f, r = 0.f;
+    for (int i = threadIdx.x; i < nblk; i += PB_N) s += partial[i];
+    for (int n = threadIdx.x; n < N; n += PB_N) r += mc_rot(R1 + 9 * n, R2 + 9 * n, 0.f, nullptr, nullptr);
+    s = sde_block_sum(s, red);
+    __syncthreads();
+    r = sde_block_sum(r, red);
+    if (threadIdx.x == 0) { out[0] = r / (float)N; out[1] = s * inv_pixels; }
+}
+
+__global__ void __launch_bounds__(PB_N) mc_bwd_kernel(const float* __restrict__ grid, const float* __restrict__ mask, const float* __restrict__ R1,
+                                                      const float* __restrict__ tA, const float* __restrict__ tB, const float* __restrict__ g_trans, float inv_pixels,
+                                                      int H, int W, float* __restrict__ d_tA, float* __restrict__ d_tB, float* __restrict__ dR_partial) {
+    __shared__ float red[36];
+    const int n = blockIdx.z;
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    const long hw = (long)H * W;
+    float acc9[9];
+#pragma unroll
+    for (int i = 0; i < 9; ++i) acc9[i] = 0.f;
+    if (x < W && y < H) {
+        const long pix = (long)y * W + x;
+        float R[9];
+#pragma unroll
+        for (int i = 0; i < 9; ++i) R[i] = sde_uniform(R1[n * 9 + i]);
+        McPix p;
+        mc_pixel(grid, R, tA, tB, n, pix, H, W, p);
+        const float g = (g_trans ? g_trans[0] : 0.f) * inv_pixels * mask[n * hw + pix];
+        const float dden = -g * p.E / (p.den * p.den);
+        float de[3], ds[3];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            de[i] = g * 2.0f * p.e[i] / p.den;
+            d_tA[((long)n * 3 + i) * hw + pix] = de[i] + dden * 2.0f * p.tA[i];
+        }
+        const Taps& t = p.t4;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            ds[j] = (R[j] * de[0] + R[3 + j] * de[1] + R[6 + j] * de[2]) + dden * 2.0f * p.s[j];
+#pragma unroll
+            for (int i = 0; i < 3; ++i) acc9[3 * i + j] = de[i] * p.s[j];
+            // grid_sample's own backward: scatter through the four taps (zeros padding: taps outside receive nothing); fp32 vector atomics
+            float* pl = d_tB + ((long)n * 3 + j) * hw;
+            if (t.okx0 && t.oky0) unsafeAtomicAdd(pl + (long)t.y0 * W + t.x0, ds[j] * (t.sy * t.ex));
+            if (t.okx1 && t.oky0) unsafeAtomicAdd(pl + (long)t.y0 * W + t.x0 + 1, ds[j] * (t.sy * t.wx));
+            if (t.okx0 && t.oky1) unsafeAtomicAdd(pl + (long)(t.y0 + 1) * W + t.x0, ds[j] * (t.ny * t.ex));
+            if (t.okx1 && t.oky1) unsafeAtomicAdd(pl + (long)(t.y0 + 1) * W + t.x0 + 1, ds[j] * (t.ny * t.wx));
+        }
+    }
+    const int blk = (n * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
+    block_sums<9>(acc9, red, dR_partial + 9 * (long)blk);
+}
+
+// d R_A2B = sum of the translation term's partials + rotation term, d R_B2A = rotation term: one wave per sample
+__global__ void __launch_bounds__(64) mc_bwd_finalize_kernel(const float* __restrict__ partial, int bps, const float* __restrict__ R1, const float* __restrict__ R2,
+                                                             const float* __restrict__ g_rot, int N, float* __restrict__ dR1, float* __restrict__ dR2) {
+    const int n = blockIdx.x, lane = threadIdx.x;
+    float acc[9];
+#pragma unroll
+    for (int i = 0; i < 9; ++i) acc[i] = 0.f;
+    for (int k = lane; k < bps; k += 64) {
+        const float* p = partial + ((long)n * bps + k) * 9;
+#pragma unroll
+        for (int i = 0; i < 9; ++i) acc[i] += p[i];
+    }
+#pragma unroll
+    for (int i = 0; i < 9; ++i) acc[i] = sde_wave_sum(acc[i]);
+    if (lane == 0) {
+        float a[9], b[9];
+        mc_rot(R1 + 9 * n, R2 + 9 * n, (g_rot ? g_rot[0] : 0.f) / (float)N, a, b);
+#pragma unroll
+        for (int i = 0; i < 9; ++i) { dR1[n * 9 + i] = acc[i] + a[i]; dR2[n * 9 + i] = b[i]; }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// motion_smoothness_loss_fn / motion_sparsity_loss_fn (motion_loss.py:L51-64).  One launch forward: per-workgroup partials, and the workgroup that
+// arrives last (device-scope ticket, left at zero again) adds them up in index order.
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ void ticket_finalize(float s, float* __restrict__ partial, int nblk, int blk, float scale, float* __restrict__ out, int* __restrict__ ticket) {
+    __shared__ int last;
+    if (threadIdx.x == 0) {
+        __hip_atomic_store(partial + blk, s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __threadfence();
+        last = (__hip_atomic_fetch_add(ticket, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == nblk - 1);
+    }
+    __syncthreads();
+    if (last && threadIdx.x == 0) {
+        __threadfence();
+        float t = 0.f;
+        for (int i = 0; i < nblk; ++i) t += __hip_atomic_load(partial + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        out[0] = t * scale;
+        __hip_atomic_store(ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+// element (i, j), i < H-1, j < W-1:  gx = f[i+1][j+1] - f[i+1][j],  gy = f[i+1][j+1] - f[i][j+1]  (the reversed gradients, cropped by one row / column)
+__global__ void __launch_bounds__(PB_N) msmooth_fwd_kernel(const float* __restrict__ f, int planes, int H, int W, float scale, float* __restrict__ partial,
+                                                           float* __restrict__ out, int* __restrict__ ticket) {
+    __shared__ float red[16];
+    const int j = blockIdx.x * 64 + (threadIdx.x & 63), i = blockIdx.y * 4 + (threadIdx.x >> 6);
+    float v = 0.f;
+    if (i < H - 1 && j < W - 1)
+        for (int p = blockIdx.z; p < planes; p += gridDim.z) {
+            const float* s = f + (long)p * H * W;
+            const float c = s[(long)(i + 1) * W + j + 1], gx = c - s[(long)(i + 1) * W + j], gy = c - s[(long)i * W + j + 1];
+            v += sqrtf(1e-24f + gx * gx + gy * gy);
+        }
+    const float s = sde_block_sum(v, red);
+    const int nblk = gridDim.x * gridDim.y * gridDim.z, blk = (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
+    ticket_finalize(s, partial, nblk, blk, scale, out, ticket);
+}
+
+__global__ void __launch_bounds__(PB_N) msmooth_bwd_kernel(const float* __restrict__ f, const float* __restrict__ gout, int planes, int H, int W, float scale,
+                                                           float* __restrict__ df) {
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (x >= W || y >= H) return;
+    const float g = gout[0] * scale;
+    for (int p = blockIdx.z; p < planes; p += gridDim.z) {
+        const float* s = f + (long)p * H * W;
+        auto elem = [&](int i, int j, float& gx, float& gy, float& r) {
+            const float c = s[(long)(i + 1) * W + j + 1];
+            gx = c - s[(long)(i + 1) * W + j]; gy = c - s[(long)i * W + j + 1];
+            r = 1.0f / sqrtf(1e-24f + gx * gx + gy * gy);
+        };
+        float d = 0.f, gx, gy, r;
+        if (y >= 1 && x >= 1) { elem(y - 1, x - 1, gx, gy, r); d += (gx + gy) * r; }      // this pixel is the element's corner f[i+1][j+1]
+        if (y >= 1 && x <= W - 2) { elem(y - 1, x, gx, gy, r); d -= gx * r; }              // ... its f[i+1][j]
+        if (y <= H - 2 && x >= 1) { elem(y, x - 1, gx, gy, r); d -= gy * r; }              // ... its f[i][j+1]
+        df[(long)p * H * W + (long)y * W + x] = g * d;
+    }
+}
+
+// one workgroup per plane: mean |f| (kept for the backward), then sum 2 m sqrt(|f| / (m + 1e-24) + 1)
+__global__ void __launch_bounds__(1024) msparse_fwd_kernel(const float* __restrict__ f, int planes, long hw, float scale, float* __restrict__ mean, float* __restrict__ partial,
+                                                           float* __restrict__ out, int* __restrict__ ticket) {
+    __shared__ float red[16];
+    __shared__ float ms;
+    const int p = blockIdx.x;
+    const float* s = f + (long)p * hw;
+    float v = 0.f;
+    for (long i = threadIdx.x; i < hw; i += 1024) v += fabsf(s[i]);
+    v = sde_block_sum(v, red);
+    if (threadIdx.x == 0) { ms = v / (float)hw; mean[p] = ms; }
+    __syncthreads();
+    const float m = ms, rm = 1.0f / (m + 1e-24f);
+    v = 0.f;
+    for (long i = threadIdx.x; i < hw; i += 1024) v += (2.0f * m) * sqrtf(fabsf(s[i]) * rm + 1.0f);
+    __syncthreads();
+    v = sde_block_sum(v, red);
+    ticket_finalize(v, partial, planes, p, scale, out, ticket);
+}
+
+__global__ void __launch_bounds__(PB_N) msparse_bwd_kernel(const float* __restrict__ f, const float* __restrict__ mean, const float* __restrict__ gout, long hw, float scale,
+                                                           float* __restrict__ df) {
+    const int p = blockIdx.y;
+    const long i = (long)blockIdx.x * PB_N + threadIdx.x;
+    if (i >= hw) return;
+    const float m = mean[p], rm = 1.0f / (m + 1e-24f), v = f[(long)p * hw + i];
+    const float sg = v > 0.f ? 1.f : (v < 0.f ? -1.f : 0.f);
+    df[(long)p * hw + i] = gout[0] * scale * m * rm * sg / sqrtf(fabsf(v) * rm + 1.0f);
+}
+
+// ------------------------------------------------------------------------------------------------
+// resize_img_avgpool = F.adaptive_avg_pool2d (camera.py:L49-54): window [floor(i H / h), ceil((i + 1) H / h))
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ int ap_lo(int i, int H, int h) { return (int)(((long)i * H) / h); }
+__device__ __forceinline__ int ap_hi(int i, int H, int h) { return (int)(((long)(i + 1) * H + h - 1) / h); }
+
+__global__ void __launch_bounds__(PB_N) avgpool_fwd_kernel(const float* __restrict__ src, float* __restrict__ dst, int planes, int H, int W, int h, int w) {
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (x >= w || y >= h) return;
+    const int y0 = ap_lo(y, H, h), y1 = ap_hi(y, H, h), x0 = ap_lo(x, W, w), x1 = ap_hi(x, W, w);
+    const float inv = 1.0f / (float)((y1 - y0) * (x1 - x0));
+    for (int p = blockIdx.z; p < planes; p += gridDim.z) {
+        const float* s = src + (long)p * H * W;
+        float acc = 0.f;
+        for (int yy = y0; yy < y1; ++yy)
+            for (int xx = x0; xx < x1; ++xx) acc += s[(long)yy * W + xx];
+        dst[((long)p * h + y) * w + x] = acc * inv;
+    }
+}
+
+// the output rows whose window contains input row y are contiguous and include floor(y h / H)
+__device__ __forceinline__ void ap_range(int y, int H, int h, int& lo, int& hi) {
+    lo = hi = (int)(((long)y * h) / H);
+    while (lo > 0 && ap_hi(lo - 1, H, h) > y) --lo;
+    while (hi + 1 < h && ap_lo(hi + 1, H, h) <= y) ++hi;
+}
+
+__global__ void __launch_bounds__(PB_N) avgpool_bwd_kernel(const float* __restrict__ dout, float* __restrict__ din, int planes, int H, int W, int h, int w) {
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (x >= W || y >= H) return;
+    int i0, i1, j0, j1;
+    ap_range(y, H, h, i0, i1);
+    ap_range(x, W, w, j0, j1);
+    for (int p = blockIdx.z; p < planes; p += gridDim.z) {
+        const float* s = dout + (long)p * h * w;
+        float acc = 0.f;
+        for (int i = i0; i <= i1; ++i) {
+            const float ry = 1.0f / (float)(ap_hi(i, H, h) - ap_lo(i, H, h));
+            for (int j = j0; j <= j1; ++j) acc += s[(long)i * w + j] * (ry / (float)(ap_hi(j, W, w) - ap_lo(j, W, w)));
+        }
+        din[((long)p * H + y) * W + x] = acc;
+    }
+}
+
+inline dim3 pix_grid(int W, int H, int z) { return dim3(sde_cdiv(W, 64), sde_cdiv(H, 4), z); }
+inline int ssim_mode(float C1, float C2) { return C1 > kFltMax ? 1 : (C2 > kFltMax ? 2 : 0); }
+constexpr int kMaxZ = 65535;
+
+}  // namespace
+
+extern "C" {
+
+int sde_view_synthesis_pp(const float* img, const float* depth, const float* K, const float* R, const float* t, int B, int C, int H, int W, float* sampled,
+                          float* Z, float* grid, uint8_t* valid, sde_stream_t stream) {
+    SDE_CHECK_ARG(img && depth && K && R && t && sampled, "sde_view_synthesis_pp: null pointer");
+    SDE_CHECK_ARG(B > 0 && B <= kMaxZ && C > 0 && H > 1 && W > 1, "sde_view_synthesis_pp: bad shape B=%d C=%d H=%d W=%d", B, C, H, W);
+    hipLaunchKernelGGL(view_synthesis_pp_kernel, pix_grid(W, H, B), dim3(PB_N), 0, (hipStream_t)stream, img, depth, K, R, t, C, H, W, sampled, Z, grid, valid);
+    SDE_CHECK_LAUNCH("sde_view_synthesis_pp");
+    return SDE_OK;
+}
+
+int sde_rgbd_num_blocks(int N, int H, int W) { return N * sde_cdiv(W, 64) * sde_cdiv(H, 4); }
+
+int sde_rgbd_fwd(const sde_rgbd_desc* d, float* sampled, float* grid, float* occ, float* err, uint8_t* valid, float* dpw, float* part1, float* part2,
+                 float* stats, sde_stream_t stream) {
+    SDE_CHECK_ARG(d && d->frame_A && d->frame_B && d->depth_A && d->depth_B && d->K && d->R && d->t, "sde_rgbd_fwd: null input");
+    SDE_CHECK_ARG(sampled && grid && occ && err && valid && part1 && stats, "sde_rgbd_fwd: null output");
+    SDE_CHECK_ARG(d->N > 0 && d->N <= kMaxZ && d->H > 1 && d->W > 1, "sde_rgbd_fwd: bad shape N=%d H=%d W=%d", d->N, d->H, d->W);
+    SDE_CHECK_ARG(!d->ssim || (dpw && part2), "sde_rgbd_fwd: SSIM term without its buffers");
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 g = pix_grid(d->W, d->H, d->N);
+    RgbdArgs a{d->frame_A, d->frame_B, d->depth_A, d->depth_B, d->K, d->R, d->t, d->N, d->H, d->W, sampled, grid, occ, err, valid, part1};
+    hipLaunchKernelGGL(rgbd_warp_kernel, g, dim3(PB_N), 0, st, a);
+    SDE_CHECK_LAUNCH("sde_rgbd_fwd/warp");
+    if (d->ssim) {
+        WssimArgs w{sampled, d->frame_A, nullptr, err, valid, part1, d->N, 3, d->H, d->W, ssim_mode(d->C1, d->C2), d->C1, d->C2, nullptr, nullptr, dpw, part2};
+        hipLaunchKernelGGL(wssim_fwd_kernel, g, dim3(PB_N), 0, st, w);
+        SDE_CHECK_LAUNCH("sde_rgbd_fwd/ssim");
+    }
+    hipLaunchKernelGGL(rgbd_finalize_kernel, dim3(d->N), dim3(PB_N), 0, st, (const float*)part1, (const float*)(d->ssim ? part2 : nullptr), (int)(g.x * g.y), d->N, stats);
+    SDE_CHECK_LAUNCH("sde_rgbd_fwd/finalize");
+    return SDE_OK;
+}
+
+int sde_rgbd_bwd(const sde_rgbd_desc* d, const float* sampled, const float* occ, const float* err, const float* dpw, const float* stats, const float* g_l1,
+                 const float* g_ssim, const float* g_dl1, float gscale_ssim, float* coef, float* d_depth, float* d_t, float* dR_partial, float* dR,
+                 sde_stream_t stream) {
+    SDE_CHECK_ARG(d && d->frame_A && d->frame_B && d->depth_A && d->K && d->R && d->t, "sde_rgbd_bwd: null input");
+    SDE_CHECK_ARG(sampled && occ && err && stats && d_depth && d_t && dR_partial && dR, "sde_rgbd_bwd: null pointer");
+    SDE_CHECK_ARG(d->N > 0 && d->N <= kMaxZ && d->H > 1 && d->W > 1, "sde_rgbd_bwd: bad shape N=%d H=%d W=%d", d->N, d->H, d->W);
+    const bool ssim = d->ssim && g_ssim;
+    SDE_CHECK_ARG(!ssim || (dpw && coef), "sde_rgbd_bwd: SSIM term without its buffers");
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 g = pix_grid(d->W, d->H, d->N);
+    if (ssim) {
+        WssimArgs w{sampled, d->frame_A, dpw, nullptr, nullptr, nullptr, d->N, 3, d->H, d->W, ssim_mode(d->C1, d->C2), d->C1, d->C2, nullptr, nullptr, nullptr, nullptr};
+        hipLaunchKernelGGL(wssim_coef_kernel, g, dim3(PB_N), 0, st, w, (const float*)nullptr, g_ssim, gscale_ssim, coef);
+        SDE_CHECK_LAUNCH("sde_rgbd_bwd/coef");
+    }
+    RgbdBwdArgs a{d->frame_A, d->frame_B, d->depth_A, d->K, d->R, d->t, sampled, occ, err, dpw, ssim ? coef : nullptr, stats, g_l1, g_dl1,
+                  d->N, d->H, d->W, d_depth, d_t, dR_partial};
+    hipLaunchKernelGGL(rgbd_bwd_kernel, g, dim3(PB_N), 0, st, a);
+    SDE_CHECK_LAUNCH("sde_rgbd_bwd/pixels");
+    hipLaunchKernelGGL(sum9_finalize_kernel, dim3(d->N), dim3(64), 0, st, (const float*)dR_partial, (int)(g.x * g.y), dR);
+    SDE_CHECK_LAUNCH("sde_rgbd_bwd/finalize");
+    return SDE_OK;
+}
+
+int sde_wssim_fwd(const float* x, const float* y, const float* w, int N, int C, int H, int W, float C1, float C2, float* map, float* avg_w, sde_stream_t stream) {
+    SDE_CHECK_ARG(x && y && w && map && avg_w, "sde_wssim_fwd: null pointer");
+    SDE_CHECK_ARG(N > 0 && N <= kMaxZ && C > 0 && H > 1 && W > 1, "sde_wssim_fwd: bad shape N=%d C=%d H=%d W=%d", N, C, H, W);
+    WssimArgs a{x, y, w, nullptr, nullptr, nullptr, N, C, H, W, ssim_mode(C1, C2), C1, C2, map, avg_w, nullptr, nullptr};
+    hipLaunchKernelGGL(wssim_fwd_kernel, pix_grid(W, H, N), dim3(PB_N), 0, (hipStream_t)stream, a);
+    SDE_CHECK_LAUNCH("sde_wssim_fwd");
+    return SDE_OK;
+}
+
+int sde_wssim_bwd(const float* x, const float* y, const float* w, const float* gout, int N, int C, int H, int W, float C1, float C2, float* coef, float* dx,
+                  float* dy, sde_stream_t stream) {
+    SDE_CHECK_ARG(x && y && w && gout && coef && (dx || dy), "sde_wssim_bwd: null pointer");
+    SDE_CHECK_ARG(N > 0 && N <= kMaxZ && C > 0 && H > 1 && W > 1, "sde_wssim_bwd: bad shape N=%d C=%d H=%d W=%d", N, C, H, W);
+    SDE_CHECK_ARG((reinterpret_cast<uintptr_t>(coef) & 15) == 0, "sde_wssim_bwd: coef must be 16-byte aligned");
+    WssimArgs a{x, y, w, nullptr, nullptr, nullptr, N, C, H, W, ssim_mode(C1, C2), C1, C2, nullptr, nullptr, nullptr, nullptr};
+    hipLaunchKernelGGL(wssim_coef_kernel, pix_grid(W, H, N), dim3(PB_N), 0, (hipStream_t)stream, a, gout, (const float*)nullptr, 0.f, coef);
+    SDE_CHECK_LAUNCH("sde_wssim_bwd/coef");
+    hipLaunchKernelGGL(wssim_gather_kernel, pix_grid(W, H, N), dim3(PB_N), 0, (hipStream_t)stream, x, y, w, (const float*)coef, C, H, W, dx, dy);
+    SDE_CHECK_LAUNCH("sde_wssim_bwd/gather");
+    return SDE_OK;
+}
+
+int sde_motion_consistency_fwd(const float* grid, const float* mask, const float* R_A2B, const float* R_B2A, const float* t_A2B, const float* t_B2A, int N, int H,
+                               int W, float* partial, float* out, sde_stream_t stream) {
+    SDE_CHECK_ARG(grid && mask && R_A2B && R_B2A && t_A2B && t_B2A && partial && out, "sde_motion_consistency_fwd: null pointer");
+    SDE_CHECK_ARG(N > 0 && N <= kMaxZ && H > 1 && W > 1, "sde_motion_consistency_fwd: bad shape N=%d H=%d W=%d", N, H, W);
+    const dim3 g = pix_grid(W, H, N);
+    hipLaunchKernelGGL(mc_fwd_kernel, g, dim3(PB_N), 0, (hipStream_t)stream, grid, mask, R_A2B, t_A2B, t_B2A, H, W, partial);
+    SDE_CHECK_LAUNCH("sde_motion_consistency_fwd/pixels");
+    hipLaunchKernelGGL(mc_finalize_kernel, dim3(1), dim3(PB_N), 0, (hipStream_t)stream, (const float*)partial, (int)(g.x * g.y * g.z), R_A2B, R_B2A, N,
+                       1.0f / ((float)N * (float)H * (float)W), out);
+    SDE_CHECK_LAUNCH("sde_motion_consistency_fwd/finalize");
+    return SDE_OK;
+}
+
+int sde_motion_consistency_bwd(const float* grid, const float* mask, const float* R_A2B, const float* R_B2A, const float* t_A2B, const float* t_B2A,
+                               const float* g_rot, const float* g_trans, int N, int H, int W, float* d_tA, float* d_tB_zeroed, float* dR_partial, float* dR_A2B,
+                               float* dR_B2A, sde_stream_t stream) {
+    SDE_CHECK_ARG(grid && mask && R_A2B && R_B2A && t_A2B && t_B2A && d_tA && d_tB_zeroed && dR_partial && dR_A2B && dR_B2A, "sde_motion_consistency_bwd: null pointer");
+    SDE_CHECK_ARG(N > 0 && N <= kMaxZ && H > 1 && W > 1, "sde_motion_consistency_bwd: bad shape N=%d H=%d W=%d", N, H, W);
+    const dim3 g = pix_grid(W, H, N);
+    hipLaunchKernelGGL(mc_bwd_kernel, g, dim3(PB_N), 0, (hipStream_t)stream, grid, mask, R_A2B, t_A2B, t_B2A, g_trans, 1.0f / ((float)N * (float)H * (float)W), H, W,
+                       d_tA, d_tB_zeroed, dR_partial);
+    SDE_CHECK_LAUNCH("sde_motion_consistency_bwd/pixels");
+    hipLaunchKernelGGL(mc_bwd_finalize_kernel, dim3(N), dim3(64), 0, (hipStream_t)stream, (const float*)dR_partial, (int)(g.x * g.y), R_A2B, R_B2A, g_rot, N, dR_A2B,
+                       dR_B2A);
+    SDE_CHECK_LAUNCH("sde_motion_consistency_bwd/finalize");
+    return SDE_OK;
+}
+
+int sde_motion_smooth_num_blocks(int planes, int H, int W) { return sde_cdiv(W - 1, 64) * sde_cdiv(H - 1, 4) * (planes < 8 ? planes : 8); }
+
+int sde_motion_smooth_fwd(const float* f, int planes, int H, int W, float* partial, float* out, int* ticket, sde_stream_t stream) {
+    SDE_CHECK_ARG(f && partial && out && ticket, "sde_motion_smooth_fwd: null pointer");
+    SDE_CHECK_ARG(planes > 0 && H > 1 && W > 1, "sde_motion_smooth_fwd: bad shape planes=%d H=%d W=%d", planes, H, W);
+    const float scale = 1.0f / ((float)planes * (float)(H - 1) * (float)(W - 1));
+    hipLaunchKernelGGL(msmooth_fwd_kernel, pix_grid(W - 1, H - 1, planes < 8 ? planes : 8), dim3(PB_N), 0, (hipStream_t)stream, f, planes, H, W, scale, partial, out, ticket);
+    SDE_CHECK_LAUNCH("sde_motion_smooth_fwd");
+    return SDE_OK;
+}
+
+int sde_motion_smooth_bwd(const float* f, const float* gout, int planes, int H, int W, float* df, sde_stream_t stream) {
+    SDE_CHECK_ARG(f && gout && df, "sde_motion_smooth_bwd: null pointer");
+    SDE_CHECK_ARG(planes > 0 && H > 1 && W > 1, "sde_motion_smooth_bwd: bad shape planes=%d H=%d W=%d", planes, H, W);
+    const float scale = 1.0f / ((float)planes * (float)(H - 1) * (float)(W - 1));
+    hipLaunchKernelGGL(msmooth_bwd_kernel, pix_grid(W, H, planes < kMaxZ ? planes : kMaxZ), dim3(PB_N), 0, (hipStream_t)stream, f, gout, planes, H, W, scale, df);
+    SDE_CHECK_LAUNCH("sde_motion_smooth_bwd");
+    return SDE_OK;
+}
+
+int sde_motion_sparsity_fwd(const float* f, int planes, long hw, float* mean, float* partial, float* out, int* ticket, sde_stream_t stream) {
+    SDE_CHECK_ARG(f && mean && partial && out && ticket, "sde_motion_sparsity_fwd: null pointer");
+    SDE_CHECK_ARG(planes > 0 && hw > 0, "sde_motion_sparsity_fwd: bad shape planes=%d hw=%ld", planes, hw);
+    hipLaunchKernelGGL(msparse_fwd_kernel, dim3(planes), dim3(1024), 0, (hipStream_t)stream, f, planes, hw, 1.0f / ((float)planes * (float)hw), mean, partial, out, ticket);
+    SDE_CHECK_LAUNCH("sde_motion_sparsity_fwd");
+    return SDE_OK;
+}
+
+int sde_motion_sparsity_bwd(const float* f, const float* mean, const float* gout, int planes, long hw, float* df, sde_stream_t stream) {
+    SDE_CHECK_ARG(f && mean && gout && df, "sde_motion_sparsity_bwd: null pointer");
+    SDE_CHECK_ARG(planes > 0 && planes <= kMaxZ && hw > 0, "sde_motion_sparsity_bwd: bad shape planes=%d hw=%ld", planes, hw);
+    hipLaunchKernelGGL(msparse_bwd_kernel, dim3(sde_cdiv(hw, PB_N), planes), dim3(PB_N), 0, (hipStream_t)stream, f, mean, gout, hw, 1.0f / ((float)planes * (float)hw), df);
+    SDE_CHECK_LAUNCH("sde_motion_sparsity_bwd");
+    return SDE_OK;
+}
+
+int sde_avgpool_fwd(const float* src, float* dst, int planes, int H, int W, int h, int w, sde_stream_t stream) {
+    SDE_CHECK_ARG(src && dst, "sde_avgpool_fwd: null pointer");
+    SDE_CHECK_ARG(planes > 0 && H > 0 && W > 0 && h > 0 && w > 0, "sde_avgpool_fwd: bad shape");
+    hipLaunchKernelGGL(avgpool_fwd_kernel, pix_grid(w, h, planes < kMaxZ ? planes : kMaxZ), dim3(PB_N), 0, (hipStream_t)stream, src, dst, planes, H, W, h, w);
+    SDE_CHECK_LAUNCH("sde_avgpool_fwd");
+    return SDE_OK;
+}
+
+int sde_avgpool_bwd(const float* dout, float* din, int planes, int H, int W, int h, int w, sde_stream_t stream) {
+    SDE_CHECK_ARG(dout && din, "sde_avgpool_bwd: null pointer");
+    SDE_CHECK_ARG(planes > 0 && H > 0 && W > 0 && h > 0 && w > 0, "sde_avgpool_bwd: bad shape");
+    hipLaunchKernelGGL(avgpool_bwd_kernel, pix_grid(W, H, planes < kMaxZ ? planes : kMaxZ), dim3(PB_N), 0, (hipStream_t)stream, dout, din, planes, H, W, h, w);
+    SDE_CHECK_LAUNCH("sde_avgpool_bwd");
+    return SDE_OK;
+}
+
+}  // extern "C"

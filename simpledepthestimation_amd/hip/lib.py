@@ -24,6 +24,11 @@ class PhotoDesc(Structure):
                 ("sx", c_float), ("sy", c_float), ("ssim_w", c_float), ("C1", c_float), ("C2", c_float), ("clip_thr", c_void_p)]
 
 
+class RgbdDesc(Structure):
+    _fields_ = [("frame_A", c_void_p), ("frame_B", c_void_p), ("depth_A", c_void_p), ("depth_B", c_void_p), ("K", c_void_p), ("R", c_void_p), ("t", c_void_p),
+                ("N", c_int32), ("H", c_int32), ("W", c_int32), ("ssim", c_int32), ("C1", c_float), ("C2", c_float)]
+
+
 _P, _I, _F = c_void_p, c_int, c_float
 _PROTOS = {
     "sde_version": ([], c_int),
@@ -86,6 +91,22 @@ _PROTOS = {
     "sde_motion_head_fwd": ([_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P], c_int),
     "sde_motion_head_bwd": ([_P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P], c_int),
     "sde_prep_input_bwd": ([_P, _P, _I, _I, _I, _I, _I, _I, _P, _P], c_int),
+    # MotionLearning loss stack (csrc/motion_loss.hip; autograd wrappers in hip/motion_loss.py)
+    "sde_view_synthesis_pp": ([_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P], c_int),
+    "sde_rgbd_num_blocks": ([_I, _I, _I], c_int),
+    "sde_rgbd_fwd": ([POINTER(RgbdDesc), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P], c_int),
+    "sde_rgbd_bwd": ([POINTER(RgbdDesc), _P, _P, _P, _P, _P, _P, _P, _P, _F, _P, _P, _P, _P, _P, _P], c_int),
+    "sde_wssim_fwd": ([_P, _P, _P, _I, _I, _I, _I, _F, _F, _P, _P, _P], c_int),
+    "sde_wssim_bwd": ([_P, _P, _P, _P, _I, _I, _I, _I, _F, _F, _P, _P, _P, _P], c_int),
+    "sde_motion_consistency_fwd": ([_P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P], c_int),
+    "sde_motion_consistency_bwd": ([_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P], c_int),
+    "sde_motion_smooth_num_blocks": ([_I, _I, _I], c_int),
+    "sde_motion_smooth_fwd": ([_P, _I, _I, _I, _P, _P, _P, _P], c_int),
+    "sde_motion_smooth_bwd": ([_P, _P, _I, _I, _I, _P, _P], c_int),
+    "sde_motion_sparsity_fwd": ([_P, _I, ctypes.c_long, _P, _P, _P, _P, _P], c_int),
+    "sde_motion_sparsity_bwd": ([_P, _P, _P, _I, ctypes.c_long, _P, _P], c_int),
+    "sde_avgpool_fwd": ([_P, _P, _I, _I, _I, _I, _I, _P], c_int),
+    "sde_avgpool_bwd": ([_P, _P, _I, _I, _I, _I, _I, _P], c_int),
 }
 
 _lib = None
