@@ -630,6 +630,30 @@ int sde_motion_sparsity_bwd(const float* f, const float* mean, const float* gout
 int sde_avgpool_fwd(const float* src, float* dst, int planes, int H, int W, int h, int w, sde_stream_t stream);
 int sde_avgpool_bwd(const float* dout, float* din, int planes, int H, int W, int h, int w, sde_stream_t stream);
 
+/* Per-scale glue of MotionLearningModel (MotionLearning.py:L126-166, L205-208), both directions stacked along the batch: N = 2B, samples [0, B) are
+ * frame 1 -> 2 and [B, 2B) frame 2 -> 1.  fp32 planar NCHW, no host synchronisation, no float atomics (forward and backward repeat bit for bit).
+ *
+ * sde_motion_prep_fwd: depth [N,1,H0,W0], motion [N,3,H0,W0] or null, t_pose [N,3], mask01 [N,1,H0,W0] or null (0/1, already dilated), target (h, w):
+ *   depth_r = adaptive_avg_pool(depth); m_r = adaptive_avg_pool(motion * mask01); t = t_pose + m_r (t_pose expanded without motion);
+ *   normalize: depth_mean = mean of depth_r over all N samples; depth_n = depth_r / depth_mean, t /= depth_mean, m_r /= depth_mean;
+ *   m_norm = m_r / sqrt(3 mean_{c,h,w}(t^2) + 1e-12) per sample.
+ *   Outputs: depth_r [N,1,h,w], depth_n (normalize only; depth_r otherwise), t [N,3,h,w], overall [N,3,h,w] = t before the division (normalize only; t
+ *   otherwise), m_norm [N,3,h,w] (with motion), and optionally depth_n_sw / t_sw: depth_n and t with the two halves of the batch exchanged.
+ *   Workspaces: partial [sde_rgbd_num_blocks(N,h,w)][2], stats [2 + 4N] (kept for the backward), ticket: one device int, zero between launches
+ *   (the kernels leave it at zero).
+ * sde_motion_prep_bwd: gradients of depth_r, depth_n, t, t_sw and m_norm (each may be null = zero) -> d_depth [N,1,H0,W0], d_motion [N,3,H0,W0] (times
+ *   mask01; null without motion), d_tpose [N,3].  The gradient flows through depth_mean and through the per-sample mean of t^2.
+ *   Workspaces: partial [sde_rgbd_num_blocks(N,h,w)][9], bstats [1 + 10N], ticket as above.
+ * sde_mask_dilate: max_pool2d(mask > 0, 2d + 1, stride 1, padding d) of [planes,H,W] as a 0/1 float map, separable; d >= 1 may exceed the image; tmp: a
+ *   second [planes,H,W] buffer. */
+int sde_motion_prep_fwd(const float* depth, const float* motion, const float* t_pose, const float* mask01, int N, int H0, int W0, int h, int w, int normalize,
+                        float* depth_r, float* depth_n, float* t, float* overall, float* m_norm, float* depth_n_sw, float* t_sw, float* partial, float* stats,
+                        int* ticket, sde_stream_t stream);
+int sde_motion_prep_bwd(const float* mask01, const float* depth_n, const float* t, const float* m_norm, const float* stats, const float* g_depth_r,
+                        const float* g_depth_n, const float* g_t, const float* g_t_sw, const float* g_m_norm, int N, int H0, int W0, int h, int w, int normalize,
+                        float* partial, float* bstats, int* ticket, float* d_depth, float* d_motion, float* d_tpose, sde_stream_t stream);
+int sde_mask_dilate(const float* mask, float* tmp, float* out, int planes, int H, int W, int d, sde_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

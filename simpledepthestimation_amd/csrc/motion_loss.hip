@@ -731,6 +731,268 @@ __global__ void __launch_bounds__(PB_N) avgpool_bwd_kernel(const float* __restri
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Per-scale glue of MotionLearningModel between the networks and the loss operators (MotionLearning.py:L126-166, L205-208), both directions stacked
+// along the batch (N = 2B).  Forward: prep_pool_kernel (pools, t = t_pose + m_r, per-workgroup sums of depth_r and t^2), prep_fwd_finalize_kernel (one
+// workgroup per sample adds them up; the one that arrives last forms the batch depth mean and the per-sample motion scale) and prep_scale_kernel (the
+// divisions and the half-swapped copies).  Backward: prep_bwd_reduce_kernel (the dot products behind d mean, d scale and d t_pose),
+// prep_bwd_finalize_kernel and prep_bwd_gather_kernel (pool transposed).
+// stats [2 + 4N]: depth_mean, 1 / depth_mean, sqrt(3 mean t^2 + 1e-12) [N], 3 mean t^2 [N], scratch [N][2].  No float atomics: every sum has a fixed order.
+// ------------------------------------------------------------------------------------------------
+struct PrepArgs {
+    const float *__restrict__ depth, *__restrict__ motion, *__restrict__ tpose, *__restrict__ mask;      // motion, mask: may be null
+    int N, H0, W0, h, w, normalize;
+    float *__restrict__ depth_r, *__restrict__ t0, *__restrict__ m_r;      // t0 = t_pose + m_r; m_r [N,3,h,w] (null without motion)
+    float *partial, *stats;                          // [workgroups][2], [2 + 4N]
+    int* ticket;                                     // one int, zero between launches
+};
+
+// Finalize kernels (one workgroup per sample, launched after the pass that wrote the partials): the workgroup adds its sample's NV partials up (256
+// threads stride the workgroups of the pass, then the block sum: fixed order), publishes them to per[n][NV] and counts on the ticket; true in every thread
+// of the workgroup that arrives last, which then does the part that needs all samples.  The arrival is kept out of the passes themselves: counting their
+// 7168 workgroups on one address cost 0.7 ms per launch, and on one address per sample still 0.2 ms (profiles/motion_prep_kernels.txt).
+template <int NV>
+__device__ __forceinline__ bool sample_sums_and_arrive(float* sums /*LDS [NV]*/, float* red /*LDS [4 * NV]*/, const float* __restrict__ partial, float* __restrict__ per,
+                                                       int n, int N, int bps, int* __restrict__ ticket) {
+    __shared__ int last;
+    const int tid = threadIdx.x;
+    float v[NV];
+#pragma unroll
+    for (int k = 0; k < NV; ++k) v[k] = 0.f;
+    for (int i = tid; i < bps; i += PB_N)
+#pragma unroll
+        for (int k = 0; k < NV; ++k) v[k] += partial[((long)n * bps + i) * NV + k];
+    block_sums<NV>(v, red, sums);
+    __syncthreads();
+    if (tid == 0) {
+#pragma unroll
+        for (int k = 0; k < NV; ++k) __hip_atomic_store(per + (long)n * NV + k, sums[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        last = (__hip_atomic_fetch_add(ticket, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == N - 1);
+        if (last) __hip_atomic_store(ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    __syncthreads();
+    if (!last) return false;
+    __threadfence();
+    return true;
+}
+
+__device__ __forceinline__ float ld_agent(const float* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+__global__ void __launch_bounds__(PB_N) prep_pool_kernel(const PrepArgs a) {
+    __shared__ float red[8];
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6), n = blockIdx.z;
+    const int H0 = a.H0, W0 = a.W0, h = a.h, w = a.w;
+    float v[2] = {0.f, 0.f};
+    if (x < w && y < h) {
+        const int y0 = ap_lo(y, H0, h), y1 = ap_hi(y, H0, h), x0 = ap_lo(x, W0, w), x1 = ap_hi(x, W0, w);
+        const float inv = 1.0f / (float)((y1 - y0) * (x1 - x0));
+        const float* d = a.depth + (long)n * H0 * W0;
+        const float* k = a.mask ? a.mask + (long)n * H0 * W0 : nullptr;
+        float acc = 0.f;
+        for (int yy = y0; yy < y1; ++yy)
+            for (int xx = x0; xx < x1; ++xx) acc += d[(long)yy * W0 + xx];
+        const long o = ((long)n * h + y) * w + x;
+        v[0] = acc * inv;
+        a.depth_r[o] = v[0];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const long oc = (((long)n * 3 + c) * h + y) * w + x;
+            float t = a.tpose[n * 3 + c];
+            if (a.motion) {
+                const float* m = a.motion + ((long)n * 3 + c) * H0 * W0;
+                acc = 0.f;
+                for (int yy = y0; yy < y1; ++yy)
+                    for (int xx = x0; xx < x1; ++xx) acc += k ? m[(long)yy * W0 + xx] * k[(long)yy * W0 + xx] : m[(long)yy * W0 + xx];
+                const float mr = acc * inv;
+                a.m_r[oc] = mr;
+                t = t + mr;
+            }
+            a.t0[oc] = t;
+            v[1] += t * t;
+        }
+    }
+    block_sums<2>(v, red, a.partial + 2 * (long)((blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x));
+}
+
+// depth mean and per-sample motion scale from the partials of prep_pool_kernel: grid N
+__global__ void __launch_bounds__(PB_N) prep_fwd_finalize_kernel(const PrepArgs a, int bps) {
+    __shared__ float red[8], sums[2];
+    const int n = blockIdx.x, N = a.N, h = a.h, w = a.w;
+    float* per = a.stats + 2 + 2 * N;                     // scratch [N][2]: sum depth_r, sum t0^2 of each sample
+    if (!sample_sums_and_arrive<2>(sums, red, a.partial, per, n, N, bps, a.ticket)) return;
+    // the workgroup that arrives last of all: depth mean over the samples in a fixed order (thread-strided, then the block sum), then one thread per sample
+    __shared__ float mu_s;
+    const float hw = (float)h * (float)w;
+    float s = 0.f;
+    if (a.normalize)
+        for (int i = threadIdx.x; i < N; i += PB_N) s += ld_agent(per + 2 * i);
+    s = sde_block_sum(s, red);
+    if (threadIdx.x == 0) {
+        mu_s = a.normalize ? s / ((float)N * hw) : 1.0f;
+        a.stats[0] = mu_s;
+        a.stats[1] = 1.0f / mu_s;
+    }
+    __syncthreads();
+    const float mu = mu_s;
+    for (int i = threadIdx.x; i < N; i += PB_N) {
+        const float q = ld_agent(per + 2 * i + 1) / (mu * mu) / hw;       // 3 mean_{c,h,w}(t^2) with t = t0 / mu
+        a.stats[2 + N + i] = q;
+        a.stats[2 + i] = sqrtf(q + 1e-12f);
+    }
+}
+
+// depth_n = depth_r / mean, t = t0 / mean, m_norm = (m_r / mean) / sqrt(3 mean t^2 + 1e-12) (in place over m_r), and the copies of depth_n and t with the two
+// halves of the batch exchanged (depth_B of the stacked RGB-D call, t_B2A of motion consistency).  Without normalisation depth_n is depth_r and t is t0.
+__global__ void __launch_bounds__(PB_N) prep_scale_kernel(const float* __restrict__ depth_r, const float* __restrict__ t0, const float* __restrict__ stats,
+                                                          int N, int h, int w, int normalize, float* __restrict__ depth_n, float* __restrict__ t,
+                                                          float* __restrict__ m, float* __restrict__ depth_n_sw, float* __restrict__ t_sw) {
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6), n = blockIdx.z;
+    if (x >= w || y >= h) return;
+    const int ns = n < N / 2 ? n + N / 2 : n - N / 2;
+    const float mu = stats[0], sq = stats[2 + n];
+    const long pix = (long)y * w + x, hw = (long)h * w;
+    float dn = depth_r[n * hw + pix];
+    if (normalize) { dn = dn / mu; depth_n[n * hw + pix] = dn; }
+    if (depth_n_sw) depth_n_sw[ns * hw + pix] = dn;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const long o = ((long)n * 3 + c) * hw + pix;
+        float tv = t0[o];
+        if (normalize) { tv = tv / mu; t[o] = tv; }
+        if (t_sw) t_sw[((long)ns * 3 + c) * hw + pix] = tv;
+        if (m) {
+            float mv = m[o];
+            if (normalize) mv = mv / mu;
+            m[o] = mv / sq;
+        }
+    }
+}
+
+struct PrepBwdArgs {
+    const float *mask, *depth_n, *t, *m_norm, *stats;                      // mask, m_norm: may be null
+    const float *g_depth_r, *g_depth_n, *g_t, *g_t_sw, *g_m_norm;          // each may be null (= zero)
+    int N, H0, W0, h, w, normalize;
+    float *partial, *bstats;                                               // [workgroups][9], [1 + 10N]: d mean per pooled pixel, c [N], scratch [N][9]
+    int* ticket;                                                           // one int, zero between launches
+    float *d_depth, *d_motion, *d_tpose;                                   // d_motion: null without motion
+};
+
+// d loss / d t of one pooled element: the direct gradient plus the one that arrives through the half-swapped copy
+__device__ __forceinline__ float prep_gt(const PrepBwdArgs& a, long o, long o_sw) {
+    float g = 0.f;
+    if (a.g_t) g = a.g_t[o];
+    if (a.g_t_sw) g += a.g_t_sw[o_sw];
+    return g;
+}
+
+// per sample: A = sum g_m_norm m_norm, Bt = sum g_t t, C = sum g_depth_n depth_n, sum g_t [3], sum t [3]; prep_bwd_finalize_kernel forms
+// c_n = -A / ((3 mean t^2 + 1e-12) h w)  (so that d t = g_t + c_n t), d t_pose and d depth_mean
+__global__ void __launch_bounds__(PB_N) prep_bwd_reduce_kernel(const PrepBwdArgs a) {
+    __shared__ float red[36];
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6), n = blockIdx.z;
+    const int h = a.h, w = a.w, N = a.N;
+    float v[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if (x < w && y < h) {
+        const int ns = n < N / 2 ? n + N / 2 : n - N / 2;
+        const long pix = (long)y * w + x, hw = (long)h * w;
+        if (a.g_depth_n) v[2] = a.g_depth_n[n * hw + pix] * a.depth_n[n * hw + pix];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const long o = ((long)n * 3 + c) * hw + pix;
+            const float g = prep_gt(a, o, ((long)ns * 3 + c) * hw + pix), tv = a.t[o];
+            if (a.m_norm && a.g_m_norm) v[0] += a.g_m_norm[o] * a.m_norm[o];
+            v[1] += g * tv;
+            v[3 + c] = g;
+            v[6 + c] = tv;
+        }
+    }
+    block_sums<9>(v, red, a.partial + 9 * (long)((blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x));
+}
+
+// c_n, d t_pose and d depth_mean from the partials of prep_bwd_reduce_kernel: grid N
+__global__ void __launch_bounds__(PB_N) prep_bwd_finalize_kernel(const PrepBwdArgs a, int bps) {
+    __shared__ float red[36], sums[9];
+    const int n = blockIdx.x, N = a.N, h = a.h, w = a.w;
+    float* per = a.bstats + 1 + N;
+    if (!sample_sums_and_arrive<9>(sums, red, a.partial, per, n, N, bps, a.ticket)) return;
+    const float hw = (float)h * (float)w, r = a.normalize ? a.stats[1] : 1.0f;
+    float tot = 0.f;
+    for (int i = threadIdx.x; i < N; i += PB_N) {         // one thread per sample; d depth_mean: thread-strided, then the block sum
+        float p[9];
+#pragma unroll
+        for (int k = 0; k < 9; ++k) p[k] = ld_agent(per + 9 * i + k);
+        const float sq = a.stats[2 + i], s = a.stats[2 + N + i];
+        const float cn = a.m_norm ? -p[0] / (sq * sq) / hw : 0.f;
+        a.bstats[1 + i] = cn;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) a.d_tpose[i * 3 + c] = r * (p[3 + c] + cn * p[6 + c]);
+        tot += ((p[1] + cn * (s * hw)) + p[0]) + p[2];
+    }
+    tot = sde_block_sum(tot, red);
+    if (threadIdx.x == 0) a.bstats[0] = a.normalize ? (-r * tot) / ((float)N * hw) : 0.f;
+}
+
+// d depth and d motion of one full-resolution pixel: the pooled gradients of the windows that contain it (a contiguous range each way), over the window areas
+__global__ void __launch_bounds__(PB_N) prep_bwd_gather_kernel(const PrepBwdArgs a) {
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6), n = blockIdx.z;
+    const int H0 = a.H0, W0 = a.W0, h = a.h, w = a.w, N = a.N;
+    if (x >= W0 || y >= H0) return;
+    int i0, i1, j0, j1;
+    ap_range(y, H0, h, i0, i1);
+    ap_range(x, W0, w, j0, j1);
+    const int ns = n < N / 2 ? n + N / 2 : n - N / 2;
+    const long hw = (long)h * w;
+    const float r = a.normalize ? a.stats[1] : 1.0f, gmu = a.bstats[0], cn = a.bstats[1 + n];
+    const float rs = 1.0f / a.stats[2 + n];
+    const bool motion = a.d_motion != nullptr;
+    float dd = 0.f, dm[3] = {0.f, 0.f, 0.f};
+    for (int i = i0; i <= i1; ++i) {
+        const float ry = 1.0f / (float)(ap_hi(i, H0, h) - ap_lo(i, H0, h));
+        for (int j = j0; j <= j1; ++j) {
+            const float wgt = ry / (float)(ap_hi(j, W0, w) - ap_lo(j, W0, w));
+            const long pix = (long)i * w + j;
+            float g = gmu;
+            if (a.g_depth_r) g += a.g_depth_r[n * hw + pix];
+            if (a.g_depth_n) g += a.g_depth_n[n * hw + pix] * r;
+            dd += g * wgt;
+            if (motion) {
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    const long o = ((long)n * 3 + c) * hw + pix;
+                    float gm = prep_gt(a, o, ((long)ns * 3 + c) * hw + pix) + cn * a.t[o];
+                    if (a.g_m_norm) gm += a.g_m_norm[o] * rs;
+                    dm[c] += (r * gm) * wgt;
+                }
+            }
+        }
+    }
+    const long o = (long)y * W0 + x, HW0 = (long)H0 * W0;
+    a.d_depth[n * HW0 + o] = dd;
+    if (motion) {
+        const float k = a.mask ? a.mask[n * HW0 + o] : 1.0f;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) a.d_motion[((long)n * 3 + c) * HW0 + o] = dm[c] * k;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Mask dilation: max_pool2d(mask > 0, 2d + 1, stride 1, padding d) as a row pass and a column pass of 2d + 1 taps each (clipped to the image)
+// ------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(PB_N) dilate_kernel(const float* __restrict__ src, float* __restrict__ dst, int H, int W, int d, int horizontal) {
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (x >= W || y >= H) return;
+    const float* s = src + (long)blockIdx.z * H * W;
+    bool on = false;
+    if (horizontal) {
+        const int lo = x - d > 0 ? x - d : 0, hi = x + d < W - 1 ? x + d : W - 1;
+        for (int xx = lo; xx <= hi; ++xx) on = on || s[(long)y * W + xx] > 0.f;
+    } else {
+        const int lo = y - d > 0 ? y - d : 0, hi = y + d < H - 1 ? y + d : H - 1;
+        for (int yy = lo; yy <= hi; ++yy) on = on || s[(long)yy * W + x] > 0.f;
+    }
+    dst[(long)blockIdx.z * H * W + (long)y * W + x] = on ? 1.0f : 0.f;
+}
+
 inline dim3 pix_grid(int W, int H, int z) { return dim3(sde_cdiv(W, 64), sde_cdiv(H, 4), z); }
 inline int ssim_mode(float C1, float C2) { return C1 > kFltMax ? 1 : (C2 > kFltMax ? 2 : 0); }
 constexpr int kMaxZ = 65535;
@@ -894,6 +1156,61 @@ int sde_avgpool_bwd(const float* dout, float* din, int planes, int H, int W, int
     SDE_CHECK_ARG(planes > 0 && H > 0 && W > 0 && h > 0 && w > 0, "sde_avgpool_bwd: bad shape");
     hipLaunchKernelGGL(avgpool_bwd_kernel, pix_grid(W, H, planes < kMaxZ ? planes : kMaxZ), dim3(PB_N), 0, (hipStream_t)stream, dout, din, planes, H, W, h, w);
     SDE_CHECK_LAUNCH("sde_avgpool_bwd");
+    return SDE_OK;
+}
+
+int sde_motion_prep_fwd(const float* depth, const float* motion, const float* t_pose, const float* mask01, int N, int H0, int W0, int h, int w, int normalize,
+                        float* depth_r, float* depth_n, float* t, float* overall, float* m_norm, float* depth_n_sw, float* t_sw, float* partial, float* stats,
+                        int* ticket, sde_stream_t stream) {
+    SDE_CHECK_ARG(depth && t_pose && depth_r && t && partial && stats && ticket, "sde_motion_prep_fwd: null pointer");
+    SDE_CHECK_ARG(N > 0 && N <= kMaxZ && N % 2 == 0 && H0 > 0 && W0 > 0 && h > 0 && w > 0 && h <= H0 && w <= W0,
+                  "sde_motion_prep_fwd: bad shape N=%d (even: both directions stacked) %dx%d -> %dx%d", N, H0, W0, h, w);
+    SDE_CHECK_ARG(!normalize || (depth_n && overall), "sde_motion_prep_fwd: scale_normalize without depth_n / overall");
+    SDE_CHECK_ARG((motion != nullptr) == (m_norm != nullptr) && (motion || !mask01), "sde_motion_prep_fwd: motion, m_norm and mask01 go together");
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 g = pix_grid(w, h, N);
+    float* t0 = normalize ? overall : t;
+    PrepArgs a{depth, motion, t_pose, mask01, N, H0, W0, h, w, normalize ? 1 : 0, depth_r, t0, m_norm, partial, stats, ticket};
+    hipLaunchKernelGGL(prep_pool_kernel, g, dim3(PB_N), 0, st, a);
+    SDE_CHECK_LAUNCH("sde_motion_prep_fwd/pool");
+    hipLaunchKernelGGL(prep_fwd_finalize_kernel, dim3(N), dim3(PB_N), 0, st, a, (int)(g.x * g.y));
+    SDE_CHECK_LAUNCH("sde_motion_prep_fwd/finalize");
+    if (normalize || m_norm || depth_n_sw || t_sw) {
+        hipLaunchKernelGGL(prep_scale_kernel, g, dim3(PB_N), 0, st, (const float*)depth_r, (const float*)t0, (const float*)stats, N, h, w, normalize ? 1 : 0, depth_n, t,
+                           m_norm, depth_n_sw, t_sw);
+        SDE_CHECK_LAUNCH("sde_motion_prep_fwd/scale");
+    }
+    return SDE_OK;
+}
+
+int sde_motion_prep_bwd(const float* mask01, const float* depth_n, const float* t, const float* m_norm, const float* stats, const float* g_depth_r,
+                        const float* g_depth_n, const float* g_t, const float* g_t_sw, const float* g_m_norm, int N, int H0, int W0, int h, int w, int normalize,
+                        float* partial, float* bstats, int* ticket, float* d_depth, float* d_motion, float* d_tpose, sde_stream_t stream) {
+    SDE_CHECK_ARG(t && stats && partial && bstats && ticket && d_depth && d_tpose, "sde_motion_prep_bwd: null pointer");
+    SDE_CHECK_ARG(N > 0 && N <= kMaxZ && N % 2 == 0 && H0 > 0 && W0 > 0 && h > 0 && w > 0 && h <= H0 && w <= W0,
+                  "sde_motion_prep_bwd: bad shape N=%d %dx%d -> %dx%d", N, H0, W0, h, w);
+    SDE_CHECK_ARG((m_norm != nullptr) == (d_motion != nullptr) && (m_norm || !mask01), "sde_motion_prep_bwd: m_norm, d_motion and mask01 go together");
+    SDE_CHECK_ARG(!g_depth_n || (normalize && depth_n), "sde_motion_prep_bwd: a gradient of depth_n without scale_normalize");
+    hipStream_t st = (hipStream_t)stream;
+    PrepBwdArgs a{mask01, depth_n, t, m_norm, stats, g_depth_r, g_depth_n, g_t, g_t_sw, g_m_norm, N, H0, W0, h, w, normalize ? 1 : 0, partial, bstats, ticket,
+                  d_depth, d_motion, d_tpose};
+    const dim3 g = pix_grid(w, h, N);
+    hipLaunchKernelGGL(prep_bwd_reduce_kernel, g, dim3(PB_N), 0, st, a);
+    SDE_CHECK_LAUNCH("sde_motion_prep_bwd/reduce");
+    hipLaunchKernelGGL(prep_bwd_finalize_kernel, dim3(N), dim3(PB_N), 0, st, a, (int)(g.x * g.y));
+    SDE_CHECK_LAUNCH("sde_motion_prep_bwd/finalize");
+    hipLaunchKernelGGL(prep_bwd_gather_kernel, pix_grid(W0, H0, N), dim3(PB_N), 0, st, a);
+    SDE_CHECK_LAUNCH("sde_motion_prep_bwd/gather");
+    return SDE_OK;
+}
+
+int sde_mask_dilate(const float* mask, float* tmp, float* out, int planes, int H, int W, int d, sde_stream_t stream) {
+    SDE_CHECK_ARG(mask && tmp && out && tmp != out && tmp != mask, "sde_mask_dilate: null or aliased pointer");
+    SDE_CHECK_ARG(planes > 0 && planes <= kMaxZ && H > 0 && W > 0 && d > 0 && d < (1 << 20), "sde_mask_dilate: bad shape planes=%d H=%d W=%d d=%d", planes, H, W, d);
+    hipLaunchKernelGGL(dilate_kernel, pix_grid(W, H, planes), dim3(PB_N), 0, (hipStream_t)stream, mask, tmp, H, W, d, 1);
+    SDE_CHECK_LAUNCH("sde_mask_dilate/rows");
+    hipLaunchKernelGGL(dilate_kernel, pix_grid(W, H, planes), dim3(PB_N), 0, (hipStream_t)stream, (const float*)tmp, out, H, W, d, 0);
+    SDE_CHECK_LAUNCH("sde_mask_dilate/columns");
     return SDE_OK;
 }
 

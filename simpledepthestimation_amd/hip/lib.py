@@ -107,6 +107,9 @@ _PROTOS = {
     "sde_motion_sparsity_bwd": ([_P, _P, _P, _I, ctypes.c_long, _P, _P], c_int),
     "sde_avgpool_fwd": ([_P, _P, _I, _I, _I, _I, _I, _P], c_int),
     "sde_avgpool_bwd": ([_P, _P, _I, _I, _I, _I, _I, _P], c_int),
+    "sde_motion_prep_fwd": ([_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P], c_int),
+    "sde_motion_prep_bwd": ([_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P], c_int),
+    "sde_mask_dilate": ([_P, _P, _P, _I, _I, _I, _I, _P], c_int),
 }
 
 _lib = None

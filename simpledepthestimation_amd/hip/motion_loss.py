@@ -257,3 +257,85 @@ def avgpool(image, size):
         _f32c(image)
         return image
     return _AvgPool.apply(image, h, w)
+
+
+class _PairPrep(torch.autograd.Function):
+    """sde_motion_prep_fwd / _bwd: (depth_r, depth_n or empty, t, m_norm or empty, t_sw, depth_n_sw, overall)."""
+
+    @staticmethod
+    def forward(ctx, depth, motion, t_pose, mask01, h, w, normalize):
+        depth, t_pose = _f32c(depth), _f32c(t_pose)
+        N, _, H0, W0 = depth.shape
+        _shape(depth, (N, 1, H0, W0), "depth"); _shape(t_pose, (N, 3), "t_pose")
+        if motion is not None:
+            motion = _f32c(motion)
+            _shape(motion, (N, 3, H0, W0), "motion")
+        if mask01 is not None:
+            if motion is None:
+                raise L.SdeHipError("pair_prep: a mask without a motion field")
+            mask01 = _f32c(mask01)
+            _shape(mask01, (N, 1, H0, W0), "mask01")
+        if N % 2 or not (0 < h <= H0 and 0 < w <= W0):
+            raise L.SdeHipError(f"pair_prep: N must be even (both directions stacked) and the target no larger than the input, got N={N} {H0}x{W0} -> {h}x{w}")
+        dev = depth.device
+        lib = L.lib()
+        e = lambda *s: torch.empty(*s, device=dev)
+        depth_r, t, t_sw, dn_sw = e(N, 1, h, w), e(N, 3, h, w), e(N, 3, h, w), e(N, 1, h, w)
+        depth_n, overall = (e(N, 1, h, w), e(N, 3, h, w)) if normalize else (None, None)
+        m_norm = e(N, 3, h, w) if motion is not None else None
+        partial, stats = e(lib.sde_rgbd_num_blocks(N, h, w), 2), e(2 + 4 * N)
+        L.check(lib.sde_motion_prep_fwd(L.ptr(depth), L.ptr(motion), L.ptr(t_pose), L.ptr(mask01), N, H0, W0, h, w, int(normalize), L.ptr(depth_r), L.ptr(depth_n),
+                                        L.ptr(t), L.ptr(overall), L.ptr(m_norm), L.ptr(dn_sw), L.ptr(t_sw), L.ptr(partial), L.ptr(stats), L.ptr(_ticket(dev)),
+                                        L.stream()), "sde_motion_prep_fwd")
+        ctx.save_for_backward(mask01, depth_n, t, m_norm, stats)
+        ctx.cfg = (N, H0, W0, h, w, bool(normalize))
+        ctx.set_materialize_grads(False)          # an output no loss term reads sends None, not a zero map
+        outs = (depth_r, depth_n if normalize else e(0), t, m_norm if m_norm is not None else e(0), t_sw, dn_sw, overall if normalize else e(0))
+        ctx.mark_non_differentiable(dn_sw, outs[6], *([] if normalize else [outs[1]]), *([] if m_norm is not None else [outs[3]]))
+        return outs
+
+    @staticmethod
+    def backward(ctx, g_dr, g_dn, g_t, g_mn, g_tsw, *_):
+        mask01, depth_n, t, m_norm, stats = ctx.saved_tensors
+        N, H0, W0, h, w, normalize = ctx.cfg
+        dev = t.device
+        lib = L.lib()
+        if not normalize:
+            g_dn = None
+        if m_norm is None:
+            g_mn = None
+        g = [None if v is None else _f32c(v) for v in (g_dr, g_dn, g_t, g_tsw, g_mn)]
+        e = lambda *s: torch.empty(*s, device=dev)
+        d_depth, d_tpose = e(N, 1, H0, W0), e(N, 3)
+        d_motion = e(N, 3, H0, W0) if m_norm is not None else None
+        partial, bstats = e(lib.sde_rgbd_num_blocks(N, h, w), 9), e(1 + 10 * N)
+        L.check(lib.sde_motion_prep_bwd(L.ptr(mask01), L.ptr(depth_n), L.ptr(t), L.ptr(m_norm), L.ptr(stats), L.ptr(g[0]), L.ptr(g[1]), L.ptr(g[2]), L.ptr(g[3]),
+                                        L.ptr(g[4]), N, H0, W0, h, w, int(normalize), L.ptr(partial), L.ptr(bstats), L.ptr(_ticket(dev)), L.ptr(d_depth),
+                                        L.ptr(d_motion), L.ptr(d_tpose), L.stream()), "sde_motion_prep_bwd")
+        return d_depth, d_motion, d_tpose, None, None, None, None
+
+
+def pair_prep(depth, motion, t_pose, mask01, size, scale_normalize=False):
+    """The per-scale glue of MotionLearningModel (MotionLearning.py:L126-166, L205-208) for both directions stacked along the batch (N = 2B: first half
+    frame 1 -> 2, second half 2 -> 1): dict(depth_r, depth_n (depth_r itself when not normalising), t, m_norm (None without motion), overall_motion (t before
+    the division by the depth mean, no gradient), and t_sw / depth_n_sw: t and depth_n with the halves of the batch exchanged, i.e. t_B2A of motion
+    consistency (its gradient flows back into t) and depth_B of the stacked RGB-D call (no gradient, as depth_B has none)).
+    Gradients reach depth, motion (times the mask) and t_pose; mask01 is a constant 0/1 map, already dilated."""
+    if mask01 is not None and mask01.requires_grad:
+        raise L.SdeHipError("pair_prep: the mask is a constant")
+    o = _PairPrep.apply(depth, motion, t_pose, mask01, int(size[-2]), int(size[-1]), bool(scale_normalize))
+    return {"depth_r": o[0], "depth_n": o[1] if scale_normalize else o[0], "t": o[2], "m_norm": o[3] if motion is not None else None, "t_sw": o[4],
+            "depth_n_sw": o[5], "overall_motion": o[6] if scale_normalize else o[2].detach()}
+
+
+def dilate_mask(mask, d):
+    """F.max_pool2d((mask > 0).float(), 2d + 1, stride=1, padding=d) of a [N,1,H,W] map as a 0/1 float map (MotionLearning.py:L109-114); no gradient.
+    d = 0 is the threshold alone."""
+    d = int(d)
+    if d <= 0:
+        return (mask > 0).float()
+    mask = _f32c(mask.detach().float())
+    N, C, H, W = mask.shape
+    tmp, out = torch.empty_like(mask), torch.empty_like(mask)
+    L.check(L.lib().sde_mask_dilate(L.ptr(mask), L.ptr(tmp), L.ptr(out), N * C, H, W, d, L.stream()), "sde_mask_dilate")
+    return out

@@ -1,6 +1,6 @@
 """``build_model(cfg)``: the drop-in entry point of the path (contract of detectron2/modeling/meta_arch/build.py:L6-23).
 
-``cfg.MODEL.META_ARCHITECTURE`` names a class registered in META_ARCH_REGISTRY (``SupDepthModel``, ``MonoDepth2Model``); the class is
+``cfg.MODEL.META_ARCHITECTURE`` names a class registered in META_ARCH_REGISTRY (``SupDepthModel``, ``MonoDepth2Model``, ``MotionLearningModel``); the class is
 instantiated with the cfg and moved to ``cfg.MODEL.DEVICE``.  No weights are loaded here.  An unknown name is a ``KeyError``."""
 import torch
 
