@@ -524,8 +524,16 @@ int sde_inv_depth_head_bwd(const void* y, const float* d_inv, const float* d_dep
  * growth_factor every growth_interval clean steps), counts the step in applied_steps when it was NOT skipped, and clears found_inf.
  * With scale_state the optimizer's step count lives on the device (GradScaler.step skips optimizer.step(), so Adam's `step` does not
  * advance on an overflow): the kernel ignores bias_corr1/2 and forms 1 - beta^(applied_steps + 1) itself from beta1_d / beta2_d.
- * The loss is multiplied by scale_state[0] on the device before backward. */
+ * The loss is multiplied by scale_state[0] on the device before backward.
+ * clip_state (optional, DEVICE float[2] = {total_norm, clip_coef}; NULL: off, the update is what it is without the field): gradient-norm
+ * clipping, torch.nn.utils.clip_grad_norm_(model.parameters(), SOLVER.CLIP_GRAD) of projects/MotionLearning/train.py:L157 without its per-tensor
+ * norms and without rescaling the gradient in memory: sde_grad_norm reads the flat gradient once (4 * n bytes) and leaves
+ * total_norm = grad_scale * ||g||_2 (the norm of the averaged gradient) and clip_coef = min(1, max_norm / (total_norm + 1e-6)) on the device;
+ * sde_adam_step multiplies grad_scale by clip_coef.  A NaN norm gives a NaN coefficient and NaN parameters, an infinite one the coefficient 0,
+ * both as in torch.  work: DEVICE float[SDE_GRAD_NORM_WORK], one partial sum per workgroup; no atomics, a fixed summation order: two calls on
+ * the same buffer give the same bits. */
 #define SDE_ADAM_MAX_SEG 8
+#define SDE_GRAD_NORM_WORK 1024
 typedef struct sde_adam_desc {
     long seg_end[SDE_ADAM_MAX_SEG];
     float seg_lr[SDE_ADAM_MAX_SEG], seg_wd[SDE_ADAM_MAX_SEG];
@@ -533,9 +541,11 @@ typedef struct sde_adam_desc {
     float beta1, beta2, eps, bias_corr1, bias_corr2, grad_scale;
     const float* scale_state;
     double beta1_d, beta2_d;       /* the betas in double (device-side bias corrections of the scale_state path) */
+    const float* clip_state;
 } sde_adam_desc;
 int sde_adam_step(float* p, const float* g, float* m, float* v, long n, const sde_adam_desc* d, sde_stream_t stream);
 int sde_grad_check(const float* g, long n, float* scale_state, sde_stream_t stream);
+int sde_grad_norm(const float* g, long n, float* work, float* clip_state, float grad_scale, float max_norm, sde_stream_t stream);
 int sde_loss_scale_update(float* scale_state, float growth_factor, float backoff_factor, int growth_interval, sde_stream_t stream);
 
 

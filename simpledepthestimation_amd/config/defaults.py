@@ -40,7 +40,7 @@ _C.MODEL.POSE_NET.GROUP_NORM = False         # GroupNorm(16) between every convo
 _C.MODEL.POSE_NET.MASK_MOTION = True         # keep the motion field only where its norm exceeds the batch mean
 _C.MODEL.POSE_NET.LEARN_SCALE = True         # rot_scale / trans_scale parameters (False: the constant 0.01)
 _C.MODEL.POSE_NET.SCALE_CONSTRAIN = "clip"   # "clip", "clip_ste" or "softplus" (GoogleMotionNet; anything else raises NotImplementedError)
-_C.MODEL.POSE_NET.BURN_IN_ITERS = 20000      # stored only: the MotionLearning training loop reads it
+_C.MODEL.POSE_NET.BURN_IN_ITERS = 20000      # > 0: engine/loops.py ramps motion_weight as clip(2 * step / BURN_IN_ITERS - 1, 0, 1) before every step
 _C.LOSS = CN()
 _C.LOSS.SSIM_WEIGHT = 0.85
 _C.LOSS.C1 = 1e-4
@@ -64,6 +64,7 @@ _C.SOLVER.POSE_LR = 1e-3
 _C.SOLVER.DEPTH_END_LR = 1e-5
 _C.SOLVER.LR_STEPS = ()
 _C.SOLVER.GAMMA = 0.1
+_C.SOLVER.CLIP_GRAD = 0                    # MotionLearning (its Base.yaml: 10): max total gradient norm of nn.utils.clip_grad_norm_; 0: no clipping
 _C.SOLVER.AMP = False                      # fp16 storage + dynamic loss scaling (engine/train_loop.py:L294-341 AMPTrainer); needs MODEL.COMPUTE_DTYPE fp16
 _C.TEST = CN()
 _C.TEST.EVAL_PERIOD = 1

@@ -1210,6 +1210,8 @@ __global__ void __launch_bounds__(256) gn_bwd_apply_kernel(const T* __restrict__
 // learning rate every iteration (polynomial decay) and nothing has to be uploaded, kept alive or ordered against the launch.
 // scale_state (optional, fp16 training): device {loss_scale, found_inf, growth_tracker}: gradients are divided by loss_scale and the
 // whole update is skipped when found_inf != 0 (engine/train_loop.py:L294-341 AMPTrainer / GradScaler.step semantics, without a host sync).
+// clip_state (optional, gradient-norm clipping): device {total_norm, clip_coef} written by sde_grad_norm in front of this launch; the gradient is
+// multiplied by clip_coef on its way into the update and never rescaled in memory.
 __global__ void __launch_bounds__(256) adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, long n,
                                                    const sde_adam_desc d) {
     float gs = d.grad_scale;
@@ -1223,6 +1225,7 @@ __global__ void __launch_bounds__(256) adam_kernel(float* __restrict__ p, const 
         bc1 = (float)(1.0 - pow(d.beta1_d, t));
         bc2 = (float)(1.0 - pow(d.beta2_d, t));
     }
+    if (d.clip_state) gs *= d.clip_state[1];             // gradient-norm clipping: the coefficient grad_norm_finalize_kernel left on the device
     const float beta1 = d.beta1, beta2 = d.beta2, rbc2 = 1.0f / sqrtf(bc2);
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
         int s = 0;
@@ -1263,6 +1266,41 @@ __global__ void loss_scale_update_kernel(float* __restrict__ state, float growth
         if (t >= (float)interval) { state[0] *= growth; state[2] = 0.f; } else state[2] = t;
     }
     state[1] = 0.f;
+}
+
+// Global L2 norm of the flat gradient and torch.nn.utils.clip_grad_norm_'s coefficient (projects/MotionLearning/train.py:L157), in two launches and
+// without atomics: every sum has one fixed order, so the same buffer gives the same bits.
+// Pass 1: at most SDE_GRAD_NORM_WORK workgroups stream the buffer once, 16 B per lane and grid stride; a lane keeps four fp32 sums of squares (one per
+// float4 component), adds them, the wave adds its lanes (DPP), thread 0 adds the four waves in order -> work[workgroup].
+__global__ void __launch_bounds__(256) grad_norm_partial_kernel(const float4* __restrict__ g4, long n4, const float* __restrict__ tail, int ntail, float* __restrict__ work) {
+    __shared__ float red[16];
+    float sx = 0.f, sy = 0.f, sz = 0.f, sw = 0.f;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
+        const float4 q = g4[i];
+        sx = fmaf(q.x, q.x, sx); sy = fmaf(q.y, q.y, sy); sz = fmaf(q.z, q.z, sz); sw = fmaf(q.w, q.w, sw);
+    }
+    float s = (sx + sy) + (sz + sw);
+    if (blockIdx.x == 0 && (int)threadIdx.x < ntail) s = fmaf(tail[threadIdx.x], tail[threadIdx.x], s);
+    s = sde_block_sum(s, red);
+    if (threadIdx.x == 0) work[blockIdx.x] = s;
+}
+
+// Finalize: one workgroup strides the nwork partials in a fixed order, the same block sum, then
+//   total_norm = grad_scale * sqrt(sum)                 (grad_scale = 1/world: the norm of the AVERAGED gradient, what DDP hands to clip_grad_norm_)
+//   clip_coef  = min(1, max_norm / (total_norm + 1e-6)) (torch's clamp(max=1): a NaN norm stays a NaN coefficient -- fminf would return 1 -- and
+//                                                        poisons the update as it does in the reference; an infinite norm gives 0, as there)
+__global__ void __launch_bounds__(256) grad_norm_finalize_kernel(const float* __restrict__ work, int nwork, float grad_scale, float max_norm, float* __restrict__ clip_state) {
+    __shared__ float red[16];
+    float s = 0.f;
+    for (int i = threadIdx.x; i < nwork; i += 256) s += work[i];
+    s = sde_block_sum(s, red);
+    if (threadIdx.x == 0) {
+        const float total = grad_scale * sqrtf(s);
+        float coef = max_norm / (total + 1e-6f);
+        if (coef > 1.0f) coef = 1.0f;                    // false for NaN: the NaN is kept
+        clip_state[0] = total;
+        clip_state[1] = coef;
+    }
 }
 
 // If the slab has more than SDE_REDUCE_ROWS rows, fold it into SDE_REDUCE_ROWS rows stored right behind it (the caller
@@ -1687,6 +1725,20 @@ int sde_grad_check(const float* g, long n, float* scale_state, sde_stream_t stre
     const long n4 = n / 4;
     hipLaunchKernelGGL(grad_check_kernel, dim3(grid_for(n4 > 0 ? n4 : 1)), dim3(256), 0, (hipStream_t)stream, (const float4*)g, n4, g + n4 * 4, (int)(n - n4 * 4), scale_state);
     SDE_CHECK_LAUNCH("sde_grad_check");
+    return SDE_OK;
+}
+
+int sde_grad_norm(const float* g, long n, float* work, float* clip_state, float grad_scale, float max_norm, sde_stream_t stream) {
+    SDE_CHECK_ARG(g && work && clip_state && n > 0 && ((uintptr_t)g & 15) == 0, "sde_grad_norm: bad argument");
+    SDE_CHECK_ARG(max_norm > 0.f && grad_scale > 0.f, "sde_grad_norm: max_norm %g and grad_scale %g must be positive", (double)max_norm, (double)grad_scale);
+    const long n4 = n / 4;
+    long nwg = (n4 + 255) / 256;
+    if (nwg < 1) nwg = 1;
+    if (nwg > SDE_GRAD_NORM_WORK) nwg = SDE_GRAD_NORM_WORK;
+    hipLaunchKernelGGL(grad_norm_partial_kernel, dim3((int)nwg), dim3(256), 0, (hipStream_t)stream, (const float4*)g, n4, g + n4 * 4, (int)(n - n4 * 4), work);
+    SDE_CHECK_LAUNCH("sde_grad_norm/partial");
+    hipLaunchKernelGGL(grad_norm_finalize_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)work, (int)nwg, grad_scale, max_norm, clip_state);
+    SDE_CHECK_LAUNCH("sde_grad_norm/finalize");
     return SDE_OK;
 }
 

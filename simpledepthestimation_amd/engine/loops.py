@@ -1,5 +1,6 @@
-"""The training loops of the two projects on the HIP path (the part the reference actually runs:
-projects/MonoDepth2/train.py:L44-121 ``do_train`` / L35-41 ``do_test`` and projects/Supervised/train.py:L70-140).
+"""The training loops of the three projects on the HIP path (the part the reference actually runs:
+projects/MonoDepth2/train.py:L44-121 ``do_train`` / L35-41 ``do_test``, projects/Supervised/train.py:L70-140 and
+projects/MotionLearning/train.py:L63-174 without its image dumps).
 
 Same order of events as the reference: resume_or_load -> for epoch: for batch: step, log every LOG_PERIOD -> LR schedule (MultiStepLR per
 epoch / polynomial per iteration) -> periodic checkpoint -> evaluation every TEST.EVAL_PERIOD epochs.  What differs, on purpose:
@@ -21,6 +22,7 @@ import torch.distributed as dist
 from ..checkpoint import DetectionCheckpointer, PeriodicCheckpointer
 from ..evaluation import build_evaluator, inference_on_dataset
 from ..modeling.depth_net.GoogleResNet import noise_ramp
+from ..modeling.pose_net.GoogleMotionNet import burn_in_weight
 from . import trainer as T
 
 log = logging.getLogger(__name__)
@@ -82,8 +84,10 @@ def do_train(cfg, model, data_loader, data_loader_test=None, resume=False, use_g
     core = model.module if hasattr(model, "module") and isinstance(model.module, torch.nn.Module) else model
     core.train()
     supervised = cfg.MODEL.META_ARCHITECTURE == "SupDepthModel"
+    motion = cfg.MODEL.META_ARCHITECTURE == "MotionLearningModel"
     graph = (next(core.parameters()).is_cuda if use_graph is None else use_graph)
-    tr = (T.supervised_trainer if supervised else T.monodepth2_trainer)(core, cfg, use_graph=graph)
+    # MotionLearning/train.py:L69-73,L157: Adam with eps 1e-7 and gradient-norm clipping; its LR rule is MonoDepth2's (MultiStepLR per epoch, two groups)
+    tr = (T.supervised_trainer if supervised else T.motion_learning_trainer if motion else T.monodepth2_trainer)(core, cfg, use_graph=graph)
     sched = EpochSchedule()
     ckpt = DetectionCheckpointer(core, cfg.OUTPUT_DIR, optimizer=tr, scheduler=sched)
     periodic = PeriodicCheckpointer(ckpt, cfg.SOLVER.CHECKPOINT_PERIOD, max_iter=cfg.SOLVER.MAX_EPOCHS)
@@ -111,6 +115,8 @@ def do_train(cfg, model, data_loader, data_loader_test=None, resume=False, use_g
         if losses:
             rec.update(total_loss=sum(losses.values()), **losses)
         rec.update(extra or {})
+        if motion:      # MotionLearning/train.py:L128-131 puts these every step; here they are read with the losses, once per flush
+            rec.update(motion_scalars())
         if _main():
             with open(out_path, "a") as f:
                 f.write(json.dumps(rec, sort_keys=True) + "\n")
@@ -123,6 +129,24 @@ def do_train(cfg, model, data_loader, data_loader_test=None, resume=False, use_g
     noisy = depth_net if hasattr(depth_net, "set_stddev") else None
     ramp = noisy is not None and cfg.MODEL.DEPTH_NET.get("RAMPUP_ITERS", 0) > 0
     noise = {}
+    # MotionLearning: the motion field's burn-in (train.py:L111-114) before every step when BURN_IN_ITERS > 0 -- the setter fills the device scalar the
+    # motion head reads, so a captured step follows it -- and the scalars its loop logs
+    pose_net = getattr(core, "pose_net", None)
+    burn_in = cfg.MODEL.POSE_NET.get("BURN_IN_ITERS", 0) if motion and hasattr(pose_net, "motion_weight") else 0
+
+    def motion_scalars():
+        out = {}
+        if hasattr(pose_net, "motion_weight"):
+            out["motion_weight"] = float(pose_net.motion_weight)
+        for k in ("trans_scale", "rot_scale"):
+            if torch.is_tensor(getattr(pose_net, k, None)):
+                out[k] = float(getattr(pose_net, k).detach())
+        if tr.clip_grad is not None:
+            out["grad_norm"] = float(tr.grad_norm())
+            # a non-finite gradient norm has already made the parameters NaN (as clip_grad_norm_ does in the reference): report it here, not a step later
+            assert out["grad_norm"] == out["grad_norm"] and abs(out["grad_norm"]) != float("inf"), out
+        return out
+
     log.info("Starting training from iteration %d", start_epoch)
     for epoch in range(start_epoch, cfg.SOLVER.MAX_EPOCHS):
         for epoch_iter, data in enumerate(data_loader):
@@ -132,6 +156,8 @@ def do_train(cfg, model, data_loader, data_loader_test=None, resume=False, use_g
             if ramp:
                 noise["noise_stddev"] = noise_ramp(cfg.MODEL.DEPTH_NET.NOISE_STDDEV, cfg.MODEL.DEPTH_NET.RAMPUP_ITERS, global_step)
                 noisy.set_stddev(noise["noise_stddev"])
+            if burn_in > 0:
+                pose_net.motion_weight = burn_in_weight(global_step, burn_in)
             meter.add(tr.step(data))
             if (epoch_iter + 1) % cfg.LOG_PERIOD == 0:
                 write(noise)

@@ -74,7 +74,8 @@ class HipTrainer:
     """Owns the flat buffers and runs one training step: loss dict = trainer.step(batch)."""
 
     def __init__(self, model, groups, adamw=False, betas=(0.9, 0.999), eps=1e-8, bucket_mb=64, use_graph=False, skip_unused=(".fc.",),
-                 adam_fn=None, overlap=None, late_from=("layer3",), cut_owner=None, amp=False, init_scale=65536.0, growth_interval=2000, pose_stream=True, cu_reserve=None):
+                 adam_fn=None, overlap=None, late_from=("layer3",), cut_owner=None, amp=False, init_scale=65536.0, growth_interval=2000, pose_stream=True, cu_reserve=None,
+                 clip_grad=None, clip_fn=None):
         self.model = model
         kinds = {type(m).__name__ for m in model.modules()}
         family = "packnet" if "PackNet01" in kinds else "resnet" if ("Bottleneck" in kinds or "BasicBlock" not in kinds) else "resnet_basic"
@@ -127,6 +128,16 @@ class HipTrainer:
         # + the count of APPLIED optimizer steps: GradScaler.step skips optimizer.step() on overflow, so Adam's `step` (bias corrections) must not
         # advance then -- the Adam kernel derives its bias corrections from this device-side count, self.t only counts calls
         self.scale_state = torch.tensor([float(init_scale), 0.0, 0.0, 0.0], device=dev, dtype=torch.float32) if self.amp else None
+        # gradient-norm clipping (nn.utils.clip_grad_norm_ of projects/MotionLearning/train.py:L157): the norm kernel leaves {total_norm, clip_coef} on
+        # the device behind the all-reduce and the Adam kernel multiplies the gradient by the coefficient; None or 0 (SOLVER.CLIP_GRAD's default): off
+        self.clip_grad = float(clip_grad) if clip_grad else None
+        if self.clip_grad is not None and not self.clip_grad > 0:
+            raise ValueError(f"clip_grad must be positive (or None / 0 for no clipping), got {clip_grad}")
+        if self.clip_grad is not None and self.amp:
+            raise ValueError("clip_grad with amp=True is not supported: the reference never combines them and the order of unscale and clip is not designed")
+        self._clip_fn = clip_fn or HN.grad_norm         # CPU tests substitute a torch restatement, as with adam_fn
+        self.clip_state = torch.zeros(2, device=dev, dtype=torch.float32) if self.clip_grad is not None else None
+        self._clip_work = torch.zeros(HN.GRAD_NORM_WORK, device=dev, dtype=torch.float32) if self.clip_grad is not None else None
         # ---- gradient buckets for the all-reduce (contiguous slices of the flat gradient)
         per = max(1, int(bucket_mb * (1 << 20) / 4))
         self.buckets = [(s, min(total, s + per)) for s in range(0, total, per)]
@@ -347,8 +358,19 @@ class HipTrainer:
             self._adam_fn(self.pflat, self.gflat, self.m, self.v, self.seg_end, lrs, wds, bias_corr, b1, b2, self.eps, 1.0 / self.world, self.adamw,
                           scale_state=self.scale_state)
             HN.loss_scale_update(self.scale_state, 2.0, 0.5, self.growth_interval)
+        elif self.clip_grad is not None:
+            # the all-reduce left the SUM over ranks: 1/world makes it the norm of the averaged gradient, the one every rank of the reference clips
+            self._clip_fn(self.gflat, self.clip_state, self.clip_grad, 1.0 / self.world, self._clip_work)
+            self._adam_fn(self.pflat, self.gflat, self.m, self.v, self.seg_end, lrs, wds, bias_corr, b1, b2, self.eps, 1.0 / self.world, self.adamw,
+                          clip_state=self.clip_state)
         else:
             self._adam_fn(self.pflat, self.gflat, self.m, self.v, self.seg_end, lrs, wds, bias_corr, b1, b2, self.eps, 1.0 / self.world, self.adamw)
+
+    def grad_norm(self):
+        """The last step's total gradient norm (what clip_grad_norm_ returns) as a 0-d device tensor: a view of the clip state, no host sync."""
+        if self.clip_state is None:
+            raise RuntimeError("grad_norm(): this trainer was built without clip_grad")
+        return self.clip_state[0]
 
     # ------------------------------------------------------------------------------------------------------------
     # ---- hipGraph path: the batch dicts of the reference's collate (data/datasets/kitti_v2.py:L196-221) hold, besides tensors, numpy
@@ -523,6 +545,15 @@ def monodepth2_trainer(model, cfg, **kw):
     groups = [ParamGroup("Depth", m.depth_net.named_parameters(prefix="depth_net"), cfg.SOLVER.DEPTH_LR, 0.0),
               ParamGroup("Pose", m.pose_net.named_parameters(prefix="pose_net"), cfg.SOLVER.POSE_LR, 0.0)]
     return HipTrainer(m, groups, adamw=False, eps=1e-8, **_amp_kw(cfg, kw))
+
+
+def motion_learning_trainer(model, cfg, **kw):
+    """Adam(depth lr, pose lr, wd 0, eps 1e-7) and clip_grad_norm_(SOLVER.CLIP_GRAD) -- projects/MotionLearning/train.py:L69-73,L157."""
+    m = model.module if hasattr(model, "module") else model
+    groups = [ParamGroup("Depth", m.depth_net.named_parameters(prefix="depth_net"), cfg.SOLVER.DEPTH_LR, 0.0),
+              ParamGroup("Pose", m.pose_net.named_parameters(prefix="pose_net"), cfg.SOLVER.POSE_LR, 0.0)]
+    kw.setdefault("clip_grad", float(cfg.SOLVER.get("CLIP_GRAD", 0)) or None)
+    return HipTrainer(m, groups, adamw=False, eps=1e-7, **_amp_kw(cfg, kw))
 
 
 def poly_lr(cfg, global_step, max_iter):

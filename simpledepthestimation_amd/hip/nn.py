@@ -83,6 +83,7 @@ L.register_protos({
     "sde_conv3d_wgrad": ([_P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P], c_int),
     "sde_adam_step": ([_P, _P, _P, _P, _LG, _P, _P], c_int),
     "sde_grad_check": ([_P, _LG, _P, _P], c_int),
+    "sde_grad_norm": ([_P, _LG, _P, _P, _F, _F, _P], c_int),
     "sde_loss_scale_update": ([_P, _F, _F, _I, _P], c_int),
 })
 
@@ -1150,18 +1151,21 @@ def conv3d_pack(x, weight, bias):
 # Fused Adam / AdamW over a flat buffer
 # ---------------------------------------------------------------------------------------------------------------
 ADAM_MAX_SEG = 8       # SDE_ADAM_MAX_SEG
+GRAD_NORM_WORK = 1024  # SDE_GRAD_NORM_WORK: floats of sde_grad_norm's workspace
 
 
 class AdamDesc(Structure):
     _fields_ = [("seg_end", c_long * ADAM_MAX_SEG), ("seg_lr", c_float * ADAM_MAX_SEG), ("seg_wd", c_float * ADAM_MAX_SEG), ("nseg", c_int32),
                 ("decoupled_wd", c_int32), ("beta1", c_float), ("beta2", c_float), ("eps", c_float), ("bias_corr1", c_float), ("bias_corr2", c_float),
-                ("grad_scale", c_float), ("scale_state", c_void_p), ("beta1_d", ctypes.c_double), ("beta2_d", ctypes.c_double)]
+                ("grad_scale", c_float), ("scale_state", c_void_p), ("beta1_d", ctypes.c_double), ("beta2_d", ctypes.c_double), ("clip_state", c_void_p)]
 
 
-def adam_step(p, g, m, v, seg_end, seg_lr, seg_wd, bias_corr, beta1=0.9, beta2=0.999, eps=1e-8, grad_scale=1.0, decoupled_wd=False, scale_state=None):
+def adam_step(p, g, m, v, seg_end, seg_lr, seg_wd, bias_corr, beta1=0.9, beta2=0.999, eps=1e-8, grad_scale=1.0, decoupled_wd=False, scale_state=None,
+              clip_state=None):
     """seg_end / seg_lr / seg_wd: HOST sequences (one entry per segment); everything travels by value in the kernel arguments.
     scale_state: optional device float[4] {loss_scale, found_inf, growth_tracker, applied_steps} (fp16 dynamic loss scaling); with it the
-    kernel forms the bias corrections itself from the device-side count of APPLIED steps and `bias_corr` is ignored."""
+    kernel forms the bias corrections itself from the device-side count of APPLIED steps and `bias_corr` is ignored.
+    clip_state: optional device float[2] {total_norm, clip_coef} that grad_norm() filled: the gradient enters the update times clip_coef."""
     nseg = len(seg_end)
     if not (0 < nseg <= ADAM_MAX_SEG and len(seg_lr) == nseg and len(seg_wd) == nseg):
         raise L.SdeHipError(f"adam_step: {nseg} segments (at most {ADAM_MAX_SEG})")
@@ -1172,6 +1176,9 @@ def adam_step(p, g, m, v, seg_end, seg_lr, seg_wd, bias_corr, beta1=0.9, beta2=0
     d.beta1, d.beta2, d.eps, d.bias_corr1, d.bias_corr2, d.grad_scale = beta1, beta2, eps, float(bias_corr[0]), float(bias_corr[1]), grad_scale
     d.scale_state = scale_state.data_ptr() if scale_state is not None else None
     d.beta1_d, d.beta2_d = float(beta1), float(beta2)
+    if clip_state is not None and not (clip_state.is_cuda and clip_state.dtype == torch.float32 and clip_state.is_contiguous() and clip_state.numel() >= 2):
+        raise L.SdeHipError("adam_step: clip_state must be a device float32 tensor of 2 elements {total_norm, clip_coef}")
+    d.clip_state = clip_state.data_ptr() if clip_state is not None else None
     if scale_state is not None and scale_state.numel() < 4:
         raise L.SdeHipError("adam_step: scale_state must hold 4 floats {loss_scale, found_inf, growth_tracker, applied_steps}")
     L.check(L.lib().sde_adam_step(L.ptr(p), L.ptr(g), L.ptr(m), L.ptr(v), p.numel(), ctypes.byref(d), L.stream()), "sde_adam_step")
@@ -1180,6 +1187,18 @@ def adam_step(p, g, m, v, seg_end, seg_lr, seg_wd, bias_corr, beta1=0.9, beta2=0
 def grad_check(g, scale_state):
     """scale_state[1] = 1 when any element of the flat fp32 gradient is inf / nan (device side, no host sync)."""
     L.check(L.lib().sde_grad_check(L.ptr(g), g.numel(), L.ptr(scale_state), L.stream()), "sde_grad_check")
+
+
+def grad_norm(g, clip_state, max_norm, grad_scale=1.0, work=None):
+    """clip_state[0] = grad_scale * ||g||_2 over the flat fp32 gradient, clip_state[1] = min(1, max_norm / (clip_state[0] + 1e-6)): torch's
+    clip_grad_norm_ coefficient, left on the device for adam_step(clip_state=...) (no host sync, no atomics; g is read once and not changed).
+    work: device float32[GRAD_NORM_WORK] scratch (allocated when None)."""
+    if work is None:
+        work = torch.empty(GRAD_NORM_WORK, device=g.device, dtype=torch.float32)
+    if g.dtype != torch.float32 or clip_state.dtype != torch.float32 or work.dtype != torch.float32 or clip_state.numel() < 2 or work.numel() < GRAD_NORM_WORK:
+        raise L.SdeHipError(f"grad_norm: float32 tensors, clip_state of 2 and work of {GRAD_NORM_WORK} elements")
+    L.check(L.lib().sde_grad_norm(L.ptr(g), g.numel(), L.ptr(work), L.ptr(clip_state), float(grad_scale), float(max_norm), L.stream()), "sde_grad_norm")
+    return clip_state
 
 
 def loss_scale_update(scale_state, growth_factor=2.0, backoff_factor=0.5, growth_interval=2000):

@@ -58,6 +58,12 @@ def _get(node, key, default):
     return node.get(key, default) if hasattr(node, "get") else getattr(node, key, default)
 
 
+def burn_in_weight(step, burn_in_iters):
+    """projects/MotionLearning/train.py:L111-114: the weight of the motion field at global step `step` (counted from 1) -- 0 over the first half of
+    the burn-in, then a linear ramp that reaches 1 at BURN_IN_ITERS."""
+    return min(max(2.0 * step / burn_in_iters - 1.0, 0.0), 1.0)
+
+
 def _head_vector(head, feat):
     """The 1x1 pose head on the spatial mean of the last feature map: [N,h,w,C] -> [N,6] fp32 (the mean is tiny: torch glue, as in PoseNet)."""
     mean = feat.float().mean(dim=(1, 2)).to(feat.dtype).view(feat.shape[0], 1, 1, feat.shape[3])
