@@ -89,7 +89,7 @@ int sde_photo_num_blocks(int B, int h, int w, int backward);
 
 /* Forward.  sampled[j] [B,3,h,w] (saved for backward), sel [B,h,w] u8 arg-min map index (order: warp0, id0, warp1, id1 ...),
  * maps (optional, may be NULL) [B,nmaps,h,w] the individual photometric maps, partial [sde_photo_num_blocks(...,0)] workspace.
- * loss_out[0] (+)= loss_scale * mean_over_pixels(reduced map). */
+ * loss_out[0] (+)= loss_scale * mean_over_pixels(reduced map).  This and sde_photo_bwd are the n = 1 case of the launch behind sde_photo_multi_fwd/_bwd. */
 int sde_photo_fwd(const sde_photo_desc* d, float* const* sampled, uint8_t* sel, float* maps, float* partial, float* loss_out,
                   float loss_scale, int accumulate, sde_stream_t stream);
 
@@ -138,7 +138,7 @@ int sde_ssim_bwd(const float* x, const float* y, const float* gout, int B, int C
 
 /* detectron2/modeling/losses/smoothness_loss.py:L42-80.  depth [B,1,h,w], img [B,3,h,w].
  * mean_part [B*32], dn [B,h,w], loss_part/s_part [sde_smooth_num_blocks] are caller workspaces that backward re-reads.
- * loss_out[0] (+)= loss_scale * smoothness_loss. */
+ * loss_out[0] (+)= loss_scale * smoothness_loss.  These two entries are the n = 1 case of the smoothness launches behind sde_mono_loss_fwd/_bwd. */
 int sde_smooth_num_blocks(int B, int h, int w);
 int sde_smooth_fwd(const float* depth, const float* img, int B, int h, int w, float* mean_part, float* dn, float* loss_part, float* s_part,
                    float* loss_out, float loss_scale, int accumulate, sde_stream_t stream);
@@ -147,7 +147,8 @@ int sde_smooth_bwd(const float* depth, const float* dn, const float* mean_part, 
 
 /* detectron2/modeling/losses/losses.py:L5-13 silog_loss against resize_img(depth_gt, 'nearest') (Supervised.py:L44-45), fused:
  * est [B,1,h,w], gt [B,1,H,W] full resolution (nearest-sampled in-kernel), mask gt > 1.  No compaction, no host sync.
- * part [sde_silog_num_blocks*3] workspace; stats[4] = (count, E[d], E[d^2], loss). */
+ * part [sde_silog_num_blocks*3] workspace; stats[4] = (count, E[d], E[d^2], loss).  These two entries are the n = 1, weight 1 case of the launches behind
+ * sde_silog_multi_fwd/_bwd. */
 int sde_silog_num_blocks(int B, int h, int w);
 int sde_silog_fwd(const float* est, const float* gt, int B, int h, int w, int H, int W, float variance_focus, float* part, float* stats,
                   sde_stream_t stream);

@@ -125,8 +125,8 @@ __device__ __forceinline__ float ssim_from_moments(float sx, float sy, float sxx
     return fminf(fmaxf((1.0f - n * __builtin_amdgcn_rcpf(d)) * 0.5f, 0.f), 1.f);     // v_rcp_f32 (1 ulp) instead of the 10-instruction IEEE division
 }
 
-// bx, by, bz / gdx, gdy: this workgroup's tile coordinates and the tile grid of ITS scale (the multi-scale launch packs the grids of all scales
-// into one linear grid; the single-scale launch passes blockIdx / gridDim)
+// bx, by, bz / gdx, gdy: this workgroup's tile coordinates and the tile grid of ITS scale (the launch packs the grids of all its scales into one
+// linear grid, photo_fwd_multi_kernel)
 template <int NCTX>
 __device__ __forceinline__ void photo_fwd_body(const PhotoArgs& a, const int bx, const int by, const int bz, const int gdx, const int gdy) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -238,14 +238,10 @@ __device__ __forceinline__ void photo_fwd_body(const PhotoArgs& a, const int bx,
     if (lp == 0) a.partial[(bz * gdy + by) * gdx + bx] = s;
 }
 
-template <int NCTX>
-__global__ void __launch_bounds__(FT_N) photo_fwd_kernel(PhotoArgs a) {
-    photo_fwd_body<NCTX>(a, blockIdx.x, blockIdx.y, blockIdx.z, gridDim.x, gridDim.y);
-}
-
 // All scales of the loss in ONE launch: the coarse scales are launch-sized on their own (31 / 19 / 14 us for 1/4 ... 1/64 of the pixels of the
 // 90 us full-resolution launch); packed behind the fine scale's workgroups they fill its tail instead.  Scale s owns the linear blocks
-// [first[s], first[s+1]); fine scale first, so the long workgroups start first.
+// [first[s], first[s+1]); fine scale first, so the long workgroups start first.  One scale on its own is the n = 1 case: the decode then yields
+// the (bx, by, bz) of a gdx x gdy x B grid.
 constexpr int PH_MAX_SCALES = 4;
 struct PhotoMulti {
     PhotoArgs a[PH_MAX_SCALES];
@@ -276,7 +272,7 @@ struct PhotoBwdArgs {
     const float* gout;      // device scalar: upstream gradient of this scale's reduced loss
     float* d_depth;         // [B,1,h,w]
     float* pose_partial;    // [nblocks][NCTX][12]  (dR row-major 9, dt 3)
-    int B, h, w, nctx, automask, reduce_mean, accumulate, clip;   // clip: sel carries LOSS.CLIP information (see photo_fwd_kernel)
+    int B, h, w, nctx, automask, reduce_mean, accumulate, clip;   // clip: sel carries LOSS.CLIP information (see photo_fwd_body)
     float sx, sy, ssim_w, C1, C2, gscale;   // gscale = 1/(B*h*w)  (mean over pixels)
 };
 
@@ -436,11 +432,6 @@ __device__ __forceinline__ void photo_bwd_body(const PhotoBwdArgs& a, const int 
     }
 }
 
-template <int NCTX, bool DENSE = false>
-__global__ void __launch_bounds__(BT_N, DENSE ? 6 : 1) photo_bwd_kernel(PhotoBwdArgs a) {
-    photo_bwd_body<NCTX>(a, blockIdx.x, blockIdx.y, blockIdx.z, gridDim.x, gridDim.y);
-}
-
 struct PhotoBwdMulti {
     PhotoBwdArgs a[PH_MAX_SCALES];
     int first[PH_MAX_SCALES + 1];
@@ -535,60 +526,22 @@ __global__ void __launch_bounds__(256) ssim_bwd_gather_kernel(const float* __res
     }
 }
 
-// Sum per-block pose partials of each sample into d_pose [NCTX][B][4][4] (last row zero).
-__global__ void pose_grad_finalize_kernel(const float* __restrict__ partial, int blocks_per_sample, int nctx, int B,
-                                          float* __restrict__ dpose0, float* __restrict__ dpose1, float* __restrict__ dpose2,
-                                          float* __restrict__ dpose3, int accumulate) {
-    // one wave per (sample, context): the lanes split the per-workgroup partials, then a fixed butterfly per output (deterministic)
-    const int b = blockIdx.x, j = blockIdx.y, lane = threadIdx.x;
-    float acc[12];
-#pragma unroll
-    for (int i = 0; i < 12; ++i) acc[i] = 0.f;
-    for (int k = lane; k < blocks_per_sample; k += 64) {
-        const float* p = partial + (((long)b * blocks_per_sample + k) * nctx + j) * 12;
-#pragma unroll
-        for (int i = 0; i < 12; ++i) acc[i] += p[i];
-    }
-#pragma unroll
-    for (int i = 0; i < 12; ++i) acc[i] = sde_wave_sum(acc[i]);
-    float* dp = j == 0 ? dpose0 : (j == 1 ? dpose1 : (j == 2 ? dpose2 : dpose3));
-    if (lane < 12) {
-        float s = 0.f;
-#pragma unroll
-        for (int i = 0; i < 12; ++i) s = lane == i ? acc[i] : s;
-        const int r = lane < 9 ? lane / 3 : lane - 9, c = lane < 9 ? lane % 3 : 3;
-        float* o = dp + b * 16 + r * 4 + c;
-        *o = accumulate ? (*o + s) : s;
-        if (!accumulate && lane < 4) dp[b * 16 + 12 + lane] = 0.f;
-    }
-}
-
 // ------------------------------------------------------------------------------------------------
-// Deterministic sum of a partial-sum slab: out[k] (+)= scale * sum(partial[0..n))
+// Deterministic sums of partial-sum slabs, one workgroup per slab: out[k] (+)= scale[k] * sum(partial_k[0..n_k))
 // ------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) reduce_partials_kernel(const float* __restrict__ partial, int n, float scale, float* __restrict__ out,
-                                                              int accumulate) {
-    __shared__ float red[16];
-    float s = 0.f;
-    for (int i = threadIdx.x; i < n; i += 256) s += partial[i];
-    s = sde_block_sum(s, red);
-    if (threadIdx.x == 0) out[0] = accumulate ? out[0] + s * scale : s * scale;
-}
-
-// one workgroup per scale: out[s] = scale[s] * sum(partial_s[0..n_s))  (the same fixed order as reduce_partials_kernel: per-scale losses bit-identical)
-struct MultiReduce { const float* partial[PH_MAX_SCALES]; int n[PH_MAX_SCALES]; float scale[PH_MAX_SCALES]; };
-__global__ void __launch_bounds__(256) reduce_partials_multi_kernel(const MultiReduce r, float* __restrict__ out) {
+struct MultiReduce { const float* partial[PH_MAX_SCALES]; int n[PH_MAX_SCALES]; float scale[PH_MAX_SCALES]; int accumulate; };
+__global__ void __launch_bounds__(256) reduce_partials_kernel(const MultiReduce r, float* __restrict__ out) {
     __shared__ float red[16];
     const int k = blockIdx.x;
     float s = 0.f;
     for (int i = threadIdx.x; i < r.n[k]; i += 256) s += r.partial[k][i];
     s = sde_block_sum(s, red);
-    if (threadIdx.x == 0) out[k] = s * r.scale[k];
+    if (threadIdx.x == 0) out[k] = r.accumulate ? out[k] + s * r.scale[k] : s * r.scale[k];
 }
 
-// pose gradients of all scales: one wave per (sample, context) walks the scales' partial slabs in order (scale-by-scale, the order in which the
-// per-scale finalize launches used to accumulate)
-struct MultiPose { const float* partial[PH_MAX_SCALES]; int blocks_per_sample[PH_MAX_SCALES]; int n; };
+// Sum the per-workgroup pose partials of each sample into d_pose [NCTX][B][4][4] (last row zero): one wave per (sample, context) walks the scales'
+// partial slabs in order, the lanes split a slab's partials, then a fixed butterfly per output (deterministic); the scales add up in scale order
+struct MultiPose { const float* partial[PH_MAX_SCALES]; int blocks_per_sample[PH_MAX_SCALES]; int n, accumulate; };
 __global__ void pose_grad_finalize_multi_kernel(const MultiPose mp, int nctx, int B, float* __restrict__ dpose0, float* __restrict__ dpose1,
                                                 float* __restrict__ dpose2, float* __restrict__ dpose3) {
     const int b = blockIdx.x, j = blockIdx.y, lane = threadIdx.x;
@@ -614,8 +567,9 @@ __global__ void pose_grad_finalize_multi_kernel(const MultiPose mp, int nctx, in
 #pragma unroll
         for (int i = 0; i < 12; ++i) s = lane == i ? tot[i] : s;
         const int r = lane < 9 ? lane / 3 : lane - 9, c = lane < 9 ? lane % 3 : 3;
-        dp[b * 16 + r * 4 + c] = s;
-        if (lane < 4) dp[b * 16 + 12 + lane] = 0.f;
+        float* o = dp + b * 16 + r * 4 + c;
+        *o = mp.accumulate ? (*o + s) : s;
+        if (!mp.accumulate && lane < 4) dp[b * 16 + 12 + lane] = 0.f;
     }
 }
 
@@ -632,10 +586,6 @@ __device__ __forceinline__ void smooth_mean_body(const float* __restrict__ depth
     for (int i = lo + threadIdx.x; i < hi; i += 256) s += 1.0f / fmaxf(depth[(long)b * hw + i], 1e-6f);
     s = sde_block_sum(s, red);
     if (threadIdx.x == 0) part[b * SM_CHUNKS + ch] = s;
-}
-
-__global__ void __launch_bounds__(256) smooth_mean_kernel(const float* __restrict__ depth, int hw, float* __restrict__ part) {
-    smooth_mean_body(depth, hw, part, blockIdx.y, blockIdx.x);
 }
 
 // forward + the upstream-independent part of the backward:
@@ -714,11 +664,6 @@ __device__ __forceinline__ void smooth_fwd_body(const float* __restrict__ depth,
     if (threadIdx.x == 0 && s_part) s_part[blk] = ss;
 }
 
-__global__ void __launch_bounds__(256) smooth_fwd_kernel(const float* __restrict__ depth, const float* __restrict__ img, const float* __restrict__ mean_part,
-                                                         int B, int h, int w, float* __restrict__ dn, float* __restrict__ loss_part, float* __restrict__ s_part) {
-    smooth_fwd_body(depth, img, mean_part, B, h, w, dn, loss_part, s_part, blockIdx.x, blockIdx.y, blockIdx.z, gridDim.x, gridDim.y);
-}
-
 __device__ __forceinline__ void smooth_bwd_body(const float* __restrict__ depth, const float* __restrict__ dn,
                                                 const float* __restrict__ mean_part, const float* __restrict__ s_part,
                                                 int blocks_per_sample, const float* __restrict__ gout, float gscale,
@@ -753,15 +698,10 @@ __device__ __forceinline__ void smooth_bwd_body(const float* __restrict__ depth,
     d_depth[p] = accumulate ? d_depth[p] + g * dd : g * dd;
 }
 
-__global__ void __launch_bounds__(256) smooth_bwd_kernel(const float* __restrict__ depth, const float* __restrict__ dn, const float* __restrict__ mean_part,
-                                                         const float* __restrict__ s_part, int blocks_per_sample, const float* __restrict__ gout, float gscale,
-                                                         int h, int w, float* __restrict__ d_depth, int accumulate) {
-    smooth_bwd_body(depth, dn, mean_part, s_part, blocks_per_sample, gout, gscale, h, w, d_depth, accumulate, blockIdx.x, blockIdx.y, blockIdx.z);
-}
-
 // Every scale of MonoDepth2's loss loop (MonoDepth2.py:L78-126) behind one launch per pass: the smoothness kernels over a linear grid whose block ranges
-// belong to the scales (each scale keeps the block partition of its single-scale launch, so every partial sum is the one that launch writes), and ONE
-// finalize for the photometric and the smoothness partial slabs that also forms the two weighted totals the reference accumulates scale by scale.
+// belong to the scales (a scale's block partition -- 64 x 4 pixel tiles, sample-major -- does not depend on the scales packed next to it, so neither do its
+// partial sums; one scale on its own is the n = 1 case), and ONE finalize for the photometric and the smoothness partial slabs that also forms the two
+// weighted totals the reference accumulates scale by scale.
 struct SmoothArgs { const float* depth; const float* img; float* mean_part; float* dn; float* loss_part; float* s_part; const float* gout; float* d_depth; float gscale; int h, w; };
 struct SmoothMulti {
     SmoothArgs a[PH_MAX_SCALES];
@@ -828,76 +768,15 @@ __global__ void __launch_bounds__(256) mono_loss_finalize_kernel(const MonoReduc
 // ------------------------------------------------------------------------------------------------
 // Masked SILog (losses.py:L10-13) against nearest-resized ground truth, no compaction, no host sync
 // ------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) silog_fwd_kernel(const float* __restrict__ est, const float* __restrict__ gt, int B, int h, int w,
-                                                        int H, int W, float sh_, float sw_, float* __restrict__ part /*[nblk][3]*/) {
-    __shared__ float red[16];
-    const long n = (long)B * h * w;
-    float c = 0.f, s1 = 0.f, s2 = 0.f;
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
-        const int x = (int)(i % w), y = (int)((i / w) % h), b = (int)(i / ((long)w * h));
-        const int ys = min((int)floorf((float)y * sh_), H - 1), xs = min((int)floorf((float)x * sw_), W - 1);
-        const float g = gt[((long)b * H + ys) * W + xs];
-        if (g > 1.0f) {
-            const float d = logf(est[i]) - logf(g);
-            c += 1.f; s1 += d; s2 += d * d;
-        }
-    }
-    c = sde_block_sum(c, red);
-    if (threadIdx.x == 0) part[blockIdx.x * 3 + 0] = c;
-    s1 = sde_block_sum(s1, red);
-    if (threadIdx.x == 0) part[blockIdx.x * 3 + 1] = s1;
-    s2 = sde_block_sum(s2, red);
-    if (threadIdx.x == 0) part[blockIdx.x * 3 + 2] = s2;
-}
-
-// stats[0..3] = (count, mean d, mean d^2, loss); loss = 10 * sqrt(E[d^2] - vf * E[d]^2)
-__global__ void silog_finalize_kernel(const float* __restrict__ part, int nblk, float vf, float* __restrict__ stats) {
-    __shared__ double sh[3][64];
-    const int t = threadIdx.x;
-    double c = 0, s1 = 0, s2 = 0;
-    for (int i = t; i < nblk; i += 64) { c += part[i * 3]; s1 += part[i * 3 + 1]; s2 += part[i * 3 + 2]; }
-    sh[0][t] = c; sh[1][t] = s1; sh[2][t] = s2;
-    __syncthreads();
-    if (t == 0) {
-        c = s1 = s2 = 0;
-        for (int i = 0; i < 64; ++i) { c += sh[0][i]; s1 += sh[1][i]; s2 += sh[2][i]; }
-        const double m1 = s1 / c, m2 = s2 / c;
-        stats[0] = (float)c; stats[1] = (float)m1; stats[2] = (float)m2;
-        stats[3] = (float)(sqrt(m2 - (double)vf * m1 * m1) * 10.0);
-    }
-}
-
-__global__ void __launch_bounds__(256) silog_bwd_kernel(const float* __restrict__ est, const float* __restrict__ gt, const float* __restrict__ stats,
-                                                        const float* __restrict__ gout, float gscale, float vf, int B, int h, int w, int H,
-                                                        int W, float sh_, float sw_, float* __restrict__ d_est, int accumulate) {
-    const long n = (long)B * h * w;
-    const float cnt = stats[0], m1 = stats[1], loss = stats[3];
-    const float g = gout[0] * gscale;
-    // d loss / d d_i = (100 / loss) * (d_i - vf * m1) / cnt        [loss = 10 sqrt(v), dv/dd_i = 2 d_i/cnt - 2 vf m1/cnt]
-    const float k = (loss > 0.f) ? 100.0f / (loss * cnt) : 0.f;
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
-        const int x = (int)(i % w), y = (int)((i / w) % h), b = (int)(i / ((long)w * h));
-        const int ys = min((int)floorf((float)y * sh_), H - 1), xs = min((int)floorf((float)x * sw_), W - 1);
-        const float gv = gt[((long)b * H + ys) * W + xs];
-        float r = 0.f;
-        if (gv > 1.0f) {
-            const float e = est[i];
-            const float d = logf(e) - logf(gv);
-            r = g * k * (d - vf * m1) / e;
-        }
-        d_est[i] = accumulate ? d_est[i] + r : r;
-    }
-}
-
-// The multi-scale form of the three kernels above (Supervised.py:L42-47 sums the loss of the four prediction scales against one ground truth):
-// every scale keeps the block partition and the summation order of the single-scale launch (bit-identical per-scale statistics), the launches are
-// one per phase instead of one per scale, and the finalize also forms sum_k weight[k] * loss[k].
+// Up to SDE_SILOG_MAX_SCALES prediction scales against one ground truth behind one launch per phase (Supervised.py:L42-47 sums the loss of the four decoder
+// scales): scale k owns the blocks [blk_end[k-1], blk_end[k]), sde_silog_num_blocks of them, which stride over its pixels -- a partition and a summation order
+// that do not depend on the other scales, so a scale's statistics are the same bit for bit alone (n = 1, the single-scale entries) or packed.
 struct SilogScales {
     const float* est[SDE_SILOG_MAX_SCALES];
     float* d_est[SDE_SILOG_MAX_SCALES];
     int h[SDE_SILOG_MAX_SCALES], w[SDE_SILOG_MAX_SCALES], blk_end[SDE_SILOG_MAX_SCALES];
     float sh[SDE_SILOG_MAX_SCALES], sw[SDE_SILOG_MAX_SCALES], weight[SDE_SILOG_MAX_SCALES];
-    int n;
+    int n, accumulate;      // accumulate: the backward adds to d_est
 };
 
 __device__ __forceinline__ int silog_scale_of(const SilogScales& a, int blk, int& first, int& count) {
@@ -934,8 +813,8 @@ __global__ void __launch_bounds__(256) silog_multi_fwd_kernel(SilogScales a, con
     if (threadIdx.x == 0) part[blockIdx.x * 3 + 2] = s2;
 }
 
-// stats[k][0..3] as silog_finalize_kernel; total[0] = sum_k weight[k] * loss[k] (scales in order, fp32).  One wave per scale, each doing exactly what the
-// single-scale finalize does (same lanes, same order), side by side.
+// stats[k][0..3] = (count, mean d, mean d^2, loss) with loss = 10 * sqrt(E[d^2] - vf * E[d]^2); total[0] (optional) = sum_k weight[k] * loss[k] (scales in
+// order, fp32).  One wave per scale, side by side: the lanes split the scale's block partials, lane 0 adds the 64 lane sums in order (fp64).
 __global__ void __launch_bounds__(64 * SDE_SILOG_MAX_SCALES) silog_multi_finalize_kernel(const float* __restrict__ part, SilogScales a, float vf,
                                                                                          float* __restrict__ stats, float* __restrict__ total) {
     __shared__ double sh[SDE_SILOG_MAX_SCALES][3][64];
@@ -958,7 +837,7 @@ __global__ void __launch_bounds__(64 * SDE_SILOG_MAX_SCALES) silog_multi_finaliz
         stats[4 * k + 3] = loss[k];
     }
     __syncthreads();
-    if (threadIdx.x == 0) {
+    if (total && threadIdx.x == 0) {
         float s = 0.f;
         for (int j = 0; j < a.n; ++j) s += a.weight[j] * loss[j];
         total[0] = s;
@@ -976,6 +855,7 @@ __global__ void __launch_bounds__(256) silog_multi_bwd_kernel(SilogScales a, con
     const long n = (long)B * h * w;
     const float cnt = stats[4 * k], m1 = stats[4 * k + 1], loss = stats[4 * k + 3];
     const float g = gout[0] * gscale * a.weight[k];
+    // d loss / d d_i = (100 / loss) * (d_i - vf * m1) / cnt        [loss = 10 sqrt(v), dv/dd_i = 2 d_i/cnt - 2 vf m1/cnt]
     const float kk = (loss > 0.f) ? 100.0f / (loss * cnt) : 0.f;
     for (long i = (long)(blockIdx.x - first) * 256 + threadIdx.x; i < n; i += (long)count * 256) {
         const int x = (int)(i % w), y = (int)((i / w) % h), b = (int)(i / ((long)w * h));
@@ -987,7 +867,7 @@ __global__ void __launch_bounds__(256) silog_multi_bwd_kernel(SilogScales a, con
             const float d = logf(e) - logf(gv);
             r = g * kk * (d - vf * m1) / e;
         }
-        d_est[i] = r;
+        d_est[i] = a.accumulate ? d_est[i] + r : r;
     }
 }
 
@@ -1077,103 +957,34 @@ int sde_photo_num_blocks(int B, int h, int w, int backward) {
     return sde_cdiv(w, FT_W - 2) * sde_cdiv(h, FT_H - 2) * B;
 }
 
-int sde_photo_fwd(const sde_photo_desc* d, float* const* sampled, uint8_t* sel, float* maps, float* partial, float* loss_out,
-                  float loss_scale, int accumulate, sde_stream_t stream) {
-    SDE_CHECK_ARG(d && d->A && d->depth && d->K && partial && loss_out, "sde_photo_fwd: null pointer");
-    SDE_CHECK_ARG(d->nctx >= 1 && d->nctx <= SDE_MAX_CTX, "sde_photo_fwd: nctx=%d out of range", d->nctx);
-    SDE_CHECK_ARG(d->B > 0 && d->h >= 4 && d->w >= 4, "sde_photo_fwd: bad shape B=%d h=%d w=%d", d->B, d->h, d->w);
-    PhotoArgs a;
-    a.A = d->A; a.depth = d->depth; a.K = d->K; a.sel = sel; a.partial = partial; a.maps = maps; a.thr = d->clip_thr;
-    for (int j = 0; j < SDE_MAX_CTX; ++j) {
-        a.ctx[j] = j < d->nctx ? d->ctx[j] : nullptr;
-        a.pose[j] = j < d->nctx ? d->pose[j] : nullptr;
-        a.sampled[j] = (j < d->nctx && sampled) ? sampled[j] : nullptr;
-        SDE_CHECK_ARG(j >= d->nctx || (a.ctx[j] && a.pose[j]), "sde_photo_fwd: null ctx/pose %d", j);
-    }
-    a.B = d->B; a.h = d->h; a.w = d->w; a.nctx = d->nctx; a.automask = d->automask; a.reduce_mean = d->reduce_mean;
-    a.sx = d->sx; a.sy = d->sy; a.ssim_w = d->ssim_w; a.C1 = d->C1; a.C2 = d->C2;
-    dim3 grid(sde_cdiv(d->w, FT_W - 2), sde_cdiv(d->h, FT_H - 2), d->B), blk(FT_W, FT_H);
-    const size_t lds = photo_fwd_lds(d->nctx);
-    hipStream_t s = (hipStream_t)stream;
-    switch (d->nctx) {
-        case 1: hipLaunchKernelGGL(photo_fwd_kernel<1>, grid, blk, lds, s, a); break;
-        case 2: hipLaunchKernelGGL(photo_fwd_kernel<2>, grid, blk, lds, s, a); break;
-        case 3: hipLaunchKernelGGL(photo_fwd_kernel<3>, grid, blk, lds, s, a); break;
-        default: hipLaunchKernelGGL(photo_fwd_kernel<4>, grid, blk, lds, s, a); break;
-    }
-    SDE_CHECK_LAUNCH("sde_photo_fwd");
-    const int nblk = grid.x * grid.y * grid.z;
-    hipLaunchKernelGGL(reduce_partials_kernel, dim3(1), dim3(256), 0, s, partial, nblk, loss_scale / ((float)d->B * d->h * d->w), loss_out,
-                       accumulate);
-    SDE_CHECK_LAUNCH("sde_photo_fwd/reduce");
-    return SDE_OK;
-}
-
-int sde_photo_bwd(const sde_photo_desc* d, const float* const* sampled, const uint8_t* sel, const float* gout, float gscale,
-                  float* d_depth, int accumulate_depth, float* pose_partial, float* const* d_pose, int accumulate_pose,
-                  sde_stream_t stream) {
-    SDE_CHECK_ARG(d && d->A && d->depth && d->K && sampled && gout && d_depth && pose_partial && d_pose, "sde_photo_bwd: null pointer");
-    SDE_CHECK_ARG(d->nctx >= 1 && d->nctx <= SDE_MAX_CTX, "sde_photo_bwd: nctx=%d out of range", d->nctx);
-    SDE_CHECK_ARG(d->reduce_mean || sel, "sde_photo_bwd: sel required for min reduce");
-    PhotoBwdArgs a;
-    a.A = d->A; a.depth = d->depth; a.K = d->K; a.sel = sel; a.gout = gout; a.d_depth = d_depth; a.pose_partial = pose_partial;
-    for (int j = 0; j < SDE_MAX_CTX; ++j) {
-        a.ctx[j] = j < d->nctx ? d->ctx[j] : nullptr;
-        a.pose[j] = j < d->nctx ? d->pose[j] : nullptr;
-        a.sampled[j] = j < d->nctx ? sampled[j] : nullptr;
-        SDE_CHECK_ARG(j >= d->nctx || (a.ctx[j] && a.pose[j] && a.sampled[j] && d_pose[j]), "sde_photo_bwd: null ctx/pose/sampled %d", j);
-    }
-    a.B = d->B; a.h = d->h; a.w = d->w; a.nctx = d->nctx; a.automask = d->automask; a.reduce_mean = d->reduce_mean;
-    a.accumulate = accumulate_depth; a.clip = d->clip_thr != nullptr;
-    a.sx = d->sx; a.sy = d->sy; a.ssim_w = d->ssim_w; a.C1 = d->C1; a.C2 = d->C2;
-    a.gscale = gscale / ((float)d->B * d->h * d->w);
-    dim3 grid(sde_cdiv(d->w, BT_W - 4), sde_cdiv(d->h, BT_H - 4), d->B), blk(BT_W, BT_H);
-    hipStream_t s = (hipStream_t)stream;
-    const size_t lds = photo_bwd_lds();
-    const bool dense = (long)grid.x * grid.y * grid.z >= 1024;      // the grid fills three workgroups per CU (768) with a second round to spare
-    switch (d->nctx) {
-        case 1: hipLaunchKernelGGL(photo_bwd_kernel<1>, grid, blk, lds, s, a); break;
-        case 2:
-            if (dense) hipLaunchKernelGGL((photo_bwd_kernel<2, true>), grid, blk, lds, s, a);
-            else hipLaunchKernelGGL(photo_bwd_kernel<2>, grid, blk, lds, s, a);
-            break;
-        case 3: hipLaunchKernelGGL(photo_bwd_kernel<3>, grid, blk, lds, s, a); break;
-        default: hipLaunchKernelGGL(photo_bwd_kernel<4>, grid, blk, lds, s, a); break;
-    }
-    SDE_CHECK_LAUNCH("sde_photo_bwd");
-    hipLaunchKernelGGL(pose_grad_finalize_kernel, dim3(d->B, d->nctx), dim3(64), 0, s, pose_partial, (int)(grid.x * grid.y), d->nctx, d->B,
-                       d_pose[0], d->nctx > 1 ? d_pose[1] : nullptr, d->nctx > 2 ? d_pose[2] : nullptr, d->nctx > 3 ? d_pose[3] : nullptr,
-                       accumulate_pose);
-    SDE_CHECK_LAUNCH("sde_photo_bwd/finalize");
-    return SDE_OK;
-}
-
-static int fill_fwd_args(const sde_photo_desc* d, float* const* sampled, uint8_t* sel, float* partial, PhotoArgs& a) {
-    SDE_CHECK_ARG(d->A && d->depth && d->K && partial && sel, "sde_photo_multi_fwd: null pointer");
-    a.A = d->A; a.depth = d->depth; a.K = d->K; a.sel = sel; a.partial = partial; a.maps = nullptr; a.thr = nullptr;
-    for (int j = 0; j < SDE_MAX_CTX; ++j) {
-        a.ctx[j] = j < d->nctx ? d->ctx[j] : nullptr;
-        a.pose[j] = j < d->nctx ? d->pose[j] : nullptr;
-        a.sampled[j] = j < d->nctx ? sampled[j] : nullptr;
-        SDE_CHECK_ARG(j >= d->nctx || (a.ctx[j] && a.pose[j] && a.sampled[j]), "sde_photo_multi_fwd: null ctx / pose / sampled %d", j);
-    }
-    a.B = d->B; a.h = d->h; a.w = d->w; a.nctx = d->nctx; a.automask = d->automask; a.reduce_mean = d->reduce_mean;
-    a.sx = d->sx; a.sy = d->sy; a.ssim_w = d->ssim_w; a.C1 = d->C1; a.C2 = d->C2;
-    return SDE_OK;
-}
-
-static int photo_multi_fwd_launch(const sde_photo_desc* d, int n, float* const* sampled, uint8_t* const* sel, float* const* partial, hipStream_t st, MultiReduce& r) {
-    SDE_CHECK_ARG(d && sampled && sel && partial && n >= 1 && n <= PH_MAX_SCALES, "sde_photo_multi_fwd: bad argument (n=%d)", n);
+// ---- photometric term: ONE launch path per pass; sde_photo_fwd / sde_photo_bwd are its n = 1 case ----
+// who: the entry the caller used (error strings).  single: the contract of the n = 1 entries -- sampled, sel and maps are optional outputs, the descriptor may
+// carry clip thresholds; the multi-scale entries require the buffers and take no thresholds.  r receives the scales' partial slabs with their 1 / (B*h*w).
+static int photo_multi_fwd_launch(const char* who, bool single, const sde_photo_desc* d, int n, float* const* sampled, uint8_t* const* sel, float* maps,
+                                  float* const* partial, hipStream_t st, MultiReduce& r) {
+    SDE_CHECK_ARG(d && sel && partial && (single || sampled) && n >= 1 && n <= PH_MAX_SCALES, "%s: bad argument (n=%d)", who, n);
     PhotoMulti m;
     m.n = n; m.first[0] = 0;
+    r.accumulate = 0;
     for (int s = 0; s < n; ++s) {
-        SDE_CHECK_ARG(d[s].nctx == d[0].nctx && d[s].B == d[0].B && d[s].nctx >= 1 && d[s].nctx <= SDE_MAX_CTX && !d[s].clip_thr && d[s].B > 0 && d[s].h >= 4 && d[s].w >= 4,
-                      "sde_photo_multi_fwd: scale %d: same batch / contexts as scale 0, no clip thresholds, h, w >= 4", s);
-        int rc = fill_fwd_args(d + s, sampled + s * SDE_MAX_CTX, sel[s], partial[s], m.a[s]);
-        if (rc) return rc;
-        m.gdx[s] = sde_cdiv(d[s].w, FT_W - 2); m.gdy[s] = sde_cdiv(d[s].h, FT_H - 2);
-        m.first[s + 1] = m.first[s] + m.gdx[s] * m.gdy[s] * d[s].B;
-        r.partial[s] = partial[s]; r.n[s] = m.gdx[s] * m.gdy[s] * d[s].B; r.scale[s] = 1.0f / ((float)d[s].B * d[s].h * d[s].w);
+        const sde_photo_desc& ds = d[s];
+        SDE_CHECK_ARG(ds.A && ds.depth && ds.K && partial[s] && (single || sel[s]), "%s: scale %d: null pointer", who, s);
+        SDE_CHECK_ARG(ds.nctx >= 1 && ds.nctx <= SDE_MAX_CTX, "%s: nctx=%d out of range", who, ds.nctx);
+        SDE_CHECK_ARG(ds.B > 0 && ds.h >= 4 && ds.w >= 4, "%s: bad shape B=%d h=%d w=%d", who, ds.B, ds.h, ds.w);
+        SDE_CHECK_ARG(ds.nctx == d[0].nctx && ds.B == d[0].B && (single || !ds.clip_thr), "%s: scale %d: same batch / contexts as scale 0, no clip thresholds", who, s);
+        PhotoArgs& a = m.a[s];
+        a.A = ds.A; a.depth = ds.depth; a.K = ds.K; a.sel = sel[s]; a.partial = partial[s]; a.maps = maps; a.thr = ds.clip_thr;
+        for (int j = 0; j < SDE_MAX_CTX; ++j) {
+            a.ctx[j] = j < ds.nctx ? ds.ctx[j] : nullptr;
+            a.pose[j] = j < ds.nctx ? ds.pose[j] : nullptr;
+            a.sampled[j] = (j < ds.nctx && sampled) ? sampled[s * SDE_MAX_CTX + j] : nullptr;
+            SDE_CHECK_ARG(j >= ds.nctx || (a.ctx[j] && a.pose[j] && (single || a.sampled[j])), "%s: null ctx / pose / sampled %d", who, j);
+        }
+        a.B = ds.B; a.h = ds.h; a.w = ds.w; a.nctx = ds.nctx; a.automask = ds.automask; a.reduce_mean = ds.reduce_mean;
+        a.sx = ds.sx; a.sy = ds.sy; a.ssim_w = ds.ssim_w; a.C1 = ds.C1; a.C2 = ds.C2;
+        m.gdx[s] = sde_cdiv(ds.w, FT_W - 2); m.gdy[s] = sde_cdiv(ds.h, FT_H - 2);
+        m.first[s + 1] = m.first[s] + m.gdx[s] * m.gdy[s] * ds.B;
+        r.partial[s] = partial[s]; r.n[s] = m.gdx[s] * m.gdy[s] * ds.B; r.scale[s] = 1.0f / ((float)ds.B * ds.h * ds.w);
     }
     for (int s = n; s < PH_MAX_SCALES; ++s) { m.gdx[s] = m.gdy[s] = 1; m.first[s + 1] = m.first[n]; r.partial[s] = nullptr; r.n[s] = 0; r.scale[s] = 0.f; m.a[s] = m.a[0]; }
     const dim3 grid(m.first[n]), blk(FT_W, FT_H);
@@ -1184,43 +995,43 @@ static int photo_multi_fwd_launch(const sde_photo_desc* d, int n, float* const* 
         case 3: hipLaunchKernelGGL(photo_fwd_multi_kernel<3>, grid, blk, lds, st, m); break;
         default: hipLaunchKernelGGL(photo_fwd_multi_kernel<4>, grid, blk, lds, st, m); break;
     }
-    SDE_CHECK_LAUNCH("sde_photo_multi_fwd");
+    SDE_CHECK_LAUNCH(who);
     return SDE_OK;
 }
 
-int sde_photo_multi_fwd(const sde_photo_desc* d, int n, float* const* sampled, uint8_t* const* sel, float* const* partial, float* loss_out,
-                        sde_stream_t stream) {
-    SDE_CHECK_ARG(loss_out, "sde_photo_multi_fwd: null loss_out");
-    MultiReduce r;
-    hipStream_t st = (hipStream_t)stream;
-    const int rc = photo_multi_fwd_launch(d, n, sampled, sel, partial, st, r);
-    if (rc) return rc;
-    hipLaunchKernelGGL(reduce_partials_multi_kernel, dim3(n), dim3(256), 0, st, r, loss_out);
-    SDE_CHECK_LAUNCH("sde_photo_multi_fwd/reduce");
+static int pose_finalize_launch(const char* who, const MultiPose& mp, int nctx, int B, float* const* d_pose, hipStream_t st) {
+    hipLaunchKernelGGL(pose_grad_finalize_multi_kernel, dim3(B, nctx), dim3(64), 0, st, mp, nctx, B, d_pose[0], nctx > 1 ? d_pose[1] : nullptr,
+                       nctx > 2 ? d_pose[2] : nullptr, nctx > 3 ? d_pose[3] : nullptr);
+    SDE_CHECK_LAUNCH(who);
     return SDE_OK;
 }
 
-// gout + s * gout_stride is scale s's upstream gradient (a device scalar); weight (host, may be null) scales it further
-static int photo_multi_bwd_launch(const sde_photo_desc* d, int n, const float* const* sampled, const uint8_t* const* sel, const float* gout, int gout_stride,
-                                  const float* weight, float* const* d_depth, float* const* pose_partial, float* const* d_pose, hipStream_t st) {
-    // d_pose == NULL: the pose partials are left for sde_photo_multi_pose_finalize (which the caller may enqueue on another stream)
-    SDE_CHECK_ARG(d && sampled && sel && gout && d_depth && pose_partial && n >= 1 && n <= PH_MAX_SCALES, "sde_photo_multi_bwd: bad argument (n=%d)", n);
+// gout + s * gout_stride is scale s's upstream gradient (a device scalar); weight (host, may be null) scales it further.  single: the contract of sde_photo_bwd
+// (clip thresholds allowed, d_pose required); d_pose == NULL otherwise leaves the pose partials for sde_photo_multi_pose_finalize (which the caller may
+// enqueue on another stream)
+static int photo_multi_bwd_launch(const char* who, bool single, const sde_photo_desc* d, int n, const float* const* sampled, const uint8_t* const* sel, const float* gout,
+                                  int gout_stride, const float* weight, float* const* d_depth, int accumulate_depth, float* const* pose_partial, float* const* d_pose,
+                                  int accumulate_pose, hipStream_t st) {
+    SDE_CHECK_ARG(d && sampled && sel && gout && d_depth && pose_partial && (d_pose || !single) && n >= 1 && n <= PH_MAX_SCALES, "%s: bad argument (n=%d)", who, n);
     PhotoBwdMulti m;
     MultiPose mp;
-    m.n = mp.n = n; m.first[0] = 0;
+    m.n = mp.n = n; m.first[0] = 0; mp.accumulate = accumulate_pose;
     for (int s = 0; s < n; ++s) {
         const sde_photo_desc& ds = d[s];
-        SDE_CHECK_ARG(ds.nctx == d[0].nctx && ds.B == d[0].B && ds.nctx >= 1 && ds.nctx <= SDE_MAX_CTX && !ds.clip_thr && ds.A && ds.depth && ds.K && d_depth[s] && pose_partial[s] &&
-                      (ds.reduce_mean || sel[s]), "sde_photo_multi_bwd: scale %d: bad descriptor", s);
+        SDE_CHECK_ARG(ds.nctx >= 1 && ds.nctx <= SDE_MAX_CTX, "%s: nctx=%d out of range", who, ds.nctx);
+        SDE_CHECK_ARG(ds.nctx == d[0].nctx && ds.B == d[0].B && (single || !ds.clip_thr) && ds.A && ds.depth && ds.K && d_depth[s] && pose_partial[s],
+                      "%s: scale %d: bad descriptor", who, s);
+        SDE_CHECK_ARG(ds.reduce_mean || sel[s], "%s: sel required for min reduce", who);
         PhotoBwdArgs& a = m.a[s];
         a.A = ds.A; a.depth = ds.depth; a.K = ds.K; a.sel = sel[s]; a.gout = gout + s * gout_stride; a.d_depth = d_depth[s]; a.pose_partial = pose_partial[s];
         for (int j = 0; j < SDE_MAX_CTX; ++j) {
             a.ctx[j] = j < ds.nctx ? ds.ctx[j] : nullptr;
             a.pose[j] = j < ds.nctx ? ds.pose[j] : nullptr;
             a.sampled[j] = j < ds.nctx ? sampled[s * SDE_MAX_CTX + j] : nullptr;
-            SDE_CHECK_ARG(j >= ds.nctx || (a.ctx[j] && a.pose[j] && a.sampled[j] && (!d_pose || d_pose[j])), "sde_photo_multi_bwd: null ctx / pose / sampled %d", j);
+            SDE_CHECK_ARG(j >= ds.nctx || (a.ctx[j] && a.pose[j] && a.sampled[j] && (!d_pose || d_pose[j])), "%s: null ctx / pose / sampled %d", who, j);
         }
-        a.B = ds.B; a.h = ds.h; a.w = ds.w; a.nctx = ds.nctx; a.automask = ds.automask; a.reduce_mean = ds.reduce_mean; a.accumulate = 0; a.clip = 0;
+        a.B = ds.B; a.h = ds.h; a.w = ds.w; a.nctx = ds.nctx; a.automask = ds.automask; a.reduce_mean = ds.reduce_mean;
+        a.accumulate = accumulate_depth; a.clip = ds.clip_thr != nullptr;
         a.sx = ds.sx; a.sy = ds.sy; a.ssim_w = ds.ssim_w; a.C1 = ds.C1; a.C2 = ds.C2;
         a.gscale = (weight ? weight[s] : 1.0f) / ((float)ds.B * ds.h * ds.w);
         m.gdx[s] = sde_cdiv(ds.w, BT_W - 4); m.gdy[s] = sde_cdiv(ds.h, BT_H - 4);
@@ -1230,43 +1041,77 @@ static int photo_multi_bwd_launch(const sde_photo_desc* d, int n, const float* c
     for (int s = n; s < PH_MAX_SCALES; ++s) { m.gdx[s] = m.gdy[s] = 1; m.first[s + 1] = m.first[n]; m.a[s] = m.a[0]; mp.partial[s] = nullptr; mp.blocks_per_sample[s] = 0; }
     const dim3 grid(m.first[n]), blk(BT_W, BT_H);
     const size_t lds = photo_bwd_lds();
+    const bool dense = m.first[n] >= 1024;      // the grid fills three workgroups per CU (768) with a second round to spare
     switch (d[0].nctx) {
         case 1: hipLaunchKernelGGL((photo_bwd_multi_kernel<1, false>), grid, blk, lds, st, m); break;
         case 2:
-            if (m.first[n] >= 1024) hipLaunchKernelGGL((photo_bwd_multi_kernel<2, true>), grid, blk, lds, st, m);
+            if (dense) hipLaunchKernelGGL((photo_bwd_multi_kernel<2, true>), grid, blk, lds, st, m);
             else hipLaunchKernelGGL((photo_bwd_multi_kernel<2, false>), grid, blk, lds, st, m);
             break;
         case 3: hipLaunchKernelGGL((photo_bwd_multi_kernel<3, false>), grid, blk, lds, st, m); break;
         default: hipLaunchKernelGGL((photo_bwd_multi_kernel<4, false>), grid, blk, lds, st, m); break;
     }
-    SDE_CHECK_LAUNCH("sde_photo_multi_bwd");
-    if (!d_pose) return SDE_OK;
-    hipLaunchKernelGGL(pose_grad_finalize_multi_kernel, dim3(d[0].B, d[0].nctx), dim3(64), 0, st, mp, d[0].nctx, d[0].B, d_pose[0], d[0].nctx > 1 ? d_pose[1] : nullptr,
-                       d[0].nctx > 2 ? d_pose[2] : nullptr, d[0].nctx > 3 ? d_pose[3] : nullptr);
-    SDE_CHECK_LAUNCH("sde_photo_multi_bwd/finalize");
+    SDE_CHECK_LAUNCH(who);
+    return d_pose ? pose_finalize_launch(who, mp, d[0].nctx, d[0].B, d_pose, st) : SDE_OK;
+}
+
+int sde_photo_fwd(const sde_photo_desc* d, float* const* sampled, uint8_t* sel, float* maps, float* partial, float* loss_out,
+                  float loss_scale, int accumulate, sde_stream_t stream) {
+    SDE_CHECK_ARG(loss_out, "sde_photo_fwd: null pointer");
+    MultiReduce r;
+    hipStream_t st = (hipStream_t)stream;
+    const int rc = photo_multi_fwd_launch("sde_photo_fwd", true, d, 1, sampled, &sel, maps, &partial, st, r);
+    if (rc) return rc;
+    r.scale[0] = loss_scale / ((float)d->B * d->h * d->w); r.accumulate = accumulate;
+    hipLaunchKernelGGL(reduce_partials_kernel, dim3(1), dim3(256), 0, st, r, loss_out);
+    SDE_CHECK_LAUNCH("sde_photo_fwd/reduce");
+    return SDE_OK;
+}
+
+int sde_photo_bwd(const sde_photo_desc* d, const float* const* sampled, const uint8_t* sel, const float* gout, float gscale,
+                  float* d_depth, int accumulate_depth, float* pose_partial, float* const* d_pose, int accumulate_pose,
+                  sde_stream_t stream) {
+    return photo_multi_bwd_launch("sde_photo_bwd", true, d, 1, sampled, &sel, gout, 0, &gscale, &d_depth, accumulate_depth, &pose_partial, d_pose, accumulate_pose,
+                                  (hipStream_t)stream);
+}
+
+int sde_photo_multi_fwd(const sde_photo_desc* d, int n, float* const* sampled, uint8_t* const* sel, float* const* partial, float* loss_out,
+                        sde_stream_t stream) {
+    SDE_CHECK_ARG(loss_out, "sde_photo_multi_fwd: null loss_out");
+    MultiReduce r;
+    hipStream_t st = (hipStream_t)stream;
+    const int rc = photo_multi_fwd_launch("sde_photo_multi_fwd", false, d, n, sampled, sel, nullptr, partial, st, r);
+    if (rc) return rc;
+    hipLaunchKernelGGL(reduce_partials_kernel, dim3(n), dim3(256), 0, st, r, loss_out);
+    SDE_CHECK_LAUNCH("sde_photo_multi_fwd/reduce");
     return SDE_OK;
 }
 
 int sde_photo_multi_bwd(const sde_photo_desc* d, int n, const float* const* sampled, const uint8_t* const* sel, const float* gout, float* const* d_depth,
                         float* const* pose_partial, float* const* d_pose, sde_stream_t stream) {
-    return photo_multi_bwd_launch(d, n, sampled, sel, gout, 1, nullptr, d_depth, pose_partial, d_pose, (hipStream_t)stream);
+    return photo_multi_bwd_launch("sde_photo_multi_bwd", false, d, n, sampled, sel, gout, 1, nullptr, d_depth, 0, pose_partial, d_pose, 0, (hipStream_t)stream);
 }
 
-// ---- photometric + smoothness terms of every scale (MonoDepth2.py:L78-126) ----
+// ---- smoothness term: ONE launch table per pass; sde_smooth_fwd / sde_smooth_bwd fill it with one scale ----
+// entry s of the table (m.B and m.first[s] are set): the scale's tensors and its block range, the partition sde_smooth_num_blocks counts
+static void smooth_multi_scale(SmoothMulti& m, int s, const float* depth, const float* img, int h, int w) {
+    SmoothArgs& a = m.a[s];
+    a.depth = depth; a.img = img; a.h = h; a.w = w;
+    m.gdx[s] = sde_cdiv(w, 64); m.gdy[s] = sde_cdiv(h, 4);
+    m.first[s + 1] = m.first[s] + m.gdx[s] * m.gdy[s] * m.B;
+}
+
 static int smooth_multi_fill(const sde_photo_desc* d, int n, SmoothMulti& m, const char* who) {
-    m.n = n; m.B = d[0].B; m.first[0] = 0; m.accumulate = 0;
+    m = SmoothMulti{};
+    m.n = n; m.B = d[0].B;
     for (int s = 0; s < n; ++s) {
         SDE_CHECK_ARG(d[s].depth && d[s].A && d[s].B == d[0].B && d[s].B > 0 && d[s].h > 1 && d[s].w > 1, "%s: scale %d: bad descriptor", who, s);
-        SmoothArgs& a = m.a[s];
-        a = SmoothArgs{};
-        a.depth = d[s].depth; a.img = d[s].A; a.h = d[s].h; a.w = d[s].w;
-        m.gdx[s] = sde_cdiv(d[s].w, 64); m.gdy[s] = sde_cdiv(d[s].h, 4);
-        m.first[s + 1] = m.first[s] + m.gdx[s] * m.gdy[s] * d[s].B;
+        smooth_multi_scale(m, s, d[s].depth, d[s].A, d[s].h, d[s].w);
     }
-    for (int s = n; s < PH_MAX_SCALES; ++s) { m.a[s] = m.a[0]; m.gdx[s] = m.gdy[s] = 1; m.first[s + 1] = m.first[n]; }
     return SDE_OK;
 }
 
+// ---- photometric + smoothness terms of every scale (MonoDepth2.py:L78-126) ----
 int sde_mono_loss_fwd(const sde_photo_desc* d, int n, const float* photo_w, const float* smooth_w, float* const* sampled, uint8_t* const* sel,
                       float* const* photo_partial, float* const* sm_mean_part, float* const* sm_dn, float* const* sm_loss_part, float* const* sm_s_part,
                       float* per_scale, float* totals, int* ticket, sde_stream_t stream) {
@@ -1291,7 +1136,7 @@ int sde_mono_loss_fwd(const sde_photo_desc* d, int n, const float* photo_w, cons
         SDE_CHECK_LAUNCH("sde_mono_loss_fwd/smooth");
     }
     MultiReduce r;
-    const int rc = photo_multi_fwd_launch(d, n, sampled, sel, photo_partial, st, r);
+    const int rc = photo_multi_fwd_launch("sde_mono_loss_fwd", false, d, n, sampled, sel, nullptr, photo_partial, st, r);
     if (rc) return rc;
     for (int s = 0; s < n; ++s) { mr.partial[s] = r.partial[s]; mr.n[s] = r.n[s]; mr.scale[s] = r.scale[s]; mr.weight[s] = photo_w[s]; }
     hipLaunchKernelGGL(mono_loss_finalize_kernel, dim3(mr.count), dim3(256), 0, st, mr, per_scale, totals, ticket);
@@ -1303,8 +1148,7 @@ int sde_mono_loss_bwd(const sde_photo_desc* d, int n, const float* photo_w, cons
                       const float* g_rec, const float* g_smooth, const float* const* sm_mean_part, const float* const* sm_dn, const float* const* sm_s_part,
                       float* const* d_depth, float* const* pose_partial, float* const* d_pose, sde_stream_t stream) {
     SDE_CHECK_ARG(d && photo_w && g_rec && d_depth && n >= 1 && n <= PH_MAX_SCALES, "sde_mono_loss_bwd: bad argument (n=%d)", n);
-    hipStream_t st = (hipStream_t)stream;
-    int rc = photo_multi_bwd_launch(d, n, sampled, sel, g_rec, 0, photo_w, d_depth, pose_partial, d_pose, st);      // writes d_depth
+    int rc = photo_multi_bwd_launch("sde_mono_loss_bwd", false, d, n, sampled, sel, g_rec, 0, photo_w, d_depth, 0, pose_partial, d_pose, 0, (hipStream_t)stream);      // writes d_depth
     if (rc) return rc;
     if (smooth_w && g_smooth) return sde_smooth_multi_bwd(d, n, smooth_w, g_smooth, sm_mean_part, sm_dn, sm_s_part, d_depth, 1, stream);      // ... the smoothness term adds to it
     return SDE_OK;
@@ -1330,7 +1174,7 @@ int sde_smooth_multi_bwd(const sde_photo_desc* d, int n, const float* smooth_w, 
 int sde_photo_multi_pose_finalize(const sde_photo_desc* d, int n, const float* const* pose_partial, float* const* d_pose, sde_stream_t stream) {
     SDE_CHECK_ARG(d && pose_partial && d_pose && n >= 1 && n <= PH_MAX_SCALES, "sde_photo_multi_pose_finalize: bad argument (n=%d)", n);
     MultiPose mp;
-    mp.n = n;
+    mp.n = n; mp.accumulate = 0;
     for (int s = 0; s < PH_MAX_SCALES; ++s) {
         const bool on = s < n;
         SDE_CHECK_ARG(!on || (pose_partial[s] && d[s].nctx == d[0].nctx && d[s].B == d[0].B && d[s].h > 0 && d[s].w > 0), "sde_photo_multi_pose_finalize: scale %d: bad descriptor", s);
@@ -1340,10 +1184,7 @@ int sde_photo_multi_pose_finalize(const sde_photo_desc* d, int n, const float* c
     const int nctx = d[0].nctx;
     SDE_CHECK_ARG(nctx >= 1 && nctx <= SDE_MAX_CTX, "sde_photo_multi_pose_finalize: nctx=%d", nctx);
     for (int j = 0; j < nctx; ++j) SDE_CHECK_ARG(d_pose[j], "sde_photo_multi_pose_finalize: null d_pose[%d]", j);
-    hipLaunchKernelGGL(pose_grad_finalize_multi_kernel, dim3(d[0].B, nctx), dim3(64), 0, (hipStream_t)stream, mp, nctx, d[0].B, d_pose[0], nctx > 1 ? d_pose[1] : nullptr,
-                       nctx > 2 ? d_pose[2] : nullptr, nctx > 3 ? d_pose[3] : nullptr);
-    SDE_CHECK_LAUNCH("sde_photo_multi_pose_finalize");
-    return SDE_OK;
+    return pose_finalize_launch("sde_photo_multi_pose_finalize", mp, nctx, d[0].B, d_pose, (hipStream_t)stream);
 }
 
 int sde_ssim_fwd(const float* x, const float* y, int B, int C, int H, int W, float C1, float C2, float* out, sde_stream_t stream) {
@@ -1375,13 +1216,17 @@ int sde_smooth_fwd(const float* depth, const float* img, int B, int h, int w, fl
     SDE_CHECK_ARG(depth && img && mean_part && loss_part && loss_out, "sde_smooth_fwd: null pointer");
     SDE_CHECK_ARG(B > 0 && h > 1 && w > 1, "sde_smooth_fwd: bad shape");
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(smooth_mean_kernel, dim3(SM_CHUNKS, B), dim3(256), 0, s, depth, h * w, mean_part);
+    SmoothMulti m = {};
+    m.n = 1; m.B = B;
+    smooth_multi_scale(m, 0, depth, img, h, w);
+    m.a[0].mean_part = mean_part; m.a[0].dn = dn; m.a[0].loss_part = loss_part; m.a[0].s_part = s_part;
+    hipLaunchKernelGGL(smooth_mean_multi_kernel, dim3(SM_CHUNKS, B, 1), dim3(256), 0, s, m);
     SDE_CHECK_LAUNCH("sde_smooth_fwd/mean");
-    dim3 grid(sde_cdiv(w, 64), sde_cdiv(h, 4), B);
-    hipLaunchKernelGGL(smooth_fwd_kernel, grid, dim3(256), 0, s, depth, img, mean_part, B, h, w, dn, loss_part, s_part);
+    hipLaunchKernelGGL(smooth_fwd_multi_kernel, dim3(m.first[1]), dim3(256), 0, s, m);
     SDE_CHECK_LAUNCH("sde_smooth_fwd");
-    hipLaunchKernelGGL(reduce_partials_kernel, dim3(1), dim3(256), 0, s, loss_part, (int)(grid.x * grid.y * grid.z), loss_scale, loss_out,
-                       accumulate);
+    MultiReduce r = {};
+    r.partial[0] = loss_part; r.n[0] = m.first[1]; r.scale[0] = loss_scale; r.accumulate = accumulate;
+    hipLaunchKernelGGL(reduce_partials_kernel, dim3(1), dim3(256), 0, s, r, loss_out);
     SDE_CHECK_LAUNCH("sde_smooth_fwd/reduce");
     return SDE_OK;
 }
@@ -1389,9 +1234,12 @@ int sde_smooth_fwd(const float* depth, const float* img, int B, int h, int w, fl
 int sde_smooth_bwd(const float* depth, const float* dn, const float* mean_part, const float* s_part, const float* gout, float gscale, int B,
                    int h, int w, float* d_depth, int accumulate, sde_stream_t stream) {
     SDE_CHECK_ARG(depth && dn && mean_part && s_part && gout && d_depth, "sde_smooth_bwd: null pointer");
-    dim3 grid(sde_cdiv(w, 64), sde_cdiv(h, 4), B);
-    hipLaunchKernelGGL(smooth_bwd_kernel, grid, dim3(256), 0, (hipStream_t)stream, depth, dn, mean_part, s_part, (int)(grid.x * grid.y), gout,
-                       gscale, h, w, d_depth, accumulate);
+    SmoothMulti m = {};
+    m.n = 1; m.B = B; m.accumulate = accumulate;
+    smooth_multi_scale(m, 0, depth, nullptr, h, w);
+    m.a[0].mean_part = (float*)mean_part; m.a[0].dn = (float*)dn; m.a[0].s_part = (float*)s_part;
+    m.a[0].gout = gout; m.a[0].gscale = gscale; m.a[0].d_depth = d_depth;
+    hipLaunchKernelGGL(smooth_bwd_multi_kernel, dim3(m.first[1]), dim3(256), 0, (hipStream_t)stream, m);
     SDE_CHECK_LAUNCH("sde_smooth_bwd");
     return SDE_OK;
 }
@@ -1402,43 +1250,52 @@ int sde_silog_num_blocks(int B, int h, int w) {
     return (int)(nb < 1 ? 1 : (nb > 1024 ? 1024 : nb));
 }
 
-int sde_silog_fwd(const float* est, const float* gt, int B, int h, int w, int H, int W, float variance_focus, float* part, float* stats,
-                  sde_stream_t stream) {
-    SDE_CHECK_ARG(est && gt && part && stats, "sde_silog_fwd: null pointer");
-    SDE_CHECK_ARG(B > 0 && h > 0 && w > 0 && H >= h && W >= w, "sde_silog_fwd: bad shape");
-    const int nb = sde_silog_num_blocks(B, h, w);
-    const float sh = (float)((double)H / (double)h), sw = (float)((double)W / (double)w);
-    hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(silog_fwd_kernel, dim3(nb), dim3(256), 0, s, est, gt, B, h, w, H, W, sh, sw, part);
-    SDE_CHECK_LAUNCH("sde_silog_fwd");
-    hipLaunchKernelGGL(silog_finalize_kernel, dim3(1), dim3(64), 0, s, part, nb, variance_focus, stats);
-    SDE_CHECK_LAUNCH("sde_silog_fwd/finalize");
-    return SDE_OK;
-}
-
-int sde_silog_bwd(const float* est, const float* gt, const float* stats, const float* gout, float gscale, float variance_focus, int B, int h,
-                  int w, int H, int W, float* d_est, int accumulate, sde_stream_t stream) {
-    SDE_CHECK_ARG(est && gt && stats && gout && d_est, "sde_silog_bwd: null pointer");
-    const int nb = sde_silog_num_blocks(B, h, w);
-    const float sh = (float)((double)H / (double)h), sw = (float)((double)W / (double)w);
-    hipLaunchKernelGGL(silog_bwd_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, est, gt, stats, gout, gscale, variance_focus, B, h, w, H,
-                       W, sh, sw, d_est, accumulate);
-    SDE_CHECK_LAUNCH("sde_silog_bwd");
-    return SDE_OK;
-}
-
-static int silog_scales(const float* const* est, float* const* d_est, const int* h, const int* w, const float* weight, int n, int B, int H, int W,
-                        SilogScales& a) {
-    SDE_CHECK_ARG(est && h && w && weight && n >= 1 && n <= SDE_SILOG_MAX_SCALES && B > 0, "sde_silog_multi: bad scale table (n=%d)", n);
-    a.n = n;
+// the launch table of n scales; shapes: check them (sde_silog_bwd never did: it takes what its forward accepted)
+static int silog_scales(const char* who, bool shapes, const float* const* est, float* const* d_est, const int* h, const int* w, const float* weight, int n, int B, int H,
+                        int W, SilogScales& a) {
+    SDE_CHECK_ARG(est && h && w && weight && n >= 1 && n <= SDE_SILOG_MAX_SCALES && (!shapes || B > 0), "%s: bad scale table (n=%d)", who, n);
+    a.n = n; a.accumulate = 0;
     int end = 0;
     for (int k = 0; k < n; ++k) {
-        SDE_CHECK_ARG(est[k] && h[k] > 0 && w[k] > 0 && H >= h[k] && W >= w[k] && (!d_est || d_est[k]), "sde_silog_multi: bad scale %d", k);
+        SDE_CHECK_ARG(est[k] && (!d_est || d_est[k]), "%s: null pointer (scale %d)", who, k);
+        SDE_CHECK_ARG(!shapes || (h[k] > 0 && w[k] > 0 && H >= h[k] && W >= w[k]), "%s: bad shape (scale %d)", who, k);
         a.est[k] = est[k]; a.d_est[k] = d_est ? d_est[k] : nullptr; a.h[k] = h[k]; a.w[k] = w[k]; a.weight[k] = weight[k];
         a.sh[k] = (float)((double)H / (double)h[k]); a.sw[k] = (float)((double)W / (double)w[k]);
         end += sde_silog_num_blocks(B, h[k], w[k]);
         a.blk_end[k] = end;
     }
+    return SDE_OK;
+}
+
+static int silog_fwd_launch(const char* who, const SilogScales& a, const float* gt, int B, int H, int W, float variance_focus, float* part, float* stats, float* total,
+                            hipStream_t s) {
+    hipLaunchKernelGGL(silog_multi_fwd_kernel, dim3(a.blk_end[a.n - 1]), dim3(256), 0, s, a, gt, B, H, W, part);
+    SDE_CHECK_LAUNCH(who);
+    hipLaunchKernelGGL(silog_multi_finalize_kernel, dim3(1), dim3(64 * a.n), 0, s, part, a, variance_focus, stats, total);
+    SDE_CHECK_LAUNCH(who);
+    return SDE_OK;
+}
+
+int sde_silog_fwd(const float* est, const float* gt, int B, int h, int w, int H, int W, float variance_focus, float* part, float* stats,
+                  sde_stream_t stream) {
+    SDE_CHECK_ARG(est && gt && part && stats, "sde_silog_fwd: null pointer");
+    const float one = 1.0f;
+    SilogScales a;
+    const int rc = silog_scales("sde_silog_fwd", true, &est, nullptr, &h, &w, &one, 1, B, H, W, a);
+    if (rc != SDE_OK) return rc;
+    return silog_fwd_launch("sde_silog_fwd", a, gt, B, H, W, variance_focus, part, stats, nullptr, (hipStream_t)stream);
+}
+
+int sde_silog_bwd(const float* est, const float* gt, const float* stats, const float* gout, float gscale, float variance_focus, int B, int h,
+                  int w, int H, int W, float* d_est, int accumulate, sde_stream_t stream) {
+    SDE_CHECK_ARG(est && gt && stats && gout && d_est, "sde_silog_bwd: null pointer");
+    const float one = 1.0f;
+    SilogScales a;
+    const int rc = silog_scales("sde_silog_bwd", false, &est, &d_est, &h, &w, &one, 1, B, H, W, a);
+    if (rc != SDE_OK) return rc;
+    a.accumulate = accumulate;
+    hipLaunchKernelGGL(silog_multi_bwd_kernel, dim3(a.blk_end[0]), dim3(256), 0, (hipStream_t)stream, a, gt, stats, gout, gscale, variance_focus, B, H, W);
+    SDE_CHECK_LAUNCH("sde_silog_bwd");
     return SDE_OK;
 }
 
@@ -1452,21 +1309,16 @@ int sde_silog_multi_fwd(const float* const* est, const float* gt, int B, const i
                         float variance_focus, float* part, float* stats, float* total, sde_stream_t stream) {
     SDE_CHECK_ARG(gt && part && stats && total, "sde_silog_multi_fwd: null pointer");
     SilogScales a;
-    const int rc = silog_scales(est, nullptr, h, w, weight, n, B, H, W, a);
+    const int rc = silog_scales("sde_silog_multi_fwd", true, est, nullptr, h, w, weight, n, B, H, W, a);
     if (rc != SDE_OK) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(silog_multi_fwd_kernel, dim3(a.blk_end[n - 1]), dim3(256), 0, s, a, gt, B, H, W, part);
-    SDE_CHECK_LAUNCH("sde_silog_multi_fwd");
-    hipLaunchKernelGGL(silog_multi_finalize_kernel, dim3(1), dim3(64 * n), 0, s, part, a, variance_focus, stats, total);
-    SDE_CHECK_LAUNCH("sde_silog_multi_fwd/finalize");
-    return SDE_OK;
+    return silog_fwd_launch("sde_silog_multi_fwd", a, gt, B, H, W, variance_focus, part, stats, total, (hipStream_t)stream);
 }
 
 int sde_silog_multi_bwd(const float* const* est, const float* gt, const float* stats, const float* gout, float gscale, float variance_focus, int B,
                         const int* h, const int* w, const float* weight, int n, int H, int W, float* const* d_est, sde_stream_t stream) {
     SDE_CHECK_ARG(gt && stats && gout && d_est, "sde_silog_multi_bwd: null pointer");
     SilogScales a;
-    const int rc = silog_scales(est, d_est, h, w, weight, n, B, H, W, a);
+    const int rc = silog_scales("sde_silog_multi_bwd", true, est, d_est, h, w, weight, n, B, H, W, a);
     if (rc != SDE_OK) return rc;
     hipLaunchKernelGGL(silog_multi_bwd_kernel, dim3(a.blk_end[n - 1]), dim3(256), 0, (hipStream_t)stream, a, gt, stats, gout, gscale, variance_focus, B, H, W);
     SDE_CHECK_LAUNCH("sde_silog_multi_bwd");

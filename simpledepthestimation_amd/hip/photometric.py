@@ -67,8 +67,7 @@ def pose_vec2mat(vec):
     return _PoseVec2Mat.apply(vec)
 
 
-def _desc(A, ctxs, poses, depth, K, sx, sy, ssim_w, C1, C2, automask, reduce_mean, clip_thr=None):
-    d = L.PhotoDesc()
+def _desc(d, A, ctxs, poses, depth, K, sx, sy, ssim_w, C1, C2, automask, reduce_mean, clip_thr=None):
     d.clip_thr = clip_thr.data_ptr() if clip_thr is not None else 0
     B, _, h, w = depth.shape
     d.A = A.data_ptr(); d.depth = depth.data_ptr(); d.K = K.data_ptr()
@@ -77,7 +76,75 @@ def _desc(A, ctxs, poses, depth, K, sx, sy, ssim_w, C1, C2, automask, reduce_mea
     d.B, d.h, d.w, d.nctx = B, h, w, len(ctxs)
     d.automask, d.reduce_mean = int(bool(automask)), int(bool(reduce_mean))
     d.sx, d.sy, d.ssim_w, d.C1, d.C2 = sx, sy, ssim_w, C1, C2
-    return d
+
+
+PH_MAX_SCALES = 4     # PH_MAX_SCALES of csrc/photometric.hip
+
+
+class _PackedScales:
+    """n scales of the photometric term marshalled for the sde_photo_* / sde_mono_loss_* entries: the PhotoDesc array and the per-scale pointer arrays
+    (sampled [n][MAX_CTX], sel [n], ...); the single-scale entries take the same arrays with n = 1.  Forward (saved is None) allocates what backward
+    re-reads (sampled, sels) and the partial slabs; backward is given saved = (sampled, sels) and allocates d_depths, the pose partials and d_pose.
+    depths / As: per scale, ctxs: scale-major, scales[s] = (sx, sy), cfg = (ssim_w, C1, C2, automask, reduce_mean)."""
+
+    def __init__(self, K, depths, As, ctxs, poses, scales, cfg, clip_thr=None, saved=None):
+        n, nctx = len(depths), len(poses)
+        B, dev, lib = depths[0].shape[0], K.device, L.lib()
+        arr = lambda: (ctypes.c_void_p * n)()
+        forward = saved is None
+        self.n = n
+        self.descs = (L.PhotoDesc * n)()
+        self.samp_arr, self.sel_arr = (ctypes.c_void_p * (n * L.MAX_CTX))(), arr()
+        if forward:
+            self.sampled, self.sels, self.partials, self.part_arr = [], [], [], arr()
+        else:
+            self.sampled, self.sels = saved
+            self.d_depths, self.pps, self.dd_arr, self.pp_arr = [], [], arr(), arr()
+        pixels = 0
+        for s in range(n):
+            _, _, h, w = depths[s].shape
+            _desc(self.descs[s], As[s], ctxs[s * nctx:(s + 1) * nctx], poses, depths[s], K, *scales[s], *cfg, clip_thr)
+            if forward:
+                self.sampled += [torch.empty(B, 3, h, w, device=dev) for _ in range(nctx)]
+                self.sels.append(torch.empty(B, h, w, device=dev, dtype=torch.uint8))
+                self.partials.append(torch.empty(lib.sde_photo_num_blocks(B, h, w, 0), device=dev)); self.part_arr[s] = self.partials[-1].data_ptr()
+            else:
+                self.d_depths.append(torch.empty_like(depths[s])); self.dd_arr[s] = self.d_depths[-1].data_ptr()
+                self.pps.append(torch.empty(lib.sde_photo_num_blocks(B, h, w, 1) * nctx * 12, device=dev)); self.pp_arr[s] = self.pps[-1].data_ptr()
+            for j in range(nctx):
+                self.samp_arr[s * L.MAX_CTX + j] = self.sampled[s * nctx + j].data_ptr()
+            self.sel_arr[s] = self.sels[s].data_ptr()
+            pixels += B * h * w
+        if not forward:
+            self.d_pose = [torch.empty(B, 4, 4, device=dev) for _ in range(nctx)]
+        # algorithmic bytes per pixel, fp32 (BASELINE.md section 2).  Forward: target 12 + contexts 12 each + depth 4; backward: target 12 + (context 12 +
+        # saved warped frame 12) per context + depth 4 + arg-min 1 + d_depth 4
+        self.nbytes = pixels * ((16 + 12 * nctx) if forward else (21 + 24 * nctx))
+        self.meta = dict(B=B, h=depths[0].shape[-2], w=depths[0].shape[-1])
+
+    @staticmethod
+    def unpack(t, n, nctx):
+        """(K, depths, As, ctxs, poses, sampled, sels, rest) of tensors saved as (K, *depths, *As, *ctxs, *poses, *sampled, *sels, *rest)."""
+        out, o = [t[0]], 1
+        for k in (n, n, n * nctx, nctx, n * nctx, n):
+            out.append(t[o:o + k]); o += k
+        return (*out, t[o:])
+
+    def backward_with_pose_handover(self, pose_stream, launch):
+        """launch(d_pose) enqueues the backward kernel on the current stream; d_pose is None when the pose partials are summed on pose_stream instead."""
+        # PoseNet on the auxiliary stream (MonoDepth2Model.forward): the pose side of this backward -- summing the partials -- goes there as well, and is
+        # enqueued BEFORE the main stream's next kernel.  Besides taking a launch off the main chain this shapes the captured graph: the HIP runtime gives
+        # a node's first captured dependant the node's own queue and the later ones the next queues round robin, and with the pose chain as the SECOND
+        # dependant it landed on the queue of the depth network's data-gradient chain and ran after it (in-graph markers, profiles/README.md round 3)
+        # (pose_stream is the caller's statement that every consumer of the pose gradients runs on that stream)
+        aux = pose_stream if L.PROFILE is None else None
+        L.timed("photo_bwd", self.nbytes, len(self.d_pose), lambda: launch(None if aux is not None else L.ptr_array(self.d_pose)), dict(self.meta, scales=self.n))
+        if aux is not None:
+            aux.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(aux):
+                L.check(L.lib().sde_photo_multi_pose_finalize(self.descs, self.n, self.pp_arr, L.ptr_array(self.d_pose), L.stream()), "sde_photo_multi_pose_finalize")
+            for t_ in self.pps + self.d_pose:
+                t_.record_stream(aux)
 
 
 class _PhotoScale(torch.autograd.Function):
@@ -89,48 +156,33 @@ class _PhotoScale(torch.autograd.Function):
         depth, K, A = _f32c(depth), _f32c(K), _f32c(A)
         ctxs = [_f32c(c) for c in ctxs]
         poses = [_f32c(p) for p in poses]
-        B, _, h, w = depth.shape
-        dev = depth.device
-        lib = L.lib()
         thr = None
         if clip > 0.0:
             # LOSS.CLIP (MonoDepth2.py:L147-149): every map is clamped at mean + clip * std of ITSELF; one extra forward yields the unclipped
             # maps, the per-map statistics stay on the device (the reference converts them to a python float: same fp32 value, no gradient)
             maps = photometric_maps(depth, K, A, ctxs, poses, sx, sy, ssim_w, C1, C2, automask, "mean" if reduce_mean else "min")["maps"]
             thr = (maps.mean((0, 2, 3)) + clip * maps.std((0, 2, 3))).contiguous()
-        d = _desc(A, ctxs, poses, depth, K, sx, sy, ssim_w, C1, C2, automask, reduce_mean, thr)
-        sampled = [torch.empty(B, 3, h, w, device=dev) for _ in range(nctx)]
-        sel = torch.empty(B, h, w, device=dev, dtype=torch.uint8)
-        partial = torch.empty(lib.sde_photo_num_blocks(B, h, w, 0), device=dev)
-        loss = torch.empty((), device=dev)
-        # algorithmic bytes (fused per scale): target 12 + contexts 12 each + depth 4 per pixel, fp32
-        L.timed("photo_fwd", B * h * w * (16 + 12 * nctx), nctx,
-                lambda: L.check(lib.sde_photo_fwd(ctypes.byref(d), L.ptr_array(sampled), L.ptr(sel), None, L.ptr(partial), L.ptr(loss), 1.0, 0, L.stream()),
-                                "sde_photo_fwd"), dict(B=B, h=h, w=w, moved=B * h * w * (16 + 24 * nctx + 1)))
-        ctx.save_for_backward(depth, K, A, sel, *ctxs, *poses, *sampled)
-        ctx.cfg = (sx, sy, ssim_w, C1, C2, automask, reduce_mean, nctx)
+        cfg = (ssim_w, C1, C2, automask, reduce_mean)
+        p = _PackedScales(K, [depth], [A], ctxs, poses, [(sx, sy)], cfg, thr)
+        loss = torch.empty((), device=depth.device)
+        L.timed("photo_fwd", p.nbytes, nctx,
+                lambda: L.check(L.lib().sde_photo_fwd(p.descs, p.samp_arr, L.ptr(p.sels[0]), None, L.ptr(p.partials[0]), L.ptr(loss), 1.0, 0, L.stream()),
+                                "sde_photo_fwd"), dict(p.meta, moved=depth.numel() * (16 + 24 * nctx + 1)))
+        ctx.save_for_backward(K, depth, A, *ctxs, *poses, *p.sampled, *p.sels)
+        ctx.cfg = (cfg, (sx, sy), nctx)
         ctx.thr = thr
         return loss
 
     @staticmethod
     def backward(ctx, gout):
-        sx, sy, ssim_w, C1, C2, automask, reduce_mean, nctx = ctx.cfg
-        t = ctx.saved_tensors
-        depth, K, A, sel = t[:4]
-        ctxs, poses, sampled = t[4:4 + nctx], t[4 + nctx:4 + 2 * nctx], t[4 + 2 * nctx:4 + 3 * nctx]
-        B, _, h, w = depth.shape
-        dev = depth.device
-        lib = L.lib()
-        d = _desc(A, ctxs, poses, depth, K, sx, sy, ssim_w, C1, C2, automask, reduce_mean, ctx.thr)
-        d_depth = torch.empty_like(depth)
-        d_pose = [torch.empty(B, 4, 4, device=dev) for _ in range(nctx)]
-        pp = torch.empty(lib.sde_photo_num_blocks(B, h, w, 1) * nctx * 12, device=dev)
+        cfg, scale, nctx = ctx.cfg
+        K, depths, As, ctxs, poses, sampled, sels, _ = _PackedScales.unpack(ctx.saved_tensors, 1, nctx)
+        p = _PackedScales(K, depths, As, ctxs, poses, [scale], cfg, ctx.thr, saved=(sampled, sels))
         gout = _f32c(gout)
-        # algorithmic bytes: target 12 + (context 12 + saved warped frame 12) per context + depth 4 + arg-min 1 + d_depth 4 per pixel
-        L.timed("photo_bwd", B * h * w * (21 + 24 * nctx), nctx,
-                lambda: L.check(lib.sde_photo_bwd(ctypes.byref(d), L.ptr_array(sampled), L.ptr(sel), L.ptr(gout), 1.0, L.ptr(d_depth), 0, L.ptr(pp),
-                                                  L.ptr_array(d_pose), 0, L.stream()), "sde_photo_bwd"), dict(B=B, h=h, w=w))
-        return (d_depth, None, None, None, None, None, None, None, None, None, None, None) + (None,) * nctx + tuple(d_pose)
+        L.timed("photo_bwd", p.nbytes, nctx,
+                lambda: L.check(L.lib().sde_photo_bwd(p.descs, p.samp_arr, L.ptr(sels[0]), L.ptr(gout), 1.0, L.ptr(p.d_depths[0]), 0, L.ptr(p.pps[0]),
+                                                      L.ptr_array(p.d_pose), 0, L.stream()), "sde_photo_bwd"), p.meta)
+        return (p.d_depths[0], None, None, None, None, None, None, None, None, None, None, None) + (None,) * nctx + tuple(p.d_pose)
 
 
 def photometric_scale_loss(depth, K, A, ctxs, poses, sx, sy, ssim_w=0.85, C1=1e-4, C2=9e-4, automask=True, reduce="min", clip=0.0):
@@ -140,7 +192,10 @@ def photometric_scale_loss(depth, K, A, ctxs, poses, sx, sy, ssim_w=0.85, C1=1e-
                              float(clip), len(ctxs), *ctxs, *poses)
 
 
-PH_MAX_SCALES = 4     # PH_MAX_SCALES of csrc/photometric.hip
+def _split_scales(rest, n, nctx):
+    """(depths, As, ctxs scale-major, poses) of an autograd argument tail, as contiguous fp32 tensors."""
+    rest = [_f32c(t) for t in rest]
+    return rest[:n], rest[n:2 * n], rest[2 * n:2 * n + n * nctx], rest[2 * n + n * nctx:]
 
 
 class _PhotoMulti(torch.autograd.Function):
@@ -148,89 +203,27 @@ class _PhotoMulti(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, K, ssim_w, C1, C2, automask, reduce_mean, n, nctx, scales, pose_stream, *rest):
-        depths, As = rest[:n], rest[n:2 * n]
-        ctxs = rest[2 * n:2 * n + n * nctx]               # scale-major
-        poses = rest[2 * n + n * nctx:]
         K = _f32c(K)
-        depths = [_f32c(d) for d in depths]; As = [_f32c(a) for a in As]
-        ctxs = [_f32c(c) for c in ctxs]; poses = [_f32c(p) for p in poses]
-        dev = K.device
-        lib = L.lib()
-        B = depths[0].shape[0]
-        descs = (L.PhotoDesc * n)()
-        sampled, sels, partials = [], [], []
-        samp_arr = (ctypes.c_void_p * (n * L.MAX_CTX))()
-        sel_arr, part_arr = (ctypes.c_void_p * n)(), (ctypes.c_void_p * n)()
-        for s in range(n):
-            _, _, h, w = depths[s].shape
-            sx, sy = scales[s]
-            d = _desc(As[s], ctxs[s * nctx:(s + 1) * nctx], poses, depths[s], K, sx, sy, ssim_w, C1, C2, automask, reduce_mean)
-            ctypes.memmove(ctypes.byref(descs, s * ctypes.sizeof(L.PhotoDesc)), ctypes.byref(d), ctypes.sizeof(L.PhotoDesc))
-            sm = [torch.empty(B, 3, h, w, device=dev) for _ in range(nctx)]
-            for j, t in enumerate(sm):
-                samp_arr[s * L.MAX_CTX + j] = t.data_ptr()
-            sampled += sm
-            sels.append(torch.empty(B, h, w, device=dev, dtype=torch.uint8)); sel_arr[s] = sels[-1].data_ptr()
-            partials.append(torch.empty(lib.sde_photo_num_blocks(B, h, w, 0), device=dev)); part_arr[s] = partials[-1].data_ptr()
-        loss = torch.empty(n, device=dev)
-        h0, w0 = depths[0].shape[-2:]
-        nbytes = sum(B * d.shape[-2] * d.shape[-1] * (16 + 12 * nctx) for d in depths)
-        L.timed("photo_fwd", nbytes, nctx, lambda: L.check(lib.sde_photo_multi_fwd(descs, n, samp_arr, sel_arr, part_arr, L.ptr(loss), L.stream()), "sde_photo_multi_fwd"),
-                dict(B=B, h=h0, w=w0, scales=n))
-        ctx.save_for_backward(K, *depths, *As, *ctxs, *poses, *sampled, *sels)
-        ctx.cfg = (ssim_w, C1, C2, automask, reduce_mean, n, nctx, scales)
+        depths, As, ctxs, poses = _split_scales(rest, n, nctx)
+        cfg = (ssim_w, C1, C2, automask, reduce_mean)
+        p = _PackedScales(K, depths, As, ctxs, poses, scales, cfg)
+        loss = torch.empty(n, device=K.device)
+        L.timed("photo_fwd", p.nbytes, nctx, lambda: L.check(L.lib().sde_photo_multi_fwd(p.descs, n, p.samp_arr, p.sel_arr, p.part_arr, L.ptr(loss), L.stream()),
+                                                             "sde_photo_multi_fwd"), dict(p.meta, scales=n))
+        ctx.save_for_backward(K, *depths, *As, *ctxs, *poses, *p.sampled, *p.sels)
+        ctx.cfg = (cfg, n, nctx, scales)
         ctx.pose_stream = pose_stream
         return loss
 
     @staticmethod
     def backward(ctx, gout):
-        ssim_w, C1, C2, automask, reduce_mean, n, nctx, scales = ctx.cfg
-        t = ctx.saved_tensors
-        K = t[0]
-        o = 1
-        depths = t[o:o + n]; o += n
-        As = t[o:o + n]; o += n
-        ctxs = t[o:o + n * nctx]; o += n * nctx
-        poses = t[o:o + nctx]; o += nctx
-        sampled = t[o:o + n * nctx]; o += n * nctx
-        sels = t[o:o + n]
-        dev = K.device
-        lib = L.lib()
-        B = depths[0].shape[0]
-        descs = (L.PhotoDesc * n)()
-        samp_arr = (ctypes.c_void_p * (n * L.MAX_CTX))()
-        sel_arr, dd_arr, pp_arr = (ctypes.c_void_p * n)(), (ctypes.c_void_p * n)(), (ctypes.c_void_p * n)()
-        d_depths, pps = [], []
-        for s in range(n):
-            _, _, h, w = depths[s].shape
-            sx, sy = scales[s]
-            d = _desc(As[s], ctxs[s * nctx:(s + 1) * nctx], poses, depths[s], K, sx, sy, ssim_w, C1, C2, automask, reduce_mean)
-            ctypes.memmove(ctypes.byref(descs, s * ctypes.sizeof(L.PhotoDesc)), ctypes.byref(d), ctypes.sizeof(L.PhotoDesc))
-            for j in range(nctx):
-                samp_arr[s * L.MAX_CTX + j] = sampled[s * nctx + j].data_ptr()
-            sel_arr[s] = sels[s].data_ptr()
-            d_depths.append(torch.empty_like(depths[s])); dd_arr[s] = d_depths[-1].data_ptr()
-            pps.append(torch.empty(lib.sde_photo_num_blocks(B, h, w, 1) * nctx * 12, device=dev)); pp_arr[s] = pps[-1].data_ptr()
-        d_pose = [torch.empty(B, 4, 4, device=dev) for _ in range(nctx)]
+        cfg, n, nctx, scales = ctx.cfg
+        K, depths, As, ctxs, poses, sampled, sels, _ = _PackedScales.unpack(ctx.saved_tensors, n, nctx)
+        p = _PackedScales(K, depths, As, ctxs, poses, scales, cfg, saved=(sampled, sels))
         gout = _f32c(gout)
-        h0, w0 = depths[0].shape[-2:]
-        nbytes = sum(B * d.shape[-2] * d.shape[-1] * (21 + 24 * nctx) for d in depths)
-        # PoseNet on the auxiliary stream (MonoDepth2Model.forward): the pose side of this backward -- summing the partials -- goes there as well, and is
-        # enqueued BEFORE the main stream's next kernel.  Besides taking a launch off the main chain this shapes the captured graph: the HIP runtime gives
-        # a node's first captured dependant the node's own queue and the later ones the next queues round robin, and with the pose chain as the SECOND
-        # dependant it landed on the queue of the depth network's data-gradient chain and ran after it (in-graph markers, profiles/README.md round 3)
-        # (pose_stream is the caller's statement that every consumer of the pose gradients runs on that stream)
-        aux = ctx.pose_stream if L.PROFILE is None else None
-        L.timed("photo_bwd", nbytes, nctx, lambda: L.check(lib.sde_photo_multi_bwd(descs, n, samp_arr, sel_arr, L.ptr(gout), dd_arr, pp_arr,
-                                                                                   None if aux is not None else L.ptr_array(d_pose), L.stream()),
-                                                          "sde_photo_multi_bwd"), dict(B=B, h=h0, w=w0, scales=n))
-        if aux is not None:
-            aux.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(aux):
-                L.check(lib.sde_photo_multi_pose_finalize(descs, n, pp_arr, L.ptr_array(d_pose), L.stream()), "sde_photo_multi_pose_finalize")
-            for t_ in pps + d_pose:
-                t_.record_stream(aux)
-        return (None,) * 10 + tuple(d_depths) + (None,) * n + (None,) * (n * nctx) + tuple(d_pose)
+        p.backward_with_pose_handover(ctx.pose_stream, lambda d_pose: L.check(
+            L.lib().sde_photo_multi_bwd(p.descs, n, p.samp_arr, p.sel_arr, L.ptr(gout), p.dd_arr, p.pp_arr, d_pose, L.stream()), "sde_photo_multi_bwd"))
+        return (None,) * 10 + tuple(p.d_depths) + (None,) * n + (None,) * (n * nctx) + tuple(p.d_pose)
 
 
 def photometric_multi_loss(depths, K, As, ctxs_per_scale, poses, scales, ssim_w=0.85, C1=1e-4, C2=9e-4, automask=True, reduce="min", pose_stream=None):
@@ -264,108 +257,55 @@ class _MonoLoss(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, K, ssim_w, C1, C2, automask, reduce_mean, n, nctx, scales, photo_w, smooth_w, pose_stream, *rest):
-        depths, As = rest[:n], rest[n:2 * n]
-        ctxs = rest[2 * n:2 * n + n * nctx]               # scale-major
-        poses = rest[2 * n + n * nctx:]
         K = _f32c(K)
-        depths = [_f32c(d) for d in depths]; As = [_f32c(a) for a in As]
-        ctxs = [_f32c(c) for c in ctxs]; poses = [_f32c(p) for p in poses]
+        depths, As, ctxs, poses = _split_scales(rest, n, nctx)
         dev = K.device
         lib = L.lib()
-        B = depths[0].shape[0]
-        descs = (L.PhotoDesc * n)()
-        sampled, sels, partials, sm = [], [], [], []
-        samp_arr = (ctypes.c_void_p * (n * L.MAX_CTX))()
+        cfg = (ssim_w, C1, C2, automask, reduce_mean)
+        p = _PackedScales(K, depths, As, ctxs, poses, scales, cfg)
+        sm, loss_parts = [], []        # loss_parts: workspaces the launch below writes; they must stay allocated until it is enqueued
         arr = lambda: (ctypes.c_void_p * n)()
-        sel_arr, part_arr, mean_arr, dn_arr, lp_arr, sp_arr = arr(), arr(), arr(), arr(), arr(), arr()
-        for s in range(n):
-            _, _, h, w = depths[s].shape
-            sx, sy = scales[s]
-            d = _desc(As[s], ctxs[s * nctx:(s + 1) * nctx], poses, depths[s], K, sx, sy, ssim_w, C1, C2, automask, reduce_mean)
-            ctypes.memmove(ctypes.byref(descs, s * ctypes.sizeof(L.PhotoDesc)), ctypes.byref(d), ctypes.sizeof(L.PhotoDesc))
-            smp = [torch.empty(B, 3, h, w, device=dev) for _ in range(nctx)]
-            for j, t in enumerate(smp):
-                samp_arr[s * L.MAX_CTX + j] = t.data_ptr()
-            sampled += smp
-            sels.append(torch.empty(B, h, w, device=dev, dtype=torch.uint8)); sel_arr[s] = sels[-1].data_ptr()
-            partials.append(torch.empty(lib.sde_photo_num_blocks(B, h, w, 0), device=dev)); part_arr[s] = partials[-1].data_ptr()
-            if smooth_w is not None:
+        mean_arr, dn_arr, lp_arr, sp_arr = arr(), arr(), arr(), arr()
+        if smooth_w is not None:
+            for s, d in enumerate(depths):
+                B, _, h, w = d.shape
                 nb = lib.sde_smooth_num_blocks(B, h, w)
                 mean_part, dn, loss_part, s_part = torch.empty(B * 32, device=dev), torch.empty(B, h, w, device=dev), torch.empty(nb, device=dev), torch.empty(nb, device=dev)
-                sm += [mean_part, dn, s_part]
+                sm += [mean_part, dn, s_part]; loss_parts.append(loss_part)
                 mean_arr[s], dn_arr[s], lp_arr[s], sp_arr[s] = mean_part.data_ptr(), dn.data_ptr(), loss_part.data_ptr(), s_part.data_ptr()
-                partials.append(loss_part)
         per_scale = torch.empty(2 * n, device=dev)
         totals = torch.empty(2, device=dev)
         pw = (ctypes.c_float * n)(*photo_w)
         sw = (ctypes.c_float * n)(*smooth_w) if smooth_w is not None else None
-        h0, w0 = depths[0].shape[-2:]
-        nbytes = sum(B * d.shape[-2] * d.shape[-1] * (16 + 12 * nctx) for d in depths)
-        L.timed("photo_fwd", nbytes, nctx, lambda: L.check(lib.sde_mono_loss_fwd(descs, n, pw, sw, samp_arr, sel_arr, part_arr, mean_arr, dn_arr, lp_arr, sp_arr,
-                                                                                 L.ptr(per_scale), L.ptr(totals), L.ptr(_ticket(dev)), L.stream()), "sde_mono_loss_fwd"),
-                dict(B=B, h=h0, w=w0, scales=n))
-        ctx.save_for_backward(K, *depths, *As, *ctxs, *poses, *sampled, *sels, *sm)
-        ctx.cfg = (ssim_w, C1, C2, automask, reduce_mean, n, nctx, scales, photo_w, smooth_w)
+        L.timed("photo_fwd", p.nbytes, nctx, lambda: L.check(lib.sde_mono_loss_fwd(p.descs, n, pw, sw, p.samp_arr, p.sel_arr, p.part_arr, mean_arr, dn_arr, lp_arr, sp_arr,
+                                                                                   L.ptr(per_scale), L.ptr(totals), L.ptr(_ticket(dev)), L.stream()), "sde_mono_loss_fwd"),
+                dict(p.meta, scales=n))
+        ctx.save_for_backward(K, *depths, *As, *ctxs, *poses, *p.sampled, *p.sels, *sm)
+        ctx.cfg = (cfg, n, nctx, scales, photo_w, smooth_w)
         ctx.pose_stream = pose_stream
         ctx.mark_non_differentiable(per_scale)
         return totals[0], totals[1], per_scale
 
     @staticmethod
     def backward(ctx, g_rec, g_smooth, _g_per_scale):
-        ssim_w, C1, C2, automask, reduce_mean, n, nctx, scales, photo_w, smooth_w = ctx.cfg
-        t = ctx.saved_tensors
-        K = t[0]
-        o = 1
-        depths = t[o:o + n]; o += n
-        As = t[o:o + n]; o += n
-        ctxs = t[o:o + n * nctx]; o += n * nctx
-        poses = t[o:o + nctx]; o += nctx
-        sampled = t[o:o + n * nctx]; o += n * nctx
-        sels = t[o:o + n]; o += n
-        sm = t[o:]
+        cfg, n, nctx, scales, photo_w, smooth_w = ctx.cfg
+        K, depths, As, ctxs, poses, sampled, sels, sm = _PackedScales.unpack(ctx.saved_tensors, n, nctx)
         dev = K.device
         lib = L.lib()
-        B = depths[0].shape[0]
-        descs = (L.PhotoDesc * n)()
-        samp_arr = (ctypes.c_void_p * (n * L.MAX_CTX))()
-        arr = lambda: (ctypes.c_void_p * n)()
-        sel_arr, dd_arr, pp_arr, mean_arr, dn_arr, sp_arr = arr(), arr(), arr(), arr(), arr(), arr()
-        d_depths, pps = [], []
-        for s in range(n):
-            _, _, h, w = depths[s].shape
-            sx, sy = scales[s]
-            d = _desc(As[s], ctxs[s * nctx:(s + 1) * nctx], poses, depths[s], K, sx, sy, ssim_w, C1, C2, automask, reduce_mean)
-            ctypes.memmove(ctypes.byref(descs, s * ctypes.sizeof(L.PhotoDesc)), ctypes.byref(d), ctypes.sizeof(L.PhotoDesc))
-            for j in range(nctx):
-                samp_arr[s * L.MAX_CTX + j] = sampled[s * nctx + j].data_ptr()
-            sel_arr[s] = sels[s].data_ptr()
-            d_depths.append(torch.empty_like(depths[s])); dd_arr[s] = d_depths[-1].data_ptr()
-            pps.append(torch.empty(lib.sde_photo_num_blocks(B, h, w, 1) * nctx * 12, device=dev)); pp_arr[s] = pps[-1].data_ptr()
-            if smooth_w is not None:
-                mean_arr[s], dn_arr[s], sp_arr[s] = sm[3 * s].data_ptr(), sm[3 * s + 1].data_ptr(), sm[3 * s + 2].data_ptr()
-        d_pose = [torch.empty(B, 4, 4, device=dev) for _ in range(nctx)]
+        p = _PackedScales(K, depths, As, ctxs, poses, scales, cfg, saved=(sampled, sels))
         if g_rec is None:                       # rec_loss not part of the objective: its gradient is zero
             g_rec = torch.zeros((), device=dev)
         g_rec = _f32c(g_rec)
         g_smooth = _f32c(g_smooth) if (g_smooth is not None and smooth_w is not None) else None
         pw = (ctypes.c_float * n)(*photo_w)
-        sw = (ctypes.c_float * n)(*smooth_w) if smooth_w is not None else None
-        h0, w0 = depths[0].shape[-2:]
-        nbytes = sum(B * d.shape[-2] * d.shape[-1] * (21 + 24 * nctx) for d in depths)
-        # the pose side goes to PoseNet's stream, enqueued before the main stream's next kernel (see _PhotoMulti.backward)
-        aux = ctx.pose_stream if L.PROFILE is None else None
-        L.timed("photo_bwd", nbytes, nctx, lambda: L.check(lib.sde_mono_loss_bwd(descs, n, pw, None, samp_arr, sel_arr, L.ptr(g_rec), None, None, None, None, dd_arr, pp_arr,
-                                                                                 None if aux is not None else L.ptr_array(d_pose), L.stream()), "sde_mono_loss_bwd"),
-                dict(B=B, h=h0, w=w0, scales=n))
-        if aux is not None:
-            aux.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(aux):
-                L.check(lib.sde_photo_multi_pose_finalize(descs, n, pp_arr, L.ptr_array(d_pose), L.stream()), "sde_photo_multi_pose_finalize")
-            for t_ in pps + d_pose:
-                t_.record_stream(aux)
+        p.backward_with_pose_handover(ctx.pose_stream, lambda d_pose: L.check(
+            lib.sde_mono_loss_bwd(p.descs, n, pw, None, p.samp_arr, p.sel_arr, L.ptr(g_rec), None, None, None, None, p.dd_arr, p.pp_arr, d_pose, L.stream()),
+            "sde_mono_loss_bwd"))
         if g_smooth is not None:
-            L.check(lib.sde_smooth_multi_bwd(descs, n, sw, L.ptr(g_smooth), mean_arr, dn_arr, sp_arr, dd_arr, 1, L.stream()), "sde_smooth_multi_bwd")
-        return (None,) * 12 + tuple(d_depths) + (None,) * n + (None,) * (n * nctx) + tuple(d_pose)
+            sw = (ctypes.c_float * n)(*smooth_w)
+            mean_arr, dn_arr, sp_arr = ((ctypes.c_void_p * n)(*[sm[3 * s + k].data_ptr() for s in range(n)]) for k in range(3))
+            L.check(lib.sde_smooth_multi_bwd(p.descs, n, sw, L.ptr(g_smooth), mean_arr, dn_arr, sp_arr, p.dd_arr, 1, L.stream()), "sde_smooth_multi_bwd")
+        return (None,) * 12 + tuple(p.d_depths) + (None,) * n + (None,) * (n * nctx) + tuple(p.d_pose)
 
 
 def mono_loss(depths, K, As, ctxs_per_scale, poses, scales, photo_w, smooth_w=None, ssim_w=0.85, C1=1e-4, C2=9e-4, automask=True, reduce="min", pose_stream=None):
@@ -389,19 +329,11 @@ def photometric_maps(depth, K, A, ctxs, poses, sx, sy, ssim_w=0.85, C1=1e-4, C2=
     depth, K, A = _f32c(depth), _f32c(K), _f32c(A)
     ctxs = [_f32c(c) for c in ctxs]; poses = [_f32c(p) for p in poses]
     B, _, h, w = depth.shape
-    dev = depth.device
-    lib = L.lib()
-    nctx = len(ctxs)
-    d = _desc(A, ctxs, poses, depth, K, sx, sy, ssim_w, C1, C2, automask, reduce == "mean")
-    nmaps = 2 * nctx if automask else nctx
-    sampled = [torch.empty(B, 3, h, w, device=dev) for _ in range(nctx)]
-    sel = torch.empty(B, h, w, device=dev, dtype=torch.uint8)
-    maps = torch.empty(B, nmaps, h, w, device=dev)
-    partial = torch.empty(lib.sde_photo_num_blocks(B, h, w, 0), device=dev)
-    loss = torch.empty((), device=dev)
-    L.check(lib.sde_photo_fwd(ctypes.byref(d), L.ptr_array(sampled), L.ptr(sel), L.ptr(maps), L.ptr(partial), L.ptr(loss), 1.0, 0, L.stream()),
-            "sde_photo_fwd")
-    return {"loss": loss, "maps": maps, "sampled": sampled, "sel": sel}
+    p = _PackedScales(K, [depth], [A], ctxs, poses, [(sx, sy)], (ssim_w, C1, C2, automask, reduce == "mean"))
+    maps = torch.empty(B, 2 * len(ctxs) if automask else len(ctxs), h, w, device=depth.device)
+    loss = torch.empty((), device=depth.device)
+    L.check(L.lib().sde_photo_fwd(p.descs, p.samp_arr, L.ptr(p.sels[0]), L.ptr(maps), L.ptr(p.partials[0]), L.ptr(loss), 1.0, 0, L.stream()), "sde_photo_fwd")
+    return {"loss": loss, "maps": maps, "sampled": p.sampled, "sel": p.sels[0]}
 
 
 class _Smooth(torch.autograd.Function):
@@ -502,7 +434,6 @@ class _SilogMulti(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, gt, vf, weights, *ests):
-        import ctypes
         ests = [_f32c(e) for e in ests]
         gt = _f32c(gt)
         n, B = len(ests), ests[0].shape[0]
@@ -523,7 +454,6 @@ class _SilogMulti(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gout):
-        import ctypes
         gt, stats, *ests = ctx.saved_tensors
         vf, weights = ctx.cfg
         n, B = len(ests), ests[0].shape[0]
