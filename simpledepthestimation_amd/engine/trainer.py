@@ -70,6 +70,13 @@ class GradCut:
         torch.autograd.backward(self.orig, [l.grad for l in self.leaves])
 
 
+def schedule_family(model):
+    """The key into hip.lib.SCHEDULES / WGRAD_BLOCKS for this model: the `schedule_family` that its depth net declares (PackNet01 itself, or the
+    ResnetEncoder inside DepthResNet / BtsModel / GoogleResNet; a pose net has no say), "resnet" where nothing is declared."""
+    net = getattr(model, "depth_net", model)
+    return next((m.schedule_family for m in net.modules() if hasattr(m, "schedule_family")), "resnet")
+
+
 class HipTrainer:
     """Owns the flat buffers and runs one training step: loss dict = trainer.step(batch)."""
 
@@ -77,8 +84,7 @@ class HipTrainer:
                  adam_fn=None, overlap=None, late_from=("layer3",), cut_owner=None, amp=False, init_scale=65536.0, growth_interval=2000, pose_stream=True, cu_reserve=None,
                  clip_grad=None, clip_fn=None):
         self.model = model
-        kinds = {type(m).__name__ for m in model.modules()}
-        family = "packnet" if "PackNet01" in kinds else "resnet" if ("Bottleneck" in kinds or "BasicBlock" not in kinds) else "resnet_basic"
+        family = schedule_family(model)
         L.apply_schedule(family)
         if not L.WGRAD_BLOCKS_LOCKED and next(model.parameters()).device.type == "cuda":
             HN.set_option(HN.OPT_WGRAD_BLOCKS, L.WGRAD_BLOCKS[family])

@@ -40,22 +40,15 @@ class _RandLayerNorm(torch.autograd.Function):
         ctx.save_for_backward(y, out if relu else None, rlnp, gamma)
         ctx.params = (gamma, beta)
         ctx.cfg = (relu, residual is not None)
-        if n_out == 1:
-            return out
-        return (out,) + tuple(out.view(out.shape) for _ in range(n_out - 1))
+        return HN.aliases(out, n_out)
 
     @staticmethod
     def backward(ctx, *douts):
         y, out, rlnp, gamma = ctx.saved_tensors
         relu, has_res = ctx.cfg
-        grads = [d.contiguous() for d in douts if d is not None]
+        grads = [d for d in HN.fan_in(douts, 3) if d is not None]
         if not grads:
             return (None,) * 10
-        if len(grads) > 3:
-            extra = grads[3]
-            for g in grads[4:]:
-                extra = extra + g
-            grads = grads[:2] + [grads[2] + extra]
         B, H, W, C = y.shape
         Cr = gamma.numel()
         dev = y.device

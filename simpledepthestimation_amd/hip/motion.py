@@ -33,15 +33,15 @@ class _PrepInput(torch.autograd.Function):
         ctx.set_materialize_grads(False)
         x = HN.prep_input(img, None, None, dtype)
         ctx.shape = tuple(img.shape)
-        return x, x.view(x.shape)
+        return HN.aliases(x, 2)
 
     @staticmethod
-    def backward(ctx, da, db):
-        grads = [g.contiguous() for g in (da, db) if g is not None]
+    def backward(ctx, *douts):
+        grads = HN.fan_in(douts, 2)
         if not grads:
             return None, None
         B, C, H, W = ctx.shape
-        d0, d1 = (grads + [None])[:2]
+        d0, d1 = grads
         dimg = torch.empty(ctx.shape, device=d0.device, dtype=torch.float32)
         L.check(L.lib().sde_prep_input_bwd(L.ptr(d0), L.ptr(d1), B, C, H, W, d0.shape[3], _dt(d0), L.ptr(dimg), L.stream()), "sde_prep_input_bwd")
         return dimg, None
@@ -75,16 +75,15 @@ class _ResizeCat(torch.autograd.Function):
         L.check(L.lib().sde_motion_resize_cat_fwd(L.ptr(field), h, w, L.ptr(skip), B, H, W, Cs, Cr, Cx, _dt(skip), L.ptr(X), L.ptr(up), L.stream()),
                 "sde_motion_resize_cat_fwd")
         ctx.meta = (B, h, w, H, W, Cs, Cr, Cx, skip.dtype)
-        return X, X.view(X.shape), up
+        return HN.aliases(X, 2) + (up,)
 
     @staticmethod
     def backward(ctx, dXa, dXb, dup):
         B, h, w, H, W, Cs, Cr, Cx, dt = ctx.meta
-        gx = [g.contiguous() for g in (dXa, dXb) if g is not None]
-        if not gx and dup is None:
+        d0, d1 = HN.fan_in((dXa, dXb), 2) or (None, None)
+        if d0 is None and dup is None:
             return None, None, None
-        dev = (gx[0] if gx else dup).device
-        d0, d1 = (gx + [None, None])[:2]
+        dev = (d0 if d0 is not None else dup).device
         dup = dup.contiguous() if dup is not None else None
         dfield = torch.empty(B, h, w, 4, device=dev, dtype=torch.float32)
         dskip = torch.empty(B, H, W, Cs, device=dev, dtype=dt) if ctx.needs_input_grad[1] else None

@@ -142,6 +142,23 @@ def _f32(t):
     return t.contiguous()
 
 
+def aliases(out, n):
+    """`out` itself for n == 1, else n aliases of it, one per consumer: backward then receives the consumers' gradients separately and the
+    kernel sums them on the fly (see fan_in), instead of autograd launching an add kernel per extra consumer."""
+    return out if n == 1 else (out,) + tuple(out.view(out.shape) for _ in range(n - 1))
+
+
+def fan_in(douts, slots):
+    """The gradients of aliases() for a backward kernel that sums `slots` of them: the None entries dropped, the others contiguous, any gradients
+    beyond `slots` folded into the last slot by torch adds (left to right), None-padded to exactly `slots` entries.  () when no gradient arrived."""
+    grads = [g.contiguous() for g in douts if g is not None]
+    if not grads:
+        return ()
+    for g in grads[slots:]:
+        grads[slots - 1] = grads[slots - 1] + g
+    return tuple(grads[:slots]) + (None,) * (slots - len(grads))
+
+
 # ---------------------------------------------------------------------------------------------------------------
 # raw (non-autograd) helpers
 # ---------------------------------------------------------------------------------------------------------------
@@ -342,20 +359,12 @@ class _Conv2d(torch.autograd.Function):
         if want_stats:
             ctx.mark_non_differentiable(stats)
             return y, stats
-        if n_out > 1:       # one alias per consumer: backward receives their gradients separately and sde_act_bwd_bias_sum adds them on the fly
-            return (y,) + tuple(y.view(y.shape) for _ in range(n_out - 1))
-        return y
+        return aliases(y, n_out)        # sde_act_bwd_bias_sum adds two of their gradients on the fly
 
     @staticmethod
     def backward(ctx, *douts):
         x0, x1, weight, y = ctx.saved_tensors
-        grads = [douts[0]] if ctx.want_stats else [g for g in douts if g is not None]
-        dy = grads[0] if grads else None
-        dy1 = None
-        if len(grads) > 1:
-            dy1 = grads[1].contiguous()
-            for g in grads[2:]:
-                dy1 = dy1 + g
+        dy, dy1 = fan_in(douts[:1] if ctx.want_stats else douts, 2) or (None, None)
         stride, pad, reflect, act, upcat, has_bias, IH, IW, OH, OW = ctx.cfg
         dt = x0.dtype
         V = vec_of(dt)
@@ -767,9 +776,7 @@ class _BatchNormAct(torch.autograd.Function):
             # data gradient can carry this BatchNorm's backward reduce pass (residual form), see _Conv2d.backward
             _HANDOVER.put_bn_out(out, y, bnp, res=True)
             ctx.res_tag = out.data_ptr()              # (this BatchNorm's backward drops the entry: the consuming convolution took its references in forward)
-        if n_out == 1:
-            return out
-        return (out,) + tuple(out.view(out.shape) for _ in range(n_out - 1))
+        return aliases(out, n_out)
 
     @staticmethod
     def backward(ctx, *douts):
@@ -779,14 +786,9 @@ class _BatchNormAct(torch.autograd.Function):
             _HANDOVER.drop_bn_out_res(ctx.res_tag)
         if not training:
             raise L.SdeHipError("BatchNorm backward in eval mode is not on the path")
-        grads = [d.contiguous() for d in douts if d is not None]
+        grads = [d for d in fan_in(douts, 3) if d is not None]
         if not grads:
             return (None,) * 12
-        if len(grads) > 3:
-            extra = grads[3]
-            for g in grads[4:]:
-                extra = extra + g
-            grads = grads[:2] + [grads[2] + extra]
         dt = y.dtype
         C = y.shape[-1]
         M = y.numel() // C
@@ -849,22 +851,16 @@ class _MaxPool(torch.autograd.Function):
         L.check(L.lib().sde_maxpool_fwd(L.ptr(x.contiguous()), B, H, W, C, dtype_code(x.dtype), L.ptr(out), L.ptr(idx), L.stream()), "sde_maxpool_fwd")
         ctx.save_for_backward(idx)
         ctx.shape = (B, H, W, C)
-        if n_out > 1:
-            return (out,) + tuple(out.view(out.shape) for _ in range(n_out - 1))
-        return out
+        return aliases(out, n_out)
 
     @staticmethod
     def backward(ctx, *douts):
         (idx,) = ctx.saved_tensors
         B, H, W, C = ctx.shape
-        grads = [g.contiguous() for g in douts if g is not None]
+        grads = fan_in(douts, 2)
         if not grads:
             return None, None
-        d0, d1 = grads[0], None
-        if len(grads) > 1:
-            d1 = grads[1]
-            for g in grads[2:]:
-                d1 = d1 + g
+        d0, d1 = grads
         dx = torch.empty(B, H, W, C, device=d0.device, dtype=d0.dtype)
         L.check(L.lib().sde_maxpool_bwd_sum(L.ptr(d0), L.ptr(d1), L.ptr(idx), B, H, W, C, dtype_code(d0.dtype), L.ptr(dx), L.stream()), "sde_maxpool_bwd_sum")
         return dx, None

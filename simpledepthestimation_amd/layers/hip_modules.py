@@ -94,6 +94,14 @@ def conv_bn(conv, bn, x, residual=None, relu=True, n_out=1):
     return bn(y, stats, residual, relu, n_out)
 
 
+def conv_norm(conv, norm, x, residual=None, relu=True, n_out=1):
+    """conv -> norm [-> + residual] [-> ReLU] for either norm layer of the ResNet blocks: BatchNorm takes its statistics from the convolution's
+    epilogue (conv_bn), RandLayerNorm runs on the plain convolution output."""
+    if isinstance(norm, HipBatchNorm2d):
+        return conv_bn(conv, norm, x, residual, relu, n_out)
+    return norm(conv(x), residual, relu, n_out)
+
+
 class HipRandLayerNorm(nn.Module):
     """RandLayerNorm (detectron2/layers/layer_norm.py:L7-33) on NHWC activations: per-sample statistics, noise-scaled in training.
 

@@ -1,7 +1,9 @@
-"""ResNet-18/34/50 encoder on the HIP convolution engine.
+"""ResNet-18/34/50 encoder on the HIP convolution engine, in the two variants the reference trains.
 
 Reference: detectron2/layers/resnet_encoder.py:L61-99 (ResnetEncoder: 5 features = relu(bn1(conv1)), layer1(maxpool), layer2-4)
-wrapping torchvision 0.9 resnetXX (v1.5: stride on the 3x3 of a Bottleneck; kaiming-normal fan_out convs, BN gamma=1/beta=0).
+wrapping torchvision 0.9 resnetXX (v1.5: stride on the 3x3 of a Bottleneck; kaiming-normal fan_out convs, BN gamma=1/beta=0), and
+detectron2/layers/resnet.py:L35-59 (ResNetTF under GoogleResNet.py:L21-68: the same network with a configurable norm layer, whose projection
+shortcut is a bare 1x1 convolution built only where the width changes): ``shortcut_norm=False``.
 Attribute / state-dict names follow torchvision (``encoder.conv1``, ``encoder.layer1.0.bn2``, ``...downsample.0``, ``encoder.fc``).
 """
 import numpy as np
@@ -9,56 +11,71 @@ import torch
 import torch.nn as nn
 
 from ..hip import nn as HN
-from .hip_modules import HipBatchNorm2d, HipConv2d, conv_bn
+from .hip_modules import HipBatchNorm2d, HipConv2d, conv_norm
 
 
-class BasicBlock(nn.Module):
+class _Block(nn.Module):
+    """What the two block types share: the shortcut.  downsample: None (identity), Sequential(conv1x1, norm) or ResNetTF's bare Sequential(conv1x1)
+    (ResNet._make_layer builds it: shortcut_norm)."""
+
+    def shortcut(self, xb):
+        if self.downsample is None:
+            return xb
+        if len(self.downsample) == 1:
+            return self.downsample[0](xb)
+        return conv_norm(self.downsample[0], self.downsample[1], xb, relu=False)
+
+
+class BasicBlock(_Block):
     expansion = 1
 
-    def __init__(self, inplanes, planes, stride=1, downsample=None):
+    def __init__(self, inplanes, planes, stride=1, downsample=None, norm_layer=HipBatchNorm2d):
         super().__init__()
         self.conv1 = HipConv2d(inplanes, planes, 3, stride, 1, bias=False)
-        self.bn1 = HipBatchNorm2d(planes)
+        self.bn1 = norm_layer(planes)
         self.conv2 = HipConv2d(planes, planes, 3, 1, 1, bias=False)
-        self.bn2 = HipBatchNorm2d(planes)
+        self.bn2 = norm_layer(planes)
         self.downsample = downsample
 
     def forward(self, x, n_out=1):
-        xa, xb = x if isinstance(x, tuple) else (x, x)       # two aliases of the block input: one per consumer (see hip.nn._BatchNormAct)
-        idt = xb if self.downsample is None else conv_bn(self.downsample[0], self.downsample[1], xb, relu=False)
-        out = conv_bn(self.conv1, self.bn1, xa)
-        return conv_bn(self.conv2, self.bn2, out, residual=idt, relu=True, n_out=n_out)
+        xa, xb = x if isinstance(x, tuple) else (x, x)       # two aliases of the block input: one per consumer (see hip.nn.aliases)
+        idt = self.shortcut(xb)
+        out = conv_norm(self.conv1, self.bn1, xa)
+        return conv_norm(self.conv2, self.bn2, out, residual=idt, relu=True, n_out=n_out)
 
 
-class Bottleneck(nn.Module):
+class Bottleneck(_Block):
     expansion = 4
 
-    def __init__(self, inplanes, planes, stride=1, downsample=None):
+    def __init__(self, inplanes, planes, stride=1, downsample=None, norm_layer=HipBatchNorm2d):
         super().__init__()
         self.conv1 = HipConv2d(inplanes, planes, 1, 1, 0, bias=False)
-        self.bn1 = HipBatchNorm2d(planes)
+        self.bn1 = norm_layer(planes)
         self.conv2 = HipConv2d(planes, planes, 3, stride, 1, bias=False)
-        self.bn2 = HipBatchNorm2d(planes)
+        self.bn2 = norm_layer(planes)
         self.conv3 = HipConv2d(planes, planes * 4, 1, 1, 0, bias=False)
-        self.bn3 = HipBatchNorm2d(planes * 4)
+        self.bn3 = norm_layer(planes * 4)
         self.downsample = downsample
 
     def forward(self, x, n_out=1):
-        xa, xb = x if isinstance(x, tuple) else (x, x)       # two aliases of the block input: one per consumer (see hip.nn._BatchNormAct)
-        idt = xb if self.downsample is None else conv_bn(self.downsample[0], self.downsample[1], xb, relu=False)
-        out = conv_bn(self.conv1, self.bn1, xa)
-        out = conv_bn(self.conv2, self.bn2, out)
-        return conv_bn(self.conv3, self.bn3, out, residual=idt, relu=True, n_out=n_out)
+        xa, xb = x if isinstance(x, tuple) else (x, x)       # two aliases of the block input: one per consumer (see hip.nn.aliases)
+        idt = self.shortcut(xb)
+        out = conv_norm(self.conv1, self.bn1, xa)
+        out = conv_norm(self.conv2, self.bn2, out)
+        return conv_norm(self.conv3, self.bn3, out, residual=idt, relu=True, n_out=n_out)
 
 
 class ResNet(nn.Module):
-    """torchvision-shaped container (conv1, bn1, layer1..4, fc); ``fc`` is kept only so checkpoints load."""
+    """torchvision-shaped container (conv1, bn1, layer1..4, fc); ``fc`` is kept only so checkpoints load.
+    shortcut_norm: the projection shortcut is conv1x1 + norm wherever the stride or the width changes (torchvision); False: ResNetTF's bare
+    conv1x1 where the width changes."""
 
-    def __init__(self, block, layers, num_classes=1000):
+    def __init__(self, block, layers, norm_layer=HipBatchNorm2d, shortcut_norm=True, num_classes=1000):
         super().__init__()
+        self.norm_layer, self.shortcut_norm = norm_layer, bool(shortcut_norm)
         self.inplanes = 64
         self.conv1 = HipConv2d(3, 64, 7, 2, 3, bias=False)
-        self.bn1 = HipBatchNorm2d(64)
+        self.bn1 = norm_layer(64)
         self.layer1 = self._make_layer(block, 64, layers[0])
         self.layer2 = self._make_layer(block, 128, layers[1], stride=2)
         self.layer3 = self._make_layer(block, 256, layers[2], stride=2)
@@ -69,13 +86,14 @@ class ResNet(nn.Module):
                 nn.init.kaiming_normal_(m.weight, mode="fan_out", nonlinearity="relu")
 
     def _make_layer(self, block, planes, blocks, stride=1):
-        downsample = None
-        if stride != 1 or self.inplanes != planes * block.expansion:
-            downsample = nn.Sequential(HipConv2d(self.inplanes, planes * block.expansion, 1, stride, 0, bias=False),
-                                       HipBatchNorm2d(planes * block.expansion))
-        layers = [block(self.inplanes, planes, stride, downsample)]
-        self.inplanes = planes * block.expansion
-        layers += [block(self.inplanes, planes) for _ in range(1, blocks)]
+        downsample, width = None, planes * block.expansion
+        if self.inplanes != width or (stride != 1 and self.shortcut_norm):
+            downsample = nn.Sequential(HipConv2d(self.inplanes, width, 1, stride, 0, bias=False), *([self.norm_layer(width)] if self.shortcut_norm else []))
+        elif stride != 1:
+            raise NotImplementedError("ResNetTF's max-pool shortcut (resnet.py:L47-48) is not on the HIP path")
+        layers = [block(self.inplanes, planes, stride, downsample, self.norm_layer)]
+        self.inplanes = width
+        layers += [block(self.inplanes, planes, 1, None, self.norm_layer) for _ in range(1, blocks)]
         return nn.Sequential(*layers)
 
 
@@ -83,20 +101,23 @@ _SPECS = {18: (BasicBlock, [2, 2, 2, 2]), 34: (BasicBlock, [3, 4, 6, 3]), 50: (B
 
 
 class ResnetEncoder(nn.Module):
-    def __init__(self, num_layers, pretrained=False, num_input_images=1, norm_layer=None):
+    def __init__(self, num_layers, pretrained=False, num_input_images=1, norm_layer=HipBatchNorm2d, shortcut_norm=True):
         super().__init__()
         if num_layers not in _SPECS:
             raise ValueError("{} is not a valid number of resnet layers".format(num_layers))
         if pretrained:
             raise RuntimeError("ImageNet weights cannot be downloaded here; load them from a local checkpoint with load_state_dict "
                                "(use ENCODER_NAME '18'/'50' instead of '18pt'/'50pt')")
-        if num_input_images != 1 or norm_layer is not None:
-            raise NotImplementedError("multi-image / custom-norm encoders are not on the path")
+        if num_input_images != 1:
+            raise NotImplementedError("multi-image encoders are not on the path")
         self.num_ch_enc = np.array([64, 64, 128, 256, 512])
         block, layers = _SPECS[num_layers]
-        self.encoder = ResNet(block, layers)
+        self.encoder = ResNet(block, layers, norm_layer, shortcut_norm)
         if num_layers > 34:
             self.num_ch_enc[1:] *= 4
+        # the weight-gradient schedule HipTrainer applies (engine.trainer.schedule_family, hip.lib.SCHEDULES).  "resnet_basic" was measured on the
+        # torchvision-shortcut basic-block networks only; the bare-shortcut variant has never been timed with it and keeps "resnet" at every depth
+        self.schedule_family = "resnet_basic" if (block is BasicBlock and shortcut_norm) else "resnet"
 
     def forward(self, x, cut=None):
         """x: NHWC normalised image (channels padded).  Returns the 5 NHWC feature maps.
@@ -115,19 +136,24 @@ class ResnetEncoder(nn.Module):
             return x
 
         if split:
-            f0, f0_pool = conv_bn(e.conv1, e.bn1, x, n_out=2)            # decoder skip + max-pool
+            f0, f0_pool = conv_norm(e.conv1, e.bn1, x, n_out=2)          # decoder skip + max-pool
             o1 = run(e.layer1, HN.max_pool_3x3_s2(f0_pool, n_out=2), 3)    # first block: convolution + residual / down-sampling path
             o2 = run(e.layer2, (o1[1], o1[2]), 3)
             o3 = run(e.layer3, (o2[1], o2[2]), 3)
             f4 = run(e.layer4, (o3[1], o3[2]), 1)
-            self.features = [f0, o1[0], o2[0], o3[0], f4]
-            return self.features
-        f0 = conv_bn(e.conv1, e.bn1, x)
+            return self._keep([f0, o1[0], o2[0], o3[0], f4])
+        f0 = conv_norm(e.conv1, e.bn1, x)
         f1 = run(e.layer1, HN.max_pool_3x3_s2(f0), 1)
         f2 = run(e.layer2, f1, 1)
         if cut is not None:
             f0, f1, f2 = cut([f0, f1, f2])
         f3 = run(e.layer3, f2, 1)
         f4 = run(e.layer4, f3, 1)
-        self.features = [f0, f1, f2, f3, f4]
-        return self.features
+        return self._keep([f0, f1, f2, f3, f4])
+
+    def _keep(self, features):
+        """The reference's torchvision wrapper keeps its last features on the module (resnet_encoder.py:L89-99); GoogleResNet.py's encoder (L59-69) does
+        not, and here that also means its activations are not held past the step."""
+        if self.encoder.shortcut_norm:
+            self.features = features
+        return features

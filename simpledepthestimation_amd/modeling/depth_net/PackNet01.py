@@ -61,6 +61,7 @@ class PackNet01(nn.Module):
         self.max_depth = cfg.MODEL.MAX_DEPTH
         self.upsample_depth = cfg.MODEL.DEPTH_NET.UPSAMPLE_DEPTH
         self.dtype = compute_dtype(cfg)
+        self.schedule_family = "packnet"                           # engine.trainer.schedule_family
         # no _grad_cut attribute: HipTrainer then all-reduces after the full backward (no two-phase overlap for this net)
 
     def scale_inv_depth(self, disp):

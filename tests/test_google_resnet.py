@@ -112,11 +112,11 @@ def test_set_stddev_reaches_every_norm():
 
 
 def test_max_pool_shortcut_is_refused():
-    from simpledepthestimation_amd.layers.google_resnet import BasicBlockTF, ResNetTF
     from simpledepthestimation_amd.layers.hip_modules import HipBatchNorm2d
-    r = ResNetTF(BasicBlockTF, [1, 1, 1, 1], HipBatchNorm2d)
+    from simpledepthestimation_amd.layers.resnet_encoder import BasicBlock, ResNet
+    r = ResNet(BasicBlock, [1, 1, 1, 1], HipBatchNorm2d, shortcut_norm=False)
     with pytest.raises(NotImplementedError, match="max-pool"):
-        r._make_layer(BasicBlockTF, 512, 1, stride=2)
+        r._make_layer(BasicBlock, 512, 1, stride=2)
 
 
 def test_new_config_keys_and_existing_defaults():

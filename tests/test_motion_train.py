@@ -205,3 +205,50 @@ def test_motion_learning_trainer_state_round_trips_through_torch_adam():
     tr.step({"x": x, "t": t})
     for (k, a), (_, b) in zip(model.state_dict().items(), model2.state_dict().items()):
         torch.testing.assert_close(a, b, rtol=1e-5, atol=1e-6, msg=k)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# the weight-gradient schedule family the trainer applies (hip.lib.SCHEDULES): declared by the networks, not read off class names
+# ---------------------------------------------------------------------------------------------------------------------------------------
+def _depth_net(name, enc="18", norm="randLN"):
+    from simpledepthestimation_amd.config import get_cfg
+    from simpledepthestimation_amd.modeling.depth_net import build_depth_net
+    cfg = get_cfg()
+    cfg.MODEL.DEPTH_NET.NAME, cfg.MODEL.DEPTH_NET.ENCODER_NAME, cfg.MODEL.DEPTH_NET.NORM = name, enc, norm
+    return build_depth_net(cfg)
+
+
+def _motion_learning_model():
+    from simpledepthestimation_amd.config import get_cfg
+    from simpledepthestimation_amd.modeling import build_model
+    cfg = get_cfg()
+    cfg.merge_from_other_cfg({"MODEL": {"META_ARCHITECTURE": "MotionLearningModel", "DEVICE": "cpu", "DEPTH_NET": {"NAME": "GoogleResNet", "NORM": "randLN"},
+                                        "POSE_NET": {"NAME": "GoogleMotionNet", "USE_DEPTH": True, "SCALE_CONSTRAIN": "clip_ste"}},
+                              "LOSS": {"NUM_SCALES": 1, "SSIM_WEIGHT": 3.0, "C1": "inf", "C2": 9e-6, "DEPTH_L1_WEIGHT": 0.0, "MOTION_SMOOTHNESS_WEIGHT": 1.0,
+                                       "MOTION_SPARSITY_WEIGHT": 0.2, "ROT_CYCLE_WEIGHT": 1e-3, "TRANS_CYCLE_WEIGHT": 5e-2, "SCALE_NORMALIZE": False}})
+    cfg.MODEL.DEPTH_NET.ENCODER_NAME = "18"        # set directly: merging would read the string as a number
+    return build_model(cfg)
+
+
+FAMILY_TABLE = [("DepthResNet-18", lambda: _depth_net("DepthResNet", "18"), "resnet_basic"),
+                ("DepthResNet-50", lambda: _depth_net("DepthResNet", "50"), "resnet"),
+                ("GoogleResNet-18-randLN", lambda: _depth_net("GoogleResNet", "18", "randLN"), "resnet"),
+                ("GoogleResNet-50-BN", lambda: _depth_net("GoogleResNet", "50", "BN"), "resnet"),
+                ("PackNet01", lambda: _depth_net("PackNet01"), "packnet"),
+                ("MotionLearningModel", _motion_learning_model, "resnet"),
+                ("Linear", lambda: nn.Linear(3, 2), "resnet")]
+
+
+@pytest.mark.parametrize("make,family", [c[1:] for c in FAMILY_TABLE], ids=[c[0] for c in FAMILY_TABLE])
+def test_schedule_family_table(make, family):
+    from simpledepthestimation_amd.engine.trainer import HipTrainer, ParamGroup, schedule_family
+    from simpledepthestimation_amd.hip import lib as L
+    model = make()
+    assert schedule_family(model) == family
+    before = (L.JOIN_LAG, L.WGRAD_GROUP, L.FIRST_GROUP)
+    try:
+        L.apply_schedule("packnet" if family != "packnet" else "resnet")      # something else, so that the trainer has to set it
+        HipTrainer(model, [ParamGroup("all", model.named_parameters(), 1e-3, 0.0)], adam_fn=torch_adam)
+        assert (L.JOIN_LAG, L.WGRAD_GROUP, L.FIRST_GROUP) == L.SCHEDULES[family]
+    finally:
+        L.JOIN_LAG, L.WGRAD_GROUP, L.FIRST_GROUP = before
