@@ -450,6 +450,16 @@ int sde_bilinear2_bwd(const void* dout, int B, int H, int W, int C, int dtype, v
 int sde_softplus_head_fwd(const void* y, int B, int H, int W, int ld, int flip, int dtype, float* out, sde_stream_t stream);
 int sde_softplus_head_bwd(const void* y, const float* dout, int B, int H, int W, int ld, int flip, int dtype, void* dy, sde_stream_t stream);
 
+/* GoogleResNetv2's up-sampling layer (csrc/deconv.hip; GoogleResNetv2.py:L42-44): y [B,2H,2W,ldy] = act(ConvTranspose2d(Cin, Cout, 3, stride 2,
+ * padding 1, output_padding 1)(x) + bias) of x [B,H,W,C], split by output parity into four convolutions of the stored input (nine tap products per
+ * input pixel; no zero-inserted image).  w_packed: [ldy][3][3][C], taps flipped -- with the ConvTranspose2d weight [Cin,Cout,3,3] read as the OIHW
+ * weight of the adjoint Conv2d(Cout -> Cin, 3, stride 2, padding 1), sde_pack_weight(Cout = Cin, Cin = Cout, Cin_pad = ldy, Cout_pad = C, for_dgrad = 1);
+ * the for_dgrad = 0 operand of the same call serves the layer's data gradient (a plain sde_conv_fwd of that adjoint) and sde_conv_wgrad of the
+ * adjoint, with x as the "output gradient", its weight gradient.  act: SDE_ACT_NONE / SDE_ACT_ELU / SDE_ACT_RELU.  fp32 (the engine's fp32 MFMA
+ * arithmetic) or bf16 storage (SDE_F16 is refused), fp32 accumulation; channels >= Cout of y are written as zeros. */
+int sde_deconv3x3s2_fwd(const void* x, const void* w_packed, const float* bias, int act, int B, int H, int W, int C, int Cout, int ldy, int dtype,
+                        void* y, sde_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------------
  * GoogleMotionNet / GooglePoseNet operators (csrc/motion.hip; detectron2/modeling/pose_net/GooglePoseNet.py), NHWC activations in fp32 or bf16
  * (SDE_F16 is refused), 16-byte channel groups.  The 3-channel motion field is fp32 [B,h,w,4] (channel 3 zero) in both modes.  No atomics:

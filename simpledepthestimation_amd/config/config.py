@@ -145,7 +145,8 @@ def get_cfg():
 
 
 def get_project_cfg(project):
-    """get_cfg() + the hot-path keys of projects/<project>/configs/Base.yaml ("MonoDepth2" or "Supervised"), from the embedded literals."""
+    """get_cfg() + the hot-path keys of projects/<project>/configs/Base.yaml ("MonoDepth2" or "Supervised"), from the embedded literals;
+    "MotionLearningWaymo": the model, loss and solver keys of projects/MotionLearning/configs/resnet18_waymo.yaml over its Base_waymo.yaml."""
     from .defaults import PROJECT_BASE
     cfg = get_cfg()
     cfg.merge_from_other_cfg(copy.deepcopy(PROJECT_BASE[project]))

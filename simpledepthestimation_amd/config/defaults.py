@@ -115,4 +115,21 @@ PROJECT_BASE = {
         "TEST": {"GT_SCALE": False},
         "LOG_PERIOD": 20,
     },
+    # projects/MotionLearning/configs/resnet18_waymo.yaml over its Base_waymo.yaml: the model, loss and solver keys (the WaymoDepth dataset blocks are not
+    # on the path; synthetic batches carry `mask` / `ctx_mask`)
+    "MotionLearningWaymo": {
+        "MODEL": {"META_ARCHITECTURE": "MotionLearningModel", "MAX_DEPTH": 80, "WITH_MASK": True,
+                  "DEPTH_NET": {"NAME": "GoogleResNetv2", "ENCODER_NAME": "18??", "UPSAMPLE_DEPTH": False, "LEARN_SCALE": False, "NORM": "randLN",
+                                "NOISE_STDDEV": 0.5, "RAMPUP_ITERS": 10000},
+                  "POSE_NET": {"NAME": "GoogleMotionNet", "USE_DEPTH": True, "GROUP_NORM": False, "MASK_MOTION": True, "LEARN_SCALE": True,
+                               "BURN_IN_ITERS": 20000, "SCALE_CONSTRAIN": "clip_ste"}},
+        "LOSS": {"NUM_SCALES": 1, "SSIM_WEIGHT": 3.0, "C1": "inf", "C2": 9e-6, "CLIP": 0.0, "DEPTH_L1_WEIGHT": 0.0, "SMOOTHNESS_WEIGHT": 1e-3,
+                 "SUPERVISED_WEIGHT": 0.0, "VARIANCE_FOCUS": 0.85, "VAR_LOSS_WEIGHT": 0.0, "MOTION_SMOOTHNESS_WEIGHT": 1.0, "MOTION_SPARSITY_WEIGHT": 0.2,
+                 "ROT_CYCLE_WEIGHT": 1e-3, "TRANS_CYCLE_WEIGHT": 5e-2, "SCALE_NORMALIZE": False},
+        "SOLVER": {"IMS_PER_BATCH": 16, "DEPTH_LR": 2e-4, "POSE_LR": 2e-4, "LR_STEPS": (200,), "GAMMA": 0.5, "MAX_EPOCHS": 200, "CHECKPOINT_PERIOD": 10,
+                   "CLIP_GRAD": 10},
+        "EVALUATORS": ("kitti_evaluator", "kitti_evaluator_0_30", "kitti_evaluator_30_50", "kitti_evaluator_50_80"),
+        "TEST": {"GT_SCALE": True},
+        "LOG_PERIOD": 20,
+    },
 }

@@ -81,6 +81,8 @@ _PROTOS = {
     "sde_bilinear2_bwd": ([_P, _I, _I, _I, _I, _I, _P, _P], c_int),
     "sde_softplus_head_fwd": ([_P, _I, _I, _I, _I, _I, _I, _P, _P], c_int),
     "sde_softplus_head_bwd": ([_P, _P, _I, _I, _I, _I, _I, _I, _P, _P], c_int),
+    # GoogleResNetv2's transposed convolution (csrc/deconv.hip; autograd wrapper in hip/nn.py)
+    "sde_deconv3x3s2_fwd": ([_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P], c_int),
     # GoogleMotionNet / GooglePoseNet operators (csrc/motion.hip; autograd wrappers in hip/motion.py)
     "sde_motion_resize_cat_fwd": ([_P, _I, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P], c_int),
     "sde_motion_resize_cat_bwd": ([_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P], c_int),

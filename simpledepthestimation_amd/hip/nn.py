@@ -731,6 +731,139 @@ def conv2d(x, weight, bias=None, stride=1, pad=0, reflect=False, act=ACT_NONE, s
 
 
 # ---------------------------------------------------------------------------------------------------------------
+# Transposed convolution 3x3 / stride 2 / padding 1 / output_padding 1 (+bias, +ReLU): GoogleResNetv2's up-sampling layer
+# ---------------------------------------------------------------------------------------------------------------
+DECONV_DIRECT = True    # forward on the parity-split kernel (sde_deconv3x3s2_fwd); False: the zero-insertion route through the convolution engine + its
+                        # ReLU pass (A/B baseline, and a second implementation to test against)
+DECONV_RULE = True      # ... except the layers deconv_direct() sends back to that route; False: every layer takes the kernel (tests, A/B)
+
+
+def deconv_direct(B, H, W, C, ldy, esize):
+    """Whether the forward of a layer takes the parity-split kernel.  Its workgroup (an 8 x 16 pixel tile x 32 output channels) walks the input channels
+    in serial 64-byte steps; a layer with 16 or more steps whose grid has fewer workgroups than the device has compute units (256) leaves that walk
+    exposed, and the engine's split-K GEMM over the zero-inserted image was measured faster there: GoogleResNetv2's 512 -> 256 layer at 16 x 6 x 10,
+    19.6 against 18.5 us (profiles/google_v2_bench.txt).  Every other layer of that network takes the kernel (1.12 - 5.0 x faster)."""
+    if not DECONV_DIRECT:
+        return False
+    if not DECONV_RULE:
+        return True
+    workgroups = B * ((H + 7) // 8) * ((W + 15) // 16) * ((ldy + 31) // 32 if ldy > 16 else 1)
+    return not (C * esize >= 16 * 64 and workgroups < 256)
+
+
+class _ConvTranspose2d(torch.autograd.Function):
+    """y = act(ConvTranspose2d(x) + bias).  The weight [Cin,Cout,3,3], read as OIHW, is the weight of the adjoint Conv2d(Cout -> Cin, 3, stride 2,
+    padding 1): the forward is that convolution's data gradient (operand: its for_dgrad pack), the data gradient its forward, the weight gradient its
+    weight gradient with x in the role of the output gradient -- every backward GEMM is the engine's, in the phase's weight-gradient schedule."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, act, owner=None):
+        if not x.is_contiguous():
+            raise L.SdeHipError("conv_transpose2d: the NHWC input must be contiguous")
+        if act not in (ACT_NONE, ACT_RELU):
+            raise L.SdeHipError(f"conv_transpose2d: activation {act} is not supported (ACT_NONE, ACT_RELU)")
+        dt = x.dtype
+        if dt not in (torch.float32, torch.bfloat16):
+            raise L.SdeHipError(f"conv_transpose2d runs in fp32 or bf16, not {dt}")
+        V = vec_of(dt)
+        B, H, W, C = x.shape
+        Cin, Cout, KH, KW = weight.shape
+        if (KH, KW) != (3, 3):
+            raise L.SdeHipError("conv_transpose2d: 3x3 kernels only")
+        if C % V or Cin > C:
+            raise L.SdeHipError(f"conv_transpose2d: weight expects {Cin} input channels, the tensor carries {C} (multiples of {V})")
+        ldy = pad_to(Cout, V)
+        pre = getattr(owner, "_packed", None) if owner is not None else None
+        if pre is not None and pre[0].dtype == dt and pre[0].shape == (C, 3, 3, ldy):
+            ctx.wb_pre, wf = pre                                   # (adjoint forward operand, its flipped data-gradient operand), packed once per step
+        else:
+            wf, ctx.wb_pre = pack_weight(weight, dt, ldy, C, for_dgrad=True), None     # [ldy][3][3][C], taps flipped
+            if owner is not None:
+                owner._pack_shapes = (dt, ldy, C)                  # WeightPacker's (dtype, Cin_pad, Cout_pad) of the ADJOINT convolution
+        b32 = _f32(bias) if bias is not None else None
+        flops = 2.0 * B * H * W * 9 * Cin * Cout                   # algorithmic: nine tap products per input pixel
+        lib = L.lib()
+        if deconv_direct(B, H, W, C, ldy, x.element_size()):
+            y = torch.empty(B, 2 * H, 2 * W, ldy, device=x.device, dtype=dt)
+            meta = dict(M=4 * B * H * W, N=ldy, K=9 * C // 4, k=3, s=2, mode=3, bytes=x.element_size() * (x.numel() + y.numel())) if L.PROFILE is not None else None
+            _timed("igemm_fwd", flops, 0, lambda: L.check(lib.sde_deconv3x3s2_fwd(L.ptr(x), L.ptr(wf), L.ptr(b32), act, B, H, W, C, Cout, ldy, dtype_code(dt),
+                                                                                   L.ptr(y), L.stream()), "sde_deconv3x3s2_fwd"), meta)
+        else:
+            # the layer as the data gradient of its adjoint: nine taps per output pixel over the virtual zero-inserted image Z[2i, 2j] = x[i, j]
+            d = _desc(x, None, SRC_ZEROINS, 3, 3, 1, 1, False, 2 * H - 1, 2 * W - 1, 2 * H, 2 * W)
+            y, _ = conv_raw(d, dt, wf, b32, ACT_NONE, Cout, ldy, False, x.device, "igemm_fwd", flops)
+            if act == ACT_RELU:
+                z, y = y, torch.empty_like(y)
+                L.check(lib.sde_relu_fwd(L.ptr(z), z.numel(), dtype_code(dt), L.ptr(y), L.stream()), "sde_relu_fwd")
+        ctx.save_for_backward(x, weight, y if act != ACT_NONE else None)
+        ctx.params = (weight, bias)
+        ctx.act = act
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, weight, y = ctx.saved_tensors
+        act, has_bias = ctx.act, ctx.params[1] is not None
+        dt = x.dtype
+        V = vec_of(dt)
+        lib = L.lib()
+        dev = x.device
+        B, H, W, C = x.shape
+        Cin, Cout = weight.shape[:2]
+        ldy = pad_to(Cout, V)
+        off_main = MAIN_STREAM is not None and torch.cuda.current_stream() != MAIN_STREAM
+        if off_main and not L.is_aux_stream(torch.cuda.current_stream()):
+            raise L.SdeHipError("conv_transpose2d backward is running on a different stream than the one the backward phase started on")
+        dy = dy.contiguous()
+        M = B * 4 * H * W
+        flops = 2.0 * B * H * W * 9 * Cin * Cout
+        # 1. activation backward + bias gradient (as _Conv2d.backward: the column partials' final sum rides in the phase's batched finalize)
+        dbias, dz = None, dy
+        if act != ACT_NONE or has_bias:
+            nblk = lib.sde_reduce_num_blocks(M, ldy)
+            part = torch.empty(nblk + REDUCE_ROWS, ldy, device=dev) if has_bias else None
+            bslot = _grad_slot(ctx.params[1]) if has_bias else None
+            dbias = (bslot if bslot is not None else torch.empty(Cout, device=dev)) if has_bias else None
+            dz = torch.empty_like(dy) if act != ACT_NONE else None
+            later = bslot is not None and WGRAD_DEFER.add_bias(part, nblk, ldy, Cout, bslot)
+            L.check(lib.sde_act_bwd_bias_sum(L.ptr(dy), None, L.ptr(y), act, M, ldy, dtype_code(dt), L.ptr(dz), L.ptr(part), None if later else L.ptr(dbias), Cout,
+                                             int(bslot is not None), L.stream()), "sde_act_bwd_bias_sum")
+            if bslot is not None:
+                dbias = None
+            if dz is None:
+                dz = dy
+        need_dx = ctx.needs_input_grad[0]
+        # the adjoint convolution: dz [B,2H,2W,ldy] -> [B,H,W,C], 3x3, stride 2, padding 1
+        d = _desc(dz, None, SRC_PLAIN, 3, 3, 2, 1, False, 2 * H, 2 * W, H, W)
+        # 2. weight gradient = the adjoint's, with x in the role of its output gradient: it lands in [Cin,Cout,3,3], the weight's own order
+        dw = side = None
+        if ctx.needs_input_grad[1]:
+            splits = lib.sde_conv_wgrad_splits(ctypes.byref(d), Cin)
+            wslot = _grad_slot(ctx.params[0])
+            esz = 4 if dt == torch.float32 else 2
+            meta = dict(M=B * H * W, N=Cin, K=9 * ldy, k=3, s=2, mode=0, splits=splits,
+                        bytes=esz * (dz.numel() + x.numel()) + 8 * splits * Cin * 9 * ldy) if L.PROFILE is not None else None
+            dw = wslot if wslot is not None else torch.empty(weight.shape, device=dev)
+            wflags = (1 if wslot is not None else 0) | (2 if is_ohwi(dw) else 0)
+            op_bytes = (dz.numel() + x.numel()) * dz.element_size()
+            dw, side = WGRAD_DEFER.weight_grad(WGradJob(d, x, dz, None, Cin, C, Cout, ldy, 9, splits, wslot, dw, wflags, 4 * splits * Cin * 9 * ldy, op_bytes,
+                                                        need_dx, off_main, flops, meta))
+        # 3. data gradient = the adjoint's forward (a plain stride-2 convolution of dz: no zero insertion)
+        dx = None
+        if need_dx:
+            wb = ctx.wb_pre if ctx.wb_pre is not None else pack_weight(weight, dt, ldy, C)       # [C][3][3][ldy]
+            dx, _ = conv_raw(d, dt, wb, None, ACT_NONE, Cin, C, False, dev, "igemm_dgrad", flops)
+        WGRAD_DEFER.join(side, (dz, x))
+        return dx, dw, dbias, None, None
+
+
+def conv_transpose2d(x, weight, bias=None, act=ACT_NONE, owner=None):
+    """y = act(F.conv_transpose2d(x, weight, bias, stride=2, padding=1, output_padding=1)) on NHWC tensors: x [B,H,W,C] -> [B,2H,2W,pad(Cout)];
+    weight [Cin,Cout,3,3] (torch's ConvTranspose2d layout), act ACT_NONE or ACT_RELU."""
+    return _ConvTranspose2d.apply(x, weight, bias, int(act), owner)
+
+
+# ---------------------------------------------------------------------------------------------------------------
 # BatchNorm (+ReLU, +residual)
 # ---------------------------------------------------------------------------------------------------------------
 class _BatchNormAct(torch.autograd.Function):

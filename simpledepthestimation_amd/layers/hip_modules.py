@@ -38,6 +38,38 @@ class HipConv2d(nn.Module):
         return f"{self.in_channels}, {self.out_channels}, k={self.kernel_size}, s={self.stride}, p={self.padding}, reflect={self.reflect}"
 
 
+class HipConvTranspose2d(nn.Module):
+    """nn.ConvTranspose2d(Cin, Cout, 3, stride=2, padding=1, output_padding=1) stand-in: ``weight`` [Cin,Cout,3,3] and ``bias`` [Cout] as torch's; the
+    arithmetic is sde_deconv3x3s2_fwd and, in backward, the convolution engine on the adjoint Conv2d(Cout -> Cin, 3, stride 2, padding 1), whose OIHW
+    weight this weight is.  ``_pack_shapes`` / ``_packed`` are therefore that adjoint's: hip.nn.WeightPacker packs the layer with the convolutions."""
+
+    SUPPORTED = "kernel_size=3, stride=2, padding=1, output_padding=1"
+
+    def __init__(self, in_channels, out_channels, kernel_size=3, stride=2, padding=1, output_padding=1, bias=True):
+        super().__init__()
+        if (int(kernel_size), int(stride), int(padding), int(output_padding)) != (3, 2, 1, 1):
+            raise NotImplementedError(f"HipConvTranspose2d supports {self.SUPPORTED} only, got kernel_size={kernel_size}, stride={stride}, "
+                                      f"padding={padding}, output_padding={output_padding}")
+        self.in_channels, self.out_channels = int(in_channels), int(out_channels)
+        self.weight = nn.Parameter(torch.empty(self.in_channels, self.out_channels, 3, 3))
+        self.bias = nn.Parameter(torch.empty(self.out_channels)) if bias else None
+        self._packed = None        # (adjoint forward operand = this layer's data-gradient operand, adjoint dgrad operand = this layer's forward operand)
+        self._pack_shapes = None
+        self.reset_parameters()
+
+    def reset_parameters(self):   # torch.nn.ConvTranspose2d default initialisation (fan_in is computed from dim 1: out_channels * 9)
+        nn.init.kaiming_uniform_(self.weight, a=math.sqrt(5))
+        if self.bias is not None:
+            bound = 1.0 / math.sqrt(self.out_channels * 9)
+            nn.init.uniform_(self.bias, -bound, bound)
+
+    def forward(self, x, act=HN.ACT_NONE):
+        return HN.conv_transpose2d(x, self.weight, self.bias, act, owner=self)
+
+    def extra_repr(self):
+        return f"{self.in_channels}, {self.out_channels}, {self.SUPPORTED}"
+
+
 class HipBatchNorm2d(nn.Module):
     """nn.BatchNorm2d stand-in: batch statistics come from the producing convolution's epilogue (stats slab)."""
 

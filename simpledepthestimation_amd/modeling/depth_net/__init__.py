@@ -3,3 +3,4 @@ from .DepthResNet import DepthResNet  # noqa: F401
 from .PackNet01 import PackNet01  # noqa: F401
 from .BTSNet import BtsModel  # noqa: F401
 from .GoogleResNet import GoogleResNet  # noqa: F401
+from .GoogleResNetv2 import GoogleResNetv2  # noqa: F401
