@@ -460,6 +460,24 @@ int sde_softplus_head_bwd(const void* y, const float* dout, int B, int H, int W,
 int sde_deconv3x3s2_fwd(const void* x, const void* w_packed, const float* bias, int act, int B, int H, int W, int C, int Cout, int ldy, int dtype,
                         void* y, sde_stream_t stream);
 
+/* Grouped 3x3 convolution, the 3x3 of a ResNeXt bottleneck (csrc/gconv.hip): y [B,OH,OW,C] = conv(x [B,H,W,C]) with Cin == Cout == C, G groups,
+ * padding 1, stride 1 or 2 (OH = (H - 1) / stride + 1), no bias, no activation.  C % 16 == 0 and C / G in {4, 8, 16, 32, 64}; fp32 or bf16 storage,
+ * fp32 accumulation; any other argument is refused before a launch.  w: the fp32 MASTER weight, [C][C/G][3][3] or, with w_ohwi set, in the
+ * trainer's channels-last order [C][3][3][C/G]: the kernels convert it on their way into LDS, there is no packed operand.  H, W are the sizes of x
+ * (of dx for the data gradient) in every call.
+ * stats (optional): [sde_gconv3x3_stats_rows + SDE_REDUCE_ROWS][C][2] per-workgroup (sum, sum of squares) of the stored outputs, the slab
+ * sde_bn_finalize / sde_bn_finalize_apply read.  sde_gconv3x3_stats_rows: from the shape alone; -1 for an unsupported one.
+ * sde_gconv3x3_wgrad: dw [C][C/G][3][3] (+)= the weight gradient; ws: sde_gconv3x3_wgrad_ws_bytes bytes of fp32 partials, summed in a fixed order
+ * by a second launch (no atomics: bit-reproducible); flags: SDE_WREDUCE_ACCUMULATE | SDE_WREDUCE_OHWI, as sde_wreduce_item.accumulate. */
+int sde_gconv3x3_stats_rows(int B, int H, int W, int C, int G, int stride, int dtype);
+int sde_gconv3x3_fwd(const void* x, const float* w, int w_ohwi, int B, int H, int W, int C, int G, int stride, int dtype, void* y, float* stats,
+                     sde_stream_t stream);
+int sde_gconv3x3_dgrad(const void* dz, const float* w, int w_ohwi, int B, int H, int W, int C, int G, int stride, int dtype, void* dx,
+                       sde_stream_t stream);
+size_t sde_gconv3x3_wgrad_ws_bytes(int B, int H, int W, int C, int G, int stride, int dtype);
+int sde_gconv3x3_wgrad(const void* x, const void* dz, int B, int H, int W, int C, int G, int stride, int dtype, float* ws, size_t ws_bytes, float* dw,
+                       int flags, sde_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------------
  * GoogleMotionNet / GooglePoseNet operators (csrc/motion.hip; detectron2/modeling/pose_net/GooglePoseNet.py), NHWC activations in fp32 or bf16
  * (SDE_F16 is refused), 16-byte channel groups.  The 3-channel motion field is fp32 [B,h,w,4] (channel 3 zero) in both modes.  No atomics:

@@ -1,6 +1,12 @@
 """BtsModel (projects/Supervised/configs/bts_r50.yaml) training step: bf16, bs 8, 352x704, hipGraph replay.  Prints one JSON line.
 
-    python scripts/bench_bts.py [--steps K] [--warmup W] [--bs B] [--dtype bf16|fp32] [--no-graph]
+    python scripts/bench_bts.py [--steps K] [--warmup W] [--bs B] [--dtype bf16|fp32] [--no-graph] [--encoder resnet50_bts|resnet101_bts|resnext101_bts]
+                                [--gconv-composed] [--layers]
+
+--gconv-composed runs the grouped convolutions of a ResNeXt encoder as dense block-diagonal layers (hip.nn.GCONV_DIRECT = False, the A/B baseline).
+--layers times, instead of the step, every distinct grouped 3x3 layer of the chosen encoder stand-alone at the workload's shapes: forward, data
+gradient and weight gradient, on the grouped kernels and on the composed route (its GEMMs only: the dense weight's assembly and pack are not counted),
+with the kernels' ideal traffic (x + y, dz + dx, x + dz) over time as a fraction of 6.3 TB/s.
 
 Also times the dilated 3x3 convolutions of the decoder's DASPP (forward only, each d of 3/6/12/18/24 at the H/8 map, 256 -> 128 channels in
 bts_r50) and reports their algorithmic TFLOP/s.
@@ -16,13 +22,13 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def make(bs, H, W, dtype, graph):
+def make(bs, H, W, dtype, graph, encoder="resnet50_bts"):
     from simpledepthestimation_amd.config import get_cfg
     from simpledepthestimation_amd.engine.trainer import supervised_trainer
     from simpledepthestimation_amd.modeling import build_model
     cfg = get_cfg()
     cfg.MODEL.META_ARCHITECTURE, cfg.MODEL.DEVICE, cfg.MODEL.DATASET, cfg.MODEL.COMPUTE_DTYPE = "SupDepthModel", "cuda:0", "kitti", dtype
-    cfg.MODEL.DEPTH_NET.NAME, cfg.MODEL.DEPTH_NET.ENCODER_NAME, cfg.MODEL.DEPTH_NET.BTS_SIZE = "BtsModel", "resnet50_bts", 512
+    cfg.MODEL.DEPTH_NET.NAME, cfg.MODEL.DEPTH_NET.ENCODER_NAME, cfg.MODEL.DEPTH_NET.BTS_SIZE = "BtsModel", encoder, 512
     cfg.SOLVER.DEPTH_LR = 2e-4
     model = build_model(cfg).train()
     tr = supervised_trainer(model, cfg, use_graph=graph)
@@ -58,6 +64,58 @@ def time_dilated(bs, H, W, dtype, reps=20):
     return res
 
 
+def grouped_layers(encoder, H, W):
+    """[(C, groups, stride, h, w, count)]: the distinct grouped 3x3 layers of the encoder with their input sizes for an H x W image."""
+    from simpledepthestimation_amd.layers.hip_modules import HipGroupedConv2d
+    from simpledepthestimation_amd.modeling.depth_net.BTSNet import BtsEncoder
+    bm = BtsEncoder(encoder).base_model
+    h, w = ((H - 1) // 2 + 1 - 1) // 2 + 1, ((W - 1) // 2 + 1 - 1) // 2 + 1          # stem convolution and max-pool, stride 2 each
+    found = {}
+    for layer in (bm.layer1, bm.layer2, bm.layer3, bm.layer4):
+        for blk in layer:
+            c = blk.conv2
+            if isinstance(c, HipGroupedConv2d):
+                key = (c.in_channels, c.groups, c.stride, h, w)
+                found[key] = found.get(key, 0) + 1
+            h, w = (h - 1) // c.stride + 1, (w - 1) // c.stride + 1
+    return [k + (n,) for k, n in found.items()]
+
+
+def time_layers(encoder, bs, H, W, dtype, reps=200):
+    from simpledepthestimation_amd.hip import lib as L
+    from simpledepthestimation_amd.hip import nn as HN
+    dt = torch.bfloat16 if dtype == "bf16" else torch.float32
+    es = 2 if dtype == "bf16" else 4
+    rows = []
+    for C, G, stride, h, w, count in grouped_layers(encoder, H, W):
+        x = torch.randn(bs, h, w, C, device="cuda").to(dt).requires_grad_(True)
+        wt = (torch.randn(C, C // G, 3, 3, device="cuda") * 0.05).requires_grad_(True)
+        oh, ow = (h - 1) // stride + 1, (w - 1) // stride + 1
+        gy = torch.randn(bs, oh, ow, C, device="cuda").to(dt)
+        nx, ny = x.numel() * es, gy.numel() * es
+        row = {"C": C, "groups": G, "stride": stride, "in": [bs, h, w], "layers": count}
+        for direct in (True, False):
+            HN.GCONV_DIRECT = direct
+            try:
+                for timed in (False, True):           # one untimed pass first (code-object load, allocator)
+                    x.grad = wt.grad = None
+                    L.PROFILE, L.PROFILE_REPEAT = ([], reps) if timed else (None, 1)
+                    HN.grouped_conv3x3(x, wt, G, stride).backward(gy)
+                    torch.cuda.synchronize()
+                rec = {}
+                for kind, _, _, e0, e1, _, rep in L.PROFILE:
+                    rec[kind] = rec.get(kind, 0.0) + e0.elapsed_time(e1) / rep * 1e3
+            finally:
+                L.PROFILE, L.PROFILE_REPEAT, HN.GCONV_DIRECT = None, 1, True
+            us = {"fwd": rec.get("igemm_fwd", 0.0), "dgrad": rec.get("igemm_dgrad", 0.0), "wgrad": rec.get("wgrad", 0.0) + rec.get("wgrad_reduce", 0.0)}
+            tag = "kernels" if direct else "composed"
+            row[tag + "_us"] = {k: round(v, 1) for k, v in us.items()}
+            if direct:
+                row["hbm_fraction"] = {k: round((nx + ny) / (us[k] * 1e-6) / 6.3e12, 3) for k in us if us[k] > 0}
+        rows.append(row)
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=20)
@@ -68,8 +126,20 @@ def main():
     ap.add_argument("--dtype", default="bf16")
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--no-dilated", action="store_true")
+    ap.add_argument("--encoder", default="resnet50_bts")
+    ap.add_argument("--gconv-composed", action="store_true")
+    ap.add_argument("--layers", action="store_true")
+    ap.add_argument("--reps", type=int, default=200, help="--layers: back-to-back launches per timed window")
     a = ap.parse_args()
-    model, tr, batch = make(a.bs, a.height, a.width, a.dtype, not a.no_graph)
+    if a.layers:
+        print(json.dumps({"workload": "bts_grouped_layers", "encoder": a.encoder, "dtype": a.dtype, "bs": a.bs, "size": [a.height, a.width],
+                          "reps": a.reps,
+                          "layers": time_layers(a.encoder, a.bs, a.height, a.width, a.dtype, a.reps)}))
+        return
+    if a.gconv_composed:
+        from simpledepthestimation_amd.hip import nn as HN
+        HN.GCONV_DIRECT = False
+    model, tr, batch = make(a.bs, a.height, a.width, a.dtype, not a.no_graph, a.encoder)
     for _ in range(a.warmup):
         out = tr.step(dict(batch))
     torch.cuda.synchronize()
@@ -81,7 +151,7 @@ def main():
     torch.cuda.synchronize()
     ms = e0.elapsed_time(e1) / a.steps
     loss = float(out["silog_loss"].detach())
-    line = {"workload": "bts_r50", "dtype": a.dtype, "bs": a.bs, "size": [a.height, a.width], "graph": not a.no_graph, "steps": a.steps,
+    line = {"workload": {"resnet50_bts": "bts_r50"}.get(a.encoder, "bts_" + a.encoder[:-4]), "gconv": "composed" if a.gconv_composed else "kernels", "dtype": a.dtype, "bs": a.bs, "size": [a.height, a.width], "graph": not a.no_graph, "steps": a.steps,
             "ms_per_step": round(ms, 3), "images_per_s": round(a.bs * 1000.0 / ms, 1), "loss": loss, "finite": loss == loss}
     if not a.no_dilated:
         line["dilated_fwd"] = time_dilated(a.bs, a.height, a.width, a.dtype)

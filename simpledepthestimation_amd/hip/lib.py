@@ -83,6 +83,12 @@ _PROTOS = {
     "sde_softplus_head_bwd": ([_P, _P, _I, _I, _I, _I, _I, _I, _P, _P], c_int),
     # GoogleResNetv2's transposed convolution (csrc/deconv.hip; autograd wrapper in hip/nn.py)
     "sde_deconv3x3s2_fwd": ([_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P], c_int),
+    # grouped 3x3 convolution of the ResNeXt bottleneck (csrc/gconv.hip; autograd wrapper in hip/nn.py)
+    "sde_gconv3x3_stats_rows": ([_I, _I, _I, _I, _I, _I, _I], c_int),
+    "sde_gconv3x3_fwd": ([_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P], c_int),
+    "sde_gconv3x3_dgrad": ([_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P], c_int),
+    "sde_gconv3x3_wgrad_ws_bytes": ([_I, _I, _I, _I, _I, _I, _I], c_size_t),
+    "sde_gconv3x3_wgrad": ([_P, _P, _I, _I, _I, _I, _I, _I, _I, _P, c_size_t, _P, _I, _P], c_int),
     # GoogleMotionNet / GooglePoseNet operators (csrc/motion.hip; autograd wrappers in hip/motion.py)
     "sde_motion_resize_cat_fwd": ([_P, _I, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P], c_int),
     "sde_motion_resize_cat_bwd": ([_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P], c_int),

@@ -864,6 +864,126 @@ def conv_transpose2d(x, weight, bias=None, act=ACT_NONE, owner=None):
 
 
 # ---------------------------------------------------------------------------------------------------------------
+# Grouped 3x3 convolution (padding 1, stride 1 or 2, no bias): the 3x3 of a ResNeXt bottleneck
+# ---------------------------------------------------------------------------------------------------------------
+GCONV_DIRECT = True     # the grouped kernels (csrc/gconv.hip); False: a dense block-diagonal weight through conv2d, 32 x the useful FLOPs at 32 groups
+                        # (A/B baseline, and a second implementation to test against)
+GCONV_CG = (4, 8, 16, 32, 64)       # supported channels per group
+
+
+def _gconv_check(x, weight, groups, stride):
+    if x.dim() != 4 or weight.dim() != 4:
+        raise L.SdeHipError("grouped_conv3x3: x is NHWC [B,H,W,C], weight [C, C/groups, 3, 3]")
+    if x.dtype not in (torch.float32, torch.bfloat16):
+        raise L.SdeHipError(f"grouped_conv3x3 runs in fp32 or bf16, not {x.dtype}")
+    C, Cg, KH, KW = weight.shape
+    if (KH, KW) != (3, 3):
+        raise L.SdeHipError(f"grouped_conv3x3: 3x3 kernels only, got {KH}x{KW}")
+    if stride not in (1, 2):
+        raise L.SdeHipError(f"grouped_conv3x3: stride 1 or 2 only, got {stride}")
+    if groups <= 0 or C != Cg * groups or x.shape[3] != C:
+        raise L.SdeHipError(f"grouped_conv3x3: channel mismatch: the weight {tuple(weight.shape)} with {groups} groups maps {Cg * groups} -> {C} channels, "
+                            f"the tensor carries {x.shape[3]} (input and output channels must be equal)")
+    if Cg not in GCONV_CG or C % 16:
+        raise L.SdeHipError(f"grouped_conv3x3: {Cg} channels per group of {C} are not supported: channels per group in {GCONV_CG}, channels a multiple of 16")
+    if weight.dtype != torch.float32 or not _dense(weight):
+        raise L.SdeHipError("grouped_conv3x3: the weight must be a dense float32 tensor (OIHW or channels-last)")
+    if not x.is_contiguous():
+        raise L.SdeHipError("grouped_conv3x3: the NHWC input must be contiguous")
+
+
+class _GroupedConv3x3(torch.autograd.Function):
+    """y = conv2d(x, weight, padding=1, stride, groups).  The kernels read the fp32 master weight in either memory order: nothing is packed.  Backward runs
+    the data gradient and then the weight gradient on the current stream: the layer joins neither WGradReducer's groups nor its side stream."""
+
+    @staticmethod
+    def forward(ctx, x, weight, groups, stride, want_stats, n_out):
+        ctx.set_materialize_grads(False)
+        if n_out > 1 and want_stats:
+            raise L.SdeHipError("grouped_conv3x3: output aliases (n_out) belong to the BatchNorm that follows when statistics are requested")
+        # x may be a BatchNorm + ReLU output registered for a fused backward reduction: this layer's data gradient does not carry one, and the entry must not linger
+        _HANDOVER.take_bn_out(x)
+        B, H, W, C = x.shape
+        Cg = C // groups
+        OH, OW = (H - 1) // stride + 1, (W - 1) // stride + 1
+        lib, code = L.lib(), dtype_code(x.dtype)
+        y = torch.empty(B, OH, OW, C, device=x.device, dtype=x.dtype)
+        stats = None
+        if want_stats:
+            rows = lib.sde_gconv3x3_stats_rows(B, H, W, C, groups, stride, code)
+            if rows <= 0:
+                raise L.SdeHipError(f"sde_gconv3x3_stats_rows failed: {lib.sde_last_error().decode()}")
+            stats = torch.empty(rows + REDUCE_ROWS, C, 2, device=x.device, dtype=torch.float32)
+        flops = 2.0 * B * OH * OW * C * 9 * Cg                     # algorithmic
+        meta = dict(M=B * OH * OW, N=C, K=9 * Cg, k=3, s=stride, mode=4, bytes=x.element_size() * (x.numel() + y.numel())) if L.PROFILE is not None else None
+        _timed("igemm_fwd", flops, 0, lambda: L.check(lib.sde_gconv3x3_fwd(L.ptr(x), _wptr(weight), int(is_ohwi(weight)), B, H, W, C, groups, stride, code, L.ptr(y),
+                                                                           L.ptr(stats), L.stream()), "sde_gconv3x3_fwd"), meta)
+        ctx.save_for_backward(x, weight)
+        ctx.param = weight
+        ctx.cfg = (groups, stride, want_stats)
+        if want_stats:
+            ctx.mark_non_differentiable(stats)
+            return y, stats
+        return aliases(y, n_out)
+
+    @staticmethod
+    def backward(ctx, *douts):
+        x, weight = ctx.saved_tensors
+        groups, stride, want_stats = ctx.cfg
+        grads = fan_in(douts[:1] if want_stats else douts, 1)
+        if not grads:
+            return (None,) * 6
+        dz = grads[0]
+        B, H, W, C = x.shape
+        Cg = C // groups
+        M = B * dz.shape[1] * dz.shape[2]
+        lib, code = L.lib(), dtype_code(x.dtype)
+        flops = 2.0 * M * C * 9 * Cg
+        esz = x.element_size()
+        dx = dw = None
+        if ctx.needs_input_grad[0]:
+            dx = torch.empty_like(x)
+            meta = dict(M=B * H * W, N=C, K=9 * Cg, k=3, s=stride, mode=4, bytes=esz * (dz.numel() + dx.numel())) if L.PROFILE is not None else None
+            _timed("igemm_dgrad", flops, 0, lambda: L.check(lib.sde_gconv3x3_dgrad(L.ptr(dz), _wptr(weight), int(is_ohwi(weight)), B, H, W, C, groups, stride, code,
+                                                                                   L.ptr(dx), L.stream()), "sde_gconv3x3_dgrad"), meta)
+        if ctx.needs_input_grad[1]:
+            wslot = _grad_slot(ctx.param)
+            dw = wslot if wslot is not None else torch.empty(weight.shape, device=x.device)      # a fresh gradient tensor is plain OIHW
+            wflags = (1 if wslot is not None else 0) | (2 if is_ohwi(dw) else 0)                   # SDE_WREDUCE_ACCUMULATE | SDE_WREDUCE_OHWI
+            ws_bytes = lib.sde_gconv3x3_wgrad_ws_bytes(B, H, W, C, groups, stride, code)
+            ws = torch.empty(ws_bytes // 4, device=x.device, dtype=torch.float32)
+            meta = dict(M=M, N=C, K=9 * Cg, k=3, s=stride, mode=4, bytes=esz * (dz.numel() + x.numel()) + 2 * ws_bytes) if L.PROFILE is not None else None
+            def call():
+                L.check(lib.sde_gconv3x3_wgrad(L.ptr(x), L.ptr(dz), B, H, W, C, groups, stride, code, L.ptr(ws), ws_bytes, _wptr(dw), wflags, L.stream()), "sde_gconv3x3_wgrad")
+            # (the profiler repeats a timed launch PROFILE_REPEAT times back to back: only the overwriting form is idempotent)
+            if wslot is None or L.PROFILE_REPEAT == 1:
+                _timed("wgrad", flops, 0, call, meta)
+            else:
+                call()
+            if wslot is not None:
+                dw = None
+        return dx, dw, None, None, None, None
+
+
+def _gconv_dense_weight(weight, groups):
+    """The dense [C,C,3,3] weight with the groups' blocks on its diagonal and zeros elsewhere; autograd gathers the blocks back."""
+    C, Cg = weight.shape[:2]
+    co = torch.arange(C, device=weight.device)
+    ci = (co // Cg * Cg)[:, None] + torch.arange(Cg, device=weight.device)[None, :]
+    return torch.zeros(C, C, 3, 3, device=weight.device, dtype=weight.dtype).index_put((co[:, None], ci), weight)
+
+
+def grouped_conv3x3(x, weight, groups, stride=1, bn_stats=False, n_out=1):
+    """y = F.conv2d(x, weight, None, stride, 1, groups=groups) on NHWC tensors, input and output channels equal: weight [C, C/groups, 3, 3] (torch's).
+    Supported: fp32 / bf16, 3x3, stride 1 or 2, C % 16 == 0, C / groups in GCONV_CG.  bn_stats / n_out as conv2d's."""
+    groups, stride = int(groups), int(stride)
+    _gconv_check(x, weight, groups, stride)
+    if GCONV_DIRECT:
+        return _GroupedConv3x3.apply(x, weight, groups, stride, bool(bn_stats), int(n_out))
+    return conv2d(x, _gconv_dense_weight(weight, groups), None, stride, 1, bn_stats=bn_stats, n_out=n_out)
+
+
+# ---------------------------------------------------------------------------------------------------------------
 # BatchNorm (+ReLU, +residual)
 # ---------------------------------------------------------------------------------------------------------------
 class _BatchNormAct(torch.autograd.Function):

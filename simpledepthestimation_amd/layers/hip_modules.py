@@ -70,6 +70,31 @@ class HipConvTranspose2d(nn.Module):
         return f"{self.in_channels}, {self.out_channels}, {self.SUPPORTED}"
 
 
+class HipGroupedConv2d(nn.Module):
+    """nn.Conv2d(channels, channels, 3, stride, padding=1, groups=groups, bias=False) stand-in, the 3x3 of a ResNeXt bottleneck: ``weight``
+    [C, C/groups, 3, 3] as torch's; the arithmetic is sde_gconv3x3_fwd / _dgrad / _wgrad, which read the fp32 weight itself (no packed operands, so
+    hip.nn.WeightPacker passes the layer by).  Same forward contract as HipConv2d towards conv_bn / conv_norm."""
+
+    SUPPORTED = f"channels a multiple of 16, channels / groups in {HN.GCONV_CG}, stride 1 or 2"
+
+    def __init__(self, channels, groups, stride=1):
+        super().__init__()
+        channels, groups, stride = int(channels), int(groups), int(stride)
+        if groups <= 0 or channels % groups or channels % 16 or channels // groups not in HN.GCONV_CG or stride not in (1, 2):
+            raise NotImplementedError(f"HipGroupedConv2d supports {self.SUPPORTED}; got channels={channels}, groups={groups}, stride={stride}")
+        self.in_channels = self.out_channels = channels
+        self.groups, self.stride, self.kernel_size, self.padding = groups, stride, 3, 1
+        self.weight = nn.Parameter(torch.empty(channels, channels // groups, 3, 3))
+        self.bias = None
+        nn.init.kaiming_uniform_(self.weight, a=math.sqrt(5))       # torch.nn.Conv2d default initialisation
+
+    def forward(self, x, bn_stats=False, n_out=1):
+        return HN.grouped_conv3x3(x, self.weight, self.groups, self.stride, bn_stats, n_out)
+
+    def extra_repr(self):
+        return f"{self.in_channels}, {self.out_channels}, k=3, s={self.stride}, p=1, groups={self.groups}"
+
+
 class HipBatchNorm2d(nn.Module):
     """nn.BatchNorm2d stand-in: batch statistics come from the producing convolution's epilogue (stats slab)."""
 

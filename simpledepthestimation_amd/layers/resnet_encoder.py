@@ -1,7 +1,8 @@
-"""ResNet-18/34/50 encoder on the HIP convolution engine, in the two variants the reference trains.
+"""ResNet-18/34/50/101 and ResNeXt encoder on the HIP convolution engine, in the two variants the reference trains.
 
 Reference: detectron2/layers/resnet_encoder.py:L61-99 (ResnetEncoder: 5 features = relu(bn1(conv1)), layer1(maxpool), layer2-4)
-wrapping torchvision 0.9 resnetXX (v1.5: stride on the 3x3 of a Bottleneck; kaiming-normal fan_out convs, BN gamma=1/beta=0), and
+wrapping torchvision 0.9 resnetXX (v1.5: stride on the 3x3 of a Bottleneck; kaiming-normal fan_out convs, BN gamma=1/beta=0; ``groups`` /
+``width_per_group`` as torchvision's ResNeXt: the 3x3 becomes a grouped convolution of width int(planes * width_per_group / 64) * groups), and
 detectron2/layers/resnet.py:L35-59 (ResNetTF under GoogleResNet.py:L21-68: the same network with a configurable norm layer, whose projection
 shortcut is a bare 1x1 convolution built only where the width changes): ``shortcut_norm=False``.
 Attribute / state-dict names follow torchvision (``encoder.conv1``, ``encoder.layer1.0.bn2``, ``...downsample.0``, ``encoder.fc``).
@@ -11,7 +12,7 @@ import torch
 import torch.nn as nn
 
 from ..hip import nn as HN
-from .hip_modules import HipBatchNorm2d, HipConv2d, conv_norm
+from .hip_modules import HipBatchNorm2d, HipConv2d, HipGroupedConv2d, conv_norm
 
 
 class _Block(nn.Module):
@@ -47,13 +48,14 @@ class BasicBlock(_Block):
 class Bottleneck(_Block):
     expansion = 4
 
-    def __init__(self, inplanes, planes, stride=1, downsample=None, norm_layer=HipBatchNorm2d):
+    def __init__(self, inplanes, planes, stride=1, downsample=None, norm_layer=HipBatchNorm2d, groups=1, base_width=64):
         super().__init__()
-        self.conv1 = HipConv2d(inplanes, planes, 1, 1, 0, bias=False)
-        self.bn1 = norm_layer(planes)
-        self.conv2 = HipConv2d(planes, planes, 3, stride, 1, bias=False)
-        self.bn2 = norm_layer(planes)
-        self.conv3 = HipConv2d(planes, planes * 4, 1, 1, 0, bias=False)
+        width = int(planes * (base_width / 64.0)) * groups            # torchvision's width rule
+        self.conv1 = HipConv2d(inplanes, width, 1, 1, 0, bias=False)
+        self.bn1 = norm_layer(width)
+        self.conv2 = HipGroupedConv2d(width, groups, stride) if groups > 1 else HipConv2d(width, width, 3, stride, 1, bias=False)
+        self.bn2 = norm_layer(width)
+        self.conv3 = HipConv2d(width, planes * 4, 1, 1, 0, bias=False)
         self.bn3 = norm_layer(planes * 4)
         self.downsample = downsample
 
@@ -70,9 +72,12 @@ class ResNet(nn.Module):
     shortcut_norm: the projection shortcut is conv1x1 + norm wherever the stride or the width changes (torchvision); False: ResNetTF's bare
     conv1x1 where the width changes."""
 
-    def __init__(self, block, layers, norm_layer=HipBatchNorm2d, shortcut_norm=True, num_classes=1000):
+    def __init__(self, block, layers, norm_layer=HipBatchNorm2d, shortcut_norm=True, num_classes=1000, groups=1, width_per_group=64):
         super().__init__()
         self.norm_layer, self.shortcut_norm = norm_layer, bool(shortcut_norm)
+        if (groups != 1 or width_per_group != 64) and block is not Bottleneck:
+            raise ValueError("BasicBlock only supports groups=1 and width_per_group=64")
+        self.block_kw = dict(groups=int(groups), base_width=int(width_per_group)) if block is Bottleneck else {}
         self.inplanes = 64
         self.conv1 = HipConv2d(3, 64, 7, 2, 3, bias=False)
         self.bn1 = norm_layer(64)
@@ -82,7 +87,7 @@ class ResNet(nn.Module):
         self.layer4 = self._make_layer(block, 512, layers[3], stride=2)
         self.fc = nn.Linear(512 * block.expansion, num_classes)
         for m in self.modules():
-            if isinstance(m, HipConv2d):
+            if isinstance(m, (HipConv2d, HipGroupedConv2d)):
                 nn.init.kaiming_normal_(m.weight, mode="fan_out", nonlinearity="relu")
 
     def _make_layer(self, block, planes, blocks, stride=1):
@@ -91,17 +96,18 @@ class ResNet(nn.Module):
             downsample = nn.Sequential(HipConv2d(self.inplanes, width, 1, stride, 0, bias=False), *([self.norm_layer(width)] if self.shortcut_norm else []))
         elif stride != 1:
             raise NotImplementedError("ResNetTF's max-pool shortcut (resnet.py:L47-48) is not on the HIP path")
-        layers = [block(self.inplanes, planes, stride, downsample, self.norm_layer)]
+        layers = [block(self.inplanes, planes, stride, downsample, self.norm_layer, **self.block_kw)]
         self.inplanes = width
-        layers += [block(self.inplanes, planes, 1, None, self.norm_layer) for _ in range(1, blocks)]
+        layers += [block(self.inplanes, planes, 1, None, self.norm_layer, **self.block_kw) for _ in range(1, blocks)]
         return nn.Sequential(*layers)
 
 
-_SPECS = {18: (BasicBlock, [2, 2, 2, 2]), 34: (BasicBlock, [3, 4, 6, 3]), 50: (Bottleneck, [3, 4, 6, 3])}
+_SPECS = {18: (BasicBlock, [2, 2, 2, 2]), 34: (BasicBlock, [3, 4, 6, 3]), 50: (Bottleneck, [3, 4, 6, 3]), 101: (Bottleneck, [3, 4, 23, 3])}
 
 
 class ResnetEncoder(nn.Module):
-    def __init__(self, num_layers, pretrained=False, num_input_images=1, norm_layer=HipBatchNorm2d, shortcut_norm=True):
+    def __init__(self, num_layers, pretrained=False, num_input_images=1, norm_layer=HipBatchNorm2d, shortcut_norm=True, groups=1, width_per_group=64,
+                 layers=None):
         super().__init__()
         if num_layers not in _SPECS:
             raise ValueError("{} is not a valid number of resnet layers".format(num_layers))
@@ -111,8 +117,9 @@ class ResnetEncoder(nn.Module):
         if num_input_images != 1:
             raise NotImplementedError("multi-image encoders are not on the path")
         self.num_ch_enc = np.array([64, 64, 128, 256, 512])
-        block, layers = _SPECS[num_layers]
-        self.encoder = ResNet(block, layers, norm_layer, shortcut_norm)
+        block, spec = _SPECS[num_layers]
+        # layers: another block count per stage for the block type of `num_layers` (small networks in tests)
+        self.encoder = ResNet(block, spec if layers is None else list(layers), norm_layer, shortcut_norm, groups=groups, width_per_group=width_per_group)
         if num_layers > 34:
             self.num_ch_enc[1:] *= 4
         # the weight-gradient schedule HipTrainer applies (engine.trainer.schedule_family, hip.lib.SCHEDULES).  "resnet_basic" was measured on the

@@ -1,4 +1,4 @@
-"""BtsModel = ResNet-50 encoder + BTS decoder (reference: detectron2/modeling/depth_net/BTSNet.py:L281-413).
+"""BtsModel = ResNet-50 / ResNet-101 / ResNeXt-101 32x8d encoder + BTS decoder (reference: detectron2/modeling/depth_net/BTSNet.py:L281-413).
 
 State-dict keys equal the reference's (``encoder.base_model.layer3.5.bn2.running_var``, ``decoder.get_depth.0.weight`` ...), so its
 checkpoints load with ``strict=True``.  The encoder is this package's ResNet encoder (layers/resnet_encoder.py) with its torchvision module
@@ -18,7 +18,8 @@ from .DepthResNet import compute_dtype
 
 logger = logging.getLogger(__name__)
 
-_ENCODERS = {"resnet50_bts": 50}
+# MODEL.DEPTH_NET.ENCODER_NAME -> (layers, groups, width per group) of the torchvision network the reference wraps (BTSNet.py:L291-306)
+_ENCODERS = {"resnet50_bts": (50, 1, 64), "resnet101_bts": (101, 1, 64), "resnext101_bts": (101, 32, 8)}
 
 
 class BtsEncoder(ResnetEncoder):
@@ -27,7 +28,8 @@ class BtsEncoder(ResnetEncoder):
     def __init__(self, encoder_name):
         if encoder_name not in _ENCODERS:
             raise NotImplementedError(f"BtsModel encoder {encoder_name!r} is not on the HIP path; supported: {sorted(_ENCODERS)}")
-        super().__init__(_ENCODERS[encoder_name])
+        num_layers, groups, width = _ENCODERS[encoder_name]
+        super().__init__(num_layers, groups=groups, width_per_group=width)
         self.encoder_name = encoder_name
         self.base_model = self._modules.pop("encoder")
         self.feat_out_channels = [64, 256, 512, 1024, 2048]
