@@ -268,6 +268,12 @@ int sde_conv_set_option(int key, int value);
  * summed in a fixed order (stacks taller than SDE_WGRAD_FOLD_ROWS as that many chunk sums first) -- bit-reproducible, no atomics. */
 #define SDE_WGRAD_FOLD_ROWS 16
 int sde_conv_wgrad_splits(const sde_conv_desc* d, int Cout);
+/* Which weight-gradient GEMM sde_conv_wgrad / sde_conv_wgrad_partial take for this layer (the dispatcher's own predicates; tests pin their
+ * cases with it): 1 = halo kernel (wgrad_halo.hip), 2 = LDS-DMA kernel (wgrad_dma.hip), 3 = register-staged kernel (conv.hip); 0 = bad descriptor. */
+#define SDE_WGRAD_HALO_KERNEL 1
+#define SDE_WGRAD_DMA_KERNEL 2
+#define SDE_WGRAD_STAGED_KERNEL 3
+int sde_conv_wgrad_variant(const sde_conv_desc* d, int Cout, int ldd);
 int sde_conv_wgrad(const sde_conv_desc* d, const void* dy, int Cout, int ldd, int Cin_real, float* slab, int splits, float* dw, int accumulate,
                    sde_stream_t stream);
 

@@ -1649,6 +1649,18 @@ int sde_conv_fwd_tiles_m(const sde_conv_desc* d, int ldy) {
 int g_wgrad_halo = 1;       // SDE_OPT_WGRAD_HALO
 int g_wgrad_dma = 1;        // SDE_OPT_WGRAD_DMA
 static bool use_whalo(const Gather& g, int dtype, int Cout, int ldd) { return g_wgrad_halo && sdeconv::whalo_applicable(g, dtype, Cout, ldd); }
+// which weight-gradient GEMM a layer takes (one place: wgrad_partial and sde_conv_wgrad_variant)
+static int wgrad_kind(const Gather& g, int dtype, int Cout, int ldd) {
+    if (use_whalo(g, dtype, Cout, ldd)) return SDE_WGRAD_HALO_KERNEL;
+    if (g_wgrad_dma && sdeconv::wgrad_dma_applicable(g, dtype, Cout, ldd)) return SDE_WGRAD_DMA_KERNEL;
+    return SDE_WGRAD_STAGED_KERNEL;
+}
+
+int sde_conv_wgrad_variant(const sde_conv_desc* d, int Cout, int ldd) {
+    Gather g;
+    if (!d || fill_gather(d, g, "sde_conv_wgrad_variant") != SDE_OK) return 0;
+    return wgrad_kind(g, d->dtype, Cout, ldd);
+}
 
 int sde_conv_wgrad_splits(const sde_conv_desc* d, int Cout) {
     {
@@ -1682,7 +1694,8 @@ static int wgrad_partial(const sde_conv_desc* d, const void* dy, int Cout, int l
     const int V = SDE_IS16(d->dtype) ? 8 : 4;
     SDE_CHECK_ARG(Cout > 0 && ldd >= Cout && ldd % V == 0, "sde_conv_wgrad: bad Cout=%d ldd=%d", Cout, ldd);
     SDE_CHECK_ARG(splits >= 1, "sde_conv_wgrad: bad splits=%d", splits);
-    if (use_whalo(p.g, d->dtype, Cout, ldd)) {
+    const int kind = wgrad_kind(p.g, d->dtype, Cout, ldd);
+    if (kind == SDE_WGRAD_HALO_KERNEL) {
         SDE_CHECK_ARG(splits == sdeconv::whalo_splits(p.g, Cout), "sde_conv_wgrad: splits=%d, this layer needs sde_conv_wgrad_splits() = %d", splits,
                       sdeconv::whalo_splits(p.g, Cout));
         sdeconv::whalo_run(p.g, d->dtype, dy, Cout, ldd, slab, splits, s);
@@ -1695,7 +1708,7 @@ static int wgrad_partial(const sde_conv_desc* d, const void* dy, int Cout, int l
     rps = sde_cdiv(rps, BR) * BR;
     SDE_CHECK_ARG((long)rps * splits >= p.g.M, "sde_conv_wgrad: split arithmetic");
     // 1x1 layers 11-16 us against 14-21 us for the register-staged kernel, 3x3 layers 22-26 us against 27-30 us (profiles/README.md item 16)
-    if (g_wgrad_dma && sdeconv::wgrad_dma_applicable(p.g, d->dtype, Cout, ldd)) {
+    if (kind == SDE_WGRAD_DMA_KERNEL) {
         sdeconv::wgrad_dma_run(p.g, d->dtype, dy, Cout, ldd, slab, splits, rps, s);
         SDE_CHECK_LAUNCH("sde_conv_wgrad (LDS-DMA)");
         g = p.g;

@@ -44,6 +44,7 @@ L.register_protos({
     "sde_conv_set_halo_min_blocks": ([_I], c_int),
     "sde_conv_set_option": ([_I, _I], c_int),
     "sde_conv_wgrad_splits": ([POINTER(ConvDesc), _I], c_int),
+    "sde_conv_wgrad_variant": ([POINTER(ConvDesc), _I, _I], c_int),
     "sde_conv_wgrad": ([POINTER(ConvDesc), _P, _I, _I, _I, _P, _I, _P, _I, _P], c_int),
     "sde_conv_wgrad_partial": ([POINTER(ConvDesc), _P, _I, _I, _P, _I, _P], c_int),
     "sde_wgrad_reduce_batched": ([_P, _I, _P], c_int),
@@ -97,6 +98,9 @@ def set_option(key, value):
     if old < 0:
         raise L.SdeHipError(f"sde_conv_set_option({key}, {value}) failed: {L.lib().sde_last_error().decode()}")
     return old
+
+
+WGRAD_HALO_KERNEL, WGRAD_DMA_KERNEL, WGRAD_STAGED_KERNEL = 1, 2, 3      # sde_conv_wgrad_variant
 
 
 def dtype_code(dt):

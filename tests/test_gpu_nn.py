@@ -9,6 +9,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import conv_bounds as CB
+
 pytestmark = pytest.mark.gpu
 dev = "cuda"
 
@@ -37,9 +39,13 @@ def relerr(a, b):
     return ((a - b).norm() / (b.norm() + 1e-30)).item()
 
 
-def check(a, b, dtype, name, f32_tol=2e-5, bf16_tol=1.5e-2):
+def check(a, b, dtype, name, f32_tol=2e-5, bf16_tol=1.5e-2, bound=None):
+    """bound (conv_bounds.Bound, the convolution tests): in addition, no element further from the fp64 reference than its a-priori limit."""
+    if bound is not None:
+        CB.assert_within(a, bound, dtype, name, l2_tol=float("inf"))          # (the relative-L2 line is the one below)
     e = relerr(a, b)
-    tol = f32_tol if dtype == torch.float32 else bf16_tol
+    # fp16: the bf16 tolerance scaled by the ratio of the unit roundoffs, 2^-11 / 2^-8
+    tol = f32_tol if dtype == torch.float32 else bf16_tol if dtype == torch.bfloat16 else bf16_tol * 2.0 ** -3
     assert e < tol, f"{name}: relative L2 error {e:.3e} > {tol}"
     mx = (a.double() - b.double()).abs().max().item()
     scale = b.abs().max().item() + 1e-30
@@ -75,7 +81,7 @@ CONV_CASES = [
 ]
 
 
-@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["f32", "bf16"])
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.float16], ids=["f32", "bf16", "fp16"])
 @pytest.mark.parametrize("case", CONV_CASES, ids=[c[0] for c in CONV_CASES])
 def test_conv_fwd_bwd(NN, case, dtype):
     name, B, H, W, Cin, Cout, k, stride, pad, reflect, has_bias, act = case
@@ -84,8 +90,8 @@ def test_conv_fwd_bwd(NN, case, dtype):
     x = torch.randn(B, Cin, H, W, generator=g)
     w = torch.randn(Cout, Cin, k, k, generator=g) / math.sqrt(Cin * k * k)
     b = torch.randn(Cout, generator=g) * 0.1 if has_bias else None
-    if dtype == torch.bfloat16:   # reference sees the same rounded operands
-        x = x.bfloat16().float(); w = w.bfloat16().float()
+    if dtype != torch.float32:   # reference sees the same rounded operands
+        x = x.to(dtype).float(); w = w.to(dtype).float()
     xr = x.clone().requires_grad_(True); wr = w.clone().requires_grad_(True)
     br = b.clone().requires_grad_(True) if has_bias else None
     xin = F.pad(xr, (1, 1, 1, 1), mode="reflect") if reflect else xr
@@ -93,9 +99,11 @@ def test_conv_fwd_bwd(NN, case, dtype):
     if act == 1:
         yr = F.elu(yr)
     gy = torch.randn(yr.shape, generator=g)
-    if dtype == torch.bfloat16:
-        gy = gy.bfloat16().float()
+    if dtype != torch.float32:
+        gy = gy.to(dtype).float()
     yr.backward(gy)
+    cb = CB.ConvCase(x, w, b, dtype, stride=stride, pad=pad, reflect=reflect, act=act)      # fp64 reference with per-element limits
+    lim = cb.backward([gy])
 
     xd = nhwc(x, dtype, V).requires_grad_(True)
     wd = w.clone().to(dev).requires_grad_(True)
@@ -104,15 +112,15 @@ def test_conv_fwd_bwd(NN, case, dtype):
     assert y.shape[:3] == (B, yr.shape[2], yr.shape[3])
     if y.shape[3] > Cout:
         assert (y[..., Cout:] == 0).all(), "padded output channels must be exact zeros"
-    check(nchw(y, Cout), yr.detach(), dtype, "y")
+    check(nchw(y, Cout), yr.detach(), dtype, "y", bound=cb.y)
     y.backward(nhwc(gy, dtype, V))
-    check(wd.grad.cpu(), wr.grad, dtype, "dW")
-    check(nchw(xd.grad, Cin), xr.grad, dtype, "dX")
+    check(wd.grad.cpu(), wr.grad, dtype, "dW", bound=lim["dW"])
+    check(nchw(xd.grad, Cin), xr.grad, dtype, "dX", bound=lim["dX"])
     if has_bias:
-        check(bd.grad.cpu(), br.grad, dtype, "dbias")
+        check(bd.grad.cpu(), br.grad, dtype, "dbias", bound=lim["dbias"])
 
 
-@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["f32", "bf16"])
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.float16], ids=["f32", "bf16", "fp16"])
 @pytest.mark.parametrize("C0,C1,Cout", [(32, 64, 32), (16, 0, 16), (256, 1024, 256), (64, 64, 128)])
 def test_conv_upsample_concat(NN, dtype, C0, C1, Cout):
     """depth_decoder.py:L102-105: upconv(i,1)(cat(upsample(x), skip)) with reflection pad, bias, ELU -- gathered on the fly."""
@@ -123,29 +131,31 @@ def test_conv_upsample_concat(NN, dtype, C0, C1, Cout):
     x1 = torch.randn(B, C1, 2 * h, 2 * w, generator=g) if C1 else None
     wt = torch.randn(Cout, C0 + C1, 3, 3, generator=g) / math.sqrt((C0 + C1) * 9)
     bs = torch.randn(Cout, generator=g) * 0.1
-    if dtype == torch.bfloat16:
-        x0 = x0.bfloat16().float(); wt = wt.bfloat16().float()
-        x1 = x1.bfloat16().float() if C1 else None
+    if dtype != torch.float32:
+        x0 = x0.to(dtype).float(); wt = wt.to(dtype).float()
+        x1 = x1.to(dtype).float() if C1 else None
     x0r = x0.clone().requires_grad_(True); x1r = x1.clone().requires_grad_(True) if C1 else None
     wr = wt.clone().requires_grad_(True); br = bs.clone().requires_grad_(True)
     up = F.interpolate(x0r, scale_factor=2, mode="nearest")
     cat = torch.cat([up, x1r], 1) if C1 else up
     yr = F.elu(F.conv2d(F.pad(cat, (1, 1, 1, 1), mode="reflect"), wr, br))
     gy = torch.randn(yr.shape, generator=g)
-    if dtype == torch.bfloat16:
-        gy = gy.bfloat16().float()
+    if dtype != torch.float32:
+        gy = gy.to(dtype).float()
     yr.backward(gy)
+    cb = CB.ConvCase(x0, wt, bs, dtype, stride=1, pad=1, reflect=True, act=1, x1=x1, upcat=True)
+    lim = cb.backward([gy])
     x0d = nhwc(x0, dtype, V).requires_grad_(True)
     x1d = nhwc(x1, dtype, V).requires_grad_(True) if C1 else None
     wd = wt.clone().to(dev).requires_grad_(True); bd = bs.clone().to(dev).requires_grad_(True)
     y = NN.conv2d(x0d, wd, bd, stride=1, pad=1, reflect=True, act=1, skip=x1d, upsample=True)
-    check(nchw(y, Cout), yr.detach(), dtype, "y")
+    check(nchw(y, Cout), yr.detach(), dtype, "y", bound=cb.y)
     y.backward(nhwc(gy, dtype, V))
-    check(wd.grad.cpu(), wr.grad, dtype, "dW")
-    check(bd.grad.cpu(), br.grad, dtype, "dbias")
-    check(nchw(x0d.grad, C0), x0r.grad, dtype, "dx0 (through nearest-upsample)")
+    check(wd.grad.cpu(), wr.grad, dtype, "dW", bound=lim["dW"])
+    check(bd.grad.cpu(), br.grad, dtype, "dbias", bound=lim["dbias"])
+    check(nchw(x0d.grad, C0), x0r.grad, dtype, "dx0 (through nearest-upsample)", bound=lim["dX"])
     if C1:
-        check(nchw(x1d.grad, C1), x1r.grad, dtype, "dx1 (skip)")
+        check(nchw(x1d.grad, C1), x1r.grad, dtype, "dx1 (skip)", bound=lim["dSkip"])
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["f32", "bf16"])
@@ -388,7 +398,7 @@ def test_weight_packer_equals_per_layer_pack(NN, dtype, layout):
         assert torch.equal(wd, NN.pack_weight(m.weight, dt, cin_pad, ldy, for_dgrad=True)), f"dgrad operand {ci}->{co} k{k}"
 
 
-@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["f32", "bf16"])
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.float16], ids=["f32", "bf16", "fp16"])
 @pytest.mark.parametrize("shape", [(2, 6, 20, 256, 512, 3, True), (1, 12, 40, 2048, 256, 1, False), (2, 6, 20, 2048, 256, 3, False)],
                          ids=["3x3_256_512_bias_elu", "1x1_2048_256_stats", "3x3_2048_256_stats"])
 def test_split_k_equals_single_pass(NN, dtype, shape):
@@ -688,12 +698,13 @@ def test_full_size_conv_properties(NN):
 
 
 HALO_CASES = [
-    # name, B, H, W, Cin, Cout, reflect, bias, act
+    # name, B, H, W, Cin, Cout, reflect, bias, act; "halo_*" run on the LDS-halo kernel (asserted), "staged_*" do not: use_halo refuses inputs narrower
+    # than 48 channels, so these two run on the register-staged 128x16 tile (also rows of tests/conv_variant_table.py, under that variant)
     ("halo_64_64_zero", 2, 16, 32, 64, 64, False, False, 0),
     ("halo_128_128_zero", 2, 16, 32, 128, 128, False, False, 0),
     ("halo_96_32_refl_elu", 2, 24, 48, 96, 32, True, True, 1),        # channel tail inside the second 64-channel block
-    ("halo_16_16_refl_elu", 2, 24, 48, 16, 16, True, True, 1),
-    ("halo_32_1_refl_head", 2, 16, 32, 32, 1, True, True, 0),
+    ("staged_16_16_refl_elu", 2, 24, 48, 16, 16, True, True, 1),
+    ("staged_32_1_refl_head", 2, 16, 32, 32, 1, True, True, 0),
     ("halo_ragged_64_64", 2, 20, 44, 64, 64, False, True, 0),         # 20x44 is not a multiple of the 8x16 tile
     ("halo_256_256_zero", 1, 16, 32, 256, 256, False, False, 0),      # 4 channel blocks, 2 N tiles
 ]
@@ -707,14 +718,26 @@ def force_halo(NN):
     L.lib().sde_conv_set_halo_min_blocks(old)
 
 
-@pytest.mark.parametrize("case", HALO_CASES, ids=[c[0] for c in HALO_CASES])
-def test_conv_halo_kernel(NN, force_halo, case):
-    """The LDS-halo 3x3 kernel (forward and data-gradient, incl. the padded 'full' gradient of reflection layers) vs fp32 CPU."""
+def fwd_variant(NN, x0, x1, upcat, reflect, ldy):
+    """sde_conv_fwd_variant of the 3x3 stride-1 layer hip.nn.conv2d builds from these NHWC inputs."""
+    import ctypes
+    from simpledepthestimation_amd.hip import lib as L
+    B, H, W, _ = x0.shape
+    H, W = (2 * H, 2 * W) if upcat else (H, W)
+    d = NN._desc(x0, x1, NN.SRC_UPCAT if upcat else NN.SRC_PLAIN, 3, 3, 1, 1, reflect, H, W, H, W)
+    return L.lib().sde_conv_fwd_variant(ctypes.byref(d), ldy)
+
+
+def halo_variant(ldy):
+    return 3128000 + (64 if ldy > 32 else 32 if ldy > 16 else 16)
+
+
+def halo_kernel_case(NN, case, dtype):
     name, B, H, W, Cin, Cout, reflect, has_bias, act = case
-    dtype, V = torch.bfloat16, 8
-    g = torch.Generator().manual_seed(len(name) * 7)
-    x = torch.randn(B, Cin, H, W, generator=g).bfloat16().float()
-    w = (torch.randn(Cout, Cin, 3, 3, generator=g) / math.sqrt(Cin * 9)).bfloat16().float()
+    V = 8
+    g = torch.Generator().manual_seed(len(name.replace("staged", "halo")) * 7)       # (the seeds the cases had under their first names)
+    x = torch.randn(B, Cin, H, W, generator=g).to(dtype).float()
+    w = (torch.randn(Cout, Cin, 3, 3, generator=g) / math.sqrt(Cin * 9)).to(dtype).float()
     b = torch.randn(Cout, generator=g) * 0.1 if has_bias else None
     xr, wr = x.clone().requires_grad_(True), w.clone().requires_grad_(True)
     br = b.clone().requires_grad_(True) if has_bias else None
@@ -722,60 +745,100 @@ def test_conv_halo_kernel(NN, force_halo, case):
     yr = F.conv2d(xin, wr, br, 1, 0 if reflect else 1)
     if act == 1:
         yr = F.elu(yr)
-    gy = torch.randn(yr.shape, generator=g).bfloat16().float()
+    gy = torch.randn(yr.shape, generator=g).to(dtype).float()
     yr.backward(gy)
+    cb = CB.ConvCase(x, w, b, dtype, stride=1, pad=1, reflect=reflect, act=act)
+    lim = cb.backward([gy])
     xd = nhwc(x, dtype, V).requires_grad_(True)
     wd = w.clone().to(dev).requires_grad_(True)
     bd = b.clone().to(dev).requires_grad_(True) if has_bias else None
+    # which kernel runs is asserted first: a dispatcher rule that re-routes a case must not leave it testing something else
+    assert fwd_variant(NN, xd, None, False, reflect, (Cout + V - 1) // V * V) == (halo_variant(Cout) if name.startswith("halo") else 128016), name
     y = NN.conv2d(xd, wd, bd, stride=1, pad=1, reflect=reflect, act=act)
-    check(nchw(y, Cout), yr.detach(), dtype, "y")
+    check(nchw(y, Cout), yr.detach(), dtype, "y", bound=cb.y)
     if y.shape[3] > Cout:
         assert (y[..., Cout:] == 0).all()
     y.backward(nhwc(gy, dtype, V))
-    check(nchw(xd.grad, Cin), xr.grad, dtype, "dX")
-    check(wd.grad.cpu(), wr.grad, dtype, "dW")
+    check(nchw(xd.grad, Cin), xr.grad, dtype, "dX", bound=lim["dX"])
+    check(wd.grad.cpu(), wr.grad, dtype, "dW", bound=lim["dW"])
 
 
-@pytest.mark.parametrize("C0,C1,Cout", [(32, 64, 32), (16, 0, 16), (64, 256, 64)])
-def test_conv_halo_upsample_concat(NN, force_halo, C0, C1, Cout):
-    dtype, V = torch.bfloat16, 8
+@pytest.mark.parametrize("case", HALO_CASES, ids=[c[0] for c in HALO_CASES])
+def test_conv_halo_kernel(NN, force_halo, case):
+    """The LDS-halo 3x3 kernel (forward and data-gradient, incl. the padded 'full' gradient of reflection layers) vs fp32 CPU."""
+    halo_kernel_case(NN, case, torch.bfloat16)
+
+
+@pytest.mark.parametrize("case", HALO_CASES, ids=[c[0] for c in HALO_CASES])
+def test_conv_halo_kernel_fp16(NN, force_halo, case):
+    halo_kernel_case(NN, case, torch.float16)
+
+
+def halo_upsample_concat_case(NN, C0, C1, Cout, dtype):
+    V = 8
     g = torch.Generator().manual_seed(C0 * 3 + C1)
     B, h, w = 2, 8, 16
-    x0 = torch.randn(B, C0, h, w, generator=g).bfloat16().float()
-    x1 = torch.randn(B, C1, 2 * h, 2 * w, generator=g).bfloat16().float() if C1 else None
-    wt = (torch.randn(Cout, C0 + C1, 3, 3, generator=g) / math.sqrt((C0 + C1) * 9)).bfloat16().float()
+    x0 = torch.randn(B, C0, h, w, generator=g).to(dtype).float()
+    x1 = torch.randn(B, C1, 2 * h, 2 * w, generator=g).to(dtype).float() if C1 else None
+    wt = (torch.randn(Cout, C0 + C1, 3, 3, generator=g) / math.sqrt((C0 + C1) * 9)).to(dtype).float()
     bs = torch.randn(Cout, generator=g) * 0.1
     x0r = x0.clone().requires_grad_(True); x1r = x1.clone().requires_grad_(True) if C1 else None
     wr = wt.clone().requires_grad_(True)
     up = F.interpolate(x0r, scale_factor=2, mode="nearest")
     cat = torch.cat([up, x1r], 1) if C1 else up
     yr = F.elu(F.conv2d(F.pad(cat, (1, 1, 1, 1), mode="reflect"), wr, bs))
-    gy = torch.randn(yr.shape, generator=g).bfloat16().float()
+    gy = torch.randn(yr.shape, generator=g).to(dtype).float()
     yr.backward(gy)
+    cb = CB.ConvCase(x0, wt, bs, dtype, stride=1, pad=1, reflect=True, act=1, x1=x1, upcat=True)
+    lim = cb.backward([gy])
     x0d = nhwc(x0, dtype, V).requires_grad_(True)
     x1d = nhwc(x1, dtype, V).requires_grad_(True) if C1 else None
     wd = wt.clone().to(dev).requires_grad_(True)
+    # (16 input channels are too narrow for the halo kernel: that case runs on the register-staged 128x16 tile)
+    assert fwd_variant(NN, x0d, x1d, True, True, Cout) == (halo_variant(Cout) if C0 + C1 >= 48 else 128016)
     y = NN.conv2d(x0d, wd, bs.to(dev), stride=1, pad=1, reflect=True, act=1, skip=x1d, upsample=True)
-    check(nchw(y, Cout), yr.detach(), dtype, "y")
+    check(nchw(y, Cout), yr.detach(), dtype, "y", bound=cb.y)
     y.backward(nhwc(gy, dtype, V))
-    check(nchw(x0d.grad, C0), x0r.grad, dtype, "dx0")
+    check(nchw(x0d.grad, C0), x0r.grad, dtype, "dx0", bound=lim["dX"])
     if C1:
-        check(nchw(x1d.grad, C1), x1r.grad, dtype, "dx1")
+        check(nchw(x1d.grad, C1), x1r.grad, dtype, "dx1", bound=lim["dSkip"])
 
 
-def test_conv_halo_batchnorm_stats(NN, force_halo):
-    """BatchNorm statistics produced by the halo kernel's epilogue (ragged tiles must not pollute them)."""
+@pytest.mark.parametrize("C0,C1,Cout", [(32, 64, 32), (16, 0, 16), (64, 256, 64)])
+def test_conv_halo_upsample_concat(NN, force_halo, C0, C1, Cout):
+    halo_upsample_concat_case(NN, C0, C1, Cout, torch.bfloat16)
+
+
+@pytest.mark.parametrize("C0,C1,Cout", [(32, 64, 32), (16, 0, 16), (64, 256, 64)])
+def test_conv_halo_upsample_concat_fp16(NN, force_halo, C0, C1, Cout):
+    halo_upsample_concat_case(NN, C0, C1, Cout, torch.float16)
+
+
+def halo_batchnorm_stats_case(NN, Cin, variant):
     g = torch.Generator().manual_seed(9)
-    B, H, W, Cin, C = 2, 20, 44, 32, 64
+    B, H, W, C = 2, 20, 44, 64
     x = (torch.randn(B, Cin, H, W, generator=g) + 0.3).bfloat16().float()
     w = (torch.randn(C, Cin, 3, 3, generator=g) / math.sqrt(Cin * 9)).bfloat16().float()
     gamma = torch.rand(C, generator=g) + 0.5; beta = torch.randn(C, generator=g) * 0.2
     yc = F.conv2d(x, w, None, 1, 1)
     yc = yc.bfloat16().float()
     o = F.relu(F.batch_norm(yc, torch.zeros(C), torch.ones(C), gamma, beta, True, 0.1, 1e-5))
-    y, stats = NN.conv2d(nhwc(x, torch.bfloat16, 8), w.to(dev), None, stride=1, pad=1, bn_stats=True)
+    xd = nhwc(x, torch.bfloat16, 8)
+    assert fwd_variant(NN, xd, None, False, False, C) == variant
+    y, stats = NN.conv2d(xd, w.to(dev), None, stride=1, pad=1, bn_stats=True)
     out = NN.batch_norm_act(y, stats, gamma.to(dev), beta.to(dev), torch.zeros(C, device=dev), torch.ones(C, device=dev))
     check(nchw(out, C), o, torch.bfloat16, "bn(halo conv)")
+
+
+def test_conv_halo_batchnorm_stats(NN, force_halo):
+    """BatchNorm statistics from the convolution's epilogue over ragged tiles.  (32 input channels are too narrow for the halo kernel -- use_halo --
+    so this case has always run on the register-staged 64x64 tile; the next test is the halo kernel's.)"""
+    halo_batchnorm_stats_case(NN, 32, 64064)
+
+
+def test_conv_halo_batchnorm_stats_on_the_halo_kernel(NN, force_halo):
+    """BatchNorm statistics produced by the halo kernel's epilogue (ragged tiles must not pollute them)."""
+    halo_batchnorm_stats_case(NN, 64, 3128064)
 
 
 @pytest.mark.parametrize("C,R,with_res,relu,dtype", [(256, 192, False, True, torch.bfloat16), (512, 96, True, True, torch.bfloat16), (2048, 23, False, False, torch.bfloat16),
@@ -863,7 +926,7 @@ def test_bn_bwd_finalize_apply_fused_equals_separate(NN, C, M, with_res, relu, n
         assert torch.equal(dr1, dr0)
 
 
-@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["f32", "bf16"])
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.float16], ids=["f32", "bf16", "fp16"])
 @pytest.mark.parametrize("act,has_bias", [(1, True), (0, False), (0, True)])
 def test_conv_output_with_two_consumers(NN, dtype, act, has_bias):
     """conv2d(..., n_out=2): two aliases of the (ELU) output -- a decoder level feeds its disparity head and the next level; backward gets the
@@ -873,25 +936,28 @@ def test_conv_output_with_two_consumers(NN, dtype, act, has_bias):
     B, H, W, Cin, Cout = 2, 12, 20, 32, 64
     x = torch.randn(B, Cin, H, W, generator=g); w = torch.randn(Cout, Cin, 3, 3, generator=g) / math.sqrt(Cin * 9)
     b = torch.randn(Cout, generator=g) * 0.1 if has_bias else None
-    if dtype == torch.bfloat16:
-        x = x.bfloat16().float(); w = w.bfloat16().float()
+    if dtype != torch.float32:
+        x = x.to(dtype).float(); w = w.to(dtype).float()
     g0, g1 = torch.randn(B, Cout, H, W, generator=g), torch.randn(B, Cout, H, W, generator=g)
-    if dtype == torch.bfloat16:
-        g0, g1 = g0.bfloat16().float(), g1.bfloat16().float()
+    if dtype != torch.float32:
+        g0, g1 = g0.to(dtype).float(), g1.to(dtype).float()
     xr = x.clone().requires_grad_(True); wr = w.clone().requires_grad_(True); br = b.clone().requires_grad_(True) if has_bias else None
     yr = F.conv2d(F.pad(xr, (1, 1, 1, 1), mode="reflect"), wr, br)
     if act == 1:
         yr = F.elu(yr)
     yr.backward(g0 + g1)
+    cb = CB.ConvCase(x, w, b, dtype, stride=1, pad=1, reflect=True, act=act)
+    lim = cb.backward([g0, g1])          # the two gradients are summed (and the sum stored in the activation dtype) by the activation-backward kernel
     xd = nhwc(x, dtype, V).requires_grad_(True); wd = w.clone().to(dev).requires_grad_(True)
     bd = b.clone().to(dev).requires_grad_(True) if has_bias else None
     ya, yb = NN.conv2d(xd, wd, bd, stride=1, pad=1, reflect=True, act=act, n_out=2)
     assert ya.data_ptr() == yb.data_ptr()
+    check(nchw(ya.detach(), Cout), yr.detach(), dtype, "y", bound=cb.y)
     torch.autograd.backward([ya, yb], [nhwc(g0, dtype, V), nhwc(g1, dtype, V)])
-    check(wd.grad.cpu(), wr.grad, dtype, "dW")
-    check(nchw(xd.grad, Cin), xr.grad, dtype, "dX")
+    check(wd.grad.cpu(), wr.grad, dtype, "dW", bound=lim["dW"])
+    check(nchw(xd.grad, Cin), xr.grad, dtype, "dX", bound=lim["dX"])
     if has_bias:
-        check(bd.grad.cpu(), br.grad, dtype, "dbias")
+        check(bd.grad.cpu(), br.grad, dtype, "dbias", bound=lim["dbias"])
     # one consumer only: the other alias's gradient is None
     xd2 = nhwc(x, dtype, V).requires_grad_(True)
     ya, yb = NN.conv2d(xd2, wd, bd, stride=1, pad=1, reflect=True, act=act, n_out=2)
