@@ -699,6 +699,45 @@ int sde_motion_prep_bwd(const float* mask01, const float* depth_n, const float* 
                         float* partial, float* bstats, int* ticket, float* d_depth, float* d_motion, float* d_tpose, sde_stream_t stream);
 int sde_mask_dilate(const float* mask, float* tmp, float* out, int planes, int H, int W, int d, sde_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------------
+ * DenseNet dense blocks without the concatenation (csrc/dense.hip; autograd wrappers in hip/dense.py): torchvision's _DenseLayer computes
+ * relu(norm1(torch.cat(features, 1))) over a map that grows by `growth_rate` channels per layer.  Here the block stays in PIECES -- the block input
+ * [M,C0] and one [M,g] tensor per layer, each NHWC-contiguous, the plain output of that layer's 3x3 convolution -- named by a descriptor that is
+ * passed to the kernels by value (no upload; legal under graph capture).  fp32 and bf16, every piece width a multiple of 8; anything else (fp16
+ * included) is refused before a launch.  Nothing allocates or synchronises, workspace sizes depend on shape only, no floating-point atomics: two
+ * runs give the same bits.
+ *
+ * sde_dense_stats: the (sum, sum of squares) slab [rows(+SDE_REDUCE_ROWS, unused)][C][2] the producing convolution wrote for a NEW piece (or
+ *   sde_channel_stats for the block input) -> rows [off, off + C) of the block's table [Ct][2] = (mean, biased variance) over `count` pixels.
+ *   One launch per piece; later layers only read the table.
+ * sde_dense_bn_relu_fwd: out [M,Cin] = relu(batch_norm(cat(pieces))), Cin = sum of the piece widths, the contiguous operand of the 1x1
+ *   convolution that follows.  table != NULL (training): batch statistics from the table's first Cin rows; running_mean / running_var (optional,
+ *   both or neither) are updated with `momentum` and the unbiased variance, as torch does.  table == NULL (eval): the running statistics.
+ *   bnp [4][Cin] (mean, rstd, scale, shift) is written for the backward pass.  Two launches (parameters, apply).
+ * sde_dense_bn_relu_bwd: g [M,Cin] = gradient of `out`; the pieces are gathered again and the ReLU mask re-derived.  part: workspace
+ *   [sde_dense_bwd_rows(M, Cin, dtype)][Cin][2].  dx [M,Cin] (one contiguous tensor); dgamma / dbeta [Cin] (either may be NULL: frozen
+ *   parameters), (+)= when accumulate_params.  Two launches (reduce, apply).
+ * sde_dense_bwd_rows: partial rows of that workspace; shape-only (negative: unsupported dtype or width).
+ * sde_dense_grad_gather: out [M,g] = [outside [M,g] +] sum over the descriptor's n tensors dx_k [M, C[k]] of their columns [off, off + g), in
+ *   that order with fp32 accumulation: the gradient of the piece that sits at channel offset `off` of its n later consumers.
+ * sde_avgpool2x2_fwd / _bwd: nn.AvgPool2d(2, 2) of a transition, x [B,H,W,C] <-> out [B,H/2,W/2,C] (odd sizes floor; the odd last row / column
+ *   receives a zero gradient). */
+#define SDE_DENSE_MAX 40
+typedef struct sde_dense_desc {
+    const void* p[SDE_DENSE_MAX];
+    int32_t C[SDE_DENSE_MAX]; /* piece widths (sde_dense_grad_gather: row widths of the dx tensors) */
+    int32_t n, reserved;
+} sde_dense_desc;
+int sde_dense_stats(const float* slab, int rows, int C, long count, float* table, int off, sde_stream_t stream);
+int sde_dense_bwd_rows(long M, int Cin, int dtype);
+int sde_dense_bn_relu_fwd(const sde_dense_desc* d, long M, int dtype, const float* table, const float* gamma, const float* beta, float* running_mean,
+                          float* running_var, float momentum, float eps, float* bnp, void* out, sde_stream_t stream);
+int sde_dense_bn_relu_bwd(const sde_dense_desc* d, long M, int dtype, const void* g, const float* bnp, float* part, float* dgamma, float* dbeta,
+                          int accumulate_params, void* dx, sde_stream_t stream);
+int sde_dense_grad_gather(const sde_dense_desc* dxs, long M, int off, int g, int dtype, const void* outside, void* out, sde_stream_t stream);
+int sde_avgpool2x2_fwd(const void* x, int B, int H, int W, int C, int dtype, void* out, sde_stream_t stream);
+int sde_avgpool2x2_bwd(const void* dout, int B, int H, int W, int C, int dtype, void* dx, sde_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,7 +1,12 @@
 """BtsModel (projects/Supervised/configs/bts_r50.yaml) training step: bf16, bs 8, 352x704, hipGraph replay.  Prints one JSON line.
 
-    python scripts/bench_bts.py [--steps K] [--warmup W] [--bs B] [--dtype bf16|fp32] [--no-graph] [--encoder resnet50_bts|resnet101_bts|resnext101_bts]
-                                [--gconv-composed] [--layers]
+    python scripts/bench_bts.py [--steps K] [--warmup W] [--bs B] [--dtype bf16|fp32] [--no-graph]
+                                [--encoder resnet50_bts|resnet101_bts|resnext101_bts|densenet121_bts] [--gconv-composed] [--layers]
+                                [--dense-composed] [--dense-ops]
+
+--dense-composed runs the dense blocks of a DenseNet encoder through cat + channel_stats + BatchNorm (hip.dense.DENSE_DIRECT = False, the A/B baseline).
+--dense-ops times, instead of the step, the norm1 of the last (widest) layer of each DenseNet-121 block stand-alone at the workload's shapes: the
+concat-free forward and backward and the gradient gather of a middle piece, against cat + channel_stats + BatchNorm forward and backward.
 
 --gconv-composed runs the grouped convolutions of a ResNeXt encoder as dense block-diagonal layers (hip.nn.GCONV_DIRECT = False, the A/B baseline).
 --layers times, instead of the step, every distinct grouped 3x3 layer of the chosen encoder stand-alone at the workload's shapes: forward, data
@@ -116,6 +121,73 @@ def time_layers(encoder, bs, H, W, dtype, reps=200):
     return rows
 
 
+def _timeit(fn, reps):
+    for _ in range(3):
+        fn()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(reps):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return round(e0.elapsed_time(e1) / reps * 1e3, 1)
+
+
+def time_dense_ops(bs, H, W, dtype, reps=20):
+    """Per block of DenseNet-121: microseconds of the last layer's norm1 + ReLU on both routes (forward; forward + backward), and of one gather."""
+    import ctypes
+    from simpledepthestimation_amd.hip import bts as HB
+    from simpledepthestimation_amd.hip import dense as HD
+    from simpledepthestimation_amd.hip import lib as L
+    from simpledepthestimation_amd.hip import nn as HN
+    from simpledepthestimation_amd.layers.hip_modules import HipBatchNorm2d
+    dt = torch.bfloat16 if dtype == "bf16" else torch.float32
+    rows = []
+    h, w = ((H - 1) // 2 + 1 - 1) // 2 + 1, ((W - 1) // 2 + 1 - 1) // 2 + 1
+    for c0, n in ((64, 6), (128, 12), (256, 24), (512, 16)):
+        widths = [c0] + [32] * (n - 1)
+        cin = sum(widths)
+        pieces = [torch.randn(bs, h, w, c, device="cuda").to(dt) for c in widths]
+        gy = torch.randn(bs, h, w, cin, device="cuda").to(dt)
+        norm = HipBatchNorm2d(cin).cuda().train()
+        head = torch.randn(bs, h, w, cin - 32, device="cuda").to(dt).requires_grad_(True)      # the composed route's concatenation so far
+        last = pieces[-1].clone().requires_grad_(True)
+        blk = HD.DenseBlock(cin)                # the block as the last layer finds it: every piece filed, the table complete
+        for p in pieces:
+            HD.dense_piece(p, blk, HB.channel_stats(p))
+
+        def run(direct, backward):
+            HD.DENSE_DIRECT = direct
+            try:
+                if direct:                      # forward: parameters + apply; backward: reduce + apply (the gathers are timed below)
+                    del blk.consumers[:]
+                    y = HD.dense_bn_relu(blk, norm)
+                else:                           # forward: cat + channel_stats + BatchNorm; backward: BatchNorm + the split of the concatenation
+                    x = HB.cat([(head, cin - 32), (last, 32)])
+                    y = norm(x, HB.channel_stats(x), relu=True)
+                if backward:
+                    y.backward(gy)
+            finally:
+                HD.DENSE_DIRECT = True
+
+        # the gather of a middle piece: the dx tensors of the n - j layers behind it
+        j = n // 2
+        dxs = [torch.randn(bs, h, w, sum(widths[:k]), device="cuda").to(dt) for k in range(j + 1, n + 1)]
+        out = torch.empty(bs, h, w, 32, device="cuda", dtype=dt)
+        desc = HD._desc(dxs)
+
+        def gather():
+            L.check(L.lib().sde_dense_grad_gather(ctypes.byref(desc), bs * h * w, sum(widths[:j]), 32, HN.dtype_code(dt), None, L.ptr(out), L.stream()), "gather")
+
+        row = {"block_input": c0, "layers": n, "Cin": cin, "map": [bs, h, w],
+               "direct_fwd_us": _timeit(lambda: run(True, False), reps), "direct_fwd_bwd_us": _timeit(lambda: run(True, True), reps),
+               "composed_fwd_us": _timeit(lambda: run(False, False), reps), "composed_fwd_bwd_us": _timeit(lambda: run(False, True), reps),
+               "gather_us": _timeit(gather, reps), "gather_sources": len(dxs)}
+        rows.append(row)
+        h, w = h // 2, w // 2
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=20)
@@ -129,6 +201,8 @@ def main():
     ap.add_argument("--encoder", default="resnet50_bts")
     ap.add_argument("--gconv-composed", action="store_true")
     ap.add_argument("--layers", action="store_true")
+    ap.add_argument("--dense-composed", action="store_true")
+    ap.add_argument("--dense-ops", action="store_true")
     ap.add_argument("--reps", type=int, default=200, help="--layers: back-to-back launches per timed window")
     a = ap.parse_args()
     if a.layers:
@@ -136,9 +210,17 @@ def main():
                           "reps": a.reps,
                           "layers": time_layers(a.encoder, a.bs, a.height, a.width, a.dtype, a.reps)}))
         return
+    if a.dense_ops:
+        print(json.dumps({"workload": "bts_dense_ops", "dtype": a.dtype, "bs": a.bs, "size": [a.height, a.width],
+                          "note": "eager calls between two events, launch path included",
+                          "blocks": time_dense_ops(a.bs, a.height, a.width, a.dtype)}))
+        return
     if a.gconv_composed:
         from simpledepthestimation_amd.hip import nn as HN
         HN.GCONV_DIRECT = False
+    if a.dense_composed:
+        from simpledepthestimation_amd.hip import dense as HD
+        HD.DENSE_DIRECT = False
     model, tr, batch = make(a.bs, a.height, a.width, a.dtype, not a.no_graph, a.encoder)
     for _ in range(a.warmup):
         out = tr.step(dict(batch))
@@ -151,7 +233,8 @@ def main():
     torch.cuda.synchronize()
     ms = e0.elapsed_time(e1) / a.steps
     loss = float(out["silog_loss"].detach())
-    line = {"workload": {"resnet50_bts": "bts_r50"}.get(a.encoder, "bts_" + a.encoder[:-4]), "gconv": "composed" if a.gconv_composed else "kernels", "dtype": a.dtype, "bs": a.bs, "size": [a.height, a.width], "graph": not a.no_graph, "steps": a.steps,
+    line = {"workload": {"resnet50_bts": "bts_r50"}.get(a.encoder, "bts_" + a.encoder[:-4]), "gconv": "composed" if a.gconv_composed else "kernels",
+            "dense": "composed" if a.dense_composed else "kernels", "dtype": a.dtype, "bs": a.bs, "size": [a.height, a.width], "graph": not a.no_graph, "steps": a.steps,
             "ms_per_step": round(ms, 3), "images_per_s": round(a.bs * 1000.0 / ms, 1), "loss": loss, "finite": loss == loss}
     if not a.no_dilated:
         line["dilated_fwd"] = time_dilated(a.bs, a.height, a.width, a.dtype)

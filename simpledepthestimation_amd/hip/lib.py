@@ -89,6 +89,14 @@ _PROTOS = {
     "sde_gconv3x3_dgrad": ([_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P], c_int),
     "sde_gconv3x3_wgrad_ws_bytes": ([_I, _I, _I, _I, _I, _I, _I], c_size_t),
     "sde_gconv3x3_wgrad": ([_P, _P, _I, _I, _I, _I, _I, _I, _I, _P, c_size_t, _P, _I, _P], c_int),
+    # DenseNet dense blocks without the concatenation (csrc/dense.hip; autograd wrappers in hip/dense.py)
+    "sde_dense_stats": ([_P, _I, _I, ctypes.c_long, _P, _I, _P], c_int),
+    "sde_dense_bwd_rows": ([ctypes.c_long, _I, _I], c_int),
+    "sde_dense_bn_relu_fwd": ([_P, ctypes.c_long, _I, _P, _P, _P, _P, _P, _F, _F, _P, _P, _P], c_int),
+    "sde_dense_bn_relu_bwd": ([_P, ctypes.c_long, _I, _P, _P, _P, _P, _P, _I, _P, _P], c_int),
+    "sde_dense_grad_gather": ([_P, ctypes.c_long, _I, _I, _I, _P, _P, _P], c_int),
+    "sde_avgpool2x2_fwd": ([_P, _I, _I, _I, _I, _I, _P, _P], c_int),
+    "sde_avgpool2x2_bwd": ([_P, _I, _I, _I, _I, _I, _P, _P], c_int),
     # GoogleMotionNet / GooglePoseNet operators (csrc/motion.hip; autograd wrappers in hip/motion.py)
     "sde_motion_resize_cat_fwd": ([_P, _I, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P], c_int),
     "sde_motion_resize_cat_bwd": ([_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P], c_int),

@@ -1,8 +1,9 @@
-"""BtsModel = ResNet-50 / ResNet-101 / ResNeXt-101 32x8d encoder + BTS decoder (reference: detectron2/modeling/depth_net/BTSNet.py:L281-413).
+"""BtsModel = ResNet-50 / ResNet-101 / ResNeXt-101 32x8d / DenseNet-121 encoder + BTS decoder (reference: detectron2/modeling/depth_net/BTSNet.py:L281-413).
 
 State-dict keys equal the reference's (``encoder.base_model.layer3.5.bn2.running_var``, ``decoder.get_depth.0.weight`` ...), so its
 checkpoints load with ``strict=True``.  The encoder is this package's ResNet encoder (layers/resnet_encoder.py) with its torchvision module
-registered under ``base_model``; the reference's `encoder` returns the same five features (relu, layer1..layer4).
+registered under ``base_model``; the reference's `encoder` returns the same five features (relu, layer1..layer4).  ``densenet121_bts`` is
+layers/densenet_encoder.py: torchvision's ``densenet121().features`` under ``base_model``, features relu0, pool0, transition1, transition2, norm5.
 """
 import logging
 
@@ -11,6 +12,7 @@ import torch.nn as nn
 
 from ...hip import nn as HN
 from ...layers.bts_decoder import BtsDecoder
+from ...layers.densenet_encoder import DenseNetEncoder
 from ...layers.hip_modules import HipBatchNorm2d
 from ...layers.resnet_encoder import ResnetEncoder
 from .build import DEPTH_NET_REGISTRY
@@ -20,6 +22,10 @@ logger = logging.getLogger(__name__)
 
 # MODEL.DEPTH_NET.ENCODER_NAME -> (layers, groups, width per group) of the torchvision network the reference wraps (BTSNet.py:L291-306)
 _ENCODERS = {"resnet50_bts": (50, 1, 64), "resnet101_bts": (101, 1, 64), "resnext101_bts": (101, 32, 8)}
+# ... -> (growth rate, block config, stem channels) of the torchvision DenseNet (BTSNet.py:L283-286).  The containers also build DenseNet-161's
+# geometry (48, (6, 12, 36, 24), 96); that name is not enabled
+_DENSENETS = {"densenet121_bts": (32, (6, 12, 24, 16), 64)}
+_SUPPORTED = sorted(list(_ENCODERS) + list(_DENSENETS))
 
 
 class BtsEncoder(ResnetEncoder):
@@ -27,7 +33,7 @@ class BtsEncoder(ResnetEncoder):
 
     def __init__(self, encoder_name):
         if encoder_name not in _ENCODERS:
-            raise NotImplementedError(f"BtsModel encoder {encoder_name!r} is not on the HIP path; supported: {sorted(_ENCODERS)}")
+            raise NotImplementedError(f"BtsModel encoder {encoder_name!r} is not on the HIP path; supported: {_SUPPORTED}")
         num_layers, groups, width = _ENCODERS[encoder_name]
         super().__init__(num_layers, groups=groups, width_per_group=width)
         self.encoder_name = encoder_name
@@ -41,18 +47,41 @@ class BtsEncoder(ResnetEncoder):
         return self.base_model
 
 
+class BtsDenseNetEncoder(DenseNetEncoder):
+    """DenseNetEncoder under the reference's encoder names (L283-286)."""
+
+    def __init__(self, encoder_name):
+        growth, blocks, stem = _DENSENETS[encoder_name]
+        super().__init__(growth, blocks, stem)
+        self.encoder_name = encoder_name
+        logger.info(f"{encoder_name}: torchvision initialisation (ImageNet weights cannot be fetched here); "
+                    "load pretrained weights through MODEL.WEIGHTS or load_state_dict")
+
+
+def build_encoder(encoder_name):
+    return BtsDenseNetEncoder(encoder_name) if encoder_name in _DENSENETS else BtsEncoder(encoder_name)
+
+
 def set_misc(model, bn_no_track_stats, fix_first_conv_block, fix_first_conv_blocks):
-    """BTSNet.py:L374-413: freeze encoder parameters by substring match on their names (``.bn`` does not match ``downsample.1``)."""
+    """BTSNet.py:L374-413: freeze encoder parameters by substring match on their names (``.bn`` does not match ``downsample.1``).  Encoders whose
+    name does not contain ``resne`` take the reference's other branch (L387-404): ``conv0``, ``norm`` and the first dense layer(s)."""
     if bn_no_track_stats:
         # bn_init_as_tf: m.eval() on every BatchNorm -- the training loop's model.train() undoes it, as in the reference
         for m in model.modules():
             if isinstance(m, HipBatchNorm2d):
                 m.eval()
-    fixing = ["base_model.conv1", ".bn"]
-    if fix_first_conv_blocks:
-        fixing += ["base_model.layer1.0", "base_model.layer1.1"]
-    elif fix_first_conv_block:
-        fixing += ["base_model.layer1.0"]
+    if "resne" in model.encoder_name:
+        fixing = ["base_model.conv1", ".bn"]
+        if fix_first_conv_blocks:
+            fixing += ["base_model.layer1.0", "base_model.layer1.1"]
+        elif fix_first_conv_block:
+            fixing += ["base_model.layer1.0"]
+    else:
+        fixing = ["conv0", "norm"]
+        if fix_first_conv_blocks:
+            fixing += ["denseblock1.denselayer1", "denseblock1.denselayer2"]
+        elif fix_first_conv_block:
+            fixing += ["denseblock1.denselayer1"]
     for name, child in model.named_children():
         if "encoder" not in name:
             continue
@@ -68,7 +97,7 @@ class BtsModel(nn.Module):
         super().__init__()
         dn = cfg.MODEL.DEPTH_NET
         self.encoder_name = dn.ENCODER_NAME
-        self.encoder = BtsEncoder(dn.ENCODER_NAME)
+        self.encoder = build_encoder(dn.ENCODER_NAME)
         self.decoder = BtsDecoder(cfg.MODEL.DATASET, cfg.MODEL.MAX_DEPTH, self.encoder.feat_out_channels, dn.BTS_SIZE)
         self.dtype = compute_dtype(cfg)
         set_misc(self, dn.BN_NO_TRACK, dn.FIX_1ST_CONV, dn.FIX_1ST_CONVS)
