@@ -261,7 +261,24 @@ int sde_conv_set_halo_min_blocks(int min_blocks);
                                 * in its epilogue; 0: it reports none (the separate bn_bwd_reduce pass runs everywhere: A/B, tests) */
 #define SDE_OPT_CU_RESERVE 11  /* compute units the persistent kernels (pgemm, chalo, whalo) leave free: their grids are sized for (CUs - n) instead of every CU.
                                 * 0 (default); a multiple of 8 <= 128.  For data-parallel runs: RCCL's channel kernels otherwise wait for a resident workgroup to end */
+#define SDE_OPT_WGRAD_DMA_RING 12 /* LDS ring of the LDS-DMA weight-gradient kernel: 0 (default) = 64 pixels x 3 stages (72 KB per workgroup), 1 = 32 pixels x 4
+                                  * stages (48 KB), 2 = 32 x 3 (36 KB).  The slim forms leave room for two workgroups of the persistent GEMM on the compute unit
+                                  * beside one of these (training forks these launches next to the data-gradient chain); the slabs are bit-identical */
+#define SDE_OPT_PGEMM_PER_CU 13  /* workgroups per compute unit the persistent GEMM sizes its grid for: 2, 3 or 4 (default 4 = whatever its LDS ring allows, 3 for
+                                  * the 64 x 64 tile).  It also decides the rows of the BatchNorm partial slabs (sde_conv_fwd_tiles_m, sde_conv_dgrad_bnbwd_rows):
+                                  * set it before asking for them.  Changes the summation order of those partial rows, no GEMM output */
 int sde_conv_set_option(int key, int value);
+/* Dynamic LDS bytes per workgroup of the kernels that share a compute unit during the backward pass (the data-gradient chain on one queue, the
+ * weight gradients beside it), for budget checks: variant = ring depth (PGEMM, 64 x 64 tile), SDE_OPT_WGRAD_DMA_RING value (WGRAD_DMA),
+ * 10 * (Cin / 16) + (Cout > 16 ? 2 : 1) (WGRAD_HALO), 0 for the others (WGRAD_STAGED: its 16-bit form; WGRAD_REDUCE: the most a launch asks for).
+ * Negative on a bad kind / variant.  Host-only: touches no device. */
+#define SDE_KERNEL_PGEMM 1
+#define SDE_KERNEL_WGRAD_DMA 2
+#define SDE_KERNEL_WGRAD_HALO 3
+#define SDE_KERNEL_WGRAD_STAGED 4
+#define SDE_KERNEL_WGRAD_SUM 5
+#define SDE_KERNEL_WGRAD_REDUCE 6
+int sde_kernel_lds_bytes(int kind, int variant);
 
 /* dW (master fp32 OIHW, [Cout,Cin_real,KH,KW]) (+)= sum over output pixels of dy^T * im2col(virtual input).
  * slab: caller workspace [splits][Cout][KH*KW*(C0+C1)] fp32, splits = sde_conv_wgrad_splits(d, Cout): one fp32 partial per pixel range,

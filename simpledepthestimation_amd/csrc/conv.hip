@@ -1004,7 +1004,7 @@ __global__ void __launch_bounds__(NTHREADS, (BMG <= 64 && sizeof(T) == 2) ? 3 : 
 //   * the item table travels BY VALUE in the kernel arguments (<= 4 KB): no device table whose upload / lifetime has to be
 //     ordered against a launch that runs long after the host has moved on; a captured hipGraph node carries it in its parameters.
 constexpr int WREDUCE_MAX = 120;
-constexpr int WREDUCE_LDS_FLOATS = 16384;        // 64 KB: two workgroups per CU
+constexpr int WREDUCE_LDS_FLOATS = 16000;        // 64 000 B: two workgroups per CU, or one beside two of the persistent GEMM's (2 x 49 920 B); the chunking changes no sum
 struct WReduceArg { const float* slab; float* dw; int end; unsigned short splits, chunk, Cout, KHW, Cin_pad, Cin_real /* | 0x8000: accumulate */; };
 static_assert(sizeof(WReduceArg) == 32, "WReduceArg packing");
 struct WReduceBatch { int n, lds_floats; WReduceArg it[WREDUCE_MAX]; };
@@ -1455,6 +1455,11 @@ int chalo_run(const IGemmP& p, int dtype, hipStream_t s);
 // weight gradient on LDS-DMA for 64-channel-multiple layers (wgrad_dma.hip)
 bool wgrad_dma_applicable(const Gather& g, int dtype, int Cout, int ldd);
 int wgrad_dma_run(const Gather& g, int dtype, const void* dy, int Cout, int ldd, float* slab, int splits, int rows_per_split, hipStream_t s);
+int wgrad_dma_lds_bytes(int ring);
+extern int g_wgrad_dma_ring;
+int pgemm_lds_bytes(int depth);
+extern int g_pgemm_per_cu;
+int whalo_lds_bytes(int NB, int CO16);
 // halo weight gradient of the small-channel 3x3 layers (wgrad_halo.hip)
 bool whalo_applicable(const Gather& g, int dtype, int Cout, int ldd);
 int whalo_splits(const Gather& g, int Cout);
@@ -1833,15 +1838,29 @@ int sde_conv_set_option(int key, int value) {
         g_wgrad_blocks = value;
         return old;
     }
-    int* slot = key == SDE_OPT_PGEMM ? &g_use_pgemm : key == SDE_OPT_PGEMM_DEPTH ? &g_pgemm_depth : key == SDE_OPT_PGEMM_3X3 ? &g_pgemm_3x3 :
+    int* slot = key == SDE_OPT_WGRAD_DMA_RING ? &sdeconv::g_wgrad_dma_ring : key == SDE_OPT_PGEMM_PER_CU ? &sdeconv::g_pgemm_per_cu : key == SDE_OPT_PGEMM ? &g_use_pgemm : key == SDE_OPT_PGEMM_DEPTH ? &g_pgemm_depth : key == SDE_OPT_PGEMM_3X3 ? &g_pgemm_3x3 :
                 key == SDE_OPT_PGEMM_TILE ? &sdeconv::g_pgemm_force_tile : key == SDE_OPT_SPLITK ? &g_splitk : key == SDE_OPT_WGRAD_HALO ? &g_wgrad_halo : key == SDE_OPT_CONV_SMALL ? &g_conv_small : key == SDE_OPT_WGRAD_DMA ? &g_wgrad_dma : key == SDE_OPT_BNBWD_FUSE ? &g_bnbwd_fuse : key == SDE_OPT_CU_RESERVE ? &sdeconv::g_cu_reserve : nullptr;
     SDE_CHECK_ARG(slot, "sde_conv_set_option: unknown key %d", key);
     SDE_CHECK_ARG(key != SDE_OPT_CU_RESERVE || (value >= 0 && value <= 128 && value % 8 == 0), "sde_conv_set_option: CU reserve must be a multiple of 8 in [0, 128], got %d", value);
     SDE_CHECK_ARG(key != SDE_OPT_PGEMM_DEPTH || value == 3 || value == 4, "sde_conv_set_option: ring depth must be 3 or 4");
+    SDE_CHECK_ARG(key != SDE_OPT_WGRAD_DMA_RING || sdeconv::wgrad_dma_lds_bytes(value) > 0, "sde_conv_set_option: bad weight-gradient ring %d", value);
+    SDE_CHECK_ARG(key != SDE_OPT_PGEMM_PER_CU || (value >= 2 && value <= 4), "sde_conv_set_option: workgroups per CU must be 2, 3 or 4, got %d", value);
     SDE_CHECK_ARG(key != SDE_OPT_PGEMM_TILE || value == 0 || value == 64064 || value == 128064 || value == 128128, "sde_conv_set_option: bad tile %d", value);
     const int old = *slot;
     *slot = value;
     return old;
+}
+
+int sde_kernel_lds_bytes(int kind, int variant) {
+    switch (kind) {
+        case SDE_KERNEL_PGEMM: return variant == 3 || variant == 4 ? sdeconv::pgemm_lds_bytes(variant) : -1;
+        case SDE_KERNEL_WGRAD_DMA: return sdeconv::wgrad_dma_lds_bytes(variant);
+        case SDE_KERNEL_WGRAD_HALO: return sdeconv::whalo_lds_bytes(variant / 10, variant % 10);
+        case SDE_KERNEL_WGRAD_STAGED: return variant == 0 ? 4 * WGTraits<bf16_t>::BR * 288 / 2 : -1;      // 16-bit tiles, one stage buffer (wgrad_partial: single_buf)
+        case SDE_KERNEL_WGRAD_SUM: return variant == 0 ? 3 * 64 * (int)sizeof(float4) : -1;
+        case SDE_KERNEL_WGRAD_REDUCE: return variant == 0 ? WREDUCE_LDS_FLOATS * (int)sizeof(float) : -1;
+        default: return -1;
+    }
 }
 
 int sde_conv_set_halo_min_blocks(int min_blocks) {

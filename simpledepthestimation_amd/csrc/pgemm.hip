@@ -698,14 +698,15 @@ __global__ void __launch_bounds__(64 * NW) pgemm_kernel(const PGemmP q) {
 // ------------------------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------------------------
-// Workgroups of a full launch: as many as fit per CU by LDS (stage ring + bias ring), at most 4, times 256 CUs.
+// Workgroups of a full launch: as many as fit per CU by LDS (stage ring + bias ring), at most SDE_OPT_PGEMM_PER_CU (default 4), times 256 CUs.
+// The ONE place the grid comes from: pg_stats_acc, fast / tm_step and the slab-row counts (pgemm_stats_rows) all derive from it, so a caller that sets
+// the option between asking for the rows and launching gets a slab of the wrong height -- set it before both.
+int g_pgemm_per_cu = 4;         // sde_conv_set_option(SDE_OPT_PGEMM_PER_CU, 2 | 3 | 4)
+int pgemm_lds_bytes(int depth) { return depth * ((64 + 64) * PG_STAGE_K_BYTES + 64 * 4); }      // the 64 x 64 tile: stage ring + bias ring
 static int pg_grid_max(int BM, int BN, int D) {
     const int lds = D * ((BM + BN) * PG_STAGE_K_BYTES + BN * 4);
     const int per_cu = (160 * 1024) / lds;
-#ifndef PG_MAX_PER_CU
-#define PG_MAX_PER_CU 4
-#endif
-    return sde_persistent_cus() * (per_cu < 1 ? 1 : (per_cu > PG_MAX_PER_CU ? PG_MAX_PER_CU : per_cu));
+    return sde_persistent_cus() * (per_cu < 1 ? 1 : (per_cu > g_pgemm_per_cu ? g_pgemm_per_cu : per_cu));
 }
 
 static bool pg_stats_acc(int tiles_n, int tiles_mn, int ksplit, int src, int BM, int BN, int D) {

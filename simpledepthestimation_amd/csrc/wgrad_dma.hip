@@ -7,9 +7,9 @@
 // wgrad_kernel (conv.hip) stages both operands through registers and 16-byte ds_write (a third of its LDS cycles are the bank conflicts of
 // those stores, profiles/r02g_sup50_sq_by_kernel.csv) with two barriers per 64-pixel stage.  Here both operands are rows of 128 bytes per
 // pixel -- dY[p][64 co] and X[p + tap][64 ci] -- i.e. exactly the row shape the persistent forward GEMM (pgemm.hip) moves by LDS-DMA:
-//   * a stage = 64 pixels x (64 co | 64 ci of K block 0 | 64 ci of K block 1) = 24 KB, global -> LDS directly (buffer_load_dwordx4 ... lds), a ring of
-//     D stages with D-1 in flight behind a counted s_waitcnt vmcnt and ONE barrier per stage; zero padding, stride and ragged pixel ranges are
-//     out-of-range source offsets (the DMA writes zeros);
+//   * a stage = PIX pixels x (64 co | 64 ci of K block 0 | 64 ci of K block 1) = 24 KB at PIX = 64, 12 KB at 32, global -> LDS directly
+//     (buffer_load_dwordx4 ... lds), a ring of D stages with D-1 in flight behind a counted s_waitcnt vmcnt and ONE barrier per stage; zero padding,
+//     stride and ragged pixel ranges are out-of-range source offsets (the DMA writes zeros);
 //   * pixels are the reduction index, so both MFMA operands are read TRANSPOSED (ds_read_b64_tr_b16); a 32-lane half reads four consecutive
 //     pixel rows x 64 bytes per instruction, and the 16-byte chunk index is XORed with 4 * ((row >> 1) & 1) -- on the SOURCE address, the LDS image
 //     of a DMA piece being lane-linear -- so those four rows hit four disjoint 16-bank groups (conflict-free);
@@ -26,8 +26,12 @@ typedef __attribute__((ext_vector_type(8))) __bf16 wd_bf16x8;
 typedef __attribute__((ext_vector_type(8))) _Float16 wd_f16x8;
 typedef __attribute__((address_space(3))) void wd_lds_void;
 
-constexpr int WD_THREADS = 256, WD_PIX = 64, WD_STAGE = 3 * WD_PIX * 128;      // 24 KB: [dY 64 rows][X block 0: 64 rows][X block 1: 64 rows]
-constexpr int WD_L = 6;                                                          // DMA instructions per wave and stage
+constexpr int WD_THREADS = 256;
+// Pixels per stage PIX = 64 (a 24 KB stage: [dY 64 rows][X block 0: 64 rows][X block 1: 64 rows]) or 32 (12 KB, the slim ring of SDE_OPT_WGRAD_DMA_RING: 36 or
+// 48 KB per workgroup instead of 72, so that two workgroups of the persistent GEMM (pgemm.hip, 49 920 B each) stay resident on the compute unit beside one
+// of these).  A wave moves PIX / 4 rows of each row group per stage, one DMA instruction per 8 rows.
+constexpr int wd_stage(int PIX) { return 3 * PIX * 128; }
+constexpr int wd_loads(int PIX) { return 3 * (PIX / 32); }                       // DMA instructions per wave and stage (feeds the counted vmcnt)
 #ifndef WD_DEPTH
 // Ring depth (stages); WD_DEPTH - 1 stages of DMA in flight.  Measured (scripts/microbench_conv.py, A/B builds in one call): the 1x1 layers do not care
 // (3 / 4 / 6: 206-299 / 192-300 / 192-302 TFLOP/s), the 3x3 layers do: 264-305 TFLOP/s at depth 3 against 168-195 at 4 or 6 -- two stages (48 KB) of rows
@@ -71,8 +75,12 @@ __device__ __forceinline__ wd_s16x4 wd_tr4(unsigned lds_addr) {
 __device__ __forceinline__ unsigned wd_lds_addr(const void* p) { return (unsigned)(unsigned long)(__attribute__((address_space(3))) const void*)p; }
 __device__ __forceinline__ wd_s16x8 wd_cat(wd_s16x4 lo, wd_s16x4 hi) { return wd_s16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]}; }
 
-template <typename T16, bool ONE_BY_ONE, int D>
+template <typename T16, bool ONE_BY_ONE, int D, int PIX>
 __global__ void __launch_bounds__(WD_THREADS) wgrad_dma_kernel(const WDmaP p) {
+    static_assert(PIX == 64 || PIX == 32, "a stage is 64 or 32 pixels (48 does not divide into 8-row DMA pieces over four waves)");
+    constexpr int WD_PIX = PIX, WD_STAGE = wd_stage(PIX), WD_L = wd_loads(PIX);
+    constexpr int NI = PIX / 32;              // 8-row DMA pieces per wave and row group
+    constexpr int KS = PIX / 16;              // 16-pixel MFMA K steps per stage
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];      // [D][WD_STAGE]
     const Gather& g = p.g;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -90,7 +98,7 @@ __global__ void __launch_bounds__(WD_THREADS) wgrad_dma_kernel(const WDmaP p) {
     const __amdgpu_buffer_rsrc_t rsk = make_rsrc(g.x1 ? g.x1 : g.x0, g.x1 ? (long)g.Bn * g.IH * g.IW * g.C1 * 2L : 0);      // the skip tensor of an up-sample + concat source
     const __amdgpu_buffer_rsrc_t rsd = make_rsrc(p.dy, (long)g.M * p.ldd * 2L);
 
-    // ---- DMA side.  Wave w fills rows 16 w .. 16 w + 15 of each of the three row groups; lane = (row lane >> 3 of a piece, 16-byte slot lane & 7).
+    // ---- DMA side.  Wave w fills rows (PIX / 4) w .. (PIX / 4) (w + 1) - 1 of each of the three row groups; lane = (row lane >> 3 of a piece, 16-byte slot lane & 7).
     const int drow = lane >> 3, dslot = lane & 7;
     int hk[2], hw_[2], hc[2];                    // K block h of the tile: filter tap (kh, kw) and channel offset; hk < 0: past the last block
 #pragma unroll
@@ -101,11 +109,11 @@ __global__ void __launch_bounds__(WD_THREADS) wgrad_dma_kernel(const WDmaP p) {
         hk[h] = kb < kblocks ? tap / g.KW : -1;
         hw_[h] = tap - (tap / g.KW) * g.KW;
     }
-    int pn[2], poh[2], pow_[2];                  // output pixel of this lane's two rows in the NEXT stage to issue
-    unsigned chunk[2];
+    int pn[NI], poh[NI], pow_[NI];               // output pixel of this lane's NI rows in the NEXT stage to issue
+    unsigned chunk[NI];
 #pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const int row = wave * 16 + i * 8 + drow;
+    for (int i = 0; i < NI; ++i) {
+        const int row = wave * (WD_PIX / 4) + i * 8 + drow;
         chunk[i] = (unsigned)((dslot ^ (((row >> 1) & 1) << 2)) * 16);
         const int m = mbeg + row;
         pn[i] = m / (g.OH * g.OW);
@@ -119,13 +127,13 @@ __global__ void __launch_bounds__(WD_THREADS) wgrad_dma_kernel(const WDmaP p) {
     bool hskip[2];
 #pragma unroll
     for (int h = 0; h < 2; ++h) hskip[h] = upcat && hc[h] >= C0;
-    const int adv_h = WD_PIX / OW, adv_w = WD_PIX - adv_h * OW;      // one stage = 64 pixels further along the row-major pixel order
+    const int adv_h = WD_PIX / OW, adv_w = WD_PIX - adv_h * OW;      // one stage = PIX pixels further along the row-major pixel order
     int issued = 0;
     auto issue = [&]() {                         // stage `issued` (uniform: every wave issues the same stages)
-        unsigned char* slot = smem + (issued % D) * WD_STAGE + (wave * 16) * 128;
-        const int mrow0 = mbeg + issued * WD_PIX + wave * 16 + drow;
+        unsigned char* slot = smem + (issued % D) * WD_STAGE + (wave * (WD_PIX / 4)) * 128;
+        const int mrow0 = mbeg + issued * WD_PIX + wave * (WD_PIX / 4) + drow;
 #pragma unroll
-        for (int i = 0; i < 2; ++i) {
+        for (int i = 0; i < NI; ++i) {
             const int m = mrow0 + i * 8;
             const bool mok = m < mend;
             const unsigned od = (unsigned)((m * ldd + co0) * 2) + chunk[i];
@@ -150,7 +158,7 @@ __global__ void __launch_bounds__(WD_THREADS) wgrad_dma_kernel(const WDmaP p) {
                 if (hskip[h]) wd_dma16(rsk, slot + (1 + h) * WD_PIX * 128 + i * 1024, off);
                 else wd_dma16(rsx, slot + (1 + h) * WD_PIX * 128 + i * 1024, off);
             }
-            if (!ONE_BY_ONE) {                   // advance this row by one stage (64 pixels)
+            if (!ONE_BY_ONE) {                   // advance this row by one stage (PIX pixels)
                 pow_[i] += adv_w; poh[i] += adv_h;
                 if (pow_[i] >= OW) { pow_[i] -= OW; ++poh[i]; }
                 while (poh[i] >= OH) { poh[i] -= OH; ++pn[i]; }
@@ -187,25 +195,34 @@ __global__ void __launch_bounds__(WD_THREADS) wgrad_dma_kernel(const WDmaP p) {
         __builtin_amdgcn_s_barrier();            // every wave's share has landed, and every wave is done with stage s - 1
         if (issued < ns) issue();                // refill the slot of stage s - 1
         const unsigned st = wd_lds_addr(smem) + (unsigned)((s % D) * WD_STAGE);
-        // all 24 reads of the stage first (16 pixels per MFMA K step: rows advance by 16 * 128 bytes, the swizzle term repeats every 4 rows;
-        // the second read of a fragment is 4 rows = 512 bytes further), one wait, then the 8 MFMAs
-        wd_s16x4 fb[4][2], fa[2][4][2];
+        // all reads of the stage first (16 pixels per MFMA K step: rows advance by 16 * 128 bytes, the swizzle term repeats every 4 rows;
+        // the second read of a fragment is 4 rows = 512 bytes further), one wait, then the MFMAs -- K steps in pixel order, whatever the stage size,
+        // so every accumulator sees the same MFMA sequence for PIX = 32 as for PIX = 64 (bit-identical slabs)
+        wd_s16x4 fb[KS][2], fa[2][KS][2];
         const unsigned ab = st + boff, aa0 = st + aoff[0], aa1 = st + aoff[1];
         fb[0][0] = wd_tr4<0>(ab); fb[0][1] = wd_tr4<512>(ab); fb[1][0] = wd_tr4<2048>(ab); fb[1][1] = wd_tr4<2560>(ab);
-        fb[2][0] = wd_tr4<4096>(ab); fb[2][1] = wd_tr4<4608>(ab); fb[3][0] = wd_tr4<6144>(ab); fb[3][1] = wd_tr4<6656>(ab);
+        if constexpr (KS == 4) { fb[2][0] = wd_tr4<4096>(ab); fb[2][1] = wd_tr4<4608>(ab); fb[3][0] = wd_tr4<6144>(ab); fb[3][1] = wd_tr4<6656>(ab); }
         fa[0][0][0] = wd_tr4<0>(aa0); fa[0][0][1] = wd_tr4<512>(aa0); fa[0][1][0] = wd_tr4<2048>(aa0); fa[0][1][1] = wd_tr4<2560>(aa0);
-        fa[0][2][0] = wd_tr4<4096>(aa0); fa[0][2][1] = wd_tr4<4608>(aa0); fa[0][3][0] = wd_tr4<6144>(aa0); fa[0][3][1] = wd_tr4<6656>(aa0);
+        if constexpr (KS == 4) { fa[0][2][0] = wd_tr4<4096>(aa0); fa[0][2][1] = wd_tr4<4608>(aa0); fa[0][3][0] = wd_tr4<6144>(aa0); fa[0][3][1] = wd_tr4<6656>(aa0); }
         fa[1][0][0] = wd_tr4<0>(aa1); fa[1][0][1] = wd_tr4<512>(aa1); fa[1][1][0] = wd_tr4<2048>(aa1); fa[1][1][1] = wd_tr4<2560>(aa1);
-        fa[1][2][0] = wd_tr4<4096>(aa1); fa[1][2][1] = wd_tr4<4608>(aa1); fa[1][3][0] = wd_tr4<6144>(aa1); fa[1][3][1] = wd_tr4<6656>(aa1);
+        if constexpr (KS == 4) { fa[1][2][0] = wd_tr4<4096>(aa1); fa[1][2][1] = wd_tr4<4608>(aa1); fa[1][3][0] = wd_tr4<6144>(aa1); fa[1][3][1] = wd_tr4<6656>(aa1); }
         // the wait names every fragment as an in/out operand, so no MFMA can be scheduled in front of it
-        asm volatile("s_waitcnt lgkmcnt(0)"
-                     : "+v"(fb[0][0]), "+v"(fb[0][1]), "+v"(fb[1][0]), "+v"(fb[1][1]), "+v"(fb[2][0]), "+v"(fb[2][1]), "+v"(fb[3][0]), "+v"(fb[3][1]),
-                       "+v"(fa[0][0][0]), "+v"(fa[0][0][1]), "+v"(fa[0][1][0]), "+v"(fa[0][1][1]), "+v"(fa[0][2][0]), "+v"(fa[0][2][1]), "+v"(fa[0][3][0]),
-                       "+v"(fa[0][3][1]), "+v"(fa[1][0][0]), "+v"(fa[1][0][1]), "+v"(fa[1][1][0]), "+v"(fa[1][1][1]), "+v"(fa[1][2][0]), "+v"(fa[1][2][1]),
-                       "+v"(fa[1][3][0]), "+v"(fa[1][3][1])
-                     :: "memory");
+        if constexpr (KS == 4) {
+            asm volatile("s_waitcnt lgkmcnt(0)"
+                         : "+v"(fb[0][0]), "+v"(fb[0][1]), "+v"(fb[1][0]), "+v"(fb[1][1]), "+v"(fb[2][0]), "+v"(fb[2][1]), "+v"(fb[3][0]), "+v"(fb[3][1]),
+                           "+v"(fa[0][0][0]), "+v"(fa[0][0][1]), "+v"(fa[0][1][0]), "+v"(fa[0][1][1]), "+v"(fa[0][2][0]), "+v"(fa[0][2][1]), "+v"(fa[0][3][0]),
+                           "+v"(fa[0][3][1]), "+v"(fa[1][0][0]), "+v"(fa[1][0][1]), "+v"(fa[1][1][0]), "+v"(fa[1][1][1]), "+v"(fa[1][2][0]), "+v"(fa[1][2][1]),
+                           "+v"(fa[1][3][0]), "+v"(fa[1][3][1])
+                         :: "memory");
+        } else {
+            asm volatile("s_waitcnt lgkmcnt(0)"
+                         : "+v"(fb[0][0]), "+v"(fb[0][1]), "+v"(fb[1][0]), "+v"(fb[1][1]),
+                           "+v"(fa[0][0][0]), "+v"(fa[0][0][1]), "+v"(fa[0][1][0]), "+v"(fa[0][1][1]),
+                           "+v"(fa[1][0][0]), "+v"(fa[1][0][1]), "+v"(fa[1][1][0]), "+v"(fa[1][1][1])
+                         :: "memory");
+        }
 #pragma unroll
-        for (int ks = 0; ks < 4; ++ks) {
+        for (int ks = 0; ks < KS; ++ks) {
             const wd_s16x8 bf = wd_cat(fb[ks][0], fb[ks][1]);
 #pragma unroll
             for (int b = 0; b < 2; ++b) acc[b] = WdMma<T16>::mma(wd_cat(fa[b][ks][0], fa[b][ks][1]), bf, acc[b]);
@@ -241,15 +258,28 @@ bool wgrad_dma_applicable(const Gather& g, int dtype, int Cout, int ldd) {
     return true;
 }
 
-template <typename T16, bool ONE, int D>
+// Ring variants (SDE_OPT_WGRAD_DMA_RING): 0 = 64 pixels x WD_DEPTH stages (72 KB), 1 = 32 x 4 (48 KB), 2 = 32 x 3 (36 KB).  The slim forms keep at most 36 KB of
+// rows in flight (the limit the depth measurement above found for the 3x3 layers) and compute bit-identical slabs.
+int g_wgrad_dma_ring = 0;
+int wgrad_dma_lds_bytes(int ring) {
+    return ring == 0 ? WD_DEPTH * wd_stage(64) : ring == 1 ? 4 * wd_stage(32) : ring == 2 ? 3 * wd_stage(32) : -1;
+}
+
+template <typename T16, bool ONE, int D, int PIX>
 static void wd_launch(const WDmaP& p, int grid, hipStream_t s) {
-    constexpr int lds = D * WD_STAGE;
+    constexpr int lds = D * wd_stage(PIX);
     static bool attr_done = false;
     if (!attr_done) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_dma_kernel<T16, ONE, D>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_dma_kernel<T16, ONE, D, PIX>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
         attr_done = true;
     }
-    hipLaunchKernelGGL((wgrad_dma_kernel<T16, ONE, D>), dim3(grid), dim3(WD_THREADS), lds, s, p);
+    hipLaunchKernelGGL((wgrad_dma_kernel<T16, ONE, D, PIX>), dim3(grid), dim3(WD_THREADS), lds, s, p);
+}
+template <typename T16, bool ONE>
+static void wd_launch_ring(const WDmaP& p, int grid, hipStream_t s) {
+    if (g_wgrad_dma_ring == 1) wd_launch<T16, ONE, 4, 32>(p, grid, s);
+    else if (g_wgrad_dma_ring == 2) wd_launch<T16, ONE, 3, 32>(p, grid, s);
+    else wd_launch<T16, ONE, WD_DEPTH, 64>(p, grid, s);
 }
 
 // same tiling (64 x 128) and pixel-split arithmetic as wgrad_kernel: rows_per_split is a multiple of 64
@@ -259,8 +289,8 @@ int wgrad_dma_run(const Gather& g, int dtype, const void* dy, int Cout, int ldd,
     const int kblocks = g.KH * g.KW * (g.Cin / 64);
     const int grid = (Cout / 64) * ((kblocks + 1) / 2) * splits;
     const bool one = g.KH == 1 && g.stride == 1 && g.pad == 0;
-    if (dtype == SDE_F16) { if (one) wd_launch<half_t, true, WD_DEPTH>(p, grid, s); else wd_launch<half_t, false, WD_DEPTH>(p, grid, s); }
-    else { if (one) wd_launch<bf16_t, true, WD_DEPTH>(p, grid, s); else wd_launch<bf16_t, false, WD_DEPTH>(p, grid, s); }
+    if (dtype == SDE_F16) { if (one) wd_launch_ring<half_t, true>(p, grid, s); else wd_launch_ring<half_t, false>(p, grid, s); }
+    else { if (one) wd_launch_ring<bf16_t, true>(p, grid, s); else wd_launch_ring<bf16_t, false>(p, grid, s); }
     return 0;
 }
 

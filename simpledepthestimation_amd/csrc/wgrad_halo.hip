@@ -232,6 +232,10 @@ static size_t wh_lds(int NB, int CO16) {
     return tile > red ? tile : red;
 }
 
+int whalo_lds_bytes(int NB, int CO16) {
+    return (NB == 1 || NB == 2 || NB == 4 || NB == 6) && (CO16 == 1 || CO16 == 2) ? (int)wh_lds(NB, CO16) : -1;
+}
+
 int whalo_splits(const Gather& g, int Cout) {
     const int NB = wh_nb(g), CO16 = Cout > 16 ? 2 : 1;
     const int total = g.Bn * sde_cdiv(g.OH, WH_TH) * sde_cdiv(g.OW, WH_TW);

@@ -223,11 +223,24 @@ SCHEDULES = {"resnet": (1, 6, 0), "resnet_basic": (1, 6, 3), "packnet": (2, 3, 0
 # 48.4 / 47.9-48.0 / 48.1 / 48.6 / 50.5 (profiles/r03ah_packnet_sweep.txt)
 WGRAD_BLOCKS = {"resnet": 256, "resnet_basic": 256, "packnet": 1024}
 WGRAD_BLOCKS_LOCKED = False      # bench.py --opt 6=... pins the value for an A/B run
+# LDS ring of the LDS-DMA weight-gradient launches that are forked beside the data-gradient chain (SDE_OPT_WGRAD_DMA_RING: 0 = 64 pixels x 3 stages, 72 KB;
+# 1 = 32 x 4, 48 KB; 2 = 32 x 3, 36 KB), per schedule family: beside a 72 KB workgroup ONE workgroup of the persistent GEMM fits on a compute unit, beside a
+# slim one two.  Same results bit for bit.  profiles/corun_lds_ab.txt, alternating runs in one call: ResNet-50 supervised 6.39 -> 6.30 (ring 1), 6.35 (ring 2),
+# MonoDepth2-R50 7.24 -> 7.11 / 7.12 ms/step; PackNet (1024 weight-gradient workgroups per launch) keeps the wide ring (profiles/README.md item 46).
+WGRAD_DMA_RINGS = {"resnet": 1, "resnet_basic": 0, "packnet": 0}
+WGRAD_DMA_RING = -1              # >= 0 (bench.py --const WGRAD_DMA_RING=...): pins the ring for an A/B run; -1: the family's
+_FAMILY = None                   # the family of the last HipTrainer built (apply_schedule); None: no trainer, ring 0
 SCHEDULE_LOCKED = False  # bench.py --const JOIN_LAG=... / WGRAD_GROUP=... pins the values for an A/B run
 
 
+def wgrad_dma_ring():
+    """The ring for a weight-gradient GEMM that is forked beside a data gradient (hip/nn.py: WGradReducer._launch)."""
+    return WGRAD_DMA_RING if WGRAD_DMA_RING >= 0 else WGRAD_DMA_RINGS.get(_FAMILY, 0)
+
+
 def apply_schedule(family):
-    global JOIN_LAG, WGRAD_GROUP, FIRST_GROUP
+    global JOIN_LAG, WGRAD_GROUP, FIRST_GROUP, _FAMILY
+    _FAMILY = family
     if not SCHEDULE_LOCKED:
         JOIN_LAG, WGRAD_GROUP, FIRST_GROUP = SCHEDULES[family]
 FIRST_GROUP_B = None            # first-group digits of the SECOND phase of a two-phase (data-parallel) backward; None = FIRST_GROUP.  The group boundaries decide

@@ -43,6 +43,7 @@ L.register_protos({
     "sde_bn_bwd_from_part": ([_P, _I, _P, _P, _P, _LG, _I, _I, _P, _P, _P, _I, _P, _P], c_int),
     "sde_conv_set_halo_min_blocks": ([_I], c_int),
     "sde_conv_set_option": ([_I, _I], c_int),
+    "sde_kernel_lds_bytes": ([_I, _I], c_int),
     "sde_conv_wgrad_splits": ([POINTER(ConvDesc), _I], c_int),
     "sde_conv_wgrad_variant": ([POINTER(ConvDesc), _I, _I], c_int),
     "sde_conv_wgrad": ([POINTER(ConvDesc), _P, _I, _I, _I, _P, _I, _P, _I, _P], c_int),
@@ -90,6 +91,8 @@ L.register_protos({
 
 
 OPT_PGEMM, OPT_PGEMM_DEPTH, OPT_PGEMM_3X3, OPT_PGEMM_TILE, OPT_SPLITK, OPT_WGRAD_BLOCKS, OPT_WGRAD_HALO, OPT_CONV_SMALL, OPT_WGRAD_DMA, OPT_BNBWD_FUSE, OPT_CU_RESERVE = 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11      # SDE_OPT_* of include/sde_hip.h
+OPT_WGRAD_DMA_RING, OPT_PGEMM_PER_CU = 12, 13
+KERNEL_PGEMM, KERNEL_WGRAD_DMA, KERNEL_WGRAD_HALO, KERNEL_WGRAD_STAGED, KERNEL_WGRAD_SUM, KERNEL_WGRAD_REDUCE = 1, 2, 3, 4, 5, 6      # SDE_KERNEL_* (sde_kernel_lds_bytes)
 
 
 def set_option(key, value):
@@ -98,6 +101,14 @@ def set_option(key, value):
     if old < 0:
         raise L.SdeHipError(f"sde_conv_set_option({key}, {value}) failed: {L.lib().sde_last_error().decode()}")
     return old
+
+
+def kernel_lds_bytes(kind, variant=0):
+    """sde_kernel_lds_bytes: dynamic LDS per workgroup of a kernel that shares compute units during backward (host-only query)."""
+    n = L.lib().sde_kernel_lds_bytes(int(kind), int(variant))
+    if n < 0:
+        raise L.SdeHipError(f"sde_kernel_lds_bytes({kind}, {variant}): bad kind / variant")
+    return n
 
 
 WGRAD_HALO_KERNEL, WGRAD_DMA_KERNEL, WGRAD_STAGED_KERNEL = 1, 2, 3      # sde_conv_wgrad_variant
@@ -582,6 +593,19 @@ class WGradReducer:
 
     @staticmethod
     def _launch(j, slab, target, side):
+        # a GEMM forked beside the data-gradient chain takes the family's slim LDS ring (two persistent-GEMM workgroups stay resident on its compute
+        # unit); an inline one (the stem, layers without a data gradient) has nothing beside it and keeps whatever SDE_OPT_WGRAD_DMA_RING says
+        ring = L.wgrad_dma_ring() if side is not None else 0
+        if ring:
+            old = set_option(OPT_WGRAD_DMA_RING, ring)
+            try:
+                return WGradReducer._launch_ring(j, slab, target, side)
+            finally:
+                set_option(OPT_WGRAD_DMA_RING, old)
+        return WGradReducer._launch_ring(j, slab, target, side)
+
+    @staticmethod
+    def _launch_ring(j, slab, target, side):
         lib = L.lib()
         if target == "reduce" and L.PROFILE is None:
             L.check(lib.sde_conv_wgrad(ctypes.byref(j.d), L.ptr(j.dz), j.Cout, j.ldy, j.Cin, L.ptr(slab), j.splits, _wptr(j.dw), j.flags, L.stream()),
