@@ -144,10 +144,14 @@ def get_cfg():
     return _C.clone()
 
 
-def get_project_cfg(project):
+def get_project_cfg(project, datasets=False):
     """get_cfg() + the hot-path keys of projects/<project>/configs/Base.yaml ("MonoDepth2" or "Supervised"), from the embedded literals;
-    "MotionLearningWaymo": the model, loss and solver keys of projects/MotionLearning/configs/resnet18_waymo.yaml over its Base_waymo.yaml."""
-    from .defaults import PROJECT_BASE
+    "MotionLearningWaymo" / "MonoDepth2Waymo" / "SupervisedWaymo": the model, loss and solver keys of projects/<project>/configs/resnet18_waymo.yaml
+    over its Base_waymo.yaml.  datasets=True also merges the project's DATASETS.TRAIN / DATASETS.TEST blocks (defaults.PROJECT_DATASETS: the WaymoDepth
+    reader, its roots as the YAML has them, the preprocess chains)."""
+    from .defaults import PROJECT_BASE, PROJECT_DATASETS
     cfg = get_cfg()
     cfg.merge_from_other_cfg(copy.deepcopy(PROJECT_BASE[project]))
+    if datasets:
+        cfg.merge_from_other_cfg({"DATASETS": copy.deepcopy(PROJECT_DATASETS[project])})
     return cfg

@@ -115,8 +115,8 @@ PROJECT_BASE = {
         "TEST": {"GT_SCALE": False},
         "LOG_PERIOD": 20,
     },
-    # projects/MotionLearning/configs/resnet18_waymo.yaml over its Base_waymo.yaml: the model, loss and solver keys (the WaymoDepth dataset blocks are not
-    # on the path; synthetic batches carry `mask` / `ctx_mask`)
+    # projects/MotionLearning/configs/resnet18_waymo.yaml over its Base_waymo.yaml: the model, loss and solver keys (the WaymoDepth dataset blocks are in
+    # PROJECT_DATASETS below)
     "MotionLearningWaymo": {
         "MODEL": {"META_ARCHITECTURE": "MotionLearningModel", "MAX_DEPTH": 80, "WITH_MASK": True,
                   "DEPTH_NET": {"NAME": "GoogleResNetv2", "ENCODER_NAME": "18??", "UPSAMPLE_DEPTH": False, "LEARN_SCALE": False, "NORM": "randLN",
@@ -131,5 +131,65 @@ PROJECT_BASE = {
         "EVALUATORS": ("kitti_evaluator", "kitti_evaluator_0_30", "kitti_evaluator_30_50", "kitti_evaluator_50_80"),
         "TEST": {"GT_SCALE": True},
         "LOG_PERIOD": 20,
+    },
+    # projects/MonoDepth2/configs/resnet18_waymo.yaml and projects/Supervised/configs/resnet18_waymo.yaml over their Base_waymo.yaml: model, loss,
+    # solver and TEST keys ("18pt" asks for ImageNet weights, as in the YAML: set ENCODER_NAME "18" to train from scratch)
+    "MonoDepth2Waymo": {
+        "MODEL": {"META_ARCHITECTURE": "MonoDepth2Model", "MAX_DEPTH": 80,
+                  "DEPTH_NET": {"NAME": "DepthResNet", "ENCODER_NAME": "18pt", "UPSAMPLE_DEPTH": False}, "POSE_NET": {"NAME": "PoseNet", "NUM_CONTEXTS": 2}},
+        "LOSS": {"SSIM_WEIGHT": 0.85, "C1": 1e-4, "C2": 9e-4, "CLIP": 0.0, "AUTOMASK": True, "SMOOTHNESS_WEIGHT": 1e-3, "PHOTOMETRIC_REDUCE": "min",
+                 "SUPERVISED_WEIGHT": 0.0, "VARIANCE_FOCUS": 0.85, "VAR_LOSS_WEIGHT": 0.0},
+        "SOLVER": {"IMS_PER_BATCH": 16, "DEPTH_LR": 2e-4, "POSE_LR": 2e-4, "LR_STEPS": (40,), "GAMMA": 0.1, "MAX_EPOCHS": 50, "CHECKPOINT_PERIOD": 1},
+        "EVALUATORS": ("kitti_evaluator", "kitti_evaluator_0_30", "kitti_evaluator_30_50", "kitti_evaluator_50_80"),
+        "TEST": {"GT_SCALE": True},
+        "LOG_PERIOD": 20,
+    },
+    "SupervisedWaymo": {
+        "MODEL": {"META_ARCHITECTURE": "SupDepthModel", "MAX_DEPTH": 80, "DEPTH_NET": {"NAME": "DepthResNet", "ENCODER_NAME": "18pt", "UPSAMPLE_DEPTH": False}},
+        "LOSS": {"VARIANCE_FOCUS": 0.85},
+        "SOLVER": {"IMS_PER_BATCH": 16, "DEPTH_LR": 1e-4, "DEPTH_END_LR": 1e-5, "MAX_EPOCHS": 50, "CHECKPOINT_PERIOD": 1},
+        "EVALUATORS": ("kitti_evaluator", "kitti_evaluator_0_30", "kitti_evaluator_30_50", "kitti_evaluator_50_80"),
+        "TEST": {"GT_SCALE": False},
+        "LOG_PERIOD": 20,
+    },
+}
+
+
+def _waymo(split, preprocess, **kw):
+    d = {"NAME": "WaymoDepth", "DATA_ROOT": f"/data2/data/waymo/{split}/image", "DEPTH_ROOT": f"/data2/data/waymo/{split}/depth",
+         "SPLIT": f"/data2/data/waymo/infos/{split}_infos.pkl", "USE_CAMS": ["FRONT"]}
+    d.update(kw)
+    d["PREPROCESS"] = preprocess
+    return d
+
+
+# The DATASETS.TRAIN / DATASETS.TEST blocks of the three Waymo projects' Base_waymo.yaml (roots as the YAMLs have them: point DATA_ROOT, DEPTH_ROOT,
+# MASK_ROOT and SPLIT at the local copy).  Kept apart from PROJECT_BASE and merged by get_project_cfg(project, datasets=True) only: models, losses
+# and benchmarks that feed synthetic batches take the project without a dataset.
+PROJECT_DATASETS = {
+    "MotionLearningWaymo": {
+        "TRAIN": _waymo("training", [{"NAME": "LoadImg", "WITH_CTX": True}, {"NAME": "LoadMask"}, {"NAME": "CropTopTo", "IMG_H": 1152},
+                                              {"NAME": "Resize", "IMG_W": 320, "IMG_H": 192}, {"NAME": "RandomFlip"}, {"NAME": "RandomImageAug"}, {"NAME": "ToTensor"}],
+                        MASK_ROOT="/data2/data/waymo/training/segmentation", DOWNSAMPLE=2, WITH_DEPTH=False, WITH_POSE=False, FORWARD_CONTEXT=1, STRIDE=1),
+        "TEST": _waymo("validation", [{"NAME": "LoadImg"}, {"NAME": "LoadDepth", "KEEP_ORIG": True}, {"NAME": "ClipDepth", "MAX_DEPTH": 80},
+                                              {"NAME": "CropTopTo", "IMG_H": 1152}, {"NAME": "Resize", "IMG_W": 320, "IMG_H": 192}, {"NAME": "ToTensor"}],
+                       DOWNSAMPLE=20, WITH_DEPTH=False, WITH_POSE=False),
+    },
+    "MonoDepth2Waymo": {
+        "TRAIN": _waymo("training", [{"NAME": "LoadImg", "WITH_CTX": True}, {"NAME": "CropTopTo", "IMG_H": 768}, {"NAME": "Resize", "IMG_W": 480, "IMG_H": 192},
+                                              {"NAME": "RandomFlip"}, {"NAME": "RandomImageAug"}, {"NAME": "ToTensor"}],
+                        DOWNSAMPLE=2, WITH_DEPTH=False, WITH_POSE=False, FORWARD_CONTEXT=1, BACKWARD_CONTEXT=1, STRIDE=1),
+        "TEST": _waymo("validation", [{"NAME": "LoadImg"}, {"NAME": "LoadDepth", "KEEP_ORIG": True}, {"NAME": "ClipDepth", "MAX_DEPTH": 80},
+                                              {"NAME": "CropTopTo", "IMG_H": 768}, {"NAME": "Resize", "IMG_W": 480, "IMG_H": 192}, {"NAME": "ToTensor"}],
+                       DOWNSAMPLE=20, WITH_DEPTH=False, WITH_POSE=False),
+    },
+    # as in the YAML: this project trains on the validation split and tests on the training split
+    "SupervisedWaymo": {
+        "TRAIN": _waymo("validation", [{"NAME": "LoadImg"}, {"NAME": "LoadDepth"}, {"NAME": "ClipDepth", "MAX_DEPTH": 80}, {"NAME": "CropTopTo", "IMG_H": 768},
+                                                {"NAME": "RandomCrop", "IMG_W": 704, "IMG_H": 352}, {"NAME": "RandomFlip"}, {"NAME": "RandomImageAug"}, {"NAME": "ToTensor"}],
+                        WITH_DEPTH=True),
+        "TEST": _waymo("training", [{"NAME": "LoadImg"}, {"NAME": "LoadDepth", "KEEP_ORIG": True}, {"NAME": "ClipDepth", "MAX_DEPTH": 80},
+                                            {"NAME": "CropTopTo", "IMG_H": 768}, {"NAME": "ToTensor"}],
+                       DOWNSAMPLE=20, WITH_DEPTH=True),
     },
 }

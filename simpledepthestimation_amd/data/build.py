@@ -44,6 +44,53 @@ class DatasetBase(data.Dataset):
         return data.default_collate(batch)
 
 
+def collate_samples(batch_list, maps=("depth",), map_lists=("ctx_depth",)):
+    """The collators' common body (datasets/kitti_v2.py:L197-221, datasets/waymo.py:L128-155): list of sample dicts -> the batch dict of SURVEY.md 8b.
+    img / img_orig stacked tensors, intrinsics / pose_gt tensors from numpy, the keys in `maps` tensors [B,1,H,W], ctx_img / ctx_img_orig and the keys
+    in `map_lists` lists (one entry per context) of numpy [B, ...] arrays, ONE flip flag for the batch (the first sample's), everything else a list."""
+    from collections import defaultdict
+    merged = defaultdict(list)
+    for ex in batch_list:
+        for k, v in ex.items():
+            merged[k].append(v)
+    ret = {}
+    for key, value in merged.items():
+        if key in ("img", "img_orig"):
+            ret[key] = torch.stack(value, 0)
+        elif key in ("intrinsics", "pose_gt"):
+            ret[key] = torch.from_numpy(np.stack(value, 0))
+        elif key in maps:
+            ret[key] = torch.from_numpy(np.stack(value, 0)[:, None, ...])
+        elif key in ("ctx_img", "ctx_img_orig"):
+            arr = np.stack([np.stack(v, 0) for v in value])
+            ret[key] = [arr[:, i] for i in range(arr.shape[1])]
+        elif key in map_lists:
+            arr = np.stack([np.stack(v, 0)[:, None, ...] for v in value])
+            ret[key] = [arr[:, i] for i in range(arr.shape[1])]
+        elif key == "flip":
+            ret[key] = value[0]
+        elif key == "aug_params":
+            ret[key] = torch.from_numpy(np.stack(value, 0))
+        else:
+            ret[key] = value
+    if "img_u8" in merged:
+        # ON_DEVICE chain (an addition of this package): when every frame of the batch has one source size they are stacked here, in the worker, so
+        # that the loader's pin-memory thread pins ONE tensor per entry and data/device_aug.py uploads each with one copy; otherwise per-frame lists
+        shapes = {v.shape for v in merged["img_u8"]} | {a.shape for v in merged.get("ctx_img_u8", []) for a in v}
+        # tap-compacted frames (Resize ON_DEVICE: "taps") of one shape may still come from two source sizes: one table pair per batch only when all agree
+        taps = merged.get("device_taps")
+        one_table = taps is None or (len(taps) == len(merged["img_u8"]) and all(np.array_equal(t[0], taps[0][0]) and np.array_equal(t[1], taps[0][1]) for t in taps))
+        if len(shapes) == 1 and one_table:
+            ret["img_u8"] = torch.from_numpy(np.stack(merged["img_u8"], 0))
+            if "ctx_img_u8" in merged:
+                ret["ctx_img_u8"] = [torch.from_numpy(np.stack([v[i] for v in merged["ctx_img_u8"]], 0)) for i in range(len(merged["ctx_img_u8"][0]))]
+            if taps is not None:
+                ret["device_taps"] = (torch.from_numpy(taps[0][0]), torch.from_numpy(taps[0][1]))
+        elif taps is not None:
+            ret["device_taps"] = [ex.get("device_taps") for ex in batch_list]          # per sample; None where Resize had nothing to drop
+    return ret
+
+
 class InferenceSampler(data.Sampler):
     """Contiguous shards of exactly the dataset (ranks may differ by one sample), distributed_sampler.py:L57-84."""
 
@@ -158,7 +205,7 @@ class DevicePrefetcher:
     the consumer transforms them -- HipTrainer.input_transform = DeviceImageAug(...) runs the kernels at the head of the step, straight into the
     captured graph's static inputs; that is the faster arrangement on this stack (bench.py --with-loader; DESIGN.md: measured both ways)."""
 
-    _RAW = ("img_u8", "ctx_img_u8", "aug_params", "device_resize")     # consumed by device_aug (which uploads them itself)
+    _RAW = ("img_u8", "ctx_img_u8", "aug_params", "device_resize", "device_taps")     # consumed by device_aug (which uploads them itself)
 
     def __init__(self, loader, device, device_aug=None, slots=4, ahead=2, pick_stream=True):
         self.loader, self.device = loader, torch.device(device)
@@ -207,14 +254,15 @@ class DevicePrefetcher:
 
     def _stage(self, batch, slot):
         if self._stream is None:
-            out = {k: self._move(None, k, v) for k, v in batch.items()}
+            out = {k: (v if k == "device_taps" else self._move(None, k, v)) for k, v in batch.items()}
             return (self.device_aug(out) if self.device_aug is not None else out), None
         bufs = self._bufs[slot]
         self._host_wait(1, slot, self._seq[slot])             # the consumer is done with the batch this slot held (normally long since)
         seq = self._seq[slot] = self._staged_count = getattr(self, "_staged_count", 0) + 1
         with torch.cuda.stream(self._stream):
             _mark("upload_begin")
-            out = {k: (v if (self.device_aug is not None and k in self._RAW) else self._move(bufs, k, v)) for k, v in batch.items()}
+            # device_taps stays on the host either way: whoever runs DeviceImageAug checks the tables against the frames before the kernel reads through them
+            out = {k: (v if ((self.device_aug is not None and k in self._RAW) or k == "device_taps") else self._move(bufs, k, v)) for k, v in batch.items()}
             if self.device_aug is not None:
                 out = self.device_aug(out, bufs)
             _mark("upload_end")

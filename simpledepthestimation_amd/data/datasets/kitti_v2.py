@@ -7,13 +7,11 @@ BACKWARD_CONTEXT -- if its neighbours at +-STRIDE frames of the same drive and c
 WITH_POSE adds data['pose_gt'], the OXTS odometry pose relative to the drive's first frame (false in every config of the two projects)."""
 import logging
 import os
-from collections import defaultdict
 
 import numpy as np
-import torch
 
 from ...geometry import pose_utils as PU
-from ..build import DATASET_REGISTRY, DatasetBase
+from ..build import DATASET_REGISTRY, DatasetBase, collate_samples
 
 logger = logging.getLogger(__name__)
 
@@ -153,36 +151,4 @@ class KittiDepthV2(DatasetBase):
         """list of sample dicts -> the batch dict of SURVEY.md 8b: img / img_orig stacked tensors, intrinsics / depth tensors from numpy,
         ctx_img / ctx_img_orig / ctx_depth as lists (one entry per context) of numpy [B, ...] arrays, ONE flip flag for the batch (the first
         sample's), everything else as a list."""
-        merged = defaultdict(list)
-        for ex in batch_list:
-            for k, v in ex.items():
-                merged[k].append(v)
-        ret = {}
-        for key, value in merged.items():
-            if key in ("img", "img_orig"):
-                ret[key] = torch.stack(value, 0)
-            elif key in ("intrinsics", "pose_gt"):
-                ret[key] = torch.from_numpy(np.stack(value, 0))
-            elif key == "depth":
-                ret[key] = torch.from_numpy(np.stack(value, 0)[:, None, ...])
-            elif key in ("ctx_img", "ctx_img_orig"):
-                arr = np.stack([np.stack(v, 0) for v in value])
-                ret[key] = [arr[:, i] for i in range(arr.shape[1])]
-            elif key == "ctx_depth":
-                arr = np.stack([np.stack(v, 0)[:, None, ...] for v in value])
-                ret[key] = [arr[:, i] for i in range(arr.shape[1])]
-            elif key == "flip":
-                ret[key] = value[0]
-            elif key == "aug_params":
-                ret[key] = torch.from_numpy(np.stack(value, 0))
-            else:
-                ret[key] = value
-        if "img_u8" in merged:
-            # ON_DEVICE chain (an addition of this package): when every frame of the batch has one source size they are stacked here, in the worker, so
-            # that the loader's pin-memory thread pins ONE tensor per entry and data/device_aug.py uploads each with one copy; otherwise per-frame lists
-            shapes = {v.shape for v in merged["img_u8"]} | {a.shape for v in merged.get("ctx_img_u8", []) for a in v}
-            if len(shapes) == 1:
-                ret["img_u8"] = torch.from_numpy(np.stack(merged["img_u8"], 0))
-                if "ctx_img_u8" in merged:
-                    ret["ctx_img_u8"] = [torch.from_numpy(np.stack([v[i] for v in merged["ctx_img_u8"]], 0)) for i in range(len(merged["ctx_img_u8"][0]))]
-        return ret
+        return collate_samples(batch_list)

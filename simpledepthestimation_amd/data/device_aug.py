@@ -6,6 +6,10 @@ data loader's workers resize and jitter ~100 frames per 5 ms step of one MI355X,
 ``ON_DEVICE: True`` on the `Resize` and `RandomImageAug` steps the workers only decode, draw the random parameters (same RNG calls in the same
 order) and rescale the small entries; the frames cross PCIe as uint8 at source size (50 MB per step) and this module produces `img`, `img_orig`,
 `ctx_img`, `ctx_img_orig` on the device, bit-identical to the CPU chain (tests/test_device_aug.py).
+
+``ON_DEVICE: "taps"`` (Waymo: 1280 x 1920 frames reduced 4-6x) goes one step further: the worker keeps only the source rows and columns the
+2-tap resize reads and sends `device_taps`, the tap tables renumbered for the cut-down frame; the kernel reads its source through the tables
+it is given, so the same launches produce the same bits from a fraction of the bytes (tests/test_waymo.py, tests/test_gpu_waymo.py).
 """
 import numpy as np
 import torch
@@ -34,7 +38,24 @@ class DeviceImageAug:
     def __init__(self, device):
         self.device = torch.device(device)
         self._taps = {}
+        self._given = {}
         self._own = {}
+
+    def given_taps(self, pair, Hs, Ws, h, w):
+        """`device_taps` of a batch -> (xtab, ytab) on the device, cached by content.  The kernel indexes the frame with whatever the tables hold, so
+        they are checked here, on the host, once per distinct pair: int32 [w][4] / [h][4], every tap inside the [Hs, Ws] frame they come with."""
+        if len(pair) != 2 or any(torch.is_tensor(t) and t.is_cuda for t in pair):
+            raise L.SdeHipError("DeviceImageAug: device_taps is one (xtab, ytab) pair of host arrays (checked here, before the kernel reads through them)")
+        xt, yt = (np.ascontiguousarray(t.numpy() if torch.is_tensor(t) else t) for t in pair)
+        key = (Hs, Ws, xt.tobytes(), yt.tobytes())
+        if key not in self._given:
+            for t, n, src in ((xt, w, Ws), (yt, h, Hs)):
+                if t.dtype != np.int32 or t.shape != (n, 4) or t[:, :2].min() < 0 or t[:, :2].max() >= src:
+                    raise L.SdeHipError(f"DeviceImageAug: device_taps do not fit the frames ({Hs} x {Ws} -> {h} x {w})")
+            if len(self._given) >= 64:          # a handful of source sizes per dataset: anything more is a leak, start over
+                self._given.clear()
+            self._given[key] = (torch.from_numpy(xt).to(self.device), torch.from_numpy(yt).to(self.device))
+        return self._given[key]
 
     def taps(self, src, dst):
         key = (src, dst)
@@ -52,9 +73,10 @@ class DeviceImageAug:
             b = bufs[key] = torch.empty(shape, dtype=dtype, device=device)
         return b
 
-    def prep(self, frames, params, h, w, bufs=None, tag="x", out=None):
+    def prep(self, frames, params, h, w, bufs=None, tag="x", out=None, tabs=None):
         """frames: uint8 device tensor [N,Hs,Ws,3]; params: float32 device tensor [N,8] -> (img [N,3,h,w], orig [N,3,h,w]).
-        out: optional (img, orig) destination tensors (the captured step's static inputs: the kernels then write them in place)."""
+        out: optional (img, orig) destination tensors (the captured step's static inputs: the kernels then write them in place).
+        tabs: optional `device_taps` (host tables of a tap-compacted batch) used in place of the plain tables of (Ws, w) / (Hs, h)."""
         if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3 or not frames.is_cuda:
             raise L.SdeHipError("DeviceImageAug: frames must be a uint8 [N,H,W,3] device tensor")
         N, Hs, Ws, _ = frames.shape
@@ -66,11 +88,12 @@ class DeviceImageAug:
             img = self._buf(bufs, ("aug.img", tag), (N, 3, h, w), torch.float32, self.device)
             orig = self._buf(bufs, ("aug.orig", tag), (N, 3, h, w), torch.float32, self.device)
         lsum = self._buf(bufs, ("aug.lsum", tag), (N,), torch.int32, self.device)
-        L.check(L.lib().sde_image_prep_u8(L.ptr(frames), N, Hs, Ws, h, w, L.ptr(self.taps(Ws, w)), L.ptr(self.taps(Hs, h)), L.ptr(params), L.ptr(lsum),
+        xtab, ytab = self.given_taps(tabs, Hs, Ws, h, w) if tabs is not None else (self.taps(Ws, w), self.taps(Hs, h))
+        L.check(L.lib().sde_image_prep_u8(L.ptr(frames), N, Hs, Ws, h, w, L.ptr(xtab), L.ptr(ytab), L.ptr(params), L.ptr(lsum),
                                           L.ptr(img), L.ptr(orig), L.stream()), "sde_image_prep_u8")
         return img, orig
 
-    def prep_multi(self, frames_list, params, h, w, bufs=None, tag="x", outs=None):
+    def prep_multi(self, frames_list, params, h, w, bufs=None, tag="x", outs=None, tabs=None):
         """G <= 4 uint8 device tensors [N,Hs,Ws,3] of ONE shape sharing the per-sample parameters (target + context frames of a batch) in one pair of
         launches -> [(img, orig)] per tensor.  outs: optional list of (img, orig) destinations (or None entries)."""
         G = len(frames_list)
@@ -91,7 +114,8 @@ class DeviceImageAug:
                             self._buf(bufs, ("aug.orig", tag, g), (N, 3, h, w), torch.float32, self.device)))
         lsum = self._buf(bufs, ("aug.lsum", tag), (G * N,), torch.int32, self.device)
         arr = lambda ts: (L.c_void_p * G)(*[t.data_ptr() for t in ts])
-        L.check(L.lib().sde_image_prep_u8_multi(arr(frames_list), G, N, Hs, Ws, h, w, L.ptr(self.taps(Ws, w)), L.ptr(self.taps(Hs, h)), L.ptr(params), L.ptr(lsum),
+        xtab, ytab = self.given_taps(tabs, Hs, Ws, h, w) if tabs is not None else (self.taps(Ws, w), self.taps(Hs, h))
+        L.check(L.lib().sde_image_prep_u8_multi(arr(frames_list), G, N, Hs, Ws, h, w, L.ptr(xtab), L.ptr(ytab), L.ptr(params), L.ptr(lsum),
                                                 arr([r[0] for r in res]), arr([r[1] for r in res]), L.stream()), "sde_image_prep_u8_multi")
         return res
 
@@ -115,7 +139,7 @@ class DeviceImageAug:
             bufs = self._own            # persistent scratch when no prefetcher slot is given (consumer-side use: one batch at a time)
         st = static or {}
         dst = lambda k, k2, i=None: ((st[k] if i is None else st[k][i]), (st[k2] if i is None else st[k2][i])) if (k in st and k2 in st) else None
-        out = {k: v for k, v in batch.items() if k not in ("img_u8", "ctx_img_u8", "aug_params", "device_resize")}
+        out = {k: v for k, v in batch.items() if k not in ("img_u8", "ctx_img_u8", "aug_params", "device_resize", "device_taps")}
         size = batch["device_resize"]
         h, w = (size[0] if isinstance(size, (list, tuple)) and isinstance(size[0], (list, tuple)) else size)
         frames = batch["img_u8"]
@@ -124,15 +148,19 @@ class DeviceImageAug:
             params = torch.as_tensor(np.stack([np.asarray(p, dtype=np.float32) for p in params], 0))
         pd = self._up(params, bufs, "params")
         ctx = batch.get("ctx_img_u8")
+        taps = batch.get("device_taps")
+        shared = taps is not None and len(taps) == 2 and not isinstance(taps[0], (tuple, list))       # ONE (xtab, ytab) for the batch, not one per sample
         if torch.is_tensor(frames):
+            if taps is not None and not shared:
+                raise L.SdeHipError("DeviceImageAug: stacked frames take one device_taps pair")
             # collated form (every frame of the batch has one source size; the collator stacked them, the loader pinned them): target frames
             # [B,Hs,Ws,3], contexts as a list of such tensors -- one upload and one pair of launches per tensor, outputs are the batch entries
             dev_frames = [self._up(frames, bufs, "img")] + [self._up(c, bufs, ("ctx", i)) for i, c in enumerate(ctx or [])]
             dsts = [dst("img", "img_orig")] + [dst("ctx_img", "ctx_img_orig", i) for i in range(len(dev_frames) - 1)]
             if len(dev_frames) <= PREP_MAX_GROUPS and all(f.shape == dev_frames[0].shape for f in dev_frames):
-                res = self.prep_multi(dev_frames, pd, h, w, bufs, "batch", dsts)            # target + context frames: ONE pair of launches
+                res = self.prep_multi(dev_frames, pd, h, w, bufs, "batch", dsts, tabs=taps)            # target + context frames: ONE pair of launches
             else:
-                res = [self.prep(f, pd, h, w, bufs, ("t", i), dsts[i]) for i, f in enumerate(dev_frames)]
+                res = [self.prep(f, pd, h, w, bufs, ("t", i), dsts[i], tabs=taps) for i, f in enumerate(dev_frames)]
             out["img"], out["img_orig"] = res[0]
             if ctx is not None:
                 out["ctx_img"], out["ctx_img_orig"] = [r[0] for r in res[1:]], [r[1] for r in res[1:]]
@@ -143,15 +171,18 @@ class DeviceImageAug:
         slots = [[frames[b]] + (list(ctx[b]) if nctx else []) for b in range(B)]
         img = torch.empty(B, 1 + nctx, 3, h, w, device=self.device)
         orig = torch.empty(B, 1 + nctx, 3, h, w, device=self.device)
-        groups = {}
+        groups, tabs_of = {}, {}
         for b in range(B):
+            t = taps if shared else (taps[b] if taps is not None else None)         # a sample's frames share its tables; two samples' compacted frames
+            tk = None if t is None else (bytes(np.asarray(t[0]).tobytes()), bytes(np.asarray(t[1]).tobytes()))     # of one shape may still need two tables
             for s_, f in enumerate(slots[b]):
-                groups.setdefault(tuple(f.shape[:2]), []).append((b, s_, f))
-        for (Hs, Ws), items in groups.items():
+                groups.setdefault((tuple(f.shape[:2]), tk), []).append((b, s_, f))
+                tabs_of[(tuple(f.shape[:2]), tk)] = t
+        for gk, items in groups.items():
             fr = self._up(np.stack([np.asarray(f) if not torch.is_tensor(f) else f.cpu().numpy() for _, _, f in items], 0), None, None)
             bi = torch.tensor([b for b, _, _ in items], device=self.device)
             si = torch.tensor([s_ for _, s_, _ in items], device=self.device)
-            j, o = self.prep(fr, pd[bi], h, w)
+            j, o = self.prep(fr, pd[bi], h, w, tabs=tabs_of[gk])
             img[bi, si], orig[bi, si] = j, o
         out["img"], out["img_orig"] = img[:, 0].contiguous(), orig[:, 0].contiguous()
         if nctx:

@@ -124,21 +124,50 @@ def resize_nearest(arr, dst_w, dst_h):
     return arr[ys[:, None], xs[None, :]]
 
 
+def compact_taps(src, dst):
+    """One axis of the tap-compacted upload: (used, table).  `used` = the sorted source indices the 2-tap rule reads at all (at most 2 * dst of them),
+    `table` = int32 [dst][4] (tap 0, tap 1, weight 0, weight 1) with the taps renumbered to positions in `used` -- so that the fixed-point rule applied
+    to img[used] with `table` is the rule applied to img with the plain table, value for value."""
+    s0, s1, w0, w1 = _linear_coefs(src, dst)
+    used = np.unique(np.concatenate([s0, s1]))
+    return used, np.stack([np.searchsorted(used, s0), np.searchsorted(used, s1), w0, w1], 1).astype(np.int32)
+
+
 @PREPROCESS_REGISTRY.register()
 class Resize(Preprocess):
     """ON_DEVICE: True (an addition of this package) leaves the uint8 frames at their source size -- the device pipeline (data/device_aug.py,
     sde_image_prep_u8) resizes them with the same fixed-point rule after the host-to-device copy -- and still rescales the intrinsics, the sparse
-    depth and the masks here (they are small and stay on the host path)."""
+    depth and the masks here (they are small and stay on the host path).
+    ON_DEVICE: "taps" is ON_DEVICE: True with the frames cut down, here in the worker, to the source rows and columns the resize reads: at a
+    reduction of s only 2 of every s rows / columns carry a tap (Waymo: 1152 x 1920 -> 192 x 320 reads 384 x 640, one ninth of the bytes).
+    `device_taps` = (xtab, ytab) are the tap tables renumbered for the cut-down frame; the kernel reads its source through them, so the device
+    result is bit-identical.  Where no row and no column can be dropped (reductions below 2x, enlargements) the step behaves as ON_DEVICE: True."""
 
     def __init__(self, cfg):
         super().__init__(cfg)
         self.img_h, self.img_w = cfg.IMG_H, cfg.IMG_W
         self.on_device = bool(cfg.get("ON_DEVICE", False))
+        self.tap_compact = cfg.get("ON_DEVICE", False) == "taps"
+        self._compact = {}           # (H, W) -> (used_y, used_x, (xtab, ytab)), or None where nothing can be dropped
+
+    def _compaction(self, H, W):
+        if (H, W) not in self._compact:
+            (uy, ytab), (ux, xtab) = compact_taps(H, self.img_h), compact_taps(W, self.img_w)
+            self._compact[(H, W)] = None if (len(uy) == H and len(ux) == W) else (uy, ux, (xtab, ytab))
+        return self._compact[(H, W)]
 
     def forward(self, data_dict):
         H, W, _ = data_dict["img"].shape
         if self.on_device:
             data_dict["device_resize"] = (self.img_h, self.img_w)
+            c = self._compaction(H, W) if self.tap_compact else None
+            if c is not None and all(a.shape[:2] == (H, W) for a in data_dict.get("ctx_img", [])):
+                uy, ux, tabs = c
+                cut = lambda a: np.take(np.take(a, uy, axis=0), ux, axis=1)          # = a[uy][:, ux]; rows first: the column gather then walks a third of the frame
+                data_dict["img"] = cut(data_dict["img"])
+                if "ctx_img" in data_dict:
+                    data_dict["ctx_img"] = [cut(a) for a in data_dict["ctx_img"]]
+                data_dict["device_taps"] = tabs
             return self._forward_rest(data_dict, H, W, images=False)
         data_dict["img"] = resize_linear_u8(data_dict["img"], self.img_w, self.img_h)
         return self._forward_rest(data_dict, H, W, images=True)

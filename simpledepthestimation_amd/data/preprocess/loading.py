@@ -1,8 +1,10 @@
-"""File loading steps (reference: detectron2/data/preprocess/loading.py:L25-79 LoadImg, LoadDepth).
+"""File loading steps (reference: detectron2/data/preprocess/loading.py:L25-123 LoadImg, LoadDepth, LoadMask, LoadLidar).
 
 The reference decodes with OpenCV (absent here); Pillow decodes the same PNG bytes: an 8-bit RGB PNG gives the array cv2.imread +
 COLOR_BGR2RGB gives, a 16-bit grayscale PNG the array cv2.imread(path, -1) gives (PNG decoding is lossless, so the arrays are equal by the
-format's definition; tests write PNGs and read them back)."""
+format's definition; tests write PNGs and read them back).  Waymo frames are JPEGs: read_rgb decodes them with Pillow's libjpeg, and JPEG
+decoding is NOT bit-exact across decoders (IDCT and chroma up-sampling differ), so parity with cv2's decoder is unpinned -- the test pins
+only that LoadImg returns the array Pillow decodes."""
 import os
 
 import numpy as np
@@ -26,6 +28,18 @@ def read_depth_png(path):
     if arr.dtype not in (np.uint16, np.int32, np.uint8):
         arr = arr.astype(np.int32)
     return arr.astype(np.float32) / 255
+
+
+def read_mask_png(path):
+    """Segmentation masks are 8- or 16-bit single-channel PNGs; the integers as float32: cv2.imread(path, -1).astype(np.float32)."""
+    from PIL import Image
+    if not os.path.isfile(path):
+        raise AssertionError(f"'{path} does not exist!'")       # the reference's text (its assert comes after cv2.imread's None has already failed)
+    with Image.open(path) as im:
+        arr = np.asarray(im)
+    if arr.dtype == bool:                                       # 1-bit PNGs decode to bool with Pillow, to 0 / 255 with cv2
+        arr = arr.astype(np.uint8) * 255
+    return arr.astype(np.float32)
 
 
 @PREPROCESS_REGISTRY.register()
@@ -63,4 +77,37 @@ class LoadDepth(Preprocess):
             data_dict["depth_orig"] = data_dict["depth"].copy()
         if self.load_ctx:
             data_dict["ctx_depth"] = [self._load(p) for p in data_dict["metadata"]["ctx_depth_dir"]]
+        return data_dict
+
+
+@PREPROCESS_REGISTRY.register()
+class LoadMask(Preprocess):
+    """`mask` and `ctx_mask` (always both: loading.py:L88-96 has no WITH_CTX switch) from metadata['mask_dir'] / ['ctx_mask_dir']."""
+
+    def forward(self, data_dict):
+        data_dict["mask"] = read_mask_png(data_dict["metadata"]["mask_dir"])
+        data_dict["ctx_mask"] = [read_mask_png(p) for p in data_dict["metadata"]["ctx_mask_dir"]]
+        return data_dict
+
+
+@PREPROCESS_REGISTRY.register()
+class LoadLidar(Preprocess):
+    """Velodyne scans: a flat float32 .bin read as [-1, LOAD_DIM], of which USE_DIM keeps the leading columns (int) or the listed ones."""
+
+    def __init__(self, cfg):
+        super().__init__(cfg)
+        self.load_ctx = cfg.get("WITH_CTX", False)
+        self.load_dim = cfg.get("LOAD_DIM", 4)
+        self.use_dim = cfg.get("USE_DIM", 3)
+
+    def _load(self, lidar_dir):
+        if os.path.splitext(lidar_dir)[-1] != ".bin":
+            raise NotImplementedError(lidar_dir)
+        scan = np.fromfile(lidar_dir, dtype=np.float32).reshape(-1, self.load_dim)
+        return scan[:, :self.use_dim] if isinstance(self.use_dim, int) else scan[:, list(self.use_dim)]
+
+    def forward(self, data_dict):
+        data_dict["lidar"] = self._load(data_dict["metadata"]["lidar_dir"])
+        if self.load_ctx:
+            data_dict["ctx_lidar"] = [self._load(p) for p in data_dict["metadata"]["ctx_lidar_dir"]]
         return data_dict
