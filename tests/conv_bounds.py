@@ -25,6 +25,28 @@ Where the engine rounds an intermediate to the storage dtype, the bound follows 
     nearest up-sampling, concat split) by a second kernel in fp32 that rounds again: the padded bound goes through the same (non-negative, linear)
     fold, plus the fold's own n-term fp32 sum and final rounding.
 
+The convolutions outside the engine follow the same scheme (Conv3x3Case, DeconvCase, Conv3dPackCase); their steps, read off the wrappers:
+  * Grouped 3x3 (hip/nn.py _GroupedConv3x3, csrc/gconv.hip): the kernels convert the fp32 master weight to the activation dtype while staging it, so
+    the operand is the weight rounded to that dtype; no bias, no activation, the gradient GEMMs read the incoming gradient itself.  K = 9 Cin / G
+    (the block-diagonal zeros of a super-group, and of the composed route's dense weight, add exact zeros).  The weight gradient is fp32 partials
+    summed by a second launch: one fp32 sum of B OH OW terms in some order.  A second backward adds a second stored dX to the first (autograd's
+    add, rounded to the activation dtype) and a second sum into the fp32 weight-gradient slot: accumulated().
+  * Dilated 3x3 (hip/bts.py dilated_conv3x3): sde_dilate_split / sde_dilate_merge copy elements (forward and, with their roles swapped, backward);
+    each of the d^2 sub-grids goes through the engine's 3x3 padding-1 layer, whose sums are the dilated convolution's term for term.  The fp64
+    dilated convolution is the reference and no rounding step is added.
+  * Transposed 3x3 stride 2 (hip/nn.py _ConvTranspose2d, csrc/deconv.hip): y = relu(sum + bias) with the bias read in fp32, K = 9 Cin + 1 for the
+    parity-split kernel and for the zero-insertion route (whose zero terms add nothing; that route stores the pre-activation and a second kernel
+    applies ReLU to the stored value: max(., 0) of a stored value is exact, so both routes round once).  Backward: sde_act_bwd_bias_sum forms
+    dz = g * [stored y > 0] and stores it in the activation dtype -- 0 or g itself, both representable, so that store is exact -- and sums dz in
+    fp32 for the bias gradient (K = B 2H 2W).  The step function is not Lipschitz: where the fp64 pre-activation lies within its own limit of
+    zero the sign of the computed one is not determined (`undecided`), dz may be 0 or g, an operand error of |g| that goes through
+    conv(|.|, |w|) like dz_err above; everywhere else the computed and the reference mask agree and dz = g exactly.  dX is the engine's stride-2
+    forward over dz (K = 9 Cout), dW its weight gradient with x in the role of the output gradient (K = B H W).
+  * Conv3d(1 -> 8) pack (hip/nn.py _Conv3dPack, csrc/conv3d.hip): weight and bias are read in fp32 (not rounded); the accumulator starts at the
+    bias and takes 27 fmaf (K = 27 + 1); dX sums 27 x 8 products; dW and dbias are per-thread, per-wave and per-workgroup fp32 sums and an fp64
+    column sum rounded to fp32 once (K = B D H W; with K in the hundreds of thousands that worst case exceeds the gradient itself and the
+    relative-L2 line of the test is the binding one -- tests/test_conv_bounds.py says where).
+
 SDE_BOUNDS_LOG=<file>: every assertion appends "<dtype> <name> <worst error / limit>" to that file (a record of how much of the bound a run
 used; the threshold is the bound itself).
 """
@@ -41,7 +63,7 @@ TINY = {torch.bfloat16: 2.0 ** -134, torch.float16: 2.0 ** -25, torch.float32: 2
 # unit roundoffs (2^-11 / 2^-8)
 L2_TOL = {torch.float32: 2e-5, torch.bfloat16: 1.5e-2, torch.float16: 1.5e-2 * 2.0 ** -3}
 DT_NAME = {torch.float32: "f32", torch.bfloat16: "bf16", torch.float16: "fp16"}
-ACT_NONE, ACT_ELU = 0, 1
+ACT_NONE, ACT_ELU, ACT_RELU = 0, 1, 2
 
 Bound = namedtuple("Bound", "ref lim")      # fp64 tensors of the result's shape
 
@@ -147,6 +169,122 @@ class ConvCase:
             if dz_err is not None:
                 err = err + dz_err.sum((0, 2, 3))
             out["dbias"] = stored(dz.sum((0, 2, 3)), err, torch.float32)
+        return out
+
+
+def accumulated(bound, n, dtype):
+    """n results, each within `bound`, added into one tensor stored in `dtype` (a second backward into an existing gradient): n times the reference and
+    the limit, and the rounding of the stored sum."""
+    return stored(n * bound.ref, n * bound.lim, dtype)
+
+
+class Conv3x3Case:
+    """y = conv2d(x, w, None, stride, padding=dilation, dilation, groups): the grouped 3x3 (groups > 1, stride 1 | 2) and the dilated 3x3 (dilation > 1)
+    operators, no bias, no activation.  x [B, Cin, H, W], w [Cout, Cin / groups, 3, 3]: fp32 CPU tensors holding storage-dtype values."""
+
+    def __init__(self, x, w, dtype, *, groups=1, stride=1, dilation=1):
+        self.dtype, self.groups, self.stride, self.dilation = dtype, groups, stride, dilation
+        self.x, self.w = x.double(), w.double()
+        self.taps = w.shape[2] * w.shape[3]
+        K = self.taps * w.shape[1]
+        self.y = stored(self._conv(self.x, self.w), (K + 3) * E32 * self._conv(self.x.abs(), self.w.abs()), dtype)
+
+    def _conv(self, x, w):
+        return F.conv2d(x, w, None, self.stride, self.dilation, self.dilation, self.groups)
+
+    def backward(self, gy):
+        """{"dX", "dW"} -> Bound for the gradient gy arriving at y (read by both gradient kernels as it is)."""
+        dz = gy.double()
+        Kd = self.taps * self.w.shape[0] // self.groups            # output channels of one group reach an input channel
+        Kw = dz.shape[0] * dz.shape[2] * dz.shape[3]
+        xs, ws = [tuple(self.x.shape)], [tuple(self.w.shape)]
+        out = {}
+        rp = _adjoint(lambda z: self._conv(z, self.w), xs, dz)[0]
+        out["dX"] = stored(rp, (Kd + 3) * E32 * _adjoint(lambda z: self._conv(z, self.w.abs()), xs, dz.abs())[0], self.dtype)
+        rw = _adjoint(lambda w0: self._conv(self.x, w0), ws, dz)[0]
+        out["dW"] = stored(rw, (Kw + 3) * E32 * _adjoint(lambda w0: self._conv(self.x.abs(), w0), ws, dz.abs())[0], torch.float32)
+        return out
+
+
+class DeconvCase:
+    """y = act(conv_transpose2d(x, w, b, stride 2, padding 1, output_padding 1)), act ACT_NONE | ACT_RELU.  x [B, Cin, H, W], w [Cin, Cout, 3, 3]: fp32 CPU
+    tensors holding storage-dtype values; b fp32 or None.  `undecided`: the elements whose ReLU mask the reference cannot decide (all False without
+    ReLU), `undecided_share` their fraction."""
+
+    def __init__(self, x, w, b, dtype, *, act=ACT_NONE):
+        assert act in (ACT_NONE, ACT_RELU) and tuple(w.shape[2:]) == (3, 3)
+        self.dtype, self.act = dtype, act
+        self.x, self.w, self.b = x.double(), w.double(), (b.double() if b is not None else None)
+        K = 9 * w.shape[0] + 1
+        pre = self._fwd(self.x, self.w, self.b)
+        err = (K + 3) * E32 * self._fwd(self.x.abs(), self.w.abs(), self.b.abs() if b is not None else None)
+        self.pre = stored(pre, err, dtype)
+        if act == ACT_RELU:
+            self.y = stored(F.relu(pre), err, dtype)                  # 1-Lipschitz
+            self.mask = (pre > 0).double()
+            self.undecided = pre.abs() <= self.pre.lim
+        else:
+            self.y, self.mask, self.undecided = self.pre, torch.ones_like(pre), torch.zeros_like(pre, dtype=torch.bool)
+        self.undecided_share = float(self.undecided.double().mean())
+
+    @staticmethod
+    def _fwd(x, w, b=None):
+        return F.conv_transpose2d(x, w, b, stride=2, padding=1, output_padding=1)
+
+    @staticmethod
+    def _adj(dz, w):
+        """the adjoint convolution Conv2d(Cout -> Cin, 3, stride 2, padding 1), whose OIHW weight is w as it stands"""
+        return F.conv2d(dz, w, None, 2, 1)
+
+    def backward(self, gy):
+        """{"dX", "dW", "dbias"} -> Bound."""
+        g = gy.double()
+        dz = g * self.mask
+        dz_err = g.abs() * self.undecided.double()                     # dz is 0 or g there; exact elsewhere
+        dz_mag = dz.abs() + dz_err
+        B, Cin, H, W = self.x.shape
+        Cout = self.w.shape[1]
+        out = {}
+        out["dX"] = stored(self._adj(dz, self.w), (9 * Cout + 3) * E32 * self._adj(dz_mag, self.w.abs()) + self._adj(dz_err, self.w.abs()), self.dtype)
+        ws = [tuple(self.w.shape)]
+        Kw = B * H * W
+        rw = _adjoint(lambda w0: self._fwd(self.x, w0), ws, dz)[0]
+        err = (Kw + 3) * E32 * _adjoint(lambda w0: self._fwd(self.x.abs(), w0), ws, dz_mag)[0] + _adjoint(lambda w0: self._fwd(self.x.abs(), w0), ws, dz_err)[0]
+        out["dW"] = stored(rw, err, torch.float32)
+        if self.b is not None:
+            Kb = B * 4 * H * W
+            out["dbias"] = stored(dz.sum((0, 2, 3)), (Kb + 3) * E32 * dz_mag.sum((0, 2, 3)) + dz_err.sum((0, 2, 3)), torch.float32)
+        return out
+
+
+class Conv3dPackCase:
+    """y = conv3d(x.unsqueeze(1), w, b, padding=1) viewed as [B, 8 D, H, W].  x [B, D, H, W] holds storage-dtype values; w [8, 1, 3, 3, 3] and b [8] are
+    read in fp32 and stay as they are."""
+
+    def __init__(self, x, w, b, dtype):
+        self.dtype = dtype
+        self.x, self.w, self.b = x.double(), w.double(), b.double()
+        self.F = w.shape[0]
+        self.y = stored(self._fwd(self.x, self.w, self.b), (27 + 1 + 3) * E32 * self._fwd(self.x.abs(), self.w.abs(), self.b.abs()), dtype)
+
+    @staticmethod
+    def _fwd(x, w, b=None):
+        B, D, H, W = x.shape
+        return F.conv3d(x.unsqueeze(1), w, b, padding=1).reshape(B, w.shape[0] * D, H, W)
+
+    def backward(self, gy):
+        """{"dX", "dW", "dbias"} -> Bound."""
+        dz = gy.double()
+        B, D, H, W = self.x.shape
+        xs, ws = [tuple(self.x.shape)], [tuple(self.w.shape)]
+        Kw = B * D * H * W
+        out = {}
+        rp = _adjoint(lambda z: self._fwd(z, self.w), xs, dz)[0]
+        out["dX"] = stored(rp, (27 * self.F + 3) * E32 * _adjoint(lambda z: self._fwd(z, self.w.abs()), xs, dz.abs())[0], self.dtype)
+        rw = _adjoint(lambda w0: self._fwd(self.x, w0), ws, dz)[0]
+        out["dW"] = stored(rw, (Kw + 3) * E32 * _adjoint(lambda w0: self._fwd(self.x.abs(), w0), ws, dz.abs())[0], torch.float32)
+        per_f = dz.reshape(B, self.F, D, H, W)
+        out["dbias"] = stored(per_f.sum((0, 2, 3, 4)), (Kw + 3) * E32 * per_f.abs().sum((0, 2, 3, 4)), torch.float32)
         return out
 
 

@@ -1,4 +1,5 @@
 """GPU: the BTS decoder's operators and BtsModel against float64 torch restatements and the reference's golden run (tests/golden/bts.npz)."""
+import functools
 import math
 import os
 
@@ -8,6 +9,7 @@ import torch
 import torch.nn.functional as F
 
 import bts_init
+import conv_bounds as CB
 
 pytestmark = pytest.mark.gpu
 dev = "cuda:0"
@@ -15,6 +17,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = np.load(os.path.join(ROOT, "tests", "golden", "bts.npz"))
 CASES = [(512, 2, 64, 128), (128, 2, 96, 320)]
 DT = {"fp32": torch.float32, "bf16": torch.bfloat16}
+REF_DT = dict(DT, fp16=torch.float16)       # the references also in fp16, for the CPU self-test of their bounds (tests/test_conv_bounds.py)
 
 
 def rel(a, b):
@@ -30,15 +33,15 @@ def nhwc(x, c_pad, dt):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("dtype", ["fp32", "bf16"])
-@pytest.mark.parametrize("d", [1, 3, 6, 12, 18, 24])
-@pytest.mark.parametrize("shape", [(2, 44, 88, 256, 128), (2, 5, 7, 37, 21)], ids=["44x88_256to128", "small_odd"])
-def test_dilated_conv_fwd_dgrad_wgrad(dtype, d, shape):
-    from simpledepthestimation_amd.hip import bts as HB
-    from simpledepthestimation_amd.hip import nn as HN
-    from simpledepthestimation_amd.layers.hip_modules import HipConv2d
+BOUNDED_DILATED = {(2, 5, 7, 37, 21), (2, 13, 19, 40, 24)}     # shapes whose fp64 adjoints take a fraction of a second on the CPU
+
+
+@functools.lru_cache(maxsize=None)
+def dilated_reference(dtype, d, shape):
+    """Operands (rounded to the storage type), the fp64 result and, for the small shapes, the per-element bounds of tests/conv_bounds.py: computed
+    once per case, never modified."""
     B, H, W, Cin, Cout = shape
-    dt = DT[dtype]
+    dt = REF_DT[dtype]
     g = torch.Generator().manual_seed(d * 7 + Cin)
     x = torch.randn(B, Cin, H, W, generator=g)
     w = torch.randn(Cout, Cin, 3, 3, generator=g) / math.sqrt(9 * Cin)
@@ -50,6 +53,22 @@ def test_dilated_conv_fwd_dgrad_wgrad(dtype, d, shape):
     wd = w.double().requires_grad_(True)
     yr = F.conv2d(xd, wd, padding=d, dilation=d)
     yr.backward(gy.double())
+    case = bw = None
+    if shape in BOUNDED_DILATED:
+        case = CB.Conv3x3Case(x, w, dt, dilation=d)
+        bw = case.backward(gy)
+    return dict(x=x, w=w, gy=gy, y=yr.detach(), dx=xd.grad, dw=wd.grad, case=case, bw=bw)
+
+
+def dilated_conv_case(dtype, d, shape):
+    from simpledepthestimation_amd.hip import bts as HB
+    from simpledepthestimation_amd.hip import nn as HN
+    from simpledepthestimation_amd.layers.hip_modules import HipConv2d
+    B, H, W, Cin, Cout = shape
+    dt = DT[dtype]
+    # (the large shape's reference is used once: not kept)
+    ref = dilated_reference(dtype, d, shape) if shape in BOUNDED_DILATED else dilated_reference.__wrapped__(dtype, d, shape)
+    x, w, gy = ref["x"], ref["w"], ref["gy"]
     conv = HipConv2d(Cin, Cout, 3, 1, 1, bias=False).to(dev)
     with torch.no_grad():
         conv.weight.copy_(w)
@@ -61,10 +80,30 @@ def test_dilated_conv_fwd_dgrad_wgrad(dtype, d, shape):
     torch.cuda.synchronize()
     tol = 2e-5 if dt == torch.float32 else 2e-2
     yo = y[..., :Cout].permute(0, 3, 1, 2)
-    assert rel(yo, yr.detach()) < tol
-    assert rel(xh.grad[..., :Cin].permute(0, 3, 1, 2), xd.grad) < tol
+    assert rel(yo, ref["y"]) < tol
+    assert rel(xh.grad[..., :Cin].permute(0, 3, 1, 2), ref["dx"]) < tol
     assert float(xh.grad[..., Cin:].abs().max() if xh.grad.shape[3] > Cin else 0) == 0.0
-    assert rel(conv.weight.grad, wd.grad) < tol
+    assert rel(conv.weight.grad, ref["dw"]) < tol
+    if ref["case"] is not None:       # every element against its a-priori limit (split and merge move data: the dilated convolution is the reference)
+        CB.assert_within(yo.detach().float().cpu(), ref["case"].y, dt, f"{dtype} dilated y", l2_tol=float("inf"))
+        CB.assert_within(xh.grad[..., :Cin].permute(0, 3, 1, 2).float().cpu(), ref["bw"]["dX"], dt, f"{dtype} dilated dX", l2_tol=float("inf"))
+        CB.assert_within(conv.weight.grad.cpu(), ref["bw"]["dW"], torch.float32, f"{dtype} dilated dW", l2_tol=float("inf"))
+
+
+@pytest.mark.parametrize("dtype", ["fp32", "bf16"])
+@pytest.mark.parametrize("d", [1, 3, 6, 12, 18, 24])
+@pytest.mark.parametrize("shape", [(2, 44, 88, 256, 128), (2, 5, 7, 37, 21)], ids=["44x88_256to128", "small_odd"])
+def test_dilated_conv_fwd_dgrad_wgrad(dtype, d, shape):
+    """small_odd: also element by element (tests/conv_bounds.py).  The 44 x 88 shape keeps the whole-tensor assertion alone: its fp64 adjoints take
+    too long on the CPU."""
+    dilated_conv_case(dtype, d, shape)
+
+
+@pytest.mark.parametrize("dtype", ["fp32", "bf16"])
+@pytest.mark.parametrize("d", [3, 6])
+def test_dilated_conv_unequal_subgrids(dtype, d):
+    """d smaller than H and W and dividing neither: sub-grids of unequal size, the last row and column of some of them missing."""
+    dilated_conv_case(dtype, d, (2, 13, 19, 40, 24))
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------

@@ -5,7 +5,9 @@ Forward and both gradients are compared with
   * F.conv2d(groups=G) on the CPU in fp32 from the operands rounded to the storage type, as tests/test_gpu_deconv.py does (relative L2: 6e-3 for y and
     1.5 x that for gradients in bf16 = 16-bit output rounding; 1e-3 in fp32), and
   * the composed route -- a dense block-diagonal weight through hip.nn.conv2d -- on the same device buffers (hip.nn.GCONV_DIRECT = False): fp32
-    accumulation both, so at most one 16-bit ulp apart (close16 of that file); in fp32 2e-5 of the maximum.
+    accumulation both, so at most one 16-bit ulp apart (close16 of that file); in fp32 2e-5 of the maximum, and
+  * element by element, an fp64 reference with the a-priori limits of tests/conv_bounds.py (Conv3x3Case): y, dX and dW of both routes, and the two
+    routes against each other.
 """
 import functools
 import math
@@ -14,6 +16,8 @@ import pytest
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
+
+import conv_bounds as CB
 
 pytestmark = pytest.mark.gpu
 dev = "cuda"
@@ -29,6 +33,7 @@ CASES = {  # name: (B, H, W, C, G, stride)
     "many_pixel_tiles": (2, 33, 47, 32, 8, 1),        # weight-gradient partials of several workgroups, several statistics rows
 }
 DT = {"fp32": torch.float32, "bf16": torch.bfloat16}
+REF_DT = dict(DT, fp16=torch.float16)       # the references also in fp16, for the CPU self-test of their bounds (tests/test_conv_bounds.py)
 
 
 def close16(a, b, dt, what):
@@ -48,7 +53,7 @@ def rel(a, b):
 def reference(name, dtype):
     """Operands (rounded to the storage type) and the CPU fp32 result: computed once per case, shared by the tests, never modified."""
     B, H, W, C, G, stride = CASES[name]
-    dt = DT[dtype]
+    dt = REF_DT[dtype]
     g = torch.Generator().manual_seed(len(name) * 13 + B)
     x = torch.randn(B, C, H, W, generator=g).to(dt).float()
     w = torch.randn(C, C // G, 3, 3, generator=g) / math.sqrt(C // G * 2.25)
@@ -59,6 +64,19 @@ def reference(name, dtype):
     gy = torch.randn(y.shape, generator=g).to(dt).float()
     y.backward(gy)
     return dict(x=x, w=w, gy=gy, y=y.detach(), dx=xr.grad, dw=wr.grad)
+
+
+@functools.lru_cache(maxsize=None)
+def bounds(name, dtype):
+    """(Conv3x3Case, its gradient bounds) of reference(name, dtype): fp64, computed once per case."""
+    B, H, W, C, G, stride = CASES[name]
+    ref = reference(name, dtype)
+    case = CB.Conv3x3Case(ref["x"], ref["w"], REF_DT[dtype], groups=G, stride=stride)
+    return case, case.backward(ref["gy"])
+
+
+def nchw(t):
+    return t.float().permute(0, 3, 1, 2)
 
 
 def nhwc(t, dt):
@@ -108,6 +126,15 @@ def test_grouped_conv3x3(name, dtype):
     assert errs["y"] < lim, f"y vs fp32 CPU: relative L2 error {errs['y']:.3e}"
     for k in ("dx", "dW"):
         assert errs[k] < glim, f"{k} vs fp32 CPU: relative L2 error {errs[k]:.3e}"
+    # every element of both routes against the fp64 reference, and the two routes against each other (the relative-L2 lines are the ones above)
+    case, bw = bounds(name, dtype)
+    for route, out in (("kernels", on), ("composed", off)):
+        CB.assert_within(nchw(out["y"]), case.y, dt, f"{dtype} gconv y ({route})", l2_tol=float("inf"))
+        CB.assert_within(nchw(out["dx"]), bw["dX"], dt, f"{dtype} gconv dX ({route})", l2_tol=float("inf"))
+        CB.assert_within(out["dw"], bw["dW"], torch.float32, f"{dtype} gconv dW ({route})", l2_tol=float("inf"))
+    CB.assert_two_kernels(nchw(on["y"]), nchw(off["y"]), case.y, dt, f"{dtype} gconv y (kernels vs composed)")
+    CB.assert_two_kernels(nchw(on["dx"]), nchw(off["dx"]), bw["dX"], dt, f"{dtype} gconv dX (kernels vs composed)")
+    CB.assert_two_kernels(on["dw"], off["dw"], bw["dW"], torch.float32, f"{dtype} gconv dW (kernels vs composed)")
     # the grouped kernels against the dense block-diagonal route on the same buffers
     if dt == torch.bfloat16:
         close16(y, off["y"], dt, "y (grouped kernels vs dense block-diagonal weight)")
@@ -131,6 +158,12 @@ def test_second_backward_accumulates_into_existing_grads(name, ohwi, dtype):
     assert rel(two["dw"], 2 * ref["dw"]) < glim
     assert rel(two["dx"].float().permute(0, 3, 1, 2), 2 * ref["dx"]) < glim
     assert rel(two["y"].float().permute(0, 3, 1, 2), ref["y"]) < (6e-3 if dt == torch.bfloat16 else 1e-3)
+    # element by element: two gradients, each within its bound, and the rounding of their stored sum (dX: autograd's add in the activation dtype; dW: the
+    # reduce launch's add into the fp32 slot)
+    case, bw = bounds(name, dtype)
+    CB.assert_within(nchw(two["y"]), case.y, dt, f"{dtype} gconv y (second backward)", l2_tol=float("inf"))
+    CB.assert_within(nchw(two["dx"]), CB.accumulated(bw["dX"], 2, dt), dt, f"{dtype} gconv dX (second backward)", l2_tol=float("inf"))
+    CB.assert_within(two["dw"], CB.accumulated(bw["dW"], 2, torch.float32), torch.float32, f"{dtype} gconv dW (second backward)", l2_tol=float("inf"))
 
 
 @pytest.mark.parametrize("dtype", ["fp32", "bf16"])

@@ -3,6 +3,7 @@
 fp32 mode is held to ~1e-5 (f32 MFMA is an exact fmaf chain; only summation order differs); bf16 mode is checked against
 an fp32 reference evaluated on the bf16-rounded operands with a tolerance that reflects bf16 output rounding (2^-8 rel).
 """
+import functools
 import math
 
 import pytest
@@ -343,33 +344,43 @@ def test_group_norm_elu(NN, dtype, C, H, W):
     check(bd.grad.cpu(), br.grad, dtype, "gn-elu dbeta", 5e-5, 3e-2)
 
 
-@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
-@pytest.mark.parametrize("B,D,H,W", [(2, 16, 5, 7), (1, 64, 9, 12), (2, 256, 3, 4),
-                                     (2, 64, 40, 36), (1, 192, 47, 50), (3, 128, 26, 33)])     # more than 64 channel groups per wave boundary / several waves per pixel row
-def test_conv3d_pack(NN, dtype, B, D, H, W):
-    """layers01.py:L223-298: x.unsqueeze(1) -> Conv3d(1, 8, 3, padding=1) -> view(b, 8*D, h, w), forward and all three gradients."""
+@functools.lru_cache(maxsize=None)
+def conv3d_reference(dtype, B, D, H, W):
+    """Operands (rounded to the storage type), the CPU fp32 result and the per-element bounds from fp64 (conv_bounds.Conv3dPackCase): computed once per
+    case, never modified."""
     g = torch.Generator().manual_seed(D + H)
     x = torch.randn(B, D, H, W, generator=g)
     w = torch.randn(8, 1, 3, 3, 3, generator=g) * 0.3
     bias = torch.randn(8, generator=g) * 0.2
-    if dtype == torch.bfloat16:
-        x = x.bfloat16().float()
+    x = CB.rounded(x, dtype)
     xr, wr, br = (t.clone().requires_grad_(True) for t in (x, w, bias))
     o = F.conv3d(xr.unsqueeze(1), wr, br, padding=1).reshape(B, 8 * D, H, W)
-    go = torch.randn(o.shape, generator=g)
-    if dtype == torch.bfloat16:
-        go = go.bfloat16().float()
+    go = CB.rounded(torch.randn(o.shape, generator=g), dtype)
     o.backward(go)
+    case = CB.Conv3dPackCase(x, w, bias, dtype)
+    return dict(x=x, w=w, bias=bias, go=go, o=o.detach(), dx=xr.grad, dw=wr.grad, db=br.grad, case=case, bw=case.backward(go))
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.float16])
+@pytest.mark.parametrize("B,D,H,W", [(2, 16, 5, 7), (1, 64, 9, 12), (2, 256, 3, 4),
+                                     (2, 64, 40, 36), (1, 192, 47, 50), (3, 128, 26, 33)])     # more than 64 channel groups per wave boundary / several waves per pixel row
+def test_conv3d_pack(NN, dtype, B, D, H, W):
+    """layers01.py:L223-298: x.unsqueeze(1) -> Conv3d(1, 8, 3, padding=1) -> view(b, 8*D, h, w), forward and all three gradients, in the three
+    activation dtypes the kernels are instantiated for (PackNet trains in fp16)."""
+    ref = conv3d_reference(dtype, B, D, H, W)
+    case, bw = ref["case"], ref["bw"]
     V = 4 if dtype == torch.float32 else 8
-    xd = nhwc(x, dtype, V).requires_grad_(True)
-    wd, bd = (t.clone().to(dev).requires_grad_(True) for t in (w, bias))
+    xd = nhwc(ref["x"], dtype, V).requires_grad_(True)
+    wd, bd = (t.clone().to(dev).requires_grad_(True) for t in (ref["w"], ref["bias"]))
     out = NN.conv3d_pack(xd, wd, bd)
-    assert out.shape == (B, H, W, 8 * D)
-    check(nchw(out, 8 * D), o.detach(), dtype, "conv3d out")
-    out.backward(nhwc(go, dtype, V))
-    check(nchw(xd.grad, D), xr.grad, dtype, "conv3d dx")
-    check(wd.grad.cpu(), wr.grad, dtype, "conv3d dw", 2e-5, 2e-5)       # gradients are accumulated in fp32 from the same rounded operands
-    check(bd.grad.cpu(), br.grad, dtype, "conv3d dbias", 2e-5, 2e-5)
+    assert out.shape == (B, H, W, 8 * D) and out.dtype == dtype
+    tag = CB.DT_NAME[dtype]
+    check(nchw(out, 8 * D), ref["o"], dtype, f"{tag} conv3d out", bound=case.y)
+    out.backward(nhwc(ref["go"], dtype, V))
+    check(nchw(xd.grad, D), ref["dx"], dtype, f"{tag} conv3d dx", bound=bw["dX"])
+    # gradients are accumulated and stored in fp32 from the same rounded operands, whatever the activation dtype
+    check(wd.grad.cpu(), ref["dw"], torch.float32, f"{tag} conv3d dw", 2e-5, 2e-5, bound=bw["dW"])
+    check(bd.grad.cpu(), ref["db"], torch.float32, f"{tag} conv3d dbias", 2e-5, 2e-5, bound=bw["dbias"])
 
 
 @pytest.mark.parametrize("layout", ["oihw", "ohwi"])
