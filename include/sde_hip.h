@@ -636,6 +636,20 @@ int sde_depth_metrics(const float* pred, int ph, int pw, const float* gt, int gh
                       sde_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Presentation (csrc/present.hip; binding in hip/present.py): N network outputs pred [N,ph,pw] fp32 of ONE source size -> what tools/demo.py
+ * shows and saves, in one launch.  ymap [H] / xmap [W] are the maps of sde_depth_metrics (restored pixel -> prediction pixel, -1 = outside:
+ * value 0); the kernel indexes pred with whatever they hold, so the caller validates them ([-1, ph) / [-1, pw)).  For every restored pixel d:
+ *   depth_full [N,H,W] fp32 = d                                   (optional, NULL skips it: the postprocess.backward() chain of the reference);
+ *   depth_u16  [N,H,W] uint16 = (uint16)(d * 255), fp32 product truncated, clamped to [0, 65535], NaN -> 0   (optional: write_depth's format);
+ *   colour = lut[min(255, (int)(powf(d, gamma) / powf(vmax, gamma) * 256))], NaN and d < 0 as d = 0, lut [256][3] uint8 (demo.py:L77).
+ * canvas [N][2H][W][3] uint8 with frame [N,H,W,3] uint8 (RGB) non-NULL: rows [0, H) the frame, rows [H, 2H) the colours (demo.py:L100-104);
+ * frame == NULL: canvas [N][H][W][3] holds the colours only.  No pointer needs more than its element's alignment.
+ * Refused before any launch: N, H, W, ph, pw <= 0, vmax <= 0, gamma <= 0, NULL pred / maps / lut / canvas.  No host synchronisation, no
+ * allocation, no atomics. */
+int sde_depth_present(const float* pred, int N, int ph, int pw, const int* ymap, const int* xmap, int H, int W, float vmax, float gamma,
+                      const uint8_t* lut, const uint8_t* frame, float* depth_full, uint16_t* depth_u16, uint8_t* canvas, sde_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * MotionLearning loss stack (csrc/motion_loss.hip; autograd wrappers in hip/motion_loss.py).  fp32, planar NCHW, no host synchronisation.
  *
  * sde_view_synthesis_pp: detectron2/geometry/camera.py:L166-202 with a per-pixel translation t [B,3,H,W] and a 3x3 rotation R [B,3,3]; the

@@ -1,0 +1,357 @@
+"""DepthPredictor: a trained model on raw camera frames (what the reference's tools/demo.py:L42-104 does per frame), without host round trips.
+
+The reference loads a frame, runs the CPU preprocess chain, the model, copies the prediction to the host, undoes the chain with numpy and renders
+the picture with matplotlib.  Here the uint8 frame is uploaded from pinned memory and everything after that is device work on one stream:
+
+    sde_image_prep_u8     the forward chain (KBCrop / CropTopTo / Resize + ToTensor) as two tap tables: a crop is an offset added to the taps,
+                          an axis that is not resized gets identity taps (i, i, 2048, 0) -- the fixed-point rule then returns the source byte;
+    model(batch)          eval mode, torch.no_grad();
+    sde_depth_present     the backward chain as the two index maps of evaluation.depth_evaluation.backward_maps, the restored depth, the 16-bit
+                          depth and the coloured, frame-stacked picture in one launch (hip/present.py).
+
+The three stages are captured once per (source size, batch size) into a graph and replayed; `stream` adds a copy stream that uploads the next
+frame and downloads the previous picture while the current frame is computed."""
+import numpy as np
+import torch
+
+from ..data.device_aug import DeviceImageAug
+from ..data.preprocess.augmentation import _linear_coefs
+from ..evaluation.depth_evaluation import backward_maps
+from ..hip import present as HP
+
+IMAGE_STEPS = ("KBCrop", "CropTopTo", "Resize")       # the steps with a backward(): DatasetEvaluator.preprocess_chain keeps the same three
+KB_H, KB_W = 352, 1216
+
+
+def _step_name(s):
+    return s if isinstance(s, str) else (s["NAME"] if isinstance(s, dict) else s.NAME)
+
+
+def chain_steps(cfg, chain=None):
+    """[(name, step config)] of the predictor's chain.  chain: step names (the form of DatasetEvaluator.preprocess_chain) or step dicts; None: the
+    image steps of cfg.DATASETS.TEST.PREPROCESS, ("KBCrop",) when it has none (demo.py:L43).  A name takes its sizes from the config's step."""
+    configured = []
+    if cfg is not None and "DATASETS" in cfg and "TEST" in cfg.DATASETS:
+        configured = [dict(s) for s in cfg.DATASETS.TEST.get("PREPROCESS", [])]
+    if chain is None:
+        chain = [s for s in configured if _step_name(s) in IMAGE_STEPS] or ["KBCrop"]
+    steps = []
+    for s in chain:
+        name = _step_name(s)
+        if name not in IMAGE_STEPS:
+            raise ValueError(f"DepthPredictor: chain step {name!r} is not one of {IMAGE_STEPS}")
+        if isinstance(s, str):
+            s = next((c for c in configured if c["NAME"] == name), {"NAME": name})
+        steps.append((name, dict(s)))
+    return steps
+
+
+def _identity_taps(n):
+    i = np.arange(n, dtype=np.int64)
+    return np.stack([i, i, np.full(n, 2048, np.int64), np.zeros(n, np.int64)], 1)
+
+
+def _resize_taps(src, dst):
+    return _identity_taps(src) if src == dst else np.stack(_linear_coefs(src, dst), 1)
+
+
+class SizePlan:
+    """Everything the predictor derives from one source size: the tap tables of the forward chain (int32 [w][4] / [h][4], taps in source
+    coordinates), the network input size, the metadata the chain's steps record, and how they move the intrinsics."""
+
+    def __init__(self, steps, Hs, Ws):
+        self.Hs, self.Ws, self.chain = int(Hs), int(Ws), tuple(n for n, _ in steps)
+        self.meta, self.k_ops = {}, []
+        h, w, oy, ox, ytab, xtab = self.Hs, self.Ws, 0, 0, None, None
+
+        def crop(y0, nh, x0, nw):
+            nonlocal h, w, oy, ox, ytab, xtab
+            if y0 < 0 or x0 < 0 or y0 + nh > h or x0 + nw > w:
+                raise ValueError(f"DepthPredictor: a {nh} x {nw} crop does not fit the {h} x {w} image ({self.Hs} x {self.Ws} frames, chain {self.chain})")
+            if ytab is None:
+                oy, ox = oy + y0, ox + x0                           # before the resize: an offset, folded into the taps below
+            else:
+                ytab, xtab = ytab[y0:y0 + nh], xtab[x0:x0 + nw]      # after it: the rows and columns of the tables
+            h, w = nh, nw
+
+        for name, cfg in steps:
+            if name == "KBCrop":
+                x0, y0 = int((w - KB_W) / 2), int(h - KB_H)
+                self.meta.update(kb_y_start=y0, kb_x_start=x0, h_before_kb_crop=h, w_before_kb_crop=w)
+                crop(y0, KB_H, x0, KB_W)
+                self.k_ops.append(("shift", x0, y0))
+            elif name == "CropTopTo":
+                y0 = int(h - int(cfg["IMG_H"]))
+                self.meta.update(crop_y_start=y0, h_before_crop=h, w_before_crop=w)
+                crop(y0, h - y0, 0, w)
+                self.k_ops.append(("shift", 0, y0))
+            else:
+                if ytab is not None:
+                    raise ValueError("DepthPredictor: two Resize steps do not compose into one 2-tap table")
+                th, tw = int(cfg["IMG_H"]), int(cfg["IMG_W"])
+                self.meta.update(h_before_resize=h, w_before_resize=w)
+                ytab, xtab = _resize_taps(h, th), _resize_taps(w, tw)
+                ytab[:, :2] += oy
+                xtab[:, :2] += ox
+                self.k_ops.append(("scale", tw / w, th / h))
+                h, w = th, tw
+        if ytab is None:
+            ytab, xtab = _identity_taps(h), _identity_taps(w)
+            ytab[:, :2] += oy
+            xtab[:, :2] += ox
+        self.h, self.w = h, w
+        self.ytab, self.xtab = np.ascontiguousarray(ytab, dtype=np.int32), np.ascontiguousarray(xtab, dtype=np.int32)
+        self._maps = {}
+
+    def maps(self, pred_hw):
+        """(ymap [Hs], xmap [Ws]) int32 host arrays for a network output of size pred_hw: backward_maps of the recorded metadata."""
+        pred_hw = (int(pred_hw[0]), int(pred_hw[1]))
+        if pred_hw not in self._maps:
+            rows, cols = backward_maps(pred_hw, self.meta, self.chain)
+            if (rows.size, cols.size) != (self.Hs, self.Ws):
+                raise ValueError(f"DepthPredictor: chain {self.chain} restores {rows.size} x {cols.size}, the frames are {self.Hs} x {self.Ws}")
+            self._maps[pred_hw] = (np.ascontiguousarray(rows, dtype=np.int32), np.ascontiguousarray(cols, dtype=np.int32))
+        return self._maps[pred_hw]
+
+    def intrinsics(self, K):
+        """K [3,3] or [N,3,3] as the forward steps leave it (KBCrop / CropTopTo move the principal point, Resize scales), in K's own dtype."""
+        K = np.array(K.cpu().numpy() if torch.is_tensor(K) else K, copy=True)
+        if not np.issubdtype(K.dtype, np.floating):
+            K = K.astype(np.float64)
+        for op, a, b in self.k_ops:
+            if op == "shift":
+                K[..., 0, 2] -= a
+                K[..., 1, 2] -= b
+            else:
+                K[..., 0, 0] *= a; K[..., 0, 2] *= a
+                K[..., 1, 1] *= b; K[..., 1, 2] *= b
+        return K
+
+
+class _Slot:
+    """One set of pinned and device buffers for N frames of one size, and the graph that runs on them."""
+
+    def __init__(self, N, Hs, Ws, device):
+        self.frames_pin = torch.empty((N, Hs, Ws, 3), dtype=torch.uint8).pin_memory()
+        self.frames = torch.empty((N, Hs, Ws, 3), dtype=torch.uint8, device=device)
+        self.K = None                # [N,3,3] float32 device tensor once intrinsics are used
+        self.K_host = None
+        self.graphs = {}             # (present, frame_in_canvas, want_u16, has K) -> (graph, outputs)
+        self.host = {}               # name -> pinned host tensor of the downloaded output
+        self.uploaded = torch.cuda.Event()
+        self.computed = torch.cuda.Event()
+        self.downloaded = torch.cuda.Event()
+        self.out = None
+
+
+class DepthPredictor:
+    def __init__(self, cfg, model=None, chain=None, device="cuda", use_graph=None, vmax=None, gamma=0.8):
+        self.cfg = cfg
+        self.device = torch.device(device)
+        if self.device.type == "cuda" and self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        if model is None:
+            from ..checkpoint.checkpoint import DetectionCheckpointer
+            from ..modeling import build_model
+            model = build_model(cfg)
+            if cfg.MODEL.WEIGHTS:
+                DetectionCheckpointer(model).load(cfg.MODEL.WEIGHTS)
+        self.model = model.to(self.device).eval()
+        self.steps = chain_steps(cfg, chain)
+        self.vmax = float(cfg.MODEL.MAX_DEPTH if vmax is None else vmax)
+        self.gamma = float(gamma)
+        if not (self.vmax > 0 and self.gamma > 0):
+            raise ValueError(f"DepthPredictor: vmax and gamma must be positive ({self.vmax}, {self.gamma})")
+        self.use_graph = (self.device.type == "cuda") if use_graph is None else bool(use_graph)
+        self._aug = DeviceImageAug(self.device)
+        self._plans, self._dev_maps, self._params, self._slots = {}, {}, {}, {}
+        self._copy_stream = None
+
+    # ---- per-size tables ------------------------------------------------------------------------------------------------------------------
+    def plan(self, Hs, Ws):
+        key = (int(Hs), int(Ws))
+        if key not in self._plans:
+            self._plans[key] = SizePlan(self.steps, *key)
+        return self._plans[key]
+
+    def _maps_on_device(self, plan, pred_hw):
+        key = (plan.Hs, plan.Ws, int(pred_hw[0]), int(pred_hw[1]))
+        if key not in self._dev_maps:
+            self._dev_maps[key] = HP.device_maps(*plan.maps(pred_hw), key[2], key[3], self.device)       # validated on the host, once
+        return self._dev_maps[key]
+
+    def _no_jitter(self, N):
+        if N not in self._params:
+            p = torch.tensor([1.0, 1.0, 1.0, 0.0, -1.0, -1.0, -1.0, -1.0], dtype=torch.float32).repeat(N, 1)
+            self._params[N] = p.to(self.device)
+        return self._params[N]
+
+    # ---- the device chain -----------------------------------------------------------------------------------------------------------------
+    def _chain(self, plan, frames, K, present, frame_in_canvas, want_u16):
+        """frames: uint8 [N,Hs,Ws,3] on the device, K: [N,3,3] float32 on the device or None.  Everything on the current stream, nothing synchronises
+        once the tables of this size are on the device (the first call of a size puts them there)."""
+        N = frames.shape[0]
+        img, _ = self._aug.prep(frames, self._no_jitter(N), plan.h, plan.w, tabs=(plan.xtab, plan.ytab))
+        batch = {"img": img}
+        if K is not None:
+            batch["intrinsics"] = K
+        with torch.no_grad():
+            pred = self.model(batch)["depth_pred"]
+        pred = pred.detach().float()
+        if pred.dim() == 4:
+            pred = pred[:, 0]
+        pred = pred.contiguous()
+        out = {"depth_net": pred, "depth": None, "canvas": None, "depth_u16": None}
+        if present:
+            ymap, xmap = self._maps_on_device(plan, pred.shape[-2:])
+            out["canvas"], out["depth"], out["depth_u16"] = HP.depth_present(pred, ymap, xmap, self.vmax, self.gamma, frame=frames if frame_in_canvas else None,
+                                                                             want_depth=True, want_u16=want_u16)
+        return out
+
+    def _slot(self, N, plan, i=0):
+        key = (N, plan.Hs, plan.Ws, i)
+        if key not in self._slots:
+            if len(self._slots) >= 16:          # a handful of source sizes per dataset: anything more is a leak, start over
+                torch.cuda.synchronize(self.device)
+                self._slots.clear()
+            self._slots[key] = _Slot(N, plan.Hs, plan.Ws, self.device)
+        return self._slots[key]
+
+    def _set_intrinsics(self, slot, plan, intrinsics, N):
+        if intrinsics is None:
+            return None
+        K = np.asarray(plan.intrinsics(intrinsics), dtype=np.float32)
+        K = np.array(np.broadcast_to(K, (N, 3, 3)))          # a copy: broadcast views are read-only
+        if slot.K is None:
+            slot.K = torch.empty((N, 3, 3), dtype=torch.float32, device=self.device)
+        if slot.K_host is None or not np.array_equal(slot.K_host, K):
+            slot.K.copy_(torch.from_numpy(K))
+            slot.K_host = K
+        return slot.K
+
+    def _run(self, slot, plan, K, flags):
+        """The chain on the slot's buffers, on the current stream: eager, or the slot's graph (captured at first use, after one eager run)."""
+        if not self.use_graph:
+            return self._chain(plan, slot.frames, K, *flags)
+        key = flags + (K is not None,)
+        if key not in slot.graphs:
+            cur = torch.cuda.current_stream()
+            side = torch.cuda.Stream(device=self.device)
+            side.wait_stream(cur)
+            with torch.cuda.stream(side):           # tables, caches and the allocator's blocks come into being here, outside the capture
+                self._chain(plan, slot.frames, K, *flags)
+            cur.wait_stream(side)
+            torch.cuda.synchronize(self.device)
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph, capture_error_mode="thread_local"):
+                out = self._chain(plan, slot.frames, K, *flags)
+            slot.graphs[key] = (graph, out)
+        graph, out = slot.graphs[key]
+        graph.replay()
+        return out
+
+    @staticmethod
+    def _as_frames(frames):
+        """One frame or N of one size -> (uint8 [N,H,W,3] tensor, host or device; whether a single frame came in)."""
+        if isinstance(frames, (list, tuple)):
+            frames = np.stack([f.cpu().numpy() if torch.is_tensor(f) else np.asarray(f) for f in frames], 0)
+        t = frames if torch.is_tensor(frames) else torch.from_numpy(np.ascontiguousarray(frames))
+        single = t.dim() == 3
+        if single:
+            t = t[None]
+        if t.dtype != torch.uint8 or t.dim() != 4 or t.shape[3] != 3:
+            raise ValueError(f"DepthPredictor: frames must be uint8 [H,W,3] or [N,H,W,3] RGB, got {t.dtype} {tuple(t.shape)}")
+        return t.contiguous(), single
+
+    def predict(self, frames, intrinsics=None, present=True, frame_in_canvas=True, want_u16=False):
+        """frames: one uint8 [H,W,3] RGB array / tensor, or N of one size.  Returns a dict of device tensors: `depth` [N,H,W] (the prediction restored
+        to the frame's size; None with present=False), `depth_net` [N,h,w] (the network output), `canvas` [N,2H or H,W,3] uint8, `depth_u16` with
+        want_u16 (int16 tensor holding write_depth's uint16 bits).  A single frame keeps the leading 1.  No host synchronisation after the first
+        call of a size."""
+        t, _ = self._as_frames(frames)
+        N, Hs, Ws, _ = t.shape
+        plan = self.plan(Hs, Ws)
+        slot = self._slot(N, plan)
+        flags = (bool(present), bool(frame_in_canvas), bool(want_u16))
+        with torch.cuda.device(self.device):
+            if t.is_cuda:
+                slot.frames.copy_(t)
+            else:
+                slot.uploaded.synchronize()              # the pinned buffer's previous upload has left it
+                slot.frames_pin.copy_(t)
+                slot.frames.copy_(slot.frames_pin, non_blocking=True)
+                slot.uploaded.record()
+            K = self._set_intrinsics(slot, plan, intrinsics, N)
+            out = self._run(slot, plan, K, flags)
+            # the slot's tensors are written again by the next call: hand out copies
+            return {k: (v.clone() if v is not None else None) for k, v in out.items()}
+
+    # ---- streaming ------------------------------------------------------------------------------------------------------------------------
+    def _download(self, slot, names):
+        """Enqueue, on the copy stream, the device -> pinned host copies of the slot's outputs once its compute has finished."""
+        cs = self._copy_stream
+        cs.wait_event(slot.computed)
+        with torch.cuda.stream(cs):
+            for k in names:
+                v = slot.out[k]
+                if v is None:
+                    continue
+                h = slot.host.get(k)
+                if h is None or h.shape != v.shape or h.dtype != v.dtype:
+                    h = slot.host[k] = torch.empty(v.shape, dtype=v.dtype).pin_memory()
+                h.copy_(v, non_blocking=True)
+            slot.downloaded.record(cs)
+
+    def _result(self, slot, names):
+        slot.downloaded.synchronize()
+        res = {k: slot.host[k].numpy()[0] for k in names if slot.out[k] is not None}
+        if "depth_u16" in res:
+            res["depth_u16"] = res["depth_u16"].view(np.uint16)
+        return res
+
+    def stream(self, frames_iter, intrinsics=None, present=True, frame_in_canvas=True, want_u16=False):
+        """Generator over host frames (uint8 [H,W,3] RGB, one at a time): yields, in order, a dict of host arrays per frame -- `depth` [H,W] fp32,
+        `canvas` [2H or H,W,3] uint8, `depth_u16` with want_u16; with present=False only `depth_net` [h,w].  The arrays are views of pinned buffers and stay valid until the next
+        iteration.  Two slots of pinned and device buffers: while frame i is computed on the current stream, the copy stream uploads frame i+1 and
+        downloads the outputs of frame i-1; result i-1 is yielded once frame i is enqueued.  A frame of another size drains the slots and switches
+        tables.  No threads."""
+        if self._copy_stream is None:
+            self._copy_stream = torch.cuda.Stream(device=self.device)
+        cs = self._copy_stream
+        flags = (bool(present), bool(frame_in_canvas), bool(want_u16))
+        names = [k for k, on in (("depth", present), ("canvas", present), ("depth_u16", present and want_u16), ("depth_net", not present)) if on]
+        pending, size, i = None, None, 0
+        with torch.cuda.device(self.device):
+            cur = torch.cuda.current_stream()
+            for frame in frames_iter:
+                t, _ = self._as_frames(frame)
+                if t.is_cuda or t.shape[0] != 1:
+                    raise ValueError("DepthPredictor.stream takes one host frame [H,W,3] per item")
+                if size is not None and tuple(t.shape) != size and pending is not None:
+                    self._download(pending, names)                      # another size: drain what is in flight, then switch tables
+                    yield self._result(pending, names)
+                    pending = None
+                size = tuple(t.shape)
+                plan = self.plan(size[1], size[2])
+                slot = self._slot(1, plan, i % 2)
+                i += 1
+                # upload frame i: its pinned buffer was last read by the upload of frame i-2 and its device buffer by the compute of frame i-2,
+                # whose result has been yielded -- both are over
+                slot.frames_pin.copy_(t)
+                cs.wait_event(slot.computed)
+                with torch.cuda.stream(cs):
+                    slot.frames.copy_(slot.frames_pin, non_blocking=True)
+                    slot.uploaded.record(cs)
+                if pending is not None:
+                    self._download(pending, names)                      # behind the upload on the copy stream, beside this frame's compute
+                K = self._set_intrinsics(slot, plan, intrinsics, 1)
+                cur.wait_event(slot.uploaded)
+                cur.wait_event(slot.downloaded)                         # the slot's outputs of frame i-2 have left the device
+                slot.out = self._run(slot, plan, K, flags)
+                slot.computed.record(cur)
+                if pending is not None:
+                    yield self._result(pending, names)
+                pending = slot
+            if pending is not None:
+                self._download(pending, names)
+                yield self._result(pending, names)

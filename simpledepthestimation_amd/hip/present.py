@@ -1,0 +1,105 @@
+"""ctypes binding of sde_depth_present (include/sde_hip.h, csrc/present.hip): network outputs -> restored depth, 16-bit depth and the coloured
+(optionally frame-stacked) picture of tools/demo.py, one launch per batch."""
+from ctypes import c_int, c_void_p
+
+import numpy as np
+import torch
+
+from . import lib as L
+
+_P, _I, _F = c_void_p, c_int, L.c_float
+L.register_protos({
+    "sde_depth_present": ([_P, _I, _I, _I, _P, _P, _I, _I, _F, _F, _P, _P, _P, _P, _P, _P], c_int),
+})
+
+_checked = {}        # (ymap.data_ptr, xmap.data_ptr, ...) -> the pair itself (kept alive, so the pointers cannot be handed out again)
+_luts = {}
+
+
+def check_maps(ymap, xmap, ph, pw, H=None, W=None):
+    """Host-side validation of one (ymap, xmap) pair, numpy arrays or host tensors: int32, lengths H / W when given, every entry in [-1, ph) /
+    [-1, pw).  The kernel indexes the prediction with whatever the maps hold."""
+    for name, m, n, lim in (("ymap", ymap, H, ph), ("xmap", xmap, W, pw)):
+        a = m.numpy() if torch.is_tensor(m) else np.asarray(m)
+        if a.dtype != np.int32 or a.ndim != 1 or a.size == 0 or (n is not None and a.size != n):
+            raise L.SdeHipError(f"depth_present: {name} must be int32 [{n if n is not None else 'n'}], got {a.dtype} {a.shape}")
+        if int(a.min()) < -1 or int(a.max()) >= lim:
+            raise L.SdeHipError(f"depth_present: {name} entries must lie in [-1, {lim}), got [{int(a.min())}, {int(a.max())}]")
+
+
+def device_maps(ymap, xmap, ph, pw, device):
+    """Validated host maps -> device tensors that depth_present accepts without looking at them again."""
+    check_maps(ymap, xmap, ph, pw)
+    ym = torch.as_tensor(np.ascontiguousarray(ymap)).to(device)
+    xm = torch.as_tensor(np.ascontiguousarray(xmap)).to(device)
+    _remember(ym, xm, ph, pw)
+    return ym, xm
+
+
+def _key(ymap, xmap, ph, pw):
+    return (ymap.data_ptr(), xmap.data_ptr(), ymap.numel(), xmap.numel(), ymap._version, xmap._version, ph, pw)
+
+
+def _remember(ymap, xmap, ph, pw):
+    if len(_checked) >= 256:
+        _checked.clear()
+    _checked[_key(ymap, xmap, ph, pw)] = (ymap, xmap)
+
+
+def default_lut(device):
+    device = torch.device(device)
+    if device not in _luts:
+        from ..utils.colormap import magma_u8
+        _luts[device] = torch.from_numpy(magma_u8()).to(device)
+    return _luts[device]
+
+
+def depth_present(pred, ymap, xmap, vmax, gamma=0.8, lut=None, frame=None, want_depth=True, want_u16=False, out=None):
+    """pred [N,ph,pw] (or [N,1,ph,pw] / [ph,pw]) fp32, ymap [H] / xmap [W] int32, lut [256,3] uint8 (default: magma), frame [N,H,W,3] uint8 or None:
+    CUDA tensors.  Returns (canvas [N, 2H or H, W, 3] uint8, depth_full [N,H,W] fp32 or None, depth_u16 [N,H,W] int16 bits of uint16 or None).
+    Device maps are validated once per distinct pair (one device -> host copy the first time a pair is seen, none after: do that first call
+    outside graph capture, or build the pair with device_maps()).  out: optional (canvas, depth_full, depth_u16) destinations.  No host sync."""
+    if pred.dim() == 2:
+        pred = pred[None]
+    elif pred.dim() == 4 and pred.shape[1] == 1:
+        pred = pred[:, 0]
+    if pred.dim() != 3 or pred.dtype != torch.float32 or not pred.is_cuda:
+        raise L.SdeHipError(f"depth_present: pred must be a float32 [N,ph,pw] device tensor, got {pred.dtype} {tuple(pred.shape)}")
+    pred = pred.contiguous()
+    N, ph, pw = pred.shape
+    if not (torch.is_tensor(ymap) and torch.is_tensor(xmap) and ymap.is_cuda and xmap.is_cuda):
+        ymap, xmap = device_maps(ymap, xmap, ph, pw, pred.device)
+    if ymap.dtype != torch.int32 or xmap.dtype != torch.int32 or ymap.dim() != 1 or xmap.dim() != 1:
+        raise L.SdeHipError("depth_present: the index maps must be 1-D int32")
+    if _key(ymap, xmap, ph, pw) not in _checked:
+        check_maps(ymap.cpu(), xmap.cpu(), ph, pw)
+        _remember(ymap, xmap, ph, pw)
+    H, W = ymap.numel(), xmap.numel()
+    dev = pred.device
+    if lut is None:
+        lut = default_lut(dev)
+    if lut.dtype != torch.uint8 or tuple(lut.shape) != (256, 3) or not lut.is_cuda:
+        raise L.SdeHipError("depth_present: lut must be a uint8 [256,3] device tensor")
+    if frame is not None:
+        if frame.dim() == 3:
+            frame = frame[None]
+        if frame.dtype != torch.uint8 or tuple(frame.shape) != (N, H, W, 3) or not frame.is_cuda:
+            raise L.SdeHipError(f"depth_present: frame must be a uint8 [{N},{H},{W},3] device tensor, got {frame.dtype} {tuple(frame.shape)}")
+    rows = 2 * H if frame is not None else H
+    canvas, depth, u16 = out if out is not None else (None, None, None)
+
+    def dst(t, shape, dtype, want):
+        if not want:
+            return None
+        if t is None:
+            return torch.empty(shape, dtype=dtype, device=dev)
+        if t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_cuda:
+            raise L.SdeHipError(f"depth_present: destination must be {dtype} {tuple(shape)}, got {t.dtype} {tuple(t.shape)}")
+        return t
+    canvas = dst(canvas, (N, rows, W, 3), torch.uint8, True)
+    depth = dst(depth, (N, H, W), torch.float32, want_depth)
+    u16 = dst(u16, (N, H, W), torch.int16, want_u16)          # torch has no arithmetic on uint16: the bits; .cpu().numpy().view(np.uint16) on the host
+    L.check(L.lib().sde_depth_present(L.ptr(pred), N, ph, pw, L.ptr(ymap), L.ptr(xmap), H, W, float(vmax), float(gamma), L.ptr(lut.contiguous()),
+                                      L.ptr(frame.contiguous() if frame is not None else None), L.ptr(depth), L.ptr(u16), L.ptr(canvas), L.stream()),
+            "sde_depth_present")
+    return canvas, depth, u16
