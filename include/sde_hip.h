@@ -650,6 +650,45 @@ int sde_depth_present(const float* pred, int N, int ph, int pw, const int* ymap,
                       const uint8_t* lut, const uint8_t* frame, float* depth_full, uint16_t* depth_u16, uint8_t* canvas, sde_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Point clouds (csrc/cloud.hip; binding in hip/cloud.py): back-projection of depth, detectron2/geometry/camera.py:L25-37 and L125-138.
+ *
+ * sde_depth_cloud: N network outputs pred [N,ph,pw] fp32 of ONE source size -> per frame a compacted list of coloured points at the restored
+ * size.  ymap [H] / xmap [W]: the maps of sde_depth_present, same contract (-1 = outside: value 0; the caller validates the ranges).
+ * frame [N,H,W,3] uint8 RGB or NULL (colour 255,255,255).  K [N,3,3] fp32, intrinsics at the restored (source) size, metres out for metres in;
+ * only fx = K[0], cx = K[2], fy = K[4], cy = K[5] are read.  Candidates are the pixels with v % step == 0 && u % step == 0, in raster order.
+ * With d the restored depth of pixel (u, v): the pixel is kept iff d is finite and min_depth < d <= max_depth (fp32 comparisons on the stored
+ * value).  A kept pixel gives one 16-byte record { float x, y, z; uint8 r, g, b, a }, written by one aligned 16-byte store, evaluated in fp32
+ * in exactly this order, nothing fused:
+ *   Kinv00 = 1 / fx;  Kinv11 = 1 / fy;  Kinv02 = (-1 * cx) / fx;  Kinv12 = (-1 * cy) / fy;          (inv_intrinsics)
+ *   x = d * (Kinv00 * (float)u + Kinv02);   y = d * (Kinv11 * (float)v + Kinv12);   z = d;   a = 255.
+ * points [N][cap][16 bytes] with cap = sde_depth_cloud_capacity(H, W, step) = ceil(H / step) * ceil(W / step), 16-byte aligned; count [N]
+ * int32, device memory.  The records of frame n fill [0, count[n]) of its cap slots in raster order; the bytes behind them are not touched.
+ * workspace: sde_depth_cloud_ws_bytes(N, H, W, step) bytes of device memory, 4-byte aligned, contents irrelevant (both queries return 0 for
+ * sizes the entry point refuses).  Three launches ordered on the stream (counts per workgroup, exclusive scan, scatter); no workgroup waits
+ * for another, no atomics, no host synchronisation, no allocation: legal under graph capture, the same bytes every run.
+ * Refused before any launch: N, H, W, ph, pw <= 0, step < 1, min_depth >= max_depth (or a NaN), NULL pred / maps / K / points / count,
+ * points off a 16-byte boundary, a workspace that is NULL or smaller than the query reports.
+ *
+ * sde_img_to_points_fwd / _bwd: img_to_points(depth [B,1,H,W], R [B,3,3], t), fp32, planar.  t [B,3] (t_per_pixel == 0) or [B,3,H*W] (!= 0).
+ *   points [B,3,H,W]: points_c = R_c0 * (u * d) + R_c1 * (v * d) + R_c2 * d + t_c           (u = column, v = row)
+ * Backward from grad [B,3,H,W]: ddepth [B,H,W] = sum_c grad_c * (R_c0 * u + R_c1 * v + R_c2); dR [B,3,3] = sum_p grad_p (x) (d_p * [u,v,1]);
+ * dt [B,3] = sum_p grad_p (NULL skips it: with a per-pixel t the gradient of t is grad itself; dR NULL skips it too, and with both NULL the second
+ * launch and the sums are left out and part may be NULL).  part: workspace of
+ * B * sde_img_to_points_num_blocks(H, W) * 12 floats; the twelve sums of a sample are per-workgroup fp32 partials added in workgroup order in
+ * fp64 by a second launch.  Refused before any launch: B, H, W <= 0, NULL depth / R / t / points (fwd), NULL grad / depth / R / ddepth, or dR / dt
+ * without part (bwd).  No atomics, no host synchronisation. */
+long sde_depth_cloud_capacity(int H, int W, int step);
+size_t sde_depth_cloud_ws_bytes(int N, int H, int W, int step);
+int sde_depth_cloud(const float* pred, int N, int ph, int pw, const int* ymap, const int* xmap, int H, int W, const uint8_t* frame, const float* K,
+                    float min_depth, float max_depth, int step, void* workspace, size_t workspace_bytes, void* points, int* count,
+                    sde_stream_t stream);
+int sde_img_to_points_num_blocks(int H, int W);
+int sde_img_to_points_fwd(const float* depth, const float* R, const float* t, int t_per_pixel, int B, int H, int W, float* points,
+                          sde_stream_t stream);
+int sde_img_to_points_bwd(const float* grad, const float* depth, const float* R, int B, int H, int W, float* part, float* ddepth, float* dR, float* dt,
+                          sde_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * MotionLearning loss stack (csrc/motion_loss.hip; autograd wrappers in hip/motion_loss.py).  fp32, planar NCHW, no host synchronisation.
  *
  * sde_view_synthesis_pp: detectron2/geometry/camera.py:L166-202 with a per-pixel translation t [B,3,H,W] and a 3x3 rotation R [B,3,3]; the

@@ -7,7 +7,9 @@ the picture with matplotlib.  Here the uint8 frame is uploaded from pinned memor
                           an axis that is not resized gets identity taps (i, i, 2048, 0) -- the fixed-point rule then returns the source byte;
     model(batch)          eval mode, torch.no_grad();
     sde_depth_present     the backward chain as the two index maps of evaluation.depth_evaluation.backward_maps, the restored depth, the 16-bit
-                          depth and the coloured, frame-stacked picture in one launch (hip/present.py).
+                          depth and the coloured, frame-stacked picture in one launch (hip/present.py);
+    sde_depth_cloud       on request (cloud=dict(min_depth=, max_depth=, step=1)): the restored depth lifted through the source-size intrinsics
+                          into a compacted list of coloured 16-byte points per frame, three launches behind the present kernel (hip/cloud.py).
 
 The three stages are captured once per (source size, batch size) into a graph and replayed; `stream` adds a copy stream that uploads the next
 frame and downloads the previous picture while the current frame is computed."""
@@ -17,6 +19,7 @@ import torch
 from ..data.device_aug import DeviceImageAug
 from ..data.preprocess.augmentation import _linear_coefs
 from ..evaluation.depth_evaluation import backward_maps
+from ..hip import cloud as HC
 from ..hip import present as HP
 
 IMAGE_STEPS = ("KBCrop", "CropTopTo", "Resize")       # the steps with a backward(): DatasetEvaluator.preprocess_chain keeps the same three
@@ -136,6 +139,8 @@ class _Slot:
         self.frames = torch.empty((N, Hs, Ws, 3), dtype=torch.uint8, device=device)
         self.K = None                # [N,3,3] float32 device tensor once intrinsics are used
         self.K_host = None
+        self.K_src = None            # [N,3,3] float32 device tensor: the intrinsics as given (source size), for the point cloud
+        self.K_src_host = None
         self.graphs = {}             # (present, frame_in_canvas, want_u16, has K) -> (graph, outputs)
         self.host = {}               # name -> pinned host tensor of the downloaded output
         self.uploaded = torch.cuda.Event()
@@ -187,9 +192,10 @@ class DepthPredictor:
         return self._params[N]
 
     # ---- the device chain -----------------------------------------------------------------------------------------------------------------
-    def _chain(self, plan, frames, K, present, frame_in_canvas, want_u16):
-        """frames: uint8 [N,Hs,Ws,3] on the device, K: [N,3,3] float32 on the device or None.  Everything on the current stream, nothing synchronises
-        once the tables of this size are on the device (the first call of a size puts them there)."""
+    def _chain(self, plan, frames, K, present, frame_in_canvas, want_u16, cloud=None, K_src=None):
+        """frames: uint8 [N,Hs,Ws,3] on the device, K: [N,3,3] float32 on the device or None; cloud: (min_depth, max_depth, step) or None, K_src: the
+        source-size intrinsics the cloud uses.  Everything on the current stream, nothing synchronises once the tables of this size are on the
+        device (the first call of a size puts them there)."""
         N = frames.shape[0]
         img, _ = self._aug.prep(frames, self._no_jitter(N), plan.h, plan.w, tabs=(plan.xtab, plan.ytab))
         batch = {"img": img}
@@ -206,6 +212,9 @@ class DepthPredictor:
             ymap, xmap = self._maps_on_device(plan, pred.shape[-2:])
             out["canvas"], out["depth"], out["depth_u16"] = HP.depth_present(pred, ymap, xmap, self.vmax, self.gamma, frame=frames if frame_in_canvas else None,
                                                                              want_depth=True, want_u16=want_u16)
+        if cloud is not None:
+            ymap, xmap = self._maps_on_device(plan, pred.shape[-2:])
+            out["points"], out["count"] = HC.depth_cloud(pred, ymap, xmap, K_src, *cloud, frame=frames)
         return out
 
     def _slot(self, N, plan, i=0):
@@ -229,22 +238,51 @@ class DepthPredictor:
             slot.K_host = K
         return slot.K
 
-    def _run(self, slot, plan, K, flags):
+    @staticmethod
+    def _cloud_args(cloud, intrinsics, N):
+        """cloud=None -> (None, None); a dict -> ((min_depth, max_depth, step), the source-size K as a float32 [N,3,3] host array).  ValueError for
+        a cloud without intrinsics, unknown keys, an empty depth range, step < 1 or a zero focal length; nothing here touches the device."""
+        if cloud is None:
+            return None, None
+        if not isinstance(cloud, dict) or not {"min_depth", "max_depth"} <= set(cloud) <= {"min_depth", "max_depth", "step"}:
+            raise ValueError(f"DepthPredictor: cloud must be None or dict(min_depth=..., max_depth=..., step=1), got {cloud!r}")
+        args = HC.check_range(cloud["min_depth"], cloud["max_depth"], cloud.get("step", 1))
+        if intrinsics is None:
+            raise ValueError("DepthPredictor: cloud needs intrinsics (the source-size K [3,3] or [N,3,3] of the frames)")
+        K = np.asarray(intrinsics.cpu().numpy() if torch.is_tensor(intrinsics) else intrinsics, dtype=np.float32)
+        K = np.array(np.broadcast_to(K, (N, 3, 3)))
+        if not (np.all(np.isfinite(K)) and np.all(K[:, 0, 0] != 0) and np.all(K[:, 1, 1] != 0)):
+            raise ValueError("DepthPredictor: cloud needs finite intrinsics with non-zero focal lengths")
+        return args, K
+
+    def _cloud_K(self, slot, K, N):
+        """The slot's device copy of the cloud's intrinsics, refreshed when they change (None without a cloud)."""
+        if K is None:
+            return None
+        if slot.K_src is None:
+            slot.K_src = torch.empty((N, 3, 3), dtype=torch.float32, device=self.device)
+        if slot.K_src_host is None or not np.array_equal(slot.K_src_host, K):
+            slot.K_src.copy_(torch.from_numpy(K))
+            slot.K_src_host = K
+        return slot.K_src
+
+    def _run(self, slot, plan, K, flags, cloud=None, K_src=None):
         """The chain on the slot's buffers, on the current stream: eager, or the slot's graph (captured at first use, after one eager run)."""
+        chain = lambda: self._chain(plan, slot.frames, K, *flags, cloud=cloud, K_src=K_src)
         if not self.use_graph:
-            return self._chain(plan, slot.frames, K, *flags)
-        key = flags + (K is not None,)
+            return chain()
+        key = flags + (K is not None,) + ((cloud,) if cloud is not None else ())       # without a cloud: the key of before
         if key not in slot.graphs:
             cur = torch.cuda.current_stream()
             side = torch.cuda.Stream(device=self.device)
             side.wait_stream(cur)
             with torch.cuda.stream(side):           # tables, caches and the allocator's blocks come into being here, outside the capture
-                self._chain(plan, slot.frames, K, *flags)
+                chain()
             cur.wait_stream(side)
             torch.cuda.synchronize(self.device)
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph, capture_error_mode="thread_local"):
-                out = self._chain(plan, slot.frames, K, *flags)
+                out = chain()
             slot.graphs[key] = (graph, out)
         graph, out = slot.graphs[key]
         graph.replay()
@@ -263,13 +301,15 @@ class DepthPredictor:
             raise ValueError(f"DepthPredictor: frames must be uint8 [H,W,3] or [N,H,W,3] RGB, got {t.dtype} {tuple(t.shape)}")
         return t.contiguous(), single
 
-    def predict(self, frames, intrinsics=None, present=True, frame_in_canvas=True, want_u16=False):
+    def predict(self, frames, intrinsics=None, present=True, frame_in_canvas=True, want_u16=False, cloud=None):
         """frames: one uint8 [H,W,3] RGB array / tensor, or N of one size.  Returns a dict of device tensors: `depth` [N,H,W] (the prediction restored
         to the frame's size; None with present=False), `depth_net` [N,h,w] (the network output), `canvas` [N,2H or H,W,3] uint8, `depth_u16` with
-        want_u16 (int16 tensor holding write_depth's uint16 bits).  A single frame keeps the leading 1.  No host synchronisation after the first
-        call of a size."""
+        want_u16 (int16 tensor holding write_depth's uint16 bits).  A single frame keeps the leading 1.  cloud=dict(min_depth=, max_depth=, step=1)
+        adds `points` [N,cap,16] uint8 and `count` [N] int32 (hip.cloud.depth_cloud of the restored depth, the frames' colours and `intrinsics` as
+        given, which it then requires; hip.cloud.as_records reads them on the host).  No host synchronisation after the first call of a size."""
         t, _ = self._as_frames(frames)
         N, Hs, Ws, _ = t.shape
+        cloud, K_cloud = self._cloud_args(cloud, intrinsics, N)
         plan = self.plan(Hs, Ws)
         slot = self._slot(N, plan)
         flags = (bool(present), bool(frame_in_canvas), bool(want_u16))
@@ -282,7 +322,7 @@ class DepthPredictor:
                 slot.frames.copy_(slot.frames_pin, non_blocking=True)
                 slot.uploaded.record()
             K = self._set_intrinsics(slot, plan, intrinsics, N)
-            out = self._run(slot, plan, K, flags)
+            out = self._run(slot, plan, K, flags, cloud, self._cloud_K(slot, K_cloud, N))
             # the slot's tensors are written again by the next call: hand out copies
             return {k: (v.clone() if v is not None else None) for k, v in out.items()}
 
@@ -304,22 +344,25 @@ class DepthPredictor:
 
     def _result(self, slot, names):
         slot.downloaded.synchronize()
-        res = {k: slot.host[k].numpy()[0] for k in names if slot.out[k] is not None}
+        res = {k: (slot.host[k].numpy() if k in ("points", "count") else slot.host[k].numpy()[0]) for k in names if slot.out[k] is not None}
         if "depth_u16" in res:
             res["depth_u16"] = res["depth_u16"].view(np.uint16)
         return res
 
-    def stream(self, frames_iter, intrinsics=None, present=True, frame_in_canvas=True, want_u16=False):
+    def stream(self, frames_iter, intrinsics=None, present=True, frame_in_canvas=True, want_u16=False, cloud=None):
         """Generator over host frames (uint8 [H,W,3] RGB, one at a time): yields, in order, a dict of host arrays per frame -- `depth` [H,W] fp32,
         `canvas` [2H or H,W,3] uint8, `depth_u16` with want_u16; with present=False only `depth_net` [h,w].  The arrays are views of pinned buffers and stay valid until the next
         iteration.  Two slots of pinned and device buffers: while frame i is computed on the current stream, the copy stream uploads frame i+1 and
         downloads the outputs of frame i-1; result i-1 is yielded once frame i is enqueued.  A frame of another size drains the slots and switches
-        tables.  No threads."""
+        tables.  No threads.  cloud (see predict) adds `points` [1,cap,16] uint8 and `count` [1] int32, the whole buffer downloaded like the other
+        outputs: hip.cloud.as_records(res["points"], res["count"])[0] is the frame's cloud."""
+        cloud, K_cloud = self._cloud_args(cloud, intrinsics, 1)
         if self._copy_stream is None:
             self._copy_stream = torch.cuda.Stream(device=self.device)
         cs = self._copy_stream
         flags = (bool(present), bool(frame_in_canvas), bool(want_u16))
-        names = [k for k, on in (("depth", present), ("canvas", present), ("depth_u16", present and want_u16), ("depth_net", not present)) if on]
+        names = [k for k, on in (("depth", present), ("canvas", present), ("depth_u16", present and want_u16), ("depth_net", not present),
+                                 ("points", cloud is not None), ("count", cloud is not None)) if on]
         pending, size, i = None, None, 0
         with torch.cuda.device(self.device):
             cur = torch.cuda.current_stream()
@@ -347,7 +390,7 @@ class DepthPredictor:
                 K = self._set_intrinsics(slot, plan, intrinsics, 1)
                 cur.wait_event(slot.uploaded)
                 cur.wait_event(slot.downloaded)                         # the slot's outputs of frame i-2 have left the device
-                slot.out = self._run(slot, plan, K, flags)
+                slot.out = self._run(slot, plan, K, flags, cloud, self._cloud_K(slot, K_cloud, 1))
                 slot.computed.record(cur)
                 if pending is not None:
                     yield self._result(pending, names)

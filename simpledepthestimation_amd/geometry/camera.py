@@ -1,6 +1,9 @@
 """Camera geometry entry points with the reference's names (detectron2/geometry/camera.py), computed by libsde_hip.so."""
+from functools import lru_cache
+
 import torch
 
+from ..hip import cloud as HC
 from ..hip import motion_loss as HM
 from ..hip import photometric as HP
 
@@ -12,6 +15,48 @@ def scale_intrinsics(K, x_scale, y_scale):
     K[..., 0, 2] *= x_scale
     K[..., 1, 2] *= y_scale
     return K
+
+
+def inv_intrinsics(K):
+    """K [B,3,3] -> the inverse of a pinhole matrix as a new tensor: 1/fx, 1/fy on the diagonal, (-1*cx)/fx, (-1*cy)/fy in the last column (that
+    operation order: sde_depth_cloud and the recorded fixture share it).  Every other entry -- skew, last row -- is carried over unchanged."""
+    assert K.dim() == 3, f"inv_intrinsics: K must be [B,3,3], got {tuple(K.shape)}"
+    focal = K.diagonal(dim1=1, dim2=2)[:, :2]              # [B,2]: fx, fy
+    centre = K[:, :2, 2]                                    # [B,2]: cx, cy
+    out = K.clone()
+    out.diagonal(dim1=1, dim2=2)[:, :2] = 1.0 / focal
+    out[:, :2, 2] = (-1.0 * centre) / focal
+    return out
+
+
+@lru_cache(maxsize=None)
+def _axes(H, W, dtype, device, normalized):
+    """The column and row coordinates of an H x W image as 1-D tensors: 0 .. W-1 / 0 .. H-1, or both spread over [-1, 1]."""
+    if normalized:
+        return tuple(torch.linspace(-1.0, 1.0, n, dtype=dtype, device=device) for n in (W, H))
+    return tuple(torch.arange(n, device=device).to(dtype) for n in (W, H))
+
+
+def meshgrid(B, H, W, dtype, device, normalized=False):
+    """-> (xs, ys), each [B,H,W] of `dtype` on `device`: every pixel's column and row coordinate (in [-1, 1] when normalized).  Plain torch; the
+    tensors are the caller's own."""
+    cols, rows = _axes(H, W, dtype, device, bool(normalized))
+    return cols.view(1, 1, W).expand(B, H, W).contiguous(), rows.view(1, H, 1).expand(B, H, W).contiguous()
+
+
+def image_grid(B, H, W, dtype, device, normalized=False):
+    """-> grid [B,3,H,W]: channel 0 the column coordinate, channel 1 the row coordinate, channel 2 ones (homogeneous pixel coordinates)."""
+    cols, rows = _axes(H, W, dtype, device, bool(normalized))
+    grid = torch.ones((B, 3, H, W), dtype=dtype, device=device)
+    grid[:, 0] = cols.view(1, 1, W)
+    grid[:, 1] = rows.view(1, H, 1)
+    return grid
+
+
+def img_to_points(depth, R, t):
+    """camera.py:L125-138: depth [B,1,H,W], R [B,3,3], t [B,3,1] or [B,3,H*W] -> points [B,3,H,W] = R (depth * image_grid) + t, one launch
+    (sde_img_to_points_fwd), differentiable in depth, R and t.  The compacted, coloured cloud of a prediction is hip.cloud.depth_cloud."""
+    return HC.img_to_points(depth, R, t)
 
 
 def resize_img(image, dst_size, mode="bilinear"):

@@ -126,6 +126,13 @@ _PROTOS = {
     "sde_motion_prep_fwd": ([_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P], c_int),
     "sde_motion_prep_bwd": ([_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P], c_int),
     "sde_mask_dilate": ([_P, _P, _P, _I, _I, _I, _I, _P], c_int),
+    # point clouds (csrc/cloud.hip; binding and autograd wrapper in hip/cloud.py)
+    "sde_depth_cloud_capacity": ([_I, _I, _I], ctypes.c_long),
+    "sde_depth_cloud_ws_bytes": ([_I, _I, _I, _I], c_size_t),
+    "sde_depth_cloud": ([_P, _I, _I, _I, _P, _P, _I, _I, _P, _P, _F, _F, _I, _P, c_size_t, _P, _P, _P], c_int),
+    "sde_img_to_points_num_blocks": ([_I, _I], c_int),
+    "sde_img_to_points_fwd": ([_P, _P, _P, _I, _I, _I, _I, _P, _P], c_int),
+    "sde_img_to_points_bwd": ([_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P], c_int),
 }
 
 _lib = None

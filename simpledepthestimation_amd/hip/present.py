@@ -46,6 +46,19 @@ def _remember(ymap, xmap, ph, pw):
     _checked[_key(ymap, xmap, ph, pw)] = (ymap, xmap)
 
 
+def ensure_checked(ymap, xmap, ph, pw, device):
+    """Maps in any accepted form -> the validated 1-D int32 device pair: host arrays are validated and uploaded; a device pair is validated once
+    (one device -> host copy the first time the pair is seen, none after).  Shared by every binding that indexes a prediction through the maps."""
+    if not (torch.is_tensor(ymap) and torch.is_tensor(xmap) and ymap.is_cuda and xmap.is_cuda):
+        return device_maps(ymap, xmap, ph, pw, device)
+    if ymap.dtype != torch.int32 or xmap.dtype != torch.int32 or ymap.dim() != 1 or xmap.dim() != 1:
+        raise L.SdeHipError("the index maps must be 1-D int32")
+    if _key(ymap, xmap, ph, pw) not in _checked:
+        check_maps(ymap.cpu(), xmap.cpu(), ph, pw)
+        _remember(ymap, xmap, ph, pw)
+    return ymap, xmap
+
+
 def default_lut(device):
     device = torch.device(device)
     if device not in _luts:
@@ -67,13 +80,7 @@ def depth_present(pred, ymap, xmap, vmax, gamma=0.8, lut=None, frame=None, want_
         raise L.SdeHipError(f"depth_present: pred must be a float32 [N,ph,pw] device tensor, got {pred.dtype} {tuple(pred.shape)}")
     pred = pred.contiguous()
     N, ph, pw = pred.shape
-    if not (torch.is_tensor(ymap) and torch.is_tensor(xmap) and ymap.is_cuda and xmap.is_cuda):
-        ymap, xmap = device_maps(ymap, xmap, ph, pw, pred.device)
-    if ymap.dtype != torch.int32 or xmap.dtype != torch.int32 or ymap.dim() != 1 or xmap.dim() != 1:
-        raise L.SdeHipError("depth_present: the index maps must be 1-D int32")
-    if _key(ymap, xmap, ph, pw) not in _checked:
-        check_maps(ymap.cpu(), xmap.cpu(), ph, pw)
-        _remember(ymap, xmap, ph, pw)
+    ymap, xmap = ensure_checked(ymap, xmap, ph, pw, pred.device)
     H, W = ymap.numel(), xmap.numel()
     dev = pred.device
     if lut is None:
