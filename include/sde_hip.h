@@ -195,7 +195,7 @@ int sde_pack_weight(const float* w, void* out, int dtype, int Cout, int Cin, int
  * built once; a workgroup transposes one (32 output channels x sde-chosen input-channel block x all taps) tile through LDS;
  * `end` = exclusive prefix sum of sde_pack_item_blocks() over the layers, total_blocks = items[n-1].end. */
 typedef struct sde_pack_item {
-    const float* src; /* master fp32 weights: [Cout][Cin][KH][KW] (src_layout SDE_W_OIHW) or [Cout][KH][KW][Cin] (SDE_W_OHWI, channels-last) */
+    const float* src; /* master fp32 weights (SDE_W_TWIN16: their 16-bit twin): [Cout][Cin][KH][KW] (src_layout SDE_W_OIHW) or [Cout][KH][KW][Cin] (SDE_W_OHWI, channels-last) */
     void* dst_fwd;    /* [Cout_pad][KH][KW][Cin_pad] in `dtype` (or NULL) */
     void* dst_dgrad;  /* [Cin_pad][KH][KW][Cout_pad], taps flipped (or NULL) */
     int32_t Cout, Cin, KH, KW, Cin_pad, Cout_pad;
@@ -204,6 +204,8 @@ typedef struct sde_pack_item {
 } sde_pack_item;
 #define SDE_W_OIHW 0 /* torch's default memory order of a conv weight */
 #define SDE_W_OHWI 1 /* torch.channels_last order of the same [Cout,Cin,KH,KW] tensor: K-major like the packed operands and the gradient slabs */
+#define SDE_W_TWIN16 2 /* src is NOT fp32 but the 16-bit twin of a channels-last master slot (sde_adam_step_twin), i.e. the forward operand itself: only dst_dgrad is
+                        * written (dst_fwd is ignored).  Needs a 16-bit `dtype`, Cin_pad == Cin, Cout_pad == Cout, both multiples of 8, src and dst_dgrad 16-byte aligned. */
 int sde_pack_item_blocks(int Cout_pad, int Cin_pad, int KH, int KW);
 int sde_pack_weights_batched(const sde_pack_item* items_dev, int n, long total_blocks, int dtype, sde_stream_t stream);
 
@@ -596,6 +598,11 @@ typedef struct sde_adam_desc {
     const float* clip_state;
 } sde_adam_desc;
 int sde_adam_step(float* p, const float* g, float* m, float* v, long n, const sde_adam_desc* d, sde_stream_t stream);
+/* The same update (p, m, v come out bit-identical to sde_adam_step) that also writes twin[i] = (twin_dtype) p_new[i] for every i < n, with the
+ * conversion of the weight pack: twin is a DEVICE buffer of n SDE_BF16 / SDE_F16 elements in the flat order of p.  Where a convolution weight sits
+ * in p channels-last without channel padding, its slot of the twin IS the packed forward operand (sde_pack_item: SDE_W_TWIN16 builds the
+ * data-gradient operand from it).  A step skipped through scale_state leaves the twin untouched, like p.  p, g, m, v 16-byte aligned, twin 8-byte. */
+int sde_adam_step_twin(float* p, const float* g, float* m, float* v, long n, const sde_adam_desc* d, void* twin, int twin_dtype, sde_stream_t stream);
 int sde_grad_check(const float* g, long n, float* scale_state, sde_stream_t stream);
 int sde_grad_norm(const float* g, long n, float* work, float* clip_state, float grad_scale, float max_norm, sde_stream_t stream);
 int sde_loss_scale_update(float* scale_state, float growth_factor, float backoff_factor, int growth_interval, sde_stream_t stream);

@@ -18,7 +18,7 @@ def fam(n):
     n = re.sub(r'\(anonymous namespace\)::', '', n); n = re.sub(r'^void ', '', n)
     n = re.sub(r'^_ZN\d+_GLOBAL__N_1\d+|^_ZN7sdeconv\d+', '', n)
     return n[:52]
-idx = [i for i, r in enumerate(rows) if 'adam_kernel' in r['Kernel_Name']]
+idx = [i for i, r in enumerate(rows) if re.search(r'adam_(twin_)?kernel', r['Kernel_Name'])]
 a, b = idx[-3] + 1, idx[-1] + 1          # the last two replayed steps
 step = rows[a:b]
 ev = []

@@ -72,5 +72,10 @@ __device__ __forceinline__ float bf2f(bf16_t v) { return (float)v; }
 __device__ __forceinline__ bf16_t f2bf(float v) { return (bf16_t)v; }
 // fp16 storage (BASELINE.json configs[4]: fp16 + dynamic loss scaling): same kernels, instantiated on _Float16
 typedef _Float16 half_t;
+// fp32 -> storage type: THE conversion of the weight pack (conv.hip) and of the Adam kernel's 16-bit twin (nn.hip), which must agree bit for bit
+template <typename T> __device__ __forceinline__ T from_f32(float v);
+template <> __device__ __forceinline__ float from_f32<float>(float v) { return v; }
+template <> __device__ __forceinline__ bf16_t from_f32<bf16_t>(float v) { return (bf16_t)v; }
+template <> __device__ __forceinline__ half_t from_f32<half_t>(float v) { return (half_t)v; }
 #define SDE_IS16(dtype) ((dtype) == SDE_BF16 || (dtype) == SDE_F16)
 #define SDE_DTYPE_OK(dtype) ((dtype) == SDE_F32 || (dtype) == SDE_BF16 || (dtype) == SDE_F16)

@@ -82,10 +82,6 @@ template <typename T> __device__ __forceinline__ float to_f32(T v);
 template <> __device__ __forceinline__ float to_f32<float>(float v) { return v; }
 template <> __device__ __forceinline__ float to_f32<bf16_t>(bf16_t v) { return (float)v; }
 template <> __device__ __forceinline__ float to_f32<half_t>(half_t v) { return (float)v; }
-template <typename T> __device__ __forceinline__ T from_f32(float v);
-template <> __device__ __forceinline__ float from_f32<float>(float v) { return v; }
-template <> __device__ __forceinline__ bf16_t from_f32<bf16_t>(float v) { return (bf16_t)v; }
-template <> __device__ __forceinline__ half_t from_f32<half_t>(float v) { return (half_t)v; }
 
 // ------------------------------------------------------------------------------------------------------------------
 // Forward / data-gradient implicit GEMM:  Y[M, Cout] = im2col(X)[M, K] * Wp[Cout, K]^T
@@ -1194,6 +1190,36 @@ __global__ void __launch_bounds__(256) pack_batched_kernel(const sde_pack_item* 
     const int n_ci_real = max(0, min(CI, it.Cin - ci0));          // channels that exist in the master weights
     const int n_ci = min(CI, it.Cin_pad - ci0), n_co = min(PACK_CO, it.Cout_pad - co0);
     const int seg = n_ci_real * khw, rs = CI * khw + 1;           // row stride odd: the transposed reads below are conflict-free
+    // 16-bit twin source (sde_adam_step_twin keeps it): the slot already IS the forward operand [co][tap][ci], only the tap-flipped transpose is left to
+    // do -- same tile walk as below, 16-byte loads of 8 values, a 16-bit LDS tile (odd row stride), no conversion: the bits are moved, so they equal
+    // what the fp32 kind writes from the master the twin was cast from.  Eligibility (no padding, multiples of 8, aligned slot) is the host's business.
+    if constexpr (sizeof(T) == 2)
+    if (it.src_layout == SDE_W_TWIN16) {
+        typedef __attribute__((ext_vector_type(8))) unsigned short us8;
+        unsigned short* t16 = reinterpret_cast<unsigned short*>(tile);
+        const unsigned short* src = reinterpret_cast<const unsigned short*>(it.src);
+        const int n8 = n_ci >> 3;
+        for (int idx = threadIdx.x; idx < n_co * khw * n8; idx += 256) {
+            const int c8 = idx % n8, t2 = idx / n8, tap = t2 % khw, co_l = t2 / khw;
+            const us8 v = *reinterpret_cast<const us8*>(src + ((size_t)(co0 + co_l) * khw + tap) * it.Cin + ci0 + c8 * 8);
+            unsigned short* d = t16 + co_l * rs + tap * n_ci + c8 * 8;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) d[j] = v[j];
+        }
+        __syncthreads();
+        const int m8 = n_co >> 3;
+        unsigned short* dstd = (unsigned short*)it.dst_dgrad;
+        for (int idx = threadIdx.x; idx < n_ci * khw * m8; idx += 256) {
+            const int o8 = idx % m8, t2 = idx / m8, tapf = t2 % khw, ci_l = t2 / khw;
+            const unsigned short* sp = t16 + (o8 * 8) * rs + (khw - 1 - tapf) * n_ci + ci_l;
+            us8 o;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) o[j] = sp[j * rs];
+            *reinterpret_cast<us8*>(dstd + ((size_t)(ci0 + ci_l) * khw + tapf) * it.Cout_pad + co0 + o8 * 8) = o;
+        }
+        return;
+    }
+    if (it.src_layout == SDE_W_TWIN16) return;         // (a twin item in an fp32 launch: there is no such operand)
     // Fast path (16-bit operands of channels-last master weights without channel padding -- every layer but the stem and the 1-channel heads):
     // float4 loads, LDS tile in source order [co][tap][ci], and 16-byte stores of 8 values -- 8 consecutive ci of the forward operand, 8
     // consecutive co of the data-gradient operand -- instead of one index computation and one 2-byte store per element.
@@ -1230,19 +1256,62 @@ __global__ void __launch_bounds__(256) pack_batched_kernel(const sde_pack_item* 
         }
         return;
     }
+    // Padded layers -- the stem and the one-channel heads -- are a handful of workgroups, alone in the launch once the other layers share the Adam
+    // kernel's twin, and a workgroup's time is its trip count: only the rows that exist are staged (the rest of the tile is never read), several loads
+    // in flight, and 16-bit operands leave in 16-byte groups below.
+    const int n_co_real = max(0, min(PACK_CO, it.Cout - co0));
     if (seg > 0 && it.src_layout == SDE_W_OHWI) {      // channels-last master weights [co][tap][ci]: contiguous along ci
-        for (int idx = threadIdx.x; idx < PACK_CO * seg; idx += 256) {
+#pragma unroll 4
+        for (int idx = threadIdx.x; idx < n_co_real * seg; idx += 256) {
             const int ci_l = idx % n_ci_real, t2 = idx / n_ci_real, tap = t2 % khw, co_l = t2 / khw;
             const int co = co0 + co_l;
-            tile[co_l * rs + ci_l * khw + tap] = co < it.Cout ? it.src[((size_t)co * khw + tap) * it.Cin + ci0 + ci_l] : 0.f;
+            tile[co_l * rs + ci_l * khw + tap] = it.src[((size_t)co * khw + tap) * it.Cin + ci0 + ci_l];
         }
     } else if (seg > 0)
-        for (int idx = threadIdx.x; idx < PACK_CO * seg; idx += 256) {
+#pragma unroll 4
+        for (int idx = threadIdx.x; idx < n_co_real * seg; idx += 256) {
             const int co_l = idx / seg, e = idx - co_l * seg;
             const int co = co0 + co_l;
-            tile[co_l * rs + e] = co < it.Cout ? it.src[((size_t)co * it.Cin + ci0) * khw + e] : 0.f;
+            tile[co_l * rs + e] = it.src[((size_t)co * it.Cin + ci0) * khw + e];
         }
     __syncthreads();
+    // 16-bit operands whose padded channel counts are whole 16-byte groups (every layer the convolutions pack): the same values as the element loops
+    // below, eight per store, an eighth of the trips
+    if constexpr (sizeof(T) == 2)
+    if (((it.Cin_pad | it.Cout_pad) & 7) == 0 && (((uintptr_t)it.dst_fwd | (uintptr_t)it.dst_dgrad) & 15) == 0) {
+        typedef __attribute__((ext_vector_type(8))) unsigned short us8;
+        if (it.dst_fwd) {
+            T* dst = (T*)it.dst_fwd;
+            const int n8 = n_ci >> 3;
+            for (int idx = threadIdx.x; idx < n_co * khw * n8; idx += 256) {
+                const int c8 = idx % n8, t2 = idx / n8, tap = t2 % khw, co_l = t2 / khw;
+                us8 o;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    const int ci_l = c8 * 8 + j;
+                    const float v = (ci_l < n_ci_real && co_l < n_co_real) ? tile[co_l * rs + ci_l * khw + tap] : 0.f;
+                    o[j] = __builtin_bit_cast(unsigned short, from_f32<T>(v));
+                }
+                *reinterpret_cast<us8*>(dst + ((size_t)(co0 + co_l) * khw + tap) * it.Cin_pad + ci0 + c8 * 8) = o;
+            }
+        }
+        if (it.dst_dgrad) {
+            T* dst = (T*)it.dst_dgrad;
+            const int m8 = n_co >> 3;
+            for (int idx = threadIdx.x; idx < n_ci * khw * m8; idx += 256) {
+                const int o8 = idx % m8, t2 = idx / m8, tapf = t2 % khw, ci_l = t2 / khw;
+                us8 o;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    const int co_l = o8 * 8 + j;
+                    const float v = (ci_l < n_ci_real && co_l < n_co_real) ? tile[co_l * rs + ci_l * khw + (khw - 1 - tapf)] : 0.f;
+                    o[j] = __builtin_bit_cast(unsigned short, from_f32<T>(v));
+                }
+                *reinterpret_cast<us8*>(dst + ((size_t)(ci0 + ci_l) * khw + tapf) * it.Cout_pad + co0 + o8 * 8) = o;
+            }
+        }
+        return;
+    }
     if (it.dst_fwd) {             // [Cout_pad][khw][Cin_pad]
         T* dst = (T*)it.dst_fwd;
         for (int idx = threadIdx.x; idx < n_co * khw * n_ci; idx += 256) {

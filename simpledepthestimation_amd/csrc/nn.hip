@@ -1212,12 +1212,13 @@ __global__ void __launch_bounds__(256) gn_bwd_apply_kernel(const T* __restrict__
 // whole update is skipped when found_inf != 0 (engine/train_loop.py:L294-341 AMPTrainer / GradScaler.step semantics, without a host sync).
 // clip_state (optional, gradient-norm clipping): device {total_norm, clip_coef} written by sde_grad_norm in front of this launch; the gradient is
 // multiplied by clip_coef on its way into the update and never rescaled in memory.
-__global__ void __launch_bounds__(256) adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, long n,
-                                                   const sde_adam_desc d) {
-    float gs = d.grad_scale;
-    float bc1 = d.bias_corr1, bc2 = d.bias_corr2;
+// The launch-wide part of the update: false when the step is skipped (overflow under loss scaling); else the gradient factor and the bias corrections.
+__device__ __forceinline__ bool adam_prologue(const sde_adam_desc& d, float& gs, float& bc1, float& rbc2) {
+    gs = d.grad_scale;
+    bc1 = d.bias_corr1;
+    float bc2 = d.bias_corr2;
     if (d.scale_state) {
-        if (d.scale_state[1] != 0.f) return;            // overflow in this step's gradients: skip (uniform over the grid)
+        if (d.scale_state[1] != 0.f) return false;      // overflow in this step's gradients: skip (uniform over the grid)
         gs /= d.scale_state[0];
         // the step count of the APPLIED updates lives on the device (a skipped step must not advance Adam's `step`): state[3], incremented
         // by loss_scale_update_kernel behind this launch
@@ -1226,19 +1227,90 @@ __global__ void __launch_bounds__(256) adam_kernel(float* __restrict__ p, const 
         bc2 = (float)(1.0 - pow(d.beta2_d, t));
     }
     if (d.clip_state) gs *= d.clip_state[1];             // gradient-norm clipping: the coefficient grad_norm_finalize_kernel left on the device
-    const float beta1 = d.beta1, beta2 = d.beta2, rbc2 = 1.0f / sqrtf(bc2);
+    rbc2 = 1.0f / sqrtf(bc2);
+    return true;
+}
+
+// One element of the update, the ONLY statement of its arithmetic: returns the new parameter, updates the moments in place.  adam_kernel and
+// adam_twin_kernel must agree bit for bit, with each other and with every earlier build of adam_kernel, so nothing is left to the compiler's choice of
+// which multiply-add to fuse (it chose differently for the two loop shapes): contraction is off in here and the fused operations are spelled out --
+// exactly those the one-element kernel has always been compiled to.  s: segment cursor, only ever moves forward (callers walk i upwards from s = 0).
+__device__ __forceinline__ float adam_update(const sde_adam_desc& d, long i, int& s, float gs, float bc1, float rbc2, float gi, float pi, float& m, float& v) {
+#pragma clang fp contract(off)
+    while (s < d.nseg - 1 && i >= d.seg_end[s]) ++s;
+    const float lr = d.seg_lr[s], wd = d.seg_wd[s], beta1 = d.beta1, beta2 = d.beta2;
+    gi *= gs;
+    if (d.decoupled_wd) pi *= __builtin_fmaf(-lr, wd, 1.0f);                    // AdamW: torch.optim.AdamW, p * (1 - lr * wd)
+    else gi += wd * pi;                                                         // Adam with L2 (wd = 0 on this path)
+    const float mi = __builtin_fmaf(1.0f - beta1, gi, beta1 * m);               // beta1 * m + (1 - beta1) * gi
+    const float vi = beta2 * v + ((1.0f - beta2) * gi) * gi;                    // beta2 * v + (1 - beta2) * gi * gi
+    m = mi; v = vi;
+    const float denom = __builtin_fmaf(sqrtf(vi), rbc2, d.eps);                 // sqrt(vi) / sqrt(bc2) + eps
+    return __builtin_fmaf(-(lr / bc1), mi / denom, pi);                         // pi - (lr / bc1) * (mi / denom)
+}
+
+__global__ void __launch_bounds__(256) adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, long n,
+                                                   const sde_adam_desc d) {
+    float gs, bc1, rbc2;
+    if (!adam_prologue(d, gs, bc1, rbc2)) return;
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
         int s = 0;
-        while (s < d.nseg - 1 && i >= d.seg_end[s]) ++s;
-        const float lr = d.seg_lr[s], wd = d.seg_wd[s];
-        float gi = g[i] * gs, pi = p[i];
-        if (d.decoupled_wd) pi *= (1.0f - lr * wd);     // AdamW: torch.optim.AdamW
-        else gi += wd * pi;                             // Adam with L2 (wd = 0 on this path)
-        const float mi = beta1 * m[i] + (1.0f - beta1) * gi;
-        const float vi = beta2 * v[i] + (1.0f - beta2) * gi * gi;
+        float mi = m[i], vi = v[i];
+        p[i] = adam_update(d, i, s, gs, bc1, rbc2, g[i], p[i], mi, vi);
         m[i] = mi; v[i] = vi;
-        const float denom = sqrtf(vi) * rbc2 + d.eps;
-        p[i] = pi - (lr / bc1) * (mi / denom);
+    }
+}
+
+// The same update, four elements per lane (16-byte accesses; the flat buffers are 16-byte aligned), that also leaves twin[i] = from_f32<T>(p[i]): the
+// 16-bit image of the parameters in the SAME flat order.  HipTrainer keeps 4-D weights channels-last in the flat buffer, so a convolution's slot of the
+// twin IS its packed forward operand [Cout][KH][KW][Cin] where no channel padding is needed, and the per-step weight pack has nothing left to cast.
+// A skipped step returns before it touches the twin: p did not change, neither does its image.
+// The twin's element: from_f32 of the STORED fp32 value.  The empty asm keeps the compiler from folding the update's last multiply-add and the
+// conversion into one v_fma_mix*_f16, which rounds the exact sum once to 16 bits -- not what a cast of the fp32 parameter gives.
+template <typename T> __device__ __forceinline__ unsigned short twin_bits(float pn) {
+    asm volatile("" : "+v"(pn));
+    return __builtin_bit_cast(unsigned short, from_f32<T>(pn));
+}
+
+template <typename T>
+__global__ void __launch_bounds__(256) adam_twin_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, long n,
+                                                        T* __restrict__ twin, const sde_adam_desc d) {
+    float gs, bc1, rbc2;
+    if (!adam_prologue(d, gs, bc1, rbc2)) return;
+    typedef __attribute__((ext_vector_type(4))) unsigned short us4;
+    typedef __attribute__((ext_vector_type(4))) float f4v;
+    const long n4 = n >> 2;
+    for (long q = (long)blockIdx.x * 256 + threadIdx.x; q < n4; q += (long)gridDim.x * 256) {
+        // g, m and v are streamed once per step and not touched again before the next optimizer launch: non-temporal, so that they do not push p and the
+        // twin (read by the pack kernels and the first layers a moment later) out of the last-level cache.  Measured 162 -> 139 us per launch at 25.6 M
+        // parameters together with one group of four per lane instead of a capped grid (profiles/twin_operands_ab.txt).
+        const f4v gq = __builtin_nontemporal_load(reinterpret_cast<const f4v*>(g) + q);
+        const f4v m0 = __builtin_nontemporal_load(reinterpret_cast<const f4v*>(m) + q), v0 = __builtin_nontemporal_load(reinterpret_cast<const f4v*>(v) + q);
+        float4 pq = reinterpret_cast<float4*>(p)[q];
+        float mx = m0.x, my = m0.y, mz = m0.z, mw = m0.w, vx = v0.x, vy = v0.y, vz = v0.z, vw = v0.w;
+        int s = 0;
+        pq.x = adam_update(d, 4 * q + 0, s, gs, bc1, rbc2, gq.x, pq.x, mx, vx);
+        pq.y = adam_update(d, 4 * q + 1, s, gs, bc1, rbc2, gq.y, pq.y, my, vy);
+        pq.z = adam_update(d, 4 * q + 2, s, gs, bc1, rbc2, gq.z, pq.z, mz, vz);
+        pq.w = adam_update(d, 4 * q + 3, s, gs, bc1, rbc2, gq.w, pq.w, mw, vw);
+        const f4v m1 = {mx, my, mz, mw}, v1 = {vx, vy, vz, vw};
+        __builtin_nontemporal_store(m1, reinterpret_cast<f4v*>(m) + q);
+        __builtin_nontemporal_store(v1, reinterpret_cast<f4v*>(v) + q);
+        reinterpret_cast<float4*>(p)[q] = pq;
+        us4 o;
+        o.x = twin_bits<T>(pq.x);
+        o.y = twin_bits<T>(pq.y);
+        o.z = twin_bits<T>(pq.z);
+        o.w = twin_bits<T>(pq.w);
+        reinterpret_cast<us4*>(twin)[q] = o;
+    }
+    const long i = 4 * n4 + threadIdx.x;                 // the last n % 4 elements
+    if (blockIdx.x == 0 && i < n) {
+        int s = 0;
+        float mi = m[i], vi = v[i];
+        const float pn = adam_update(d, i, s, gs, bc1, rbc2, g[i], p[i], mi, vi);
+        m[i] = mi; v[i] = vi; p[i] = pn;
+        reinterpret_cast<unsigned short*>(twin)[i] = twin_bits<T>(pn);
     }
 }
 
@@ -1707,16 +1779,36 @@ int sde_gn_relu_res_bwd(const void* dout, const void* out, const void* x, const 
     return SDE_OK;
 }
 
-int sde_adam_step(float* p, const float* g, float* m, float* v, long n, const sde_adam_desc* d, sde_stream_t stream) {
-    SDE_CHECK_ARG(p && g && m && v && d && n > 0, "sde_adam_step: null pointer");
+static int adam_check(const char* who, float* p, const float* g, float* m, float* v, long n, const sde_adam_desc* d) {
+    SDE_CHECK_ARG(p && g && m && v && d && n > 0, "%s: null pointer", who);
     SDE_CHECK_ARG(d->nseg > 0 && d->nseg <= SDE_ADAM_MAX_SEG && (d->scale_state ? (d->beta1_d > 0.0 && d->beta1_d < 1.0 && d->beta2_d > 0.0 && d->beta2_d < 1.0)
                                                                                   : (d->bias_corr1 > 0.f && d->bias_corr2 > 0.f)),
-                  "sde_adam_step: bad descriptor (nseg %d)", d->nseg);
+                  "%s: bad descriptor (nseg %d)", who, d->nseg);
     for (int i = 0; i < d->nseg; ++i)
-        SDE_CHECK_ARG(d->seg_end[i] > (i ? d->seg_end[i - 1] : 0) && d->seg_end[i] <= n, "sde_adam_step: segment %d ends at %ld (n = %ld)", i, d->seg_end[i], n);
-    SDE_CHECK_ARG(d->seg_end[d->nseg - 1] == n, "sde_adam_step: the segments must cover the buffer");
+        SDE_CHECK_ARG(d->seg_end[i] > (i ? d->seg_end[i - 1] : 0) && d->seg_end[i] <= n, "%s: segment %d ends at %ld (n = %ld)", who, i, d->seg_end[i], n);
+    SDE_CHECK_ARG(d->seg_end[d->nseg - 1] == n, "%s: the segments must cover the buffer", who);
+    return SDE_OK;
+}
+
+int sde_adam_step(float* p, const float* g, float* m, float* v, long n, const sde_adam_desc* d, sde_stream_t stream) {
+    const int rc = adam_check("sde_adam_step", p, g, m, v, n, d);
+    if (rc != SDE_OK) return rc;
     hipLaunchKernelGGL(adam_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, *d);
     SDE_CHECK_LAUNCH("sde_adam_step");
+    return SDE_OK;
+}
+
+int sde_adam_step_twin(float* p, const float* g, float* m, float* v, long n, const sde_adam_desc* d, void* twin, int twin_dtype, sde_stream_t stream) {
+    const int rc = adam_check("sde_adam_step_twin", p, g, m, v, n, d);
+    if (rc != SDE_OK) return rc;
+    SDE_CHECK_ARG(twin && SDE_IS16(twin_dtype), "sde_adam_step_twin: the twin is a bf16 or fp16 buffer (dtype %d)", twin_dtype);
+    SDE_CHECK_ARG((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0 && ((uintptr_t)twin & 7) == 0,
+                  "sde_adam_step_twin: p, g, m, v must be 16-byte aligned and the twin 8-byte aligned");
+    SDE_CHECK_ARG(n < (1L << 39), "sde_adam_step_twin: n too large");
+    const dim3 grid((unsigned)(((n >> 2) + 256) / 256));       // one group of four per lane (+ block 0's tail lanes)
+    if (twin_dtype == SDE_BF16) hipLaunchKernelGGL(adam_twin_kernel<bf16_t>, grid, dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, (bf16_t*)twin, *d);
+    else hipLaunchKernelGGL(adam_twin_kernel<half_t>, grid, dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, (half_t*)twin, *d);
+    SDE_CHECK_LAUNCH("sde_adam_step_twin");
     return SDE_OK;
 }
 

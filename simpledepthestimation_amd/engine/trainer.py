@@ -82,7 +82,7 @@ class HipTrainer:
 
     def __init__(self, model, groups, adamw=False, betas=(0.9, 0.999), eps=1e-8, bucket_mb=64, use_graph=False, skip_unused=(".fc.",),
                  adam_fn=None, overlap=None, late_from=("layer3",), cut_owner=None, amp=False, init_scale=65536.0, growth_interval=2000, pose_stream=True, cu_reserve=None,
-                 clip_grad=None, clip_fn=None):
+                 clip_grad=None, clip_fn=None, twin_operands=None):
         self.model = model
         family = schedule_family(model)
         L.apply_schedule(family)
@@ -186,6 +186,18 @@ class HipTrainer:
         self._packer = None            # built lazily after the first eager step (needs the operand shapes seen in forward)
         self._one = None
         self.batch_pack = adam_fn is None
+        # 16-bit twin of pflat, written by the Adam kernel (sde_adam_step_twin): the forward operand of every convolution whose packed operand is the plain
+        # cast of its master slot is a VIEW of it, and the per-step pack shrinks to those layers' data-gradient transposes (16-bit -> 16-bit) plus the few
+        # layers that need padding.  Allocated with the packer (the compute dtype is known then; fp32 compute has no twin).  False restores the per-step
+        # full pack and sde_adam_step exactly (A/B lever: hip.lib.TWIN_OPERANDS, bench.py --const TWIN_OPERANDS=0); a substituted adam_fn (CPU tests)
+        # takes that route by itself.
+        # NOTE: with the twin the step no longer re-reads the fp32 weights.  step() notices in-place writes THROUGH a parameter (model.load_state_dict,
+        # p.copy_(): they bump its version counter) and refreshes by itself; writes it cannot see (p.data, a raw kernel, pflat) need refresh_operands().
+        if twin_operands is None:
+            twin_operands = bool(L.TWIN_OPERANDS)
+        self.twin_operands = bool(twin_operands) and adam_fn is None
+        self.twin = None
+        self._versions = None
         # one weight-gradient slab reduction launch per backward phase (None: immediate mode, every layer reduces and joins at once)
         self._wreduce = HN.WGradReducer() if adam_fn is None else None
 
@@ -272,12 +284,32 @@ class HipTrainer:
             self.scale_state.copy_(torch.tensor([float(sd["loss_scale"]), 0.0, float(sd.get("growth_tracker", 0.0)), float(self.t)]))
         elif self.amp:
             self.scale_state[3] = float(self.t)
+        self.refresh_operands()                     # a checkpoint load usually comes with new parameters: the twin follows them
 
     def _fwd_bwd(self, batch):
         L.mark("step_start")
+        pk = self._packer
+        # with the twin: the data-gradient operands of the layers that share it are first read when backward starts, so their transpose runs on the side
+        # stream under the forward pass (hip.lib.TWIN_PACK_FORK; A/B in profiles/twin_operands_ab.txt -- the gradient fill gained nothing there and stays
+        # here).  The fork event is recorded BEFORE the main stream's next kernel is enqueued and waited for AFTER it: the runtime gives a node's first
+        # captured dependant its queue, and that has to be the forward chain.
+        # (pk.n > 0: there IS such a kernel, the pack of the padded layers; a model without one keeps the transposes on the main stream.)  run_dgrad() holds
+        # only operands that backward reads; what a forward pass reads -- a transposed convolution's -- is in run().
+        fork = pk is not None and pk.n_dgrad > 0 and pk.n > 0 and bool(L.TWIN_PACK_FORK) and L.SIDE_STREAM and self.device.type == "cuda"
         self.gflat.zero_()
-        if self._packer is not None:
-            self._packer.run()                      # every conv operand of the step in one launch
+        if fork:
+            ev = torch.cuda.Event()
+            ev.record()
+        if pk is not None:
+            pk.run()                                # every conv operand of the step in one launch (with the twin: of the layers that do not share it)
+        if fork:
+            side = L.side_stream()
+            side.wait_event(ev)
+            with torch.cuda.stream(side):
+                pk.run_dgrad()
+                L.mark("pack_dgrad_end")
+        elif pk is not None:
+            pk.run_dgrad()                          # ... and the data-gradient operands of those that do, from the twin
         L.POSE_STREAM = self.pose_stream and self.device.type == "cuda"
         try:
             out = self.model(batch)
@@ -293,14 +325,43 @@ class HipTrainer:
         if self._one is None or self._one.dtype != losses.dtype or self._one.device != losses.device or self._one.shape != losses.shape:
             self._one = torch.ones_like(losses)         # d loss / d loss, kept: backward() would launch a fill for it every step
         L.mark("loss_fwd_end")
+        if fork:
+            torch.cuda.current_stream().wait_stream(side)
         self._backward(lambda: losses.backward(gradient=self._one), first_of_two=self._cut is not None)
         L.mark("bwd_joined")
         if self._packer is None and self.batch_pack:
             try:
-                self._packer = HN.WeightPacker(self.model)
+                self._build_packer()
             except Exception:
                 self.batch_pack = False             # model without HIP convolutions
         return loss_dict
+
+    def _slot_of(self, w):
+        """Offset of a parameter's slot in the flat buffers, None when it does not live there."""
+        off = self._off.get(id(w))
+        return off if off is not None and w.data_ptr() == self.pflat.data_ptr() + 4 * off else None
+
+    def _build_packer(self):
+        convs = [m for m in self.model.modules() if getattr(m, "_pack_shapes", None) is not None]
+        dt = convs[0]._pack_shapes[0] if convs else None
+        if self.twin_operands and dt in (torch.bfloat16, torch.float16):
+            twin = torch.zeros(self.numel, device=self.device, dtype=dt)
+            self._packer = HN.WeightPacker(self.model, twin, self._slot_of)
+            self.twin = twin                        # (only once the packer stands: a failed build leaves the trainer on the route without a twin)
+            self.refresh_operands()                 # the twin and every operand valid from here on; the Adam kernel keeps the twin current
+        else:
+            self._packer = HN.WeightPacker(self.model)
+
+    def refresh_operands(self):
+        """Re-derive the 16-bit twin and every packed operand from the fp32 parameters (one eager launch).  With twin_operands the step no longer re-reads
+        the fp32 weights, so whoever writes parameters other than through step() -- loading a checkpoint into the model, an EMA swap, a manual
+        re-initialisation -- calls this before the next step.  load_state_dict() does it by itself.  A no-op without a packer or a twin."""
+        if self._packer is not None and self.twin is not None:
+            self._packer.refresh()
+            self._versions = self._param_versions()
+
+    def _param_versions(self):
+        return sum(p._version for g in self.groups for _, p in g.named_params)
 
     def _backward(self, run, first_of_two=False):
         """One backward phase with the convolutions' weight-gradient reductions deferred to a single launch at its end."""
@@ -357,20 +418,21 @@ class HipTrainer:
         b1, b2 = self.betas
         bias_corr = (1.0 - b1 ** self.t, 1.0 - b2 ** self.t)       # by value: no per-step device scalar to keep ordered with the launch
         lrs, wds = [g.lr for g in self.groups], [g.weight_decay for g in self.groups]
+        tw = {"twin": self.twin} if self.twin is not None else {}       # (a substituted adam_fn never sees the keyword: it has no twin)
         if self.amp:
             # GradScaler.step + update without a host sync: the check raises found_inf on the device, the optimizer kernel divides by the
             # scale and skips itself on overflow, the update kernel backs the scale off or counts towards growth
             HN.grad_check(self.gflat, self.scale_state)
             self._adam_fn(self.pflat, self.gflat, self.m, self.v, self.seg_end, lrs, wds, bias_corr, b1, b2, self.eps, 1.0 / self.world, self.adamw,
-                          scale_state=self.scale_state)
+                          scale_state=self.scale_state, **tw)
             HN.loss_scale_update(self.scale_state, 2.0, 0.5, self.growth_interval)
         elif self.clip_grad is not None:
             # the all-reduce left the SUM over ranks: 1/world makes it the norm of the averaged gradient, the one every rank of the reference clips
             self._clip_fn(self.gflat, self.clip_state, self.clip_grad, 1.0 / self.world, self._clip_work)
             self._adam_fn(self.pflat, self.gflat, self.m, self.v, self.seg_end, lrs, wds, bias_corr, b1, b2, self.eps, 1.0 / self.world, self.adamw,
-                          clip_state=self.clip_state)
+                          clip_state=self.clip_state, **tw)
         else:
-            self._adam_fn(self.pflat, self.gflat, self.m, self.v, self.seg_end, lrs, wds, bias_corr, b1, b2, self.eps, 1.0 / self.world, self.adamw)
+            self._adam_fn(self.pflat, self.gflat, self.m, self.v, self.seg_end, lrs, wds, bias_corr, b1, b2, self.eps, 1.0 / self.world, self.adamw, **tw)
 
     def grad_norm(self):
         """The last step's total gradient norm (what clip_grad_norm_ returns) as a 0-d device tensor: a view of the clip state, no host sync."""
@@ -485,6 +547,8 @@ class HipTrainer:
 
     def step(self, batch):
         """One optimisation step.  Returns {loss name: 0-d device tensor} (no host sync)."""
+        if self.twin is not None and self._param_versions() != self._versions:
+            self.refresh_operands()                 # someone wrote a parameter in place since the twin was last derived (e.g. model.load_state_dict)
         if self.input_transform is not None:
             L.mark("pre_transform")
             batch = self.input_transform(batch, None, self._static_batch if self.use_graph else None)

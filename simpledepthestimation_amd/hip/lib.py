@@ -261,6 +261,12 @@ FORK_MIN_BYTES = 0              # layers with fewer operand bytes keep their wei
                                 # 10 / 25 / 50 / 100 MB -> 7.52 / 7.93 / 8.77 / 7.78 ms/step against 7.26-7.28 at 0: bench.py --const FORK_MIN_BYTES=...)
 
 
+# HipTrainer's 16-bit twin of the flat parameter buffer (engine/trainer.py; profiles/twin_operands_ab.txt keeps the A/B runs):
+TWIN_OPERANDS = 1       # 0: per-step full weight pack from fp32 + sde_adam_step, the route before the twin (bench.py --const TWIN_OPERANDS=0)
+TWIN_PACK_FORK = 1      # 1: the twin's data-gradient transposes on the side stream under the forward pass, joined before backward; 0: head of the step.
+                        # Supervised-R50, four alternating runs each: full pack 6.264, twin at the head 6.244, forked 6.215 ms/step (parent spread 0.013)
+
+
 def side_stream():
     """Per-device helper stream: weight-gradient GEMMs run there concurrently with the data-gradient GEMM of the same layers (fork / join with
     stream / event waits, so they are captured into the step's hipGraph as a parallel branch)."""

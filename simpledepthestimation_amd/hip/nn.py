@@ -84,6 +84,7 @@ L.register_protos({
     "sde_conv3d_wgrad_num_blocks": ([_I, _I, _I, _I, _I], c_int),
     "sde_conv3d_wgrad": ([_P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P], c_int),
     "sde_adam_step": ([_P, _P, _P, _P, _LG, _P, _P], c_int),
+    "sde_adam_step_twin": ([_P, _P, _P, _P, _LG, _P, _P, _I, _P], c_int),
     "sde_grad_check": ([_P, _LG, _P, _P], c_int),
     "sde_grad_norm": ([_P, _LG, _P, _P, _F, _F, _P], c_int),
     "sde_loss_scale_update": ([_P, _F, _F, _I, _P], c_int),
@@ -701,19 +702,44 @@ class PackItem(Structure):
                 ("Cin_pad", c_int32), ("Cout_pad", c_int32), ("src_layout", c_int32), ("reserved", c_int32), ("end", ctypes.c_int64)]
 
 
+W_OIHW, W_OHWI, W_TWIN16 = 0, 1, 2      # SDE_W_*: sde_pack_item.src_layout
+TWIN_ALIGN = 16                          # bytes: every GEMM loader fetches a packed operand in 16-byte pieces (uint4 loads, LDS-DMA dwordx4), see DESIGN.md 5.2
+
+
+def twin_eligible(Cout, Cin, cin_pad, ldy, ohwi, slot_offset, esize=2, base_align=0):
+    """True when a convolution's forward operand [ldy][KH][KW][cin_pad] is exactly the cast of its master slot, so that the slot of the 16-bit twin
+    (sde_adam_step_twin) can BE the operand: channels-last master, no channel padding on either side, whole 16-byte pieces along both channel axes
+    (the data-gradient pack moves 8 elements at a time), and the slot's twin address on the loaders' 16-byte boundary.
+    slot_offset: elements from the start of the flat buffer; base_align: the twin allocation's address modulo TWIN_ALIGN (torch allocations: 0).
+    Slots are multiples of 4 elements only, so a slot behind a one-element bias sits at 8 bytes modulo 16 and stays on the per-step pack."""
+    per = TWIN_ALIGN // esize
+    return bool(ohwi and esize == 2 and ldy == Cout and cin_pad == Cin and Cout % per == 0 and Cin % per == 0
+                and (base_align + slot_offset * esize) % TWIN_ALIGN == 0)
+
+
 class WeightPacker:
     """Packs the forward and data-gradient operands of every convolution of a model in ONE kernel launch per step.
 
     Build it after one forward pass (each HipConv2d then knows the padded shapes its operands need); call run() whenever the master
-    weights changed (HipTrainer does, at the start of every step, inside the captured graph)."""
+    weights changed (HipTrainer does, at the start of every step, inside the captured graph).
 
-    def __init__(self, model):
+    With `twin` (HipTrainer(twin_operands=True): the 16-bit image of the flat parameter buffer that the Adam kernel keeps, `offset_of(weight)` = the
+    weight's slot offset in it) every layer that twin_eligible() accepts gets its slot of the twin as forward operand and leaves the fp32 table:
+    run() packs the rest (stem, one-channel heads, misaligned slots) from fp32 as before -- everything the forward pass reads, so also, from the twin, the
+    "data-gradient" operand of a shared transposed convolution, which is that layer's forward operand; run_dgrad() builds the other shared layers'
+    data-gradient operands from the twin and is safe to run beside the forward pass; refresh() re-derives everything, twin slots included, from the fp32 masters (eager; whenever someone other than the Adam
+    kernel wrote parameters)."""
+
+    def __init__(self, model, twin=None, offset_of=None):
         import numpy as np
         convs = [m for m in model.modules() if getattr(m, "_pack_shapes", None) is not None]
         if not convs:
             raise L.SdeHipError("WeightPacker: run one forward pass first")
         self.dtype = convs[0]._pack_shapes[0]
-        items, end = [], 0
+        if twin is not None and not (twin.dtype == self.dtype and twin.element_size() == 2 and twin.is_contiguous()):
+            raise L.SdeHipError(f"WeightPacker: the twin is {twin.dtype}, the operands {self.dtype}")
+        rest, dgrad, full = [], [], []        # per-step table of the head of the step, per-step twin table, refresh table; `end` is each table's own prefix sum
+        n_shared = 0
         self._keep = []
         for m in convs:
             dt, cin_pad, ldy = m._pack_shapes
@@ -721,30 +747,64 @@ class WeightPacker:
                 raise L.SdeHipError("WeightPacker: mixed compute dtypes")
             w = m.weight
             Cout, Cin, KH, KW = w.shape
-            wp = torch.empty(ldy, KH, KW, cin_pad, device=w.device, dtype=dt)
-            wd = torch.empty(cin_pad, KH, KW, ldy, device=w.device, dtype=dt)
-            m._packed = (wp, wd)
             nb = L.lib().sde_pack_item_blocks(ldy, cin_pad, KH, KW)
             if nb <= 0:
                 raise L.SdeHipError(f"WeightPacker: unsupported kernel size {KH}x{KW}")
-            end += nb
             if not _dense(w):
                 raise L.SdeHipError("WeightPacker: conv weights must be dense (OIHW or channels-last)")
-            items.append((w.data_ptr(), wp.data_ptr(), wd.data_ptr(), Cout, Cin, KH, KW, cin_pad, ldy, 1 if is_ohwi(w) else 0, 0, end))
+            off = offset_of(w) if twin is not None else None
+            ohwi = is_ohwi(w) or (KH * KW == 1 and w.is_contiguous())        # (a 1x1 weight is the same memory either way)
+            shared = off is not None and twin_eligible(Cout, Cin, cin_pad, ldy, ohwi, off, twin.element_size(), twin.data_ptr() % TWIN_ALIGN)
+            wp = twin[off:off + w.numel()].view(ldy, KH, KW, cin_pad) if shared else torch.empty(ldy, KH, KW, cin_pad, device=w.device, dtype=dt)
+            wd = torch.empty(cin_pad, KH, KW, ldy, device=w.device, dtype=dt)
+            m._packed = (wp, wd)
+            shape = (Cout, Cin, KH, KW, cin_pad, ldy)
+            item = (w.data_ptr(), wp.data_ptr(), wd.data_ptr()) + shape + (W_OHWI if is_ohwi(w) else W_OIHW, 0)
+            full.append(item + (nb,))
+            if shared:
+                # a layer whose forward pass reads the "data-gradient" operand (a transposed convolution IS the data gradient of its adjoint) needs it at the
+                # head of the step like any forward operand: its twin item rides in run()'s table, not in the one that may run beside the forward pass
+                early = bool(getattr(m, "FORWARD_READS_DGRAD_OPERAND", False))
+                (rest if early else dgrad).append((wp.data_ptr(), None, wd.data_ptr()) + shape + (W_TWIN16, 0, nb))
+                n_shared += 1
+            else:
+                rest.append(item + (nb,))
             self._keep.append((w, wp, wd))
         dev = convs[0].weight.device
 
         def table(rows):
-            arr = (PackItem * len(rows))(*[PackItem(*it) for it in rows])
-            return torch.from_numpy(np.frombuffer(bytes(arr), dtype=np.uint8).copy()).to(dev)
-        self.items = table(items)
-        self.n, self.total = len(items), end
+            if not rows:
+                return None, 0, 0
+            end, out = 0, []
+            for it in rows:
+                end += it[-1]
+                out.append(PackItem(*it[:-1], end))
+            arr = (PackItem * len(out))(*out)
+            return torch.from_numpy(np.frombuffer(bytes(arr), dtype=np.uint8).copy()).to(dev), len(out), end
+        self.items, self.n, self.total = table(rest)
+        self.items_dgrad, self.n_dgrad, self.total_dgrad = table(dgrad)
+        self.items_full, self.n_full, self.total_full = table(full) if n_shared else (self.items, self.n, self.total)
+        self.n_shared = n_shared
         self._ptrs = [w.data_ptr() for w, _, _ in self._keep]
 
-    def run(self):
+    def _launch(self, items, n, total):
         if any(w.data_ptr() != p for (w, _, _), p in zip(self._keep, self._ptrs)):
             raise L.SdeHipError("WeightPacker: a weight tensor moved (e.g. flattened after the packer was built); rebuild the packer")
-        L.check(L.lib().sde_pack_weights_batched(L.ptr(self.items), self.n, self.total, dtype_code(self.dtype), L.stream()), "sde_pack_weights_batched")
+        if n:
+            L.check(L.lib().sde_pack_weights_batched(L.ptr(items), n, total, dtype_code(self.dtype), L.stream()), "sde_pack_weights_batched")
+
+    def run(self):
+        """Both operands of every layer that does not share the twin, from the fp32 masters (all layers when there is no twin), and the operands that a
+        shared layer's FORWARD pass reads besides its slot of the twin (transposed convolutions)."""
+        self._launch(self.items, self.n, self.total)
+
+    def run_dgrad(self):
+        """The data-gradient operands of the layers whose forward operand is a slot of the twin, transposed from that slot: read by backward only."""
+        self._launch(self.items_dgrad, self.n_dgrad, self.total_dgrad)
+
+    def refresh(self):
+        """Every operand of every layer from the fp32 masters, the shared slots of the twin included."""
+        self._launch(self.items_full, self.n_full, self.total_full)
 
 
 def conv2d(x, weight, bias=None, stride=1, pad=0, reflect=False, act=ACT_NONE, skip=None, upsample=False, bn_stats=False, owner=None, n_out=1):
@@ -1438,11 +1498,12 @@ class AdamDesc(Structure):
 
 
 def adam_step(p, g, m, v, seg_end, seg_lr, seg_wd, bias_corr, beta1=0.9, beta2=0.999, eps=1e-8, grad_scale=1.0, decoupled_wd=False, scale_state=None,
-              clip_state=None):
+              clip_state=None, twin=None):
     """seg_end / seg_lr / seg_wd: HOST sequences (one entry per segment); everything travels by value in the kernel arguments.
     scale_state: optional device float[4] {loss_scale, found_inf, growth_tracker, applied_steps} (fp16 dynamic loss scaling); with it the
     kernel forms the bias corrections itself from the device-side count of APPLIED steps and `bias_corr` is ignored.
-    clip_state: optional device float[2] {total_norm, clip_coef} that grad_norm() filled: the gradient enters the update times clip_coef."""
+    clip_state: optional device float[2] {total_norm, clip_coef} that grad_norm() filled: the gradient enters the update times clip_coef.
+    twin: optional bf16 / fp16 device tensor of p.numel() elements: the kernel also leaves twin[i] = cast(p[i]) (sde_adam_step_twin; same p, m, v)."""
     nseg = len(seg_end)
     if not (0 < nseg <= ADAM_MAX_SEG and len(seg_lr) == nseg and len(seg_wd) == nseg):
         raise L.SdeHipError(f"adam_step: {nseg} segments (at most {ADAM_MAX_SEG})")
@@ -1458,6 +1519,12 @@ def adam_step(p, g, m, v, seg_end, seg_lr, seg_wd, bias_corr, beta1=0.9, beta2=0
     d.clip_state = clip_state.data_ptr() if clip_state is not None else None
     if scale_state is not None and scale_state.numel() < 4:
         raise L.SdeHipError("adam_step: scale_state must hold 4 floats {loss_scale, found_inf, growth_tracker, applied_steps}")
+    if twin is not None:
+        if not (twin.is_cuda and twin.dtype in (torch.bfloat16, torch.float16) and twin.is_contiguous() and twin.numel() == p.numel()):
+            raise L.SdeHipError("adam_step: twin must be a contiguous bf16 / fp16 device tensor with as many elements as p")
+        L.check(L.lib().sde_adam_step_twin(L.ptr(p), L.ptr(g), L.ptr(m), L.ptr(v), p.numel(), ctypes.byref(d), L.ptr(twin), dtype_code(twin.dtype), L.stream()),
+                "sde_adam_step_twin")
+        return
     L.check(L.lib().sde_adam_step(L.ptr(p), L.ptr(g), L.ptr(m), L.ptr(v), p.numel(), ctypes.byref(d), L.stream()), "sde_adam_step")
 
 

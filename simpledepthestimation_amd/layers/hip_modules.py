@@ -44,6 +44,7 @@ class HipConvTranspose2d(nn.Module):
     weight this weight is.  ``_pack_shapes`` / ``_packed`` are therefore that adjoint's: hip.nn.WeightPacker packs the layer with the convolutions."""
 
     SUPPORTED = "kernel_size=3, stride=2, padding=1, output_padding=1"
+    FORWARD_READS_DGRAD_OPERAND = True      # _packed[1] is this layer's FORWARD operand: hip.nn.WeightPacker must have it ready before the forward pass starts
 
     def __init__(self, in_channels, out_channels, kernel_size=3, stride=2, padding=1, output_padding=1, bias=True):
         super().__init__()
