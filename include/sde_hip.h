@@ -696,6 +696,32 @@ int sde_img_to_points_bwd(const float* grad, const float* depth, const float* R,
                           sde_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Raw LiDAR scans -> sparse depth maps (csrc/lidar.hip; binding and host twin in hip/lidar.py): the inverse of the point clouds above, and the
+ * routine that wrote the proj_depth/velodyne caches of the Eigen split (generate_depth_map of monodepth2 / packnet-sfm).
+ *
+ * pts [B][cap][stride] fp32, stride 3 or 4, only x, y, z are read; count [B] int32 in device memory, 0 <= count[b] <= cap, rows behind count[b]
+ * are never read (a count above cap is treated as cap).  proj [B][3][4] fp32 row-major: the whole scanner-to-image matrix (KITTI: P_rect_0c *
+ * R_rect_00 * Tr_velo_to_cam).  origin [B][2] int32 (x0, y0): the top-left corner, in full-image pixels, of the H x W window that is written.
+ * depth [B][H][W] fp32: EVERY element is written, 0 where no point lands.  Per point, in fp32, in exactly this order, nothing fused:
+ *   u = m00 * x + m01 * y + m02 * z + m03;   v, w likewise from rows 1 and 2;   d = w, or x with SDE_LIDAR_VEL_DEPTH;
+ *   kept iff x, y, z are finite, w > 0, 0 < d < inf, and (SDE_LIDAR_FRONT_ONLY) x >= 0;
+ *   px = (int)rintf(u / w) - 1 - x0;   py = (int)rintf(v / w) - 1 - y0        (round-half-even; - 1: the routine's 1-based pixel convention);
+ *   kept iff 0 <= px < W and 0 <= py < H (and |rintf(.)| < 1e9, so that the conversion is defined).
+ * The smallest d that reaches a pixel wins it (integer atomicMin on the bit pattern: order-independent, bit-reproducible); min(d, max_depth) is
+ * applied when the map is finalised, max_depth <= 0 (or NaN): no clipping.
+ * Deviation from the published routine: w > 0 and d > 0.  The routine lets a point behind the image plane project mirrored into the image and
+ * take the pixel with a negative depth, and zeroes that pixel at the end (depth[depth < 0] = 0), hiding whatever positive depth lay there;
+ * with its x >= 0 pre-filter and a forward camera that needs a point less than the camera offset in front of the scanner.  Here such a point
+ * is dropped and the pixel keeps its closest positive depth.
+ * Three launches ordered on the stream (fill, scatter, finalise), each one grid-stride grid over all B; no host synchronisation, no allocation,
+ * no workspace: legal under graph capture.  Refused before any launch: stride not 3 or 4, H, W or cap <= 0, B < 0, unknown flag bits, a NULL
+ * pointer with B > 0.  B == 0 returns 0 and launches nothing. */
+#define SDE_LIDAR_VEL_DEPTH 1
+#define SDE_LIDAR_FRONT_ONLY 2
+int sde_lidar_depth(const float* pts, int cap, int stride, const int* count, int B, const float* proj, const int* origin, int H, int W,
+                    int flags, float max_depth, float* depth, sde_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * MotionLearning loss stack (csrc/motion_loss.hip; autograd wrappers in hip/motion_loss.py).  fp32, planar NCHW, no host synchronisation.
  *
  * sde_view_synthesis_pp: detectron2/geometry/camera.py:L166-202 with a per-pixel translation t [B,3,H,W] and a 3x3 rotation R [B,3,3]; the

@@ -15,6 +15,7 @@ import torch.utils.data as data
 
 from ..utils.registry import Registry
 from .preprocess import build_preprocess
+from .preprocess.loading import LIDAR_RAW
 
 DATASET_REGISTRY = Registry("DATASET")
 
@@ -69,7 +70,8 @@ def collate_samples(batch_list, maps=("depth",), map_lists=("ctx_depth",)):
             ret[key] = [arr[:, i] for i in range(arr.shape[1])]
         elif key == "flip":
             ret[key] = value[0]
-        elif key == "aug_params":
+        elif key == "aug_params" or key in LIDAR_RAW:
+            # LidarDepth ON_DEVICE: lidar_points [B,MAX_POINTS,3], lidar_count / lidar_clip / lidar_flags [B], lidar_window(_orig) [B,4], lidar_proj [B,3,4]
             ret[key] = torch.from_numpy(np.stack(value, 0))
         else:
             ret[key] = value
@@ -205,7 +207,9 @@ class DevicePrefetcher:
     the consumer transforms them -- HipTrainer.input_transform = DeviceImageAug(...) runs the kernels at the head of the step, straight into the
     captured graph's static inputs; that is the faster arrangement on this stack (bench.py --with-loader; DESIGN.md: measured both ways)."""
 
-    _RAW = ("img_u8", "ctx_img_u8", "aug_params", "device_resize", "device_taps")     # consumed by device_aug (which uploads them itself)
+    _RAW = ("img_u8", "ctx_img_u8", "aug_params", "device_resize", "device_taps") + LIDAR_RAW     # consumed by device_aug (which uploads them itself)
+    # steering entries whoever runs DeviceImageAug reads on the host (output sizes, flags): never uploaded, so that reading them synchronises nothing
+    _HOST = ("device_taps", "lidar_window", "lidar_window_orig", "lidar_clip", "lidar_flags")
 
     def __init__(self, loader, device, device_aug=None, slots=4, ahead=2, pick_stream=True):
         self.loader, self.device = loader, torch.device(device)
@@ -254,7 +258,7 @@ class DevicePrefetcher:
 
     def _stage(self, batch, slot):
         if self._stream is None:
-            out = {k: (v if k == "device_taps" else self._move(None, k, v)) for k, v in batch.items()}
+            out = {k: (v if k in self._HOST else self._move(None, k, v)) for k, v in batch.items()}
             return (self.device_aug(out) if self.device_aug is not None else out), None
         bufs = self._bufs[slot]
         self._host_wait(1, slot, self._seq[slot])             # the consumer is done with the batch this slot held (normally long since)
@@ -262,7 +266,7 @@ class DevicePrefetcher:
         with torch.cuda.stream(self._stream):
             _mark("upload_begin")
             # device_taps stays on the host either way: whoever runs DeviceImageAug checks the tables against the frames before the kernel reads through them
-            out = {k: (v if ((self.device_aug is not None and k in self._RAW) or k == "device_taps") else self._move(bufs, k, v)) for k, v in batch.items()}
+            out = {k: (v if ((self.device_aug is not None and k in self._RAW) or k in self._HOST) else self._move(bufs, k, v)) for k, v in batch.items()}
             if self.device_aug is not None:
                 out = self.device_aug(out, bufs)
             _mark("upload_end")

@@ -2,7 +2,8 @@
 
 On-disk formats: the split file lists ``<date>/<date>_drive_<drive>_sync/<cam>/data/<img_id>.png`` entries (whitespace separated); images
 are 8-bit PNGs; ``calib_cam_to_cam.txt`` holds ``key: v0 v1 ...`` lines, ``P_rect_0<cam digit>`` (3x4, row-major) gives the intrinsics K;
-depth ground truth is a 16-bit PNG (or a velodyne .npz).  A sample survives only if its files exist, and -- with FORWARD_CONTEXT /
+depth ground truth is a 16-bit PNG (or a velodyne .npz), or -- DEPTH_TYPE: "lidar", an addition of this package -- it is projected from the raw scan
+``velodyne_points/data/<img_id>.bin`` by the `LidarDepth` step (the sample then carries `lidar_proj`, the scanner-to-image matrix).  A sample survives only if its files exist, and -- with FORWARD_CONTEXT /
 BACKWARD_CONTEXT -- if its neighbours at +-STRIDE frames of the same drive and camera are in the list.
 WITH_POSE adds data['pose_gt'], the OXTS odometry pose relative to the drive's first frame (false in every config of the two projects)."""
 import logging
@@ -56,7 +57,7 @@ class KittiDepthV2(DatasetBase):
                 date, drive, cam, img_id = parse_split_entry(entry)
                 count += 1
                 if not os.path.isfile(self._get_img_dir(date, drive, cam, img_id)) \
-                        or (self.with_depth and not os.path.isfile(self._get_depth_dir(date, drive, cam, img_id))) or cam not in self.use_cams:
+                        or (self.with_depth and not os.path.isfile(self._gt_source(date, drive, cam, img_id))) or cam not in self.use_cams:
                     continue
                 metas.append((date, drive, cam, img_id))
         self.metadatas = sorted(metas)
@@ -104,7 +105,22 @@ class KittiDepthV2(DatasetBase):
                 "intrinsics": self.intrinsics(date, cam)}
         if self.with_pose:
             data["pose_gt"] = self._get_pose(date, drive, img_id)
+        if self.depth_type == "lidar":
+            data["lidar_proj"] = self.lidar_proj(date, cam)
         return self.preprocess(data)
+
+    def lidar_proj(self, date, cam):
+        """[3,4] float32 scanner-to-image matrix of a date and camera (geometry.camera.velo_to_image), cached; every sample gets its own copy."""
+        key = (date, cam, "velo2im")
+        if key not in self.calib_cache:
+            from ...geometry.camera import velo_to_image
+            self.calib_cache[key] = velo_to_image(read_calib(os.path.join(self.data_root, date, "calib_cam_to_cam.txt")),
+                                                  read_calib(os.path.join(self.data_root, date, "calib_velo_to_cam.txt")), cam)
+        return self.calib_cache[key].copy()
+
+    def _gt_source(self, date, drive, cam, img_id):
+        """The file a sample's ground truth comes from: the raw scan for DEPTH_TYPE "lidar", the depth file otherwise."""
+        return self._get_lidar_dir(date, drive, cam, img_id) if self.depth_type == "lidar" else self._get_depth_dir(date, drive, cam, img_id)
 
     def _get_oxts_dir(self, date, drive, img_id):
         return os.path.join(self.data_root, date, f"{date}_drive_{drive}_sync", "oxts", "data", f"{img_id}.txt")
@@ -134,7 +150,7 @@ class KittiDepthV2(DatasetBase):
         return os.path.join(self.data_root, date, f"{date}_drive_{drive}_sync", cam, "data", f"{img_id}.png")
 
     def _get_depth_dir(self, date, drive, cam, img_id):
-        if self.depth_type == "none":
+        if self.depth_type in ("none", "lidar"):
             return ""
         if self.depth_type == "velodyne":
             return os.path.join(self.depth_root, date, f"{date}_drive_{drive}_sync", "proj_depth", "velodyne", cam, f"{img_id}.npz")

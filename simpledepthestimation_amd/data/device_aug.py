@@ -33,7 +33,8 @@ class DeviceImageAug:
     """batch dict with the raw entries of the ON_DEVICE chain (`img_u8`: list of B uint8 [Hs,Ws,3] frames, `ctx_img_u8`: list of B lists of context
     frames, `aug_params`: list of B float32 [8], `device_resize`: (h, w)) -> the same dict with `img`, `img_orig` ([B,3,h,w] fp32 device tensors),
     `ctx_img`, `ctx_img_orig` (lists of those) in their place.  Frames are grouped by source size (KITTI drives differ by a few pixels): one
-    pair of launches per size.  Everything runs on the current stream; nothing synchronises."""
+    pair of launches per size.  The raw entries of LidarDepth ON_DEVICE (`lidar_points`, ...) become `depth` (and `depth_orig`): see `lidar`.
+    Everything runs on the current stream; nothing synchronises."""
 
     def __init__(self, device):
         self.device = torch.device(device)
@@ -131,12 +132,49 @@ class DeviceImageAug:
         b.copy_(t, non_blocking=True)
         return b
 
+    def lidar(self, batch, bufs, static=None):
+        """The raw entries of LidarDepth ON_DEVICE (data/preprocess/loading.py) -> `depth` [B,1,h,w] projected into the batch's final window by
+        sde_lidar_depth, plus -- with `lidar_window_orig` -- `depth_orig`, a list of B device tensors [H,W] at each sample's full size, unclipped
+        (one call per distinct size).  The steering entries (windows, clip, flags) are read on the host: the prefetcher leaves them there."""
+        from ..hip import lidar as HL
+        from .preprocess.loading import LIDAR_RAW
+        out = {k: v for k, v in batch.items() if k not in LIDAR_RAW}
+        host = lambda k: (batch[k].cpu() if torch.is_tensor(batch[k]) else torch.as_tensor(np.asarray(batch[k]))).numpy()
+        win, flags, clip = host("lidar_window").astype(np.int32).reshape(-1, 4), host("lidar_flags").reshape(-1), host("lidar_clip").reshape(-1)
+        B = win.shape[0]
+        if len({(int(r[2]), int(r[3])) for r in win}) != 1 or len(set(flags.tolist())) != 1 or len(set(clip.tolist())) != 1:
+            raise L.SdeHipError("DeviceImageAug: the samples of a batch must share one depth window size, one LidarDepth flag set and one clip")
+        w, h = int(win[0, 2]), int(win[0, 3])
+        vel, front = bool(int(flags[0]) & HL.VEL_DEPTH), bool(int(flags[0]) & HL.FRONT_ONLY)
+        pts = self._up(batch["lidar_points"], bufs, "lidar.points")
+        cnt = self._up(batch["lidar_count"], bufs, "lidar.count")
+        proj = self._up(batch["lidar_proj"], bufs, "lidar.proj")
+        origin = self._up(torch.from_numpy(np.ascontiguousarray(win[:, :2])), bufs, "lidar.origin")
+        dst = (static or {}).get("depth")
+        if not (torch.is_tensor(dst) and dst.is_cuda and dst.dtype == torch.float32 and tuple(dst.shape) == (B, 1, h, w) and dst.is_contiguous()):
+            dst = self._buf(bufs, "lidar.depth", (B, 1, h, w), torch.float32, self.device)
+        out["depth"] = HL.lidar_depth(pts, cnt, proj, origin, h, w, vel, front, float(clip[0]), out=dst)
+        if "lidar_window_orig" in batch:
+            full = host("lidar_window_orig").astype(np.int32).reshape(-1, 4)
+            maps = [None] * B
+            for size in sorted({(int(r[3]), int(r[2])) for r in full}):
+                idx = [b for b in range(B) if (int(full[b, 3]), int(full[b, 2])) == size]
+                sel = (lambda t: t) if len(idx) == B else (lambda t, i=torch.tensor(idx, device=self.device): t.index_select(0, i))
+                o = self._up(torch.from_numpy(np.ascontiguousarray(full[idx, :2])), bufs, ("lidar.origin_orig", size))
+                d = HL.lidar_depth(sel(pts), sel(cnt), sel(proj), o, size[0], size[1], vel, front, None)      # a fresh tensor: evaluators keep it
+                for j, b in enumerate(idx):
+                    maps[b] = d[j, 0]
+            out["depth_orig"] = maps
+        return out
+
     def __call__(self, batch, bufs=None, static=None):
         """static: optional dict holding destination tensors under the output keys (HipTrainer's static batch): the kernels write into them."""
-        if "img_u8" not in batch:
-            return batch
         if bufs is None:
             bufs = self._own            # persistent scratch when no prefetcher slot is given (consumer-side use: one batch at a time)
+        if "lidar_points" in batch:
+            batch = self.lidar(batch, bufs, static)
+        if "img_u8" not in batch:
+            return batch
         st = static or {}
         dst = lambda k, k2, i=None: ((st[k] if i is None else st[k][i]), (st[k2] if i is None else st[k2][i])) if (k in st and k2 in st) else None
         out = {k: v for k, v in batch.items() if k not in ("img_u8", "ctx_img_u8", "aug_params", "device_resize", "device_taps")}

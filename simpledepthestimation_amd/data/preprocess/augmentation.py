@@ -37,6 +37,12 @@ def _crop(data_dict, ys, xs):
     for k in _CROPPED_LISTS:
         if k in data_dict:
             data_dict[k] = [a[ys, xs] for a in data_dict[k]]
+    if "lidar_window" in data_dict:
+        # LidarDepth ON_DEVICE: the depth map does not exist yet; the crop moves and shrinks the window it will be projected into
+        x0, y0, w, h = (int(v) for v in data_dict["lidar_window"])
+        y_start, x_start = ys.indices(h)[0], xs.indices(w)[0]           # the slice's start as numpy resolves it on the h x w image
+        new_h, new_w = data_dict["img"].shape[:2]
+        data_dict["lidar_window"] = np.array([x0 + x_start, y0 + y_start, new_w, new_h], dtype=np.int32)
 
 
 @PREPROCESS_REGISTRY.register()
@@ -158,6 +164,10 @@ class Resize(Preprocess):
 
     def forward(self, data_dict):
         H, W, _ = data_dict["img"].shape
+        if "lidar_window" in data_dict and (H, W) != (self.img_h, self.img_w):
+            # resize_depth is a last-write scatter of the valid pixels; it does not fold into a projection window
+            raise ValueError("Resize behind LidarDepth with ON_DEVICE: True is not supported: the sparse depth would have to be scattered to its scaled "
+                             "positions after the projection.  Use LidarDepth in host mode (ON_DEVICE: False) in front of a Resize.")
         if self.on_device:
             data_dict["device_resize"] = (self.img_h, self.img_w)
             c = self._compaction(H, W) if self.tap_compact else None
@@ -243,6 +253,9 @@ class ClipDepth(Preprocess):
             data_dict["depth"] = np.clip(data_dict["depth"], 0, self.max_depth)
         if "ctx_depth" in data_dict:
             data_dict["ctx_depth"] = [np.clip(d, 0, self.max_depth) for d in data_dict["ctx_depth"]]
+        if "lidar_clip" in data_dict:              # LidarDepth ON_DEVICE: the kernel clips when it finalises the map (depths are >= 0 there)
+            prev = float(data_dict["lidar_clip"])
+            data_dict["lidar_clip"] = np.float32(min(prev, self.max_depth) if prev > 0 else self.max_depth)
         return data_dict
 
 

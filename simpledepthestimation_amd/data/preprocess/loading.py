@@ -111,3 +111,54 @@ class LoadLidar(Preprocess):
         if self.load_ctx:
             data_dict["ctx_lidar"] = [self._load(p) for p in data_dict["metadata"]["ctx_lidar_dir"]]
         return data_dict
+
+
+LIDAR_RAW = ("lidar_points", "lidar_count", "lidar_window", "lidar_clip", "lidar_flags", "lidar_proj", "lidar_window_orig")
+
+
+@PREPROCESS_REGISTRY.register()
+class LidarDepth(Preprocess):
+    """Depth ground truth projected from the raw scan (an addition of this package; the routine is generate_depth_map of monodepth2 / packnet-sfm,
+    stated in include/sde_hip.h).  Stands where LoadDepth stands, behind LoadLidar and LoadImg; needs `lidar`, `lidar_proj` (KittiDepthV2 with
+    DEPTH_TYPE: "lidar") and `img`.
+
+    Host mode: `depth` [H,W] float32 at the image's size from hip.lidar.lidar_depth_np (`depth_orig` with KEEP_ORIG); `lidar` and `lidar_proj` are
+    removed, every later step works as behind LoadDepth.
+    ON_DEVICE: True: nothing is projected here.  The step emits `lidar_points` [MAX_POINTS,3] float32 (zero-padded; pre-filtered to x >= 0 with
+    FRONT_ONLY, which is what the kernel would drop), `lidar_count`, `lidar_window` int32 [x0, y0, w, h] (the whole image), `lidar_clip` (0: none),
+    `lidar_flags`; KBCrop / CropTopTo / RandomCrop move and shrink the window, ClipDepth records its MAX_DEPTH, and data/device_aug.py projects
+    straight into the final window on the GPU (sde_lidar_depth).  KEEP_ORIG keeps the whole-image window as `lidar_window_orig`.  The capacity is
+    fixed so that batches stack and the prefetcher's persistent buffers never change shape; a scan with more points raises."""
+
+    def __init__(self, cfg):
+        super().__init__(cfg)
+        self.vel_depth = bool(cfg.get("VEL_DEPTH", False))
+        self.front_only = bool(cfg.get("FRONT_ONLY", True))
+        self.keep_orig_for_eval = cfg.get("KEEP_ORIG", False)
+        self.on_device = bool(cfg.get("ON_DEVICE", False))
+        self.max_points = int(cfg.get("MAX_POINTS", 131072))
+
+    def forward(self, data_dict):
+        from ...hip.lidar import flag_bits, lidar_depth_np
+        scan = np.asarray(data_dict.pop("lidar"), dtype=np.float32)[:, :3]
+        H, W = data_dict["img"].shape[:2]
+        if not self.on_device:
+            data_dict["depth"] = lidar_depth_np(scan, data_dict.pop("lidar_proj"), (0, 0), H, W, self.vel_depth, self.front_only)
+            if self.keep_orig_for_eval:
+                data_dict["depth_orig"] = data_dict["depth"].copy()
+            return data_dict
+        if self.front_only:
+            scan = scan[scan[:, 0] >= 0]
+        if len(scan) > self.max_points:
+            raise ValueError(f"LidarDepth: the scan {data_dict['metadata'].get('lidar_dir', '')} has {len(scan)} points, MAX_POINTS is {self.max_points}: raise MAX_POINTS")
+        points = np.zeros((self.max_points, 3), dtype=np.float32)
+        points[:len(scan)] = scan
+        data_dict["lidar_points"] = points
+        data_dict["lidar_count"] = np.int32(len(scan))
+        data_dict["lidar_window"] = np.array([0, 0, W, H], dtype=np.int32)
+        data_dict["lidar_clip"] = np.float32(0)
+        data_dict["lidar_flags"] = np.int32(flag_bits(self.vel_depth, self.front_only))
+        data_dict["lidar_proj"] = np.ascontiguousarray(data_dict["lidar_proj"], dtype=np.float32)
+        if self.keep_orig_for_eval:
+            data_dict["lidar_window_orig"] = data_dict["lidar_window"].copy()
+        return data_dict

@@ -1,6 +1,7 @@
 """Camera geometry entry points with the reference's names (detectron2/geometry/camera.py), computed by libsde_hip.so."""
 from functools import lru_cache
 
+import numpy as np
 import torch
 
 from ..hip import cloud as HC
@@ -57,6 +58,20 @@ def img_to_points(depth, R, t):
     """camera.py:L125-138: depth [B,1,H,W], R [B,3,3], t [B,3,1] or [B,3,H*W] -> points [B,3,H,W] = R (depth * image_grid) + t, one launch
     (sde_img_to_points_fwd), differentiable in depth, R and t.  The compacted, coloured cloud of a prediction is hip.cloud.depth_cloud."""
     return HC.img_to_points(depth, R, t)
+
+
+def velo_to_image(cam_calib, velo_calib, cam):
+    """The scanner-to-image matrix of a KITTI raw date -> [3,4] float32: P_rect_0c @ R_rect_00 @ Tr_velo_to_cam, the `P_velo2im` of the published
+    generate_depth_map.  cam_calib / velo_calib: the parsed calib_cam_to_cam.txt / calib_velo_to_cam.txt ({key: array}); cam: 'image_02', '02' or 2.
+    The product is formed in float64 from the parsed values and rounded once.  The matrix is what hip.lidar.lidar_depth takes as `proj`."""
+    c = str(cam)[-1]
+    R = np.eye(4, dtype=np.float64)
+    R[:3, :3] = np.asarray(cam_calib["R_rect_00"], dtype=np.float64).reshape(3, 3)
+    T = np.eye(4, dtype=np.float64)
+    T[:3, :3] = np.asarray(velo_calib["R"], dtype=np.float64).reshape(3, 3)
+    T[:3, 3] = np.asarray(velo_calib["T"], dtype=np.float64).reshape(3)
+    P = np.asarray(cam_calib[f"P_rect_0{c}"], dtype=np.float64).reshape(3, 4)
+    return (P @ R @ T).astype(np.float32)
 
 
 def resize_img(image, dst_size, mode="bilinear"):
