@@ -722,6 +722,40 @@ int sde_lidar_depth(const float* pts, int cap, int stride, const int* count, int
                     int flags, float max_depth, float* depth, sde_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Optical flow between two frames from depth and relative pose (csrc/flow.hip; binding in hip/flow.py): img_to_points into points_to_img,
+ * detectron2/geometry/camera.py:L125-163, for N predictions of ONE source size in one launch.
+ *
+ * pred [N,ph,pw] fp32: the depth of frame A at the network's size.  ymap [H] / xmap [W]: the maps of sde_depth_present, same contract (-1 =
+ * outside: value 0; the caller validates the ranges).  K [N,3,3] fp32, intrinsics at the restored (source) size; only fx = K[0], cx = K[2],
+ * fy = K[4], cy = K[5] are read.  T [N,4,4] fp32 row-major, the pose A -> B: with R = T[:3,:3], t = T[:3,3], p_B = R p_A + t (only those twelve
+ * entries are read).  motion [N,3,ph,pw] fp32 or NULL: a per-pixel translation added to t, read through the same maps, 0 outside them; NULL
+ * gives the rigid (ego-motion) flow.  For the restored pixel (u, v), u = column, v = row, with d its restored depth and m its restored motion,
+ * evaluated in fp32 in exactly this order, nothing fused (every division and the square root correctly rounded):
+ *   Kinv00 = 1 / fx;  Kinv11 = 1 / fy;  Kinv02 = (-1 * cx) / fx;  Kinv12 = (-1 * cy) / fy;                       (sde_depth_cloud's)
+ *   px = d * (Kinv00 * (float)u + Kinv02);   py = d * (Kinv11 * (float)v + Kinv12);   pz = d;
+ *   s_r = t_r + m_r;   q_r = ((R_r0 * px + R_r1 * py) + R_r2 * pz) + s_r                                          for the rows r = x, y, z;
+ *   nx = fx * qx + cx * qz;   ny = fy * qy + cy * qz;   den = qz + 1e-6f;   X = nx / den;   Y = ny / den;
+ *   valid bit 0 (value 1): the pixel is inside both maps, d is finite and > 0, qz > 0, X and Y are finite;
+ *   valid bit 1 (value 2): bit 0 and 0 <= X < (float)(W - 1) and 0 <= Y < (float)(H - 1)         (the reference's valid_proj_mask, L154-156);
+ *   flow = (X - (float)u, Y - (float)v) where bit 0 is set, else (0, 0).
+ * Outputs, device memory, each optional (NULL skips it) but at least one: flow [N,H,W,2] fp32 in pixels of the restored size, valid [N,H,W]
+ * uint8, and canvas, the flow in the colours of the wheel [ncols][3] uint8 (the Middlebury wheel has 55 entries; hip/flow.py builds it).  With
+ * (fx, fy) the flow of a pixel with bit 0, in fp32:
+ *   fu = fx / max_flow;  fv = fy / max_flow;  rad = min(1, sqrtf(fu * fu + fv * fv));
+ *   a = atan2f(-fv, -fu) / (float)pi;   fk = (a + 1) * 0.5f * (float)(ncols - 1);   k0 = (int)fk clamped to [0, ncols - 1];
+ *   k1 = k0 + 1, or 0 when that is ncols;   f = fk - (float)k0;
+ *   per channel, c0 = wheel[k0][ch] / 255.f and c1 = wheel[k1][ch] / 255.f:   col = (1 - f) * c0 + f * c1;   col = 1 - rad * (1 - col);
+ *   byte = (uint8)(255.f * col), truncated, clamped to [0, 255]                    (zero flow is white, |flow| >= max_flow the pure wheel colour).
+ * Pixels without bit 0 are black.  canvas [N][2H][W][3] with frame [N,H,W,3] uint8 (RGB) non-NULL: rows [0, H) the frame, rows [H, 2H) the
+ * colours, as sde_depth_present stacks them; frame == NULL: canvas [N][H][W][3] holds the colours only (frame is ignored without a canvas).
+ * No pointer needs more than its element's alignment.  One launch, no atomics, no workspace, no host synchronisation, no allocation: legal
+ * under graph capture, the same bytes every run.  Refused before any launch: N, H, W, ph, pw <= 0, max_flow <= 0 (or a NaN), ncols <= 0 or
+ * > 256, NULL pred / maps / K / T, all three outputs NULL, a canvas without a wheel. */
+int sde_pair_flow(const float* pred, int N, int ph, int pw, const int* ymap, const int* xmap, int H, int W, const float* K, const float* T,
+                  const float* motion, const uint8_t* wheel, int ncols, float max_flow, const uint8_t* frame, float* flow, uint8_t* valid,
+                  uint8_t* canvas, sde_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * MotionLearning loss stack (csrc/motion_loss.hip; autograd wrappers in hip/motion_loss.py).  fp32, planar NCHW, no host synchronisation.
  *
  * sde_view_synthesis_pp: detectron2/geometry/camera.py:L166-202 with a per-pixel translation t [B,3,H,W] and a 3x3 rotation R [B,3,3]; the

@@ -12,14 +12,19 @@ the picture with matplotlib.  Here the uint8 frame is uploaded from pinned memor
                           into a compacted list of coloured 16-byte points per frame, three launches behind the present kernel (hip/cloud.py).
 
 The three stages are captured once per (source size, batch size) into a graph and replayed; `stream` adds a copy stream that uploads the next
-frame and downloads the previous picture while the current frame is computed."""
+frame and downloads the previous picture while the current frame is computed.
+
+PairPredictor (below) runs a model that has a pose network on a window of frames: the same chain, plus the pose network and sde_pair_flow, the
+relative camera poses and the dense optical flow they imply with the target's depth (hip/flow.py)."""
 import numpy as np
 import torch
 
 from ..data.device_aug import DeviceImageAug
 from ..data.preprocess.augmentation import _linear_coefs
 from ..evaluation.depth_evaluation import backward_maps
+from ..geometry.pose_utils import invert_pose_np
 from ..hip import cloud as HC
+from ..hip import flow as HF
 from ..hip import present as HP
 
 IMAGE_STEPS = ("KBCrop", "CropTopTo", "Resize")       # the steps with a backward(): DatasetEvaluator.preprocess_chain keeps the same three
@@ -149,7 +154,11 @@ class _Slot:
         self.out = None
 
 
-class DepthPredictor:
+class _Predictor:
+    """What DepthPredictor and PairPredictor share: the model, the chain's per-size tables, the slots of pinned and device buffers, eager run or
+    graph capture and replay, and the two-slot pipeline behind `stream`."""
+    NAME = "DepthPredictor"
+
     def __init__(self, cfg, model=None, chain=None, device="cuda", use_graph=None, vmax=None, gamma=0.8):
         self.cfg = cfg
         self.device = torch.device(device)
@@ -166,7 +175,7 @@ class DepthPredictor:
         self.vmax = float(cfg.MODEL.MAX_DEPTH if vmax is None else vmax)
         self.gamma = float(gamma)
         if not (self.vmax > 0 and self.gamma > 0):
-            raise ValueError(f"DepthPredictor: vmax and gamma must be positive ({self.vmax}, {self.gamma})")
+            raise ValueError(f"{self.NAME}: vmax and gamma must be positive ({self.vmax}, {self.gamma})")
         self.use_graph = (self.device.type == "cuda") if use_graph is None else bool(use_graph)
         self._aug = DeviceImageAug(self.device)
         self._plans, self._dev_maps, self._params, self._slots = {}, {}, {}, {}
@@ -191,32 +200,6 @@ class DepthPredictor:
             self._params[N] = p.to(self.device)
         return self._params[N]
 
-    # ---- the device chain -----------------------------------------------------------------------------------------------------------------
-    def _chain(self, plan, frames, K, present, frame_in_canvas, want_u16, cloud=None, K_src=None):
-        """frames: uint8 [N,Hs,Ws,3] on the device, K: [N,3,3] float32 on the device or None; cloud: (min_depth, max_depth, step) or None, K_src: the
-        source-size intrinsics the cloud uses.  Everything on the current stream, nothing synchronises once the tables of this size are on the
-        device (the first call of a size puts them there)."""
-        N = frames.shape[0]
-        img, _ = self._aug.prep(frames, self._no_jitter(N), plan.h, plan.w, tabs=(plan.xtab, plan.ytab))
-        batch = {"img": img}
-        if K is not None:
-            batch["intrinsics"] = K
-        with torch.no_grad():
-            pred = self.model(batch)["depth_pred"]
-        pred = pred.detach().float()
-        if pred.dim() == 4:
-            pred = pred[:, 0]
-        pred = pred.contiguous()
-        out = {"depth_net": pred, "depth": None, "canvas": None, "depth_u16": None}
-        if present:
-            ymap, xmap = self._maps_on_device(plan, pred.shape[-2:])
-            out["canvas"], out["depth"], out["depth_u16"] = HP.depth_present(pred, ymap, xmap, self.vmax, self.gamma, frame=frames if frame_in_canvas else None,
-                                                                             want_depth=True, want_u16=want_u16)
-        if cloud is not None:
-            ymap, xmap = self._maps_on_device(plan, pred.shape[-2:])
-            out["points"], out["count"] = HC.depth_cloud(pred, ymap, xmap, K_src, *cloud, frame=frames)
-        return out
-
     def _slot(self, N, plan, i=0):
         key = (N, plan.Hs, plan.Ws, i)
         if key not in self._slots:
@@ -238,25 +221,8 @@ class DepthPredictor:
             slot.K_host = K
         return slot.K
 
-    @staticmethod
-    def _cloud_args(cloud, intrinsics, N):
-        """cloud=None -> (None, None); a dict -> ((min_depth, max_depth, step), the source-size K as a float32 [N,3,3] host array).  ValueError for
-        a cloud without intrinsics, unknown keys, an empty depth range, step < 1 or a zero focal length; nothing here touches the device."""
-        if cloud is None:
-            return None, None
-        if not isinstance(cloud, dict) or not {"min_depth", "max_depth"} <= set(cloud) <= {"min_depth", "max_depth", "step"}:
-            raise ValueError(f"DepthPredictor: cloud must be None or dict(min_depth=..., max_depth=..., step=1), got {cloud!r}")
-        args = HC.check_range(cloud["min_depth"], cloud["max_depth"], cloud.get("step", 1))
-        if intrinsics is None:
-            raise ValueError("DepthPredictor: cloud needs intrinsics (the source-size K [3,3] or [N,3,3] of the frames)")
-        K = np.asarray(intrinsics.cpu().numpy() if torch.is_tensor(intrinsics) else intrinsics, dtype=np.float32)
-        K = np.array(np.broadcast_to(K, (N, 3, 3)))
-        if not (np.all(np.isfinite(K)) and np.all(K[:, 0, 0] != 0) and np.all(K[:, 1, 1] != 0)):
-            raise ValueError("DepthPredictor: cloud needs finite intrinsics with non-zero focal lengths")
-        return args, K
-
-    def _cloud_K(self, slot, K, N):
-        """The slot's device copy of the cloud's intrinsics, refreshed when they change (None without a cloud)."""
+    def _source_K(self, slot, K, N):
+        """The slot's device copy of the source-size intrinsics (the point cloud's, the flow's), refreshed when they change (None without any)."""
         if K is None:
             return None
         if slot.K_src is None:
@@ -266,12 +232,10 @@ class DepthPredictor:
             slot.K_src_host = K
         return slot.K_src
 
-    def _run(self, slot, plan, K, flags, cloud=None, K_src=None):
-        """The chain on the slot's buffers, on the current stream: eager, or the slot's graph (captured at first use, after one eager run)."""
-        chain = lambda: self._chain(plan, slot.frames, K, *flags, cloud=cloud, K_src=K_src)
+    def _replay(self, slot, key, chain):
+        """chain() on the current stream: eager, or the slot's graph of that key (captured at first use, after one eager run)."""
         if not self.use_graph:
             return chain()
-        key = flags + (K is not None,) + ((cloud,) if cloud is not None else ())       # without a cloud: the key of before
         if key not in slot.graphs:
             cur = torch.cuda.current_stream()
             side = torch.cuda.Stream(device=self.device)
@@ -301,30 +265,15 @@ class DepthPredictor:
             raise ValueError(f"DepthPredictor: frames must be uint8 [H,W,3] or [N,H,W,3] RGB, got {t.dtype} {tuple(t.shape)}")
         return t.contiguous(), single
 
-    def predict(self, frames, intrinsics=None, present=True, frame_in_canvas=True, want_u16=False, cloud=None):
-        """frames: one uint8 [H,W,3] RGB array / tensor, or N of one size.  Returns a dict of device tensors: `depth` [N,H,W] (the prediction restored
-        to the frame's size; None with present=False), `depth_net` [N,h,w] (the network output), `canvas` [N,2H or H,W,3] uint8, `depth_u16` with
-        want_u16 (int16 tensor holding write_depth's uint16 bits).  A single frame keeps the leading 1.  cloud=dict(min_depth=, max_depth=, step=1)
-        adds `points` [N,cap,16] uint8 and `count` [N] int32 (hip.cloud.depth_cloud of the restored depth, the frames' colours and `intrinsics` as
-        given, which it then requires; hip.cloud.as_records reads them on the host).  No host synchronisation after the first call of a size."""
-        t, _ = self._as_frames(frames)
-        N, Hs, Ws, _ = t.shape
-        cloud, K_cloud = self._cloud_args(cloud, intrinsics, N)
-        plan = self.plan(Hs, Ws)
-        slot = self._slot(N, plan)
-        flags = (bool(present), bool(frame_in_canvas), bool(want_u16))
-        with torch.cuda.device(self.device):
-            if t.is_cuda:
-                slot.frames.copy_(t)
-            else:
-                slot.uploaded.synchronize()              # the pinned buffer's previous upload has left it
-                slot.frames_pin.copy_(t)
-                slot.frames.copy_(slot.frames_pin, non_blocking=True)
-                slot.uploaded.record()
-            K = self._set_intrinsics(slot, plan, intrinsics, N)
-            out = self._run(slot, plan, K, flags, cloud, self._cloud_K(slot, K_cloud, N))
-            # the slot's tensors are written again by the next call: hand out copies
-            return {k: (v.clone() if v is not None else None) for k, v in out.items()}
+    def _upload(self, slot, t):
+        """Frames t (uint8 [N,H,W,3], host or device) into the slot's device buffer, on the current stream."""
+        if t.is_cuda:
+            slot.frames.copy_(t)
+        else:
+            slot.uploaded.synchronize()              # the pinned buffer's previous upload has left it
+            slot.frames_pin.copy_(t)
+            slot.frames.copy_(slot.frames_pin, non_blocking=True)
+            slot.uploaded.record()
 
     # ---- streaming ------------------------------------------------------------------------------------------------------------------------
     def _download(self, slot, names):
@@ -342,6 +291,115 @@ class DepthPredictor:
                 h.copy_(v, non_blocking=True)
             slot.downloaded.record(cs)
 
+    def _pump(self, items, names, run, result):
+        """The two-slot pipeline behind `stream`.  items: host uint8 tensors [N,H,W,3], one per result; run(slot, plan) enqueues the chain on the
+        slot's buffers and returns its outputs; result(slot, names) turns the downloaded outputs into what is yielded.  While item i is computed
+        on the current stream, the copy stream uploads item i+1 and downloads the outputs of item i-1; result i-1 is yielded once item i is
+        enqueued.  An item of another size drains the slots and switches tables.  No threads."""
+        if self._copy_stream is None:
+            self._copy_stream = torch.cuda.Stream(device=self.device)
+        cs = self._copy_stream
+        pending, size, i = None, None, 0
+        with torch.cuda.device(self.device):
+            cur = torch.cuda.current_stream()
+            for t in items:
+                if size is not None and tuple(t.shape) != size and pending is not None:
+                    self._download(pending, names)                      # another size: drain what is in flight, then switch tables
+                    yield result(pending, names)
+                    pending = None
+                size = tuple(t.shape)
+                plan = self.plan(size[1], size[2])
+                slot = self._slot(size[0], plan, i % 2)
+                i += 1
+                # upload item i: its pinned buffer was last read by the upload of item i-2 and its device buffer by the compute of item i-2,
+                # whose result has been yielded -- both are over
+                slot.frames_pin.copy_(t)
+                cs.wait_event(slot.computed)
+                with torch.cuda.stream(cs):
+                    slot.frames.copy_(slot.frames_pin, non_blocking=True)
+                    slot.uploaded.record(cs)
+                if pending is not None:
+                    self._download(pending, names)                      # behind the upload on the copy stream, beside this item's compute
+                cur.wait_event(slot.uploaded)
+                cur.wait_event(slot.downloaded)                         # the slot's outputs of item i-2 have left the device
+                slot.out = run(slot, plan)
+                slot.computed.record(cur)
+                if pending is not None:
+                    yield result(pending, names)
+                pending = slot
+            if pending is not None:
+                self._download(pending, names)
+                yield result(pending, names)
+
+
+class DepthPredictor(_Predictor):
+    # ---- the device chain -----------------------------------------------------------------------------------------------------------------
+    def _chain(self, plan, frames, K, present, frame_in_canvas, want_u16, cloud=None, K_src=None):
+        """frames: uint8 [N,Hs,Ws,3] on the device, K: [N,3,3] float32 on the device or None; cloud: (min_depth, max_depth, step) or None, K_src: the
+        source-size intrinsics the cloud uses.  Everything on the current stream, nothing synchronises once the tables of this size are on the
+        device (the first call of a size puts them there)."""
+        N = frames.shape[0]
+        img, _ = self._aug.prep(frames, self._no_jitter(N), plan.h, plan.w, tabs=(plan.xtab, plan.ytab))
+        batch = {"img": img}
+        if K is not None:
+            batch["intrinsics"] = K
+        with torch.no_grad():
+            pred = self.model(batch)["depth_pred"]
+        pred = pred.detach().float()
+        if pred.dim() == 4:
+            pred = pred[:, 0]
+        pred = pred.contiguous()
+        out = {"depth_net": pred, "depth": None, "canvas": None, "depth_u16": None}
+        if present:
+            ymap, xmap = self._maps_on_device(plan, pred.shape[-2:])
+            out["canvas"], out["depth"], out["depth_u16"] = HP.depth_present(pred, ymap, xmap, self.vmax, self.gamma, frame=frames if frame_in_canvas else None,
+                                                                             want_depth=True, want_u16=want_u16)
+        if cloud is not None:
+            ymap, xmap = self._maps_on_device(plan, pred.shape[-2:])
+            out["points"], out["count"] = HC.depth_cloud(pred, ymap, xmap, K_src, *cloud, frame=frames)
+        return out
+
+    @staticmethod
+    def _cloud_args(cloud, intrinsics, N):
+        """cloud=None -> (None, None); a dict -> ((min_depth, max_depth, step), the source-size K as a float32 [N,3,3] host array).  ValueError for
+        a cloud without intrinsics, unknown keys, an empty depth range, step < 1 or a zero focal length; nothing here touches the device."""
+        if cloud is None:
+            return None, None
+        if not isinstance(cloud, dict) or not {"min_depth", "max_depth"} <= set(cloud) <= {"min_depth", "max_depth", "step"}:
+            raise ValueError(f"DepthPredictor: cloud must be None or dict(min_depth=..., max_depth=..., step=1), got {cloud!r}")
+        args = HC.check_range(cloud["min_depth"], cloud["max_depth"], cloud.get("step", 1))
+        if intrinsics is None:
+            raise ValueError("DepthPredictor: cloud needs intrinsics (the source-size K [3,3] or [N,3,3] of the frames)")
+        K = np.asarray(intrinsics.cpu().numpy() if torch.is_tensor(intrinsics) else intrinsics, dtype=np.float32)
+        K = np.array(np.broadcast_to(K, (N, 3, 3)))
+        if not (np.all(np.isfinite(K)) and np.all(K[:, 0, 0] != 0) and np.all(K[:, 1, 1] != 0)):
+            raise ValueError("DepthPredictor: cloud needs finite intrinsics with non-zero focal lengths")
+        return args, K
+
+    def _run(self, slot, plan, K, flags, cloud=None, K_src=None):
+        """The chain on the slot's buffers, on the current stream: eager, or the slot's graph (captured at first use, after one eager run)."""
+        key = flags + (K is not None,) + ((cloud,) if cloud is not None else ())       # without a cloud: the key of before
+        return self._replay(slot, key, lambda: self._chain(plan, slot.frames, K, *flags, cloud=cloud, K_src=K_src))
+
+    def predict(self, frames, intrinsics=None, present=True, frame_in_canvas=True, want_u16=False, cloud=None):
+        """frames: one uint8 [H,W,3] RGB array / tensor, or N of one size.  Returns a dict of device tensors: `depth` [N,H,W] (the prediction restored
+        to the frame's size; None with present=False), `depth_net` [N,h,w] (the network output), `canvas` [N,2H or H,W,3] uint8, `depth_u16` with
+        want_u16 (int16 tensor holding write_depth's uint16 bits).  A single frame keeps the leading 1.  cloud=dict(min_depth=, max_depth=, step=1)
+        adds `points` [N,cap,16] uint8 and `count` [N] int32 (hip.cloud.depth_cloud of the restored depth, the frames' colours and `intrinsics` as
+        given, which it then requires; hip.cloud.as_records reads them on the host).  No host synchronisation after the first call of a size."""
+        t, _ = self._as_frames(frames)
+        N, Hs, Ws, _ = t.shape
+        cloud, K_cloud = self._cloud_args(cloud, intrinsics, N)
+        plan = self.plan(Hs, Ws)
+        slot = self._slot(N, plan)
+        flags = (bool(present), bool(frame_in_canvas), bool(want_u16))
+        with torch.cuda.device(self.device):
+            self._upload(slot, t)
+            K = self._set_intrinsics(slot, plan, intrinsics, N)
+            out = self._run(slot, plan, K, flags, cloud, self._source_K(slot, K_cloud, N))
+            # the slot's tensors are written again by the next call: hand out copies
+            return {k: (v.clone() if v is not None else None) for k, v in out.items()}
+
     def _result(self, slot, names):
         slot.downloaded.synchronize()
         res = {k: (slot.host[k].numpy() if k in ("points", "count") else slot.host[k].numpy()[0]) for k in names if slot.out[k] is not None}
@@ -357,44 +415,205 @@ class DepthPredictor:
         tables.  No threads.  cloud (see predict) adds `points` [1,cap,16] uint8 and `count` [1] int32, the whole buffer downloaded like the other
         outputs: hip.cloud.as_records(res["points"], res["count"])[0] is the frame's cloud."""
         cloud, K_cloud = self._cloud_args(cloud, intrinsics, 1)
-        if self._copy_stream is None:
-            self._copy_stream = torch.cuda.Stream(device=self.device)
-        cs = self._copy_stream
         flags = (bool(present), bool(frame_in_canvas), bool(want_u16))
         names = [k for k, on in (("depth", present), ("canvas", present), ("depth_u16", present and want_u16), ("depth_net", not present),
                                  ("points", cloud is not None), ("count", cloud is not None)) if on]
-        pending, size, i = None, None, 0
-        with torch.cuda.device(self.device):
-            cur = torch.cuda.current_stream()
+
+        def items():
             for frame in frames_iter:
                 t, _ = self._as_frames(frame)
                 if t.is_cuda or t.shape[0] != 1:
                     raise ValueError("DepthPredictor.stream takes one host frame [H,W,3] per item")
-                if size is not None and tuple(t.shape) != size and pending is not None:
-                    self._download(pending, names)                      # another size: drain what is in flight, then switch tables
-                    yield self._result(pending, names)
-                    pending = None
-                size = tuple(t.shape)
-                plan = self.plan(size[1], size[2])
-                slot = self._slot(1, plan, i % 2)
-                i += 1
-                # upload frame i: its pinned buffer was last read by the upload of frame i-2 and its device buffer by the compute of frame i-2,
-                # whose result has been yielded -- both are over
-                slot.frames_pin.copy_(t)
-                cs.wait_event(slot.computed)
-                with torch.cuda.stream(cs):
-                    slot.frames.copy_(slot.frames_pin, non_blocking=True)
-                    slot.uploaded.record(cs)
-                if pending is not None:
-                    self._download(pending, names)                      # behind the upload on the copy stream, beside this frame's compute
-                K = self._set_intrinsics(slot, plan, intrinsics, 1)
-                cur.wait_event(slot.uploaded)
-                cur.wait_event(slot.downloaded)                         # the slot's outputs of frame i-2 have left the device
-                slot.out = self._run(slot, plan, K, flags, cloud, self._cloud_K(slot, K_cloud, 1))
-                slot.computed.record(cur)
-                if pending is not None:
-                    yield self._result(pending, names)
-                pending = slot
-            if pending is not None:
-                self._download(pending, names)
-                yield self._result(pending, names)
+                yield t
+
+        def run(slot, plan):
+            K = self._set_intrinsics(slot, plan, intrinsics, 1)
+            return self._run(slot, plan, K, flags, cloud, self._source_K(slot, K_cloud, 1))
+        yield from self._pump(items(), names, run, self._result)
+
+
+# ---- frame pairs: ego-motion and optical flow ------------------------------------------------------------------------------------------------
+PAIR_ARCHS = ("MonoDepth2Model", "MotionLearningModel")
+SINGLE_CONTEXT_NETS = ("GooglePoseNet", "GoogleMotionNet")
+
+
+def window_offsets(cfg):
+    """The frame offsets of the model's context frames relative to the target, in the order the dataset emits `ctx_img`: ascending from
+    -BACKWARD_CONTEXT * STRIDE to +FORWARD_CONTEXT * STRIDE without 0 (DATASETS.TRAIN, data/datasets/kitti_v2.py).  Their number must be the
+    pose network's: MODEL.POSE_NET.NUM_CONTEXTS for PoseNet, 1 for GooglePoseNet / GoogleMotionNet.  A config without the three keys gets the
+    projects' layouts: (+1,) for one context, (-1, +1) for two.  ValueError for a meta-architecture without a pose network."""
+    arch = cfg.MODEL.META_ARCHITECTURE
+    if arch not in PAIR_ARCHS:
+        raise ValueError(f"PairPredictor: {arch} has no pose network (pose_net); use DepthPredictor for depth alone")
+    n = 1 if cfg.MODEL.POSE_NET.NAME in SINGLE_CONTEXT_NETS else int(cfg.MODEL.POSE_NET.NUM_CONTEXTS)
+    train = cfg.DATASETS.TRAIN if "DATASETS" in cfg and "TRAIN" in cfg.DATASETS else {}
+    back, fwd, stride = (int(train.get(k, 0)) for k in ("BACKWARD_CONTEXT", "FORWARD_CONTEXT", "STRIDE"))
+    if back == 0 and fwd == 0:
+        if n not in (1, 2):
+            raise ValueError(f"PairPredictor: {n} context frames need DATASETS.TRAIN.BACKWARD_CONTEXT / FORWARD_CONTEXT / STRIDE")
+        return (1,) if n == 1 else (-1, 1)
+    if stride <= 0:
+        raise ValueError("PairPredictor: DATASETS.TRAIN.STRIDE must be positive when BACKWARD_CONTEXT / FORWARD_CONTEXT ask for context frames")
+    offsets = tuple(o for o in range(-back * stride, fwd * stride + 1, stride) if o != 0)
+    if len(offsets) != n:
+        raise ValueError(f"PairPredictor: the dataset emits {len(offsets)} context frames {offsets}, the pose network takes {n}")
+    return offsets
+
+
+def next_context(offsets):
+    """Which context gives the pose target -> next frame: (index into the contexts, whether that pose has to be inverted).  The context at
+    +STRIDE when there is one, else the one at -STRIDE inverted (STRIDE: the smallest distance among the offsets)."""
+    stride = min(abs(o) for o in offsets)
+    if stride in offsets:
+        return offsets.index(stride), False
+    return offsets.index(-stride), True
+
+
+def as_window(frames, n):
+    """A window of 1 + n frames (the target, then the contexts in `ctx_img` order; a list or one [1+n,H,W,3] array) -> uint8 [1+n,H,W,3] tensor."""
+    if isinstance(frames, (list, tuple)):
+        if len(frames) != 1 + n:
+            raise ValueError(f"PairPredictor: a window holds the target and {n} context frame(s), got {len(frames)} frame(s)")
+        shapes = {tuple(f.shape) for f in frames}
+        if len(shapes) != 1:
+            raise ValueError(f"PairPredictor: the frames of a window must have one size, got {sorted(shapes)}")
+    t, _ = _Predictor._as_frames(frames)
+    if t.shape[0] != 1 + n:
+        raise ValueError(f"PairPredictor: a window holds the target and {n} context frame(s), got {t.shape[0]} frame(s)")
+    return t
+
+
+class PairPredictor(_Predictor):
+    """A trained MonoDepth2 or MotionLearning model on a window of raw frames: depth of the target as DepthPredictor gives it, the relative
+    camera pose target -> context of every context frame, and the dense optical flow those two imply.  Device work on one stream:
+
+        sde_image_prep_u8     every frame of the window, one launch;
+        depth net             on the target (MotionLearning with POSE_NET.USE_DEPTH: on target and context, whose depth the pose input carries);
+        pose net              on the input the meta-architecture assembles in training: MonoDepth2 cat([img] + ctx_img, 1) of the prepared,
+                              un-normalised frames; MotionLearning both directions stacked along the batch, of which target -> context is kept;
+        sde_pair_flow         one launch over the n contexts: flow, validity and the wheel-coloured picture at the frame's size, from the network
+                              output, the poses (and GoogleMotionNet's motion field unless rigid_only) and the source-size intrinsics;
+        sde_depth_present     the target's restored depth and stacked picture.
+
+    Captured once per (source size, flags) into a graph and replayed.  Poses and flow are up to the scale of the monocular depth."""
+    NAME = "PairPredictor"
+
+    def __init__(self, cfg, model=None, chain=None, device="cuda", use_graph=None, vmax=None, gamma=0.8):
+        self.offsets = window_offsets(cfg)                   # raises for a configuration without a pose network, before anything is built
+        self.n = len(self.offsets)
+        self.next_context = next_context(self.offsets)
+        _Predictor.__init__(self, cfg, model=model, chain=chain, device=device, use_graph=use_graph, vmax=vmax, gamma=gamma)
+        if not hasattr(self.model, "pose_net"):
+            raise ValueError(f"PairPredictor: {type(self.model).__name__} has no pose_net; use DepthPredictor for depth alone")
+        self.stacked = cfg.MODEL.POSE_NET.NAME in SINGLE_CONTEXT_NETS          # MotionLearning's both-directions input
+        self.pose_use_depth = self.stacked and bool(cfg.MODEL.POSE_NET.USE_DEPTH)
+
+    def pose_input(self, img, depth_all=None):
+        """The pose network's input from the prepared window img [1+n,3,h,w] (and, with USE_DEPTH, the depth [2,1,h,w] of target and context)."""
+        if not self.stacked:
+            return torch.cat([img[j:j + 1] for j in range(1 + self.n)], 1)                 # MonoDepth2.py: cat([img] + ctx_img, 1)
+        a = torch.cat([img, depth_all], 1) if self.pose_use_depth else img                  # MotionLearning.py:L63-75: (1, 2) | (2, 1)
+        return torch.cat([a, torch.cat([a[1:], a[:1]], 0)], 1)
+
+    def _chain(self, plan, frames, K, K_src, present, rigid_only, max_flow):
+        N = 1 + self.n
+        img, _ = self._aug.prep(frames, self._no_jitter(N), plan.h, plan.w, tabs=(plan.xtab, plan.ytab))
+        nd = 2 if self.pose_use_depth else 1                   # frames the depth net sees
+        batch = {"img": img[:nd]}
+        if K is not None:
+            batch["intrinsics"] = K[:nd]
+        with torch.no_grad():
+            depth_all = self.model.run_depth_net(batch)["depth_pred"][0].detach().float()
+            pb = self.model.pose_net({"pose_net_input": self.pose_input(img, depth_all if self.pose_use_depth else None)})
+        pose = (pb["pose_pred"][:1] if self.stacked else torch.cat(list(pb["pose_pred"]), 0)).detach().float().contiguous()      # [n,4,4]
+        motion = pb.get("motion_pred") if self.stacked else None
+        if motion is not None:
+            motion = motion[:1].detach().float().contiguous()
+        pred = depth_all[:1, 0].contiguous()
+        out = {"depth_net": pred, "depth": None, "canvas": None, "pose": pose, "motion": motion}
+        ymap, xmap = self._maps_on_device(plan, pred.shape[-2:])
+        out["flow"], out["flow_valid"], out["flow_canvas"] = HF.pair_flow(pred.expand(self.n, -1, -1), ymap, xmap, K_src, pose,
+                                                                          motion=None if rigid_only else motion, max_flow=max_flow, want_canvas=present)
+        if present:
+            out["canvas"], out["depth"], _ = HP.depth_present(pred, ymap, xmap, self.vmax, self.gamma, frame=frames[:1], want_depth=True, want_u16=False)
+        return out
+
+    def _source_intrinsics(self, intrinsics):
+        if intrinsics is None:
+            raise ValueError("PairPredictor: the flow needs intrinsics (the source-size K [3,3] of the frames)")
+        K = np.asarray(intrinsics.cpu().numpy() if torch.is_tensor(intrinsics) else intrinsics, dtype=np.float32)
+        if K.shape != (3, 3) or not (np.all(np.isfinite(K)) and K[0, 0] != 0 and K[1, 1] != 0):
+            raise ValueError("PairPredictor: intrinsics must be a finite [3,3] matrix with non-zero focal lengths")
+        return K
+
+    def _run(self, slot, plan, intrinsics, K_host, present, rigid_only, max_flow):
+        N = 1 + self.n
+        K = self._set_intrinsics(slot, plan, intrinsics, N)
+        K_src = self._source_K(slot, np.array(np.broadcast_to(K_host, (self.n, 3, 3))), self.n)
+        max_flow = float(0.05 * plan.Ws if max_flow is None else max_flow)
+        if not max_flow > 0:
+            raise ValueError(f"PairPredictor: max_flow must be positive, got {max_flow}")
+        key = ("pair", bool(present), bool(rigid_only), max_flow)
+        return self._replay(slot, key, lambda: self._chain(plan, slot.frames, K, K_src, bool(present), bool(rigid_only), max_flow))
+
+    def predict(self, frames, intrinsics, present=True, rigid_only=False, max_flow=None):
+        """frames: the window, a list of 1 + n uint8 [H,W,3] RGB frames of one size -- the target, then the n context frames in the order the dataset
+        emits `ctx_img` (self.offsets, ascending, e.g. the frames at -1 and +1).  intrinsics: the source-size K [3,3] of the frames.  Returns a
+        dict of device tensors: `depth` [1,H,W], `canvas` [1,2H,W,3], `depth_net` [1,h,w] as DepthPredictor returns them for the target; `pose`
+        [n,4,4], target -> context j (p_ctx = R p_target + t); `flow` [n,H,W,2] in pixels of the frame, target -> context j; `flow_valid`
+        [n,H,W] uint8 (bit 0: defined, bit 1: lands inside the context frame); `flow_canvas` [n,H,W,3] uint8, the flow on the colour wheel;
+        `motion` [n,3,h,w], GoogleMotionNet's per-pixel translation, else None.  rigid_only: the flow of the camera motion alone (`motion` is
+        still returned).  max_flow: the flow length, in pixels, that reaches full saturation in `flow_canvas`; default 5 % of the frame's
+        width -- a presentation constant, like gamma.  present=False skips the three pictures.  Translations, and with them the flow's share
+        that comes from them, are up to the scale of the monocular depth.  No host synchronisation after the first call of a size."""
+        t = as_window(frames, self.n)
+        K_host = self._source_intrinsics(intrinsics)
+        plan = self.plan(t.shape[1], t.shape[2])
+        slot = self._slot(t.shape[0], plan)
+        with torch.cuda.device(self.device):
+            self._upload(slot, t)
+            out = self._run(slot, plan, intrinsics, K_host, present, rigid_only, max_flow)
+            return {k: (v.clone() if v is not None else None) for k, v in out.items()}
+
+    def _result(self, slot, names):
+        slot.downloaded.synchronize()
+        res = {k: slot.host[k].numpy() for k in names if slot.out[k] is not None}
+        for k in ("depth", "canvas", "depth_net"):
+            if k in res:
+                res[k] = res[k][0]
+        j, inverted = self.next_context
+        res["pose_next"] = invert_pose_np(res["pose"][j]) if inverted else res["pose"][j].copy()
+        return res
+
+    def stream(self, frames_iter, intrinsics, present=True, rigid_only=False, max_flow=None):
+        """Generator over host frames of a sequence (uint8 [H,W,3] RGB, one at a time, one size).  Keeps a sliding window and yields, in order, one
+        dict of host arrays per target frame that has all its context frames: the outputs of `predict` (`depth` [H,W], `canvas` [2H,W,3], `pose`,
+        `flow`, `flow_valid`, `flow_canvas`, `motion`; with present=False `depth_net` instead of the pictures), `index`, the target's position in
+        the sequence, and `pose_next` [4,4], the pose target -> next frame: the context at +STRIDE when the model has one; otherwise the inverse of
+        the pose to the context at -STRIDE, which is the step previous frame -> target of a model that only looks back.  geometry.pose_utils.accumulate_poses over the yielded `pose_next` is the camera's trajectory, up to the scale of the
+        monocular depth.  The arrays are views of pinned buffers and stay valid until the next iteration; uploads, compute and downloads
+        overlap as in DepthPredictor.stream."""
+        K_host = self._source_intrinsics(intrinsics)
+        names = [k for k, on in (("depth", present), ("canvas", present), ("depth_net", not present), ("pose", True), ("flow", True), ("flow_valid", True),
+                                 ("flow_canvas", present), ("motion", True)) if on]
+        lo, hi = min(self.offsets + (0,)), max(self.offsets + (0,))
+        targets = []
+
+        def windows():
+            held = {}                                          # position in the sequence -> frame, for the span of one window
+            for i, frame in enumerate(frames_iter):
+                t, _ = self._as_frames(frame)
+                if t.is_cuda or t.shape[0] != 1:
+                    raise ValueError("PairPredictor.stream takes one host frame [H,W,3] per item")
+                held[i] = t[0]
+                held.pop(i - (hi - lo) - 1, None)
+                target = i - hi
+                if target + lo >= 0:
+                    targets.append(target)
+                    yield as_window([held[target]] + [held[target + o] for o in self.offsets], self.n)
+
+        def result(slot, names):
+            res = self._result(slot, names)
+            res["index"] = targets.pop(0)
+            return res
+        yield from self._pump(windows(), names, lambda slot, plan: self._run(slot, plan, intrinsics, K_host, present, rigid_only, max_flow), result)

@@ -60,6 +60,22 @@ def img_to_points(depth, R, t):
     return HC.img_to_points(depth, R, t)
 
 
+def points_to_img(points, R, t):
+    """camera.py:L141-163: points [B,3,H,W], R [B,3,3], t [B,3,1] or [B,3,H*W] -> (coords [B,H,W,2] = (X, Y) of R points + t divided by its
+    depth + 1e-6, Z [B,H,W,1] = that depth clamped to >= 1e-5, valid [B,H,W,1] bool = X, Y finite, 0 <= X < W - 1, 0 <= Y < H - 1 and depth > 0).
+    With R = K R_AB and t = K t_AB the coordinates are pixels of frame B.  Torch operators on any device and dtype, differentiable; the fused
+    training path is view_synthesis, the fused inference path (depth and pose -> flow, validity, colours) is hip.flow.pair_flow."""
+    if points.dim() != 4 or points.shape[1] != 3 or R.dim() != 3 or t.dim() != 3:
+        raise ValueError(f"points_to_img: points [B,3,H,W], R [B,3,3], t [B,3,1 or H*W] expected, got {tuple(points.shape)}, {tuple(R.shape)}, {tuple(t.shape)}")
+    B, _, H, W = points.shape
+    proj = R.bmm(points.reshape(B, 3, -1)) + t
+    depth = proj[:, 2]
+    X = proj[:, 0] / (depth + 1e-6)
+    Y = proj[:, 1] / (depth + 1e-6)
+    valid = X.isfinite() & (X >= 0) & (X < W - 1) & Y.isfinite() & (Y >= 0) & (Y < H - 1) & (depth > 0)
+    return torch.stack([X, Y], -1).view(B, H, W, 2), depth.clamp(min=1e-5).view(B, H, W, 1), valid.view(B, H, W, 1)
+
+
 def velo_to_image(cam_calib, velo_calib, cam):
     """The scanner-to-image matrix of a KITTI raw date -> [3,4] float32: P_rect_0c @ R_rect_00 @ Tr_velo_to_cam, the `P_velo2im` of the published
     generate_depth_map.  cam_calib / velo_calib: the parsed calib_cam_to_cam.txt / calib_velo_to_cam.txt ({key: array}); cam: 'image_02', '02' or 2.

@@ -56,6 +56,31 @@ def invert_pose_np(T):
     return out
 
 
+def accumulate_poses(rel):
+    """Relative poses T(i -> i+1), [n,4,4] (array or tensor; p_{i+1} = T_i p_i, what a pose network predicts for consecutive frames) ->
+    camera-to-world poses [n+1,4,4] float64 with frame 0 as the world: W_0 = I, W_{i+1} = W_i T_i^-1.  A few hundred 4x4 products per sequence:
+    float64 on the host.  With a monocular network the translations, and so the trajectory, are known up to one scale factor."""
+    rel = np.asarray(rel.detach().cpu().numpy() if torch.is_tensor(rel) else rel, dtype=np.float64)
+    if rel.ndim != 3 or rel.shape[1:] != (4, 4):
+        raise ValueError(f"accumulate_poses: relative poses [n,4,4] expected, got {rel.shape}")
+    out = np.empty((rel.shape[0] + 1, 4, 4), np.float64)
+    out[0] = np.eye(4)
+    for i, T in enumerate(rel):
+        out[i + 1] = out[i] @ invert_pose_np(T)
+    return out
+
+
+def write_kitti_poses(path, W):
+    """Camera-to-world poses [n,4,4] (or [n,3,4]) -> a text file in the KITTI odometry format: one line per pose, the twelve numbers of its
+    first three rows, row by row, separated by blanks."""
+    W = np.asarray(W.detach().cpu().numpy() if torch.is_tensor(W) else W, dtype=np.float64)
+    if W.ndim != 3 or W.shape[1] not in (3, 4) or W.shape[2] != 4:
+        raise ValueError(f"write_kitti_poses: poses [n,4,4] or [n,3,4] expected, got {W.shape}")
+    with open(path, "w") as f:
+        for P in W:
+            f.write(" ".join(repr(float(v)) for v in P[:3].reshape(-1)) + "\n")      # the shortest text that reads back to the same float64
+
+
 def euler2mat(angle):
     """[B,3] Euler angles -> [B,3,3] rotation (pose_utils.py:L98-127): the rotation block of pose_vec2mat with a zero translation."""
     vec = torch.cat([torch.zeros_like(angle), angle], 1)

@@ -135,6 +135,8 @@ _PROTOS = {
     "sde_img_to_points_bwd": ([_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P], c_int),
     # raw LiDAR scans -> sparse depth maps (csrc/lidar.hip; binding and host twin in hip/lidar.py)
     "sde_lidar_depth": ([_P, _I, _I, _P, _I, _P, _P, _I, _I, _I, _F, _P, _P], c_int),
+    # optical flow from depth and relative pose (csrc/flow.hip; binding in hip/flow.py)
+    "sde_pair_flow": ([_P, _I, _I, _I, _P, _P, _I, _I, _P, _P, _P, _P, _I, _F, _P, _P, _P, _P, _P], c_int),
 }
 
 _lib = None

@@ -9,7 +9,15 @@ frame is uploaded and the previous picture downloaded meanwhile.
 
 With --save-cloud --intrinsics fx fy cx cy, `<stem>.ply` holds the frame's coloured point cloud: every pixel (every --cloud-step-th in both
 directions) whose depth lies in (MODEL.MIN_DEPTH where the config has one, else 0; MODEL.MAX_DEPTH], lifted through the given intrinsics of the
-input frames, in raster order.  The file is a binary_little_endian PLY whose vertex is the 16-byte record of sde_depth_cloud."""
+input frames, in raster order.  The file is a binary_little_endian PLY whose vertex is the 16-byte record of sde_depth_cloud.
+
+With --pairs --intrinsics fx fy cx cy the input is a sequence and the model one with a pose network (MonoDepth2, MotionLearning): frames go through
+PairPredictor.stream, and every frame that has all its context frames gets its `<stem>.png` as above.  --save-flow adds `<stem>_flow.png`, the
+optical flow from that frame to the next one (the previous one for a model that only looks back) on the Middlebury colour wheel, white where
+nothing moves and black where the flow is undefined, and `<stem>.flo`, the same flow as a Middlebury .flo file in pixels; --rigid-only leaves the
+per-pixel motion field of a GoogleMotionNet out of it.  --save-trajectory writes `trajectory.txt`, the camera-to-world pose of the frames in the
+KITTI odometry format (12 numbers per line), frame by frame from the first one on -- every STRIDE-th frame when the model was trained with a
+STRIDE above 1 --, up to the scale of the monocular depth."""
 import argparse
 import os
 import sys
@@ -26,11 +34,23 @@ def parse_args(argv=None):
     p.add_argument("--no-frame", action="store_true", help="pictures hold the coloured depth only, without the camera frame on top")
     p.add_argument("--save-cloud", action="store_true", help="also write <stem>.ply: the coloured point cloud of the frame (needs --intrinsics)")
     p.add_argument("--intrinsics", type=float, nargs=4, metavar=("FX", "FY", "CX", "CY"), help="pinhole intrinsics of the input frames, in pixels")
+    p.add_argument("--pairs", action="store_true", help="treat --input as a sequence: depth, camera motion and optical flow from a model with a pose network "
+                                                        "(needs --intrinsics)")
+    p.add_argument("--save-flow", action="store_true", help="with --pairs: also write <stem>_flow.png, the flow to the next frame in colours, and <stem>.flo")
+    p.add_argument("--save-trajectory", action="store_true", help="with --pairs: also write trajectory.txt, the camera poses in the KITTI odometry format")
+    p.add_argument("--rigid-only", action="store_true", help="with --pairs: the flow of the camera motion alone, without the per-pixel motion field")
     p.add_argument("--cloud-step", type=int, default=1, help="the cloud takes every N-th pixel of every N-th row (default 1: all)")
     p.add_argument("--opts", default=[], nargs=argparse.REMAINDER, help="config overrides as KEY VALUE pairs, e.g. MODEL.WEIGHTS model.pth")
     args = p.parse_args(argv)
     if args.save_cloud and args.intrinsics is None:
         p.error("--save-cloud needs --intrinsics fx fy cx cy")
+    if args.pairs and args.intrinsics is None:
+        raise ValueError("--pairs needs --intrinsics fx fy cx cy: the flow is computed through the frames' intrinsics")
+    for flag in ("save_flow", "save_trajectory", "rigid_only"):
+        if getattr(args, flag) and not args.pairs:
+            p.error(f"--{flag.replace('_', '-')} needs --pairs")
+    if args.pairs and (args.save_cloud or args.save_depth or args.no_frame):
+        p.error("--pairs does not combine with --save-cloud, --save-depth or --no-frame")
     if args.cloud_step < 1:
         p.error("--cloud-step must be at least 1")
     return args
@@ -60,6 +80,51 @@ def write_ply(path, records):
         records.tofile(f)
 
 
+def trajectory_steps(results, offsets):
+    """The chain of poses frame -> next frame that the records of PairPredictor.stream give, as a list of [4,4] arrays, and the position in the
+    sequence of the frame the chain starts at.  A model with a context at -STRIDE supplies the step INTO its first target (the inverse of that
+    target's pose to the context), so that the chain starts STRIDE frames earlier; with STRIDE above 1 every STRIDE-th record is chained."""
+    from ..geometry.pose_utils import invert_pose_np
+    stride = min(abs(o) for o in offsets)
+    chain = [r for r in results if (r["index"] - results[0]["index"]) % stride == 0]
+    steps, start = [r["pose_next"] for r in chain], chain[0]["index"]
+    if stride not in offsets:                        # a model that only looks back: pose_next already is the step previous frame -> target
+        return steps, start - stride
+    if -stride in offsets:
+        steps.insert(0, invert_pose_np(chain[0]["pose"][offsets.index(-stride)]))
+        start -= stride
+    return steps, start
+
+
+def run_pairs(args, cfg, files):
+    import numpy as np
+    from PIL import Image
+
+    from ..data.preprocess.loading import read_rgb
+    from ..engine.predictor import PairPredictor
+    from ..geometry.pose_utils import accumulate_poses, write_kitti_poses
+    from ..hip.flow import write_flo
+    predictor = PairPredictor(cfg)
+    fx, fy, cx, cy = args.intrinsics
+    K = np.array([[fx, 0, cx], [0, fy, cy], [0, 0, 1]], dtype=np.float32)
+    j = predictor.next_context[0]                    # the context whose flow is saved: the next frame, or the previous one
+    kept = []
+    for res in predictor.stream((read_rgb(f) for f in files), K, rigid_only=args.rigid_only):
+        stem = os.path.splitext(os.path.basename(files[res["index"]]))[0]
+        Image.fromarray(res["canvas"]).save(os.path.join(args.output, stem + ".png"), format="PNG", compress_level=3)
+        if args.save_flow:
+            Image.fromarray(res["flow_canvas"][j]).save(os.path.join(args.output, stem + "_flow.png"), format="PNG", compress_level=3)
+            write_flo(os.path.join(args.output, stem + ".flo"), res["flow"][j])
+        kept.append({"index": res["index"], "pose": res["pose"].copy(), "pose_next": res["pose_next"]})
+    if not kept:
+        raise SystemExit(f"--pairs: {len(files)} frame(s) are fewer than one window of the model (offsets {predictor.offsets})")
+    if args.save_trajectory:
+        steps, _ = trajectory_steps(kept, predictor.offsets)
+        write_kitti_poses(os.path.join(args.output, "trajectory.txt"), accumulate_poses(np.stack(steps)))
+    print(f"{len(kept)} picture(s) written to {args.output}")
+    return 0
+
+
 def main(argv=None):
     args = parse_args(argv)
     import numpy as np
@@ -76,6 +141,8 @@ def main(argv=None):
     cfg.freeze()
     files = input_files(args.input)
     os.makedirs(args.output, exist_ok=True)
+    if args.pairs:
+        return run_pairs(args, cfg, files)
     predictor = DepthPredictor(cfg)
     extra = {}
     if args.save_cloud:
