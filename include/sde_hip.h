@@ -756,6 +756,49 @@ int sde_pair_flow(const float* pred, int N, int ph, int pw, const int* ymap, con
                   uint8_t* canvas, sde_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Temporally fused depth for frame sequences (csrc/temporal.hip; binding and host twin in hip/temporal.py): the previous frame's depth is
+ * forward-projected into the current camera, overlaps are resolved by a z-buffer, and the result is blended with the current prediction
+ * where the two agree.  No counterpart in the reference.
+ *
+ * prev, cur [N,h,w] fp32: the previous frame's (fused) depth and the current prediction, both at the network's size.  K [N,3,3] fp32, the
+ * intrinsics AT THAT SIZE; only fx = K[0], cx = K[2], fy = K[4], cy = K[5] are read.  T [N,4,4] fp32 row-major, the pose previous -> current:
+ * with R = T[:3,:3], t = T[:3,3], p_cur = R p_prev + t (only those twelve entries are read).  motion [N,3,h,w] fp32 or NULL: a per-pixel
+ * translation on the PREVIOUS frame's grid, added to t.  zbuf [N,h,w] uint32: workspace, every element is overwritten.  alpha in [0, 1): the
+ * weight of the warped depth in the blend; tol > 0: the relative difference up to which the two depths count as the same surface.
+ * Three launches ordered on the stream, each one grid-stride grid over all N:
+ *   fill     every zbuf element <- 0x7f800000 (+inf).
+ *   scatter  for the previous frame's pixel (u, v), u = column, v = row, d = prev[n,v,u], m its motion (0 with motion == NULL), in fp32 in
+ *            exactly the operation order of sde_pair_flow above, nothing fused:
+ *              Kinv00 = 1 / fx;  Kinv11 = 1 / fy;  Kinv02 = (-1 * cx) / fx;  Kinv12 = (-1 * cy) / fy;
+ *              px = d * (Kinv00 * (float)u + Kinv02);   py = d * (Kinv11 * (float)v + Kinv12);   pz = d;
+ *              s_r = t_r + m_r;   q_r = ((R_r0 * px + R_r1 * py) + R_r2 * pz) + s_r                               for the rows r = x, y, z;
+ *              nx = fx * qx + cx * qz;   ny = fy * qy + cy * qz;   den = qz + 1e-6f;   X = nx / den;   Y = ny / den;
+ *            kept iff d is finite and > 0, qz > 0, qz is finite, X and Y are finite;  rx = rintf(X), ry = rintf(Y) (round-half-even), kept iff
+ *            |rx|, |ry| < 1e9f (so that the conversion is defined) and 0 <= rx < w, 0 <= ry < h;  then ONE no-return
+ *            atomicMin(zbuf[n,ry,rx], bits of qz).  Positive finite floats order like their bit patterns and a minimum does not depend on
+ *            the order of arrival: the same bytes every run.
+ *   fuse     for the current frame's pixel i:  z = zbuf[i];  if z is empty (+inf), z = the unsigned minimum of the non-empty entries among
+ *            the up to eight neighbours inside the image, and, if there is one, the pixel is FILLED;  if z is still empty the pixel is a hole.
+ *              wv = hole ? 0 : float(z);   c = cur[i];   c_ok = c finite and > 0;
+ *              diff = wv - c;   lim = tol * fminf(wv, c);   consistent = !hole && c_ok && fabsf(diff) <= lim;
+ *              fused[i] = consistent ? c + alpha * diff : c;
+ *              state[i] bits 0-1: 0 NEW (a hole, or c not usable), 1 FUSED (consistent), 2 NEARER (inconsistent, diff < 0: the warped surface
+ *              lies in front of the prediction), 3 FARTHER (inconsistent, diff > 0);  bit 2 (value 4): FILLED;
+ *              warped[i] = wv.
+ * fused [N,h,w] fp32 is always written and may alias prev and / or cur (a state buffer updated in place); state [N,h,w] uint8 and warped
+ * [N,h,w] fp32 may each be NULL.  A prev of zeros scatters nothing: fused == cur and state == 0 everywhere, the first frame of a sequence.
+ * The splat is nearest-pixel and the hole filling one ring wide; alpha is fixed and the warped depth is not re-aligned in scale.
+ * No allocation, no host synchronisation, no workspace besides zbuf: legal under graph capture.  Refused before any launch: N, h or w <= 0,
+ * alpha outside [0, 1) (or a NaN), tol <= 0 (or a NaN), NULL prev / cur / K / T / zbuf / fused. */
+#define SDE_TEMPORAL_NEW 0
+#define SDE_TEMPORAL_FUSED 1
+#define SDE_TEMPORAL_NEARER 2
+#define SDE_TEMPORAL_FARTHER 3
+#define SDE_TEMPORAL_FILLED 4
+int sde_depth_warp_fuse(const float* prev, const float* cur, const float* K, const float* T, const float* motion, int N, int h, int w,
+                        float alpha, float tol, uint32_t* zbuf, float* fused, uint8_t* state, float* warped, sde_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * MotionLearning loss stack (csrc/motion_loss.hip; autograd wrappers in hip/motion_loss.py).  fp32, planar NCHW, no host synchronisation.
  *
  * sde_view_synthesis_pp: detectron2/geometry/camera.py:L166-202 with a per-pixel translation t [B,3,H,W] and a 3x3 rotation R [B,3,3]; the

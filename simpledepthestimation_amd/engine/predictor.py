@@ -26,6 +26,7 @@ from ..geometry.pose_utils import invert_pose_np
 from ..hip import cloud as HC
 from ..hip import flow as HF
 from ..hip import present as HP
+from ..hip import temporal as HT
 
 IMAGE_STEPS = ("KBCrop", "CropTopTo", "Resize")       # the steps with a backward(): DatasetEvaluator.preprocess_chain keeps the same three
 KB_H, KB_W = 352, 1216
@@ -232,12 +233,15 @@ class _Predictor:
             slot.K_src_host = K
         return slot.K_src
 
-    def _replay(self, slot, key, chain):
-        """chain() on the current stream: eager, or the slot's graph of that key (captured at first use, after one eager run)."""
+    def _replay(self, slot, key, chain, persistent=()):
+        """chain() on the current stream: eager, or the slot's graph of that key (captured at first use, after one eager run).  persistent:
+        tensors the chain updates in place from run to run; the eager run before the capture must not count as a step, so they are put back
+        to what they held before it."""
         if not self.use_graph:
             return chain()
         if key not in slot.graphs:
             cur = torch.cuda.current_stream()
+            saved = [t.clone() for t in persistent]
             side = torch.cuda.Stream(device=self.device)
             side.wait_stream(cur)
             with torch.cuda.stream(side):           # tables, caches and the allocator's blocks come into being here, outside the capture
@@ -247,6 +251,8 @@ class _Predictor:
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph, capture_error_mode="thread_local"):
                 out = chain()
+            for t, keep in zip(persistent, saved):
+                t.copy_(keep)
             slot.graphs[key] = (graph, out)
         graph, out = slot.graphs[key]
         graph.replay()
@@ -469,6 +475,45 @@ def next_context(offsets):
     return offsets.index(-stride), True
 
 
+def temporal_context(offsets):
+    """The context whose pose steps the temporal fusion from one frame to the next: next_context(offsets), which must lie one frame away."""
+    j, inverted = next_context(offsets)
+    if abs(offsets[j]) != 1:
+        raise ValueError(f"PairPredictor: temporal fusion needs a context one frame away, the model's context offsets are {tuple(offsets)}")
+    return j, inverted
+
+
+def temporal_args(temporal):
+    """temporal=None -> None; dict(alpha=0.5, tol=0.05) (either key may be left out) -> (alpha, tol) as the kernel receives them."""
+    if temporal is None:
+        return None
+    if not isinstance(temporal, dict) or not set(temporal) <= {"alpha", "tol"}:
+        raise ValueError(f"PairPredictor: temporal must be None or dict(alpha=0.5, tol=0.05), got {temporal!r}")
+    return HT.check_params(temporal.get("alpha", 0.5), temporal.get("tol", 0.05))
+
+
+class _TemporalState:
+    """What the temporal fusion keeps on the device from one window to the next, for one network size: the fused depth of the last target, the
+    pose (and motion field) that carries it into the next target, and the z-buffer.  The graphs of both slots read and write these tensors."""
+
+    def __init__(self, h, w, with_motion, device):
+        self.depth = torch.zeros((1, h, w), dtype=torch.float32, device=device)
+        self.eye = torch.eye(4, dtype=torch.float32, device=device)[None].contiguous()
+        self.T = self.eye.clone()
+        self.motion = torch.zeros((1, 3, h, w), dtype=torch.float32, device=device) if with_motion else None
+        self.zbuf = torch.empty((1, h, w), dtype=torch.int32, device=device)
+
+    def tensors(self):
+        return [t for t in (self.depth, self.T, self.motion) if t is not None]
+
+    def reset(self):
+        """An empty state, on the current stream: a depth of zeros scatters nothing, so the next window comes out as it was predicted."""
+        self.depth.zero_()
+        self.T.copy_(self.eye)
+        if self.motion is not None:
+            self.motion.zero_()
+
+
 def as_window(frames, n):
     """A window of 1 + n frames (the target, then the contexts in `ctx_img` order; a list or one [1+n,H,W,3] array) -> uint8 [1+n,H,W,3] tensor."""
     if isinstance(frames, (list, tuple)):
@@ -495,7 +540,15 @@ class PairPredictor(_Predictor):
                               output, the poses (and GoogleMotionNet's motion field unless rigid_only) and the source-size intrinsics;
         sde_depth_present     the target's restored depth and stacked picture.
 
-    Captured once per (source size, flags) into a graph and replayed.  Poses and flow are up to the scale of the monocular depth."""
+    Captured once per (source size, flags) into a graph and replayed.  Poses and flow are up to the scale of the monocular depth.
+
+    `stream(..., temporal=dict(alpha=0.5, tol=0.05))` makes the sequence's depth consistent over time (hip/temporal.py, sde_depth_warp_fuse): the
+    fused depth of the previous target is forward-projected into the current camera with the pose the model estimated, and blended with the
+    current prediction where the two agree.  With a context at +1 the pose (and, unless rigid_only, the motion field) of window k is kept on
+    the device for the warp of window k + 1; a model that only looks back inverts the current window's pose to the context at -1 on the device
+    and warps rigidly, because its motion field lies on the current frame's grid, not on the previous one's.  The pictures come from the fused
+    map; the flow, the pose network and the depth network keep the raw prediction.  The intrinsics of the warp are the network-size ones, so
+    the depth network's output must have the network's input size."""
     NAME = "PairPredictor"
 
     def __init__(self, cfg, model=None, chain=None, device="cuda", use_graph=None, vmax=None, gamma=0.8):
@@ -507,6 +560,7 @@ class PairPredictor(_Predictor):
             raise ValueError(f"PairPredictor: {type(self.model).__name__} has no pose_net; use DepthPredictor for depth alone")
         self.stacked = cfg.MODEL.POSE_NET.NAME in SINGLE_CONTEXT_NETS          # MotionLearning's both-directions input
         self.pose_use_depth = self.stacked and bool(cfg.MODEL.POSE_NET.USE_DEPTH)
+        self._temporal = {}                                   # source size -> _TemporalState
 
     def pose_input(self, img, depth_all=None):
         """The pose network's input from the prepared window img [1+n,3,h,w] (and, with USE_DEPTH, the depth [2,1,h,w] of target and context)."""
@@ -515,7 +569,13 @@ class PairPredictor(_Predictor):
         a = torch.cat([img, depth_all], 1) if self.pose_use_depth else img                  # MotionLearning.py:L63-75: (1, 2) | (2, 1)
         return torch.cat([a, torch.cat([a[1:], a[:1]], 0)], 1)
 
-    def _chain(self, plan, frames, K, K_src, present, rigid_only, max_flow):
+    def _temporal_state(self, plan):
+        key = (plan.Hs, plan.Ws)
+        if key not in self._temporal:
+            self._temporal[key] = _TemporalState(plan.h, plan.w, self.stacked, self.device)
+        return self._temporal[key]
+
+    def _chain(self, plan, frames, K, K_src, present, rigid_only, max_flow, temporal=None, want_u16=False, cloud=None):
         N = 1 + self.n
         img, _ = self._aug.prep(frames, self._no_jitter(N), plan.h, plan.w, tabs=(plan.xtab, plan.ytab))
         nd = 2 if self.pose_use_depth else 1                   # frames the depth net sees
@@ -532,10 +592,34 @@ class PairPredictor(_Predictor):
         pred = depth_all[:1, 0].contiguous()
         out = {"depth_net": pred, "depth": None, "canvas": None, "pose": pose, "motion": motion}
         ymap, xmap = self._maps_on_device(plan, pred.shape[-2:])
+        shown = pred
+        if temporal is not None:
+            alpha, tol, st = temporal
+            j, inverted = temporal_context(self.offsets)
+            if tuple(pred.shape) != tuple(st.depth.shape):
+                raise ValueError(f"PairPredictor: temporal fusion needs the depth at the network's size {tuple(st.depth.shape[1:])}, "
+                                 f"the depth network gives {tuple(pred.shape[1:])}")
+            if inverted:                                        # previous -> current = the inverse of this window's pose to the context at -1
+                Rt, t = pose[j, :3, :3].t(), pose[j, :3, 3]       # [R^T | -R^T t], term by term: separate fp32 roundings, left to right
+                st.T[0, :3, :3].copy_(Rt)
+                st.T[0, :3, 3].copy_(-(Rt[:, 0] * t[0] + Rt[:, 1] * t[1] + Rt[:, 2] * t[2]))
+            carried = not inverted and not rigid_only and motion is not None
+            _, out["temporal_state"], _ = HT.warp_fuse(st.depth, pred, K[:1], st.T, motion=st.motion if carried else None, alpha=alpha, tol=tol,
+                                                       out=st.depth, zbuf=st.zbuf)
+            shown = st.depth.clone()                            # the state moves on with the next window, on the other slot: this slot's copy
+            out["depth_net"], out["depth_net_raw"] = shown, pred
+            if not inverted:                                    # this window's pose to the frame at +1 carries the fused map into the next window
+                st.T.copy_(pose[j:j + 1])
+                if carried:
+                    st.motion.copy_(motion)
         out["flow"], out["flow_valid"], out["flow_canvas"] = HF.pair_flow(pred.expand(self.n, -1, -1), ymap, xmap, K_src, pose,
                                                                           motion=None if rigid_only else motion, max_flow=max_flow, want_canvas=present)
         if present:
-            out["canvas"], out["depth"], _ = HP.depth_present(pred, ymap, xmap, self.vmax, self.gamma, frame=frames[:1], want_depth=True, want_u16=False)
+            out["canvas"], out["depth"], u16 = HP.depth_present(shown, ymap, xmap, self.vmax, self.gamma, frame=frames[:1], want_depth=True, want_u16=want_u16)
+            if want_u16:
+                out["depth_u16"] = u16
+        if cloud is not None:                                   # the target's cloud, from the depth the pictures show
+            out["points"], out["count"] = HC.depth_cloud(shown, ymap, xmap, K_src[:1], *cloud, frame=frames[:1])
         return out
 
     def _source_intrinsics(self, intrinsics):
@@ -546,7 +630,7 @@ class PairPredictor(_Predictor):
             raise ValueError("PairPredictor: intrinsics must be a finite [3,3] matrix with non-zero focal lengths")
         return K
 
-    def _run(self, slot, plan, intrinsics, K_host, present, rigid_only, max_flow):
+    def _run(self, slot, plan, intrinsics, K_host, present, rigid_only, max_flow, temporal=None, want_u16=False, cloud=None):
         N = 1 + self.n
         K = self._set_intrinsics(slot, plan, intrinsics, N)
         K_src = self._source_K(slot, np.array(np.broadcast_to(K_host, (self.n, 3, 3))), self.n)
@@ -554,9 +638,13 @@ class PairPredictor(_Predictor):
         if not max_flow > 0:
             raise ValueError(f"PairPredictor: max_flow must be positive, got {max_flow}")
         key = ("pair", bool(present), bool(rigid_only), max_flow)
-        return self._replay(slot, key, lambda: self._chain(plan, slot.frames, K, K_src, bool(present), bool(rigid_only), max_flow))
+        if temporal is None and not want_u16 and cloud is None:
+            return self._replay(slot, key, lambda: self._chain(plan, slot.frames, K, K_src, bool(present), bool(rigid_only), max_flow))
+        key += ((temporal[:2] if temporal is not None else None),) + ((bool(want_u16), cloud) if want_u16 or cloud is not None else ())
+        return self._replay(slot, key, lambda: self._chain(plan, slot.frames, K, K_src, bool(present), bool(rigid_only), max_flow, temporal, bool(want_u16), cloud),
+                            persistent=temporal[2].tensors() if temporal is not None else ())
 
-    def predict(self, frames, intrinsics, present=True, rigid_only=False, max_flow=None):
+    def predict(self, frames, intrinsics, present=True, rigid_only=False, max_flow=None, temporal=None):
         """frames: the window, a list of 1 + n uint8 [H,W,3] RGB frames of one size -- the target, then the n context frames in the order the dataset
         emits `ctx_img` (self.offsets, ascending, e.g. the frames at -1 and +1).  intrinsics: the source-size K [3,3] of the frames.  Returns a
         dict of device tensors: `depth` [1,H,W], `canvas` [1,2H,W,3], `depth_net` [1,h,w] as DepthPredictor returns them for the target; `pose`
@@ -565,7 +653,10 @@ class PairPredictor(_Predictor):
         `motion` [n,3,h,w], GoogleMotionNet's per-pixel translation, else None.  rigid_only: the flow of the camera motion alone (`motion` is
         still returned).  max_flow: the flow length, in pixels, that reaches full saturation in `flow_canvas`; default 5 % of the frame's
         width -- a presentation constant, like gamma.  present=False skips the three pictures.  Translations, and with them the flow's share
-        that comes from them, are up to the scale of the monocular depth.  No host synchronisation after the first call of a size."""
+        that comes from them, are up to the scale of the monocular depth.  No host synchronisation after the first call of a size.  predict keeps
+        nothing from call to call: temporal fusion is `stream`'s, and anything but temporal=None is refused."""
+        if temporal is not None:
+            raise ValueError("PairPredictor.predict is stateless: temporal fusion needs the frames in order, use stream(..., temporal=...)")
         t = as_window(frames, self.n)
         K_host = self._source_intrinsics(intrinsics)
         plan = self.plan(t.shape[1], t.shape[2])
@@ -578,24 +669,43 @@ class PairPredictor(_Predictor):
     def _result(self, slot, names):
         slot.downloaded.synchronize()
         res = {k: slot.host[k].numpy() for k in names if slot.out[k] is not None}
-        for k in ("depth", "canvas", "depth_net"):
+        for k in ("depth", "canvas", "depth_net", "depth_net_raw", "temporal_state", "depth_u16"):
             if k in res:
                 res[k] = res[k][0]
+        if "depth_u16" in res:
+            res["depth_u16"] = res["depth_u16"].view(np.uint16)
         j, inverted = self.next_context
         res["pose_next"] = invert_pose_np(res["pose"][j]) if inverted else res["pose"][j].copy()
         return res
 
-    def stream(self, frames_iter, intrinsics, present=True, rigid_only=False, max_flow=None):
+    def stream(self, frames_iter, intrinsics, present=True, rigid_only=False, max_flow=None, temporal=None, want_u16=False, cloud=None):
         """Generator over host frames of a sequence (uint8 [H,W,3] RGB, one at a time, one size).  Keeps a sliding window and yields, in order, one
         dict of host arrays per target frame that has all its context frames: the outputs of `predict` (`depth` [H,W], `canvas` [2H,W,3], `pose`,
         `flow`, `flow_valid`, `flow_canvas`, `motion`; with present=False `depth_net` instead of the pictures), `index`, the target's position in
         the sequence, and `pose_next` [4,4], the pose target -> next frame: the context at +STRIDE when the model has one; otherwise the inverse of
         the pose to the context at -STRIDE, which is the step previous frame -> target of a model that only looks back.  geometry.pose_utils.accumulate_poses over the yielded `pose_next` is the camera's trajectory, up to the scale of the
         monocular depth.  The arrays are views of pinned buffers and stay valid until the next iteration; uploads, compute and downloads
-        overlap as in DepthPredictor.stream."""
+        overlap as in DepthPredictor.stream.
+
+        temporal=dict(alpha=0.5, tol=0.05): temporally fused depth (see the class).  `depth` and `canvas` then come from the fused map, and every
+        record also holds `depth_net` [h,w], the fused map at the network's size, `depth_net_raw` [h,w], the prediction it was fused with, and
+        `temporal_state` [h,w] uint8: bits 0-1 the class of the pixel (0 new, 1 fused, 2 / 3 the warped surface lies nearer / farther than the
+        prediction, which is kept), bit 2 set where a one-pixel hole of the warp was filled.  alpha in [0, 1) is the weight of the warped
+        depth, tol > 0 the relative difference up to which the two count as one surface.  Every call starts from an empty state: its first
+        window is the raw prediction, with state 0 everywhere.  ValueError for a model without a context one frame away.
+
+        want_u16 (with present) adds `depth_u16` [H,W] and cloud=dict(min_depth=, max_depth=, step=1) adds `points` [1,cap,16] and `count` [1] of
+        the target, as DepthPredictor.stream yields them, from the depth the pictures show (the fused one with temporal)."""
         K_host = self._source_intrinsics(intrinsics)
-        names = [k for k, on in (("depth", present), ("canvas", present), ("depth_net", not present), ("pose", True), ("flow", True), ("flow_valid", True),
-                                 ("flow_canvas", present), ("motion", True)) if on]
+        fuse = temporal_args(temporal)
+        cloud, _ = DepthPredictor._cloud_args(cloud, K_host, 1)
+        want_u16 = bool(want_u16 and present)
+        if fuse is not None:
+            temporal_context(self.offsets)
+        names = [k for k, on in (("depth", present), ("canvas", present), ("depth_net", not present or fuse is not None), ("depth_net_raw", fuse is not None),
+                                 ("temporal_state", fuse is not None), ("pose", True), ("flow", True), ("flow_valid", True), ("flow_canvas", present),
+                                 ("motion", True), ("depth_u16", want_u16), ("points", cloud is not None), ("count", cloud is not None)) if on]
+        live = []                                              # the state this call has reset and is advancing
         lo, hi = min(self.offsets + (0,)), max(self.offsets + (0,))
         targets = []
 
@@ -616,4 +726,13 @@ class PairPredictor(_Predictor):
             res = self._result(slot, names)
             res["index"] = targets.pop(0)
             return res
-        yield from self._pump(windows(), names, lambda slot, plan: self._run(slot, plan, intrinsics, K_host, present, rigid_only, max_flow), result)
+
+        def run(slot, plan):
+            if fuse is None:
+                return self._run(slot, plan, intrinsics, K_host, present, rigid_only, max_flow, want_u16=want_u16, cloud=cloud)
+            st = self._temporal_state(plan)
+            if not live or live[0] is not st:                  # the first window of this call, or frames of another size: an empty state
+                st.reset()
+                live[:] = [st]
+            return self._run(slot, plan, intrinsics, K_host, present, rigid_only, max_flow, temporal=fuse + (st,), want_u16=want_u16, cloud=cloud)
+        yield from self._pump(windows(), names, run, result)

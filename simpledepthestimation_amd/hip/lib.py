@@ -137,6 +137,8 @@ _PROTOS = {
     "sde_lidar_depth": ([_P, _I, _I, _P, _I, _P, _P, _I, _I, _I, _F, _P, _P], c_int),
     # optical flow from depth and relative pose (csrc/flow.hip; binding in hip/flow.py)
     "sde_pair_flow": ([_P, _I, _I, _I, _P, _P, _I, _I, _P, _P, _P, _P, _I, _F, _P, _P, _P, _P, _P], c_int),
+    # temporally fused depth: forward warp, z-buffer, blend (csrc/temporal.hip; binding and host twin in hip/temporal.py)
+    "sde_depth_warp_fuse": ([_P, _P, _P, _P, _P, _I, _I, _I, _F, _F, _P, _P, _P, _P, _P], c_int),
 }
 
 _lib = None

@@ -12,12 +12,20 @@ directions) whose depth lies in (MODEL.MIN_DEPTH where the config has one, else 
 input frames, in raster order.  The file is a binary_little_endian PLY whose vertex is the 16-byte record of sde_depth_cloud.
 
 With --pairs --intrinsics fx fy cx cy the input is a sequence and the model one with a pose network (MonoDepth2, MotionLearning): frames go through
-PairPredictor.stream, and every frame that has all its context frames gets its `<stem>.png` as above.  --save-flow adds `<stem>_flow.png`, the
+PairPredictor.stream, and every frame that has all its context frames gets its `<stem>.png` as above (and, with --save-depth / --save-cloud, its `<stem>_depth.png` /
+`<stem>.ply`).  --save-flow adds `<stem>_flow.png`, the
 optical flow from that frame to the next one (the previous one for a model that only looks back) on the Middlebury colour wheel, white where
 nothing moves and black where the flow is undefined, and `<stem>.flo`, the same flow as a Middlebury .flo file in pixels; --rigid-only leaves the
 per-pixel motion field of a GoogleMotionNet out of it.  --save-trajectory writes `trajectory.txt`, the camera-to-world pose of the frames in the
 KITTI odometry format (12 numbers per line), frame by frame from the first one on -- every STRIDE-th frame when the model was trained with a
-STRIDE above 1 --, up to the scale of the monocular depth."""
+STRIDE above 1 --, up to the scale of the monocular depth.
+
+--stabilise (with --pairs) makes the sequence's depth consistent over time: PairPredictor.stream(..., temporal=dict(alpha, tol)) warps the fused
+depth of the previous frame into the current camera with the pose the model estimated and blends it with the current prediction where the two
+agree within --stabilise-tol (relative; default 0.05), with weight --stabilise-alpha (default 0.5) for the warped depth.  The pictures then show
+the fused depth.  --save-state adds `<stem>_state.png`, the class of every pixel at the network's size in four fixed colours: dark grey where
+the pixel is new (nothing was warped there), green where the two depths were fused, orange / blue where the warped surface lies nearer / farther
+than the prediction, which is then kept.  The model needs a context one frame away."""
 import argparse
 import os
 import sys
@@ -39,6 +47,11 @@ def parse_args(argv=None):
     p.add_argument("--save-flow", action="store_true", help="with --pairs: also write <stem>_flow.png, the flow to the next frame in colours, and <stem>.flo")
     p.add_argument("--save-trajectory", action="store_true", help="with --pairs: also write trajectory.txt, the camera poses in the KITTI odometry format")
     p.add_argument("--rigid-only", action="store_true", help="with --pairs: the flow of the camera motion alone, without the per-pixel motion field")
+    p.add_argument("--stabilise", action="store_true", help="with --pairs: temporally fused depth (the previous frame's depth warped by the estimated pose and "
+                                                            "blended with the prediction)")
+    p.add_argument("--stabilise-alpha", type=float, default=0.5, help="with --stabilise: weight of the warped depth in the blend, in [0, 1) (default 0.5)")
+    p.add_argument("--stabilise-tol", type=float, default=0.05, help="with --stabilise: relative depth difference up to which the two are blended (default 0.05)")
+    p.add_argument("--save-state", action="store_true", help="with --stabilise: also write <stem>_state.png, the class of every pixel in four colours")
     p.add_argument("--cloud-step", type=int, default=1, help="the cloud takes every N-th pixel of every N-th row (default 1: all)")
     p.add_argument("--opts", default=[], nargs=argparse.REMAINDER, help="config overrides as KEY VALUE pairs, e.g. MODEL.WEIGHTS model.pth")
     args = p.parse_args(argv)
@@ -46,11 +59,15 @@ def parse_args(argv=None):
         p.error("--save-cloud needs --intrinsics fx fy cx cy")
     if args.pairs and args.intrinsics is None:
         raise ValueError("--pairs needs --intrinsics fx fy cx cy: the flow is computed through the frames' intrinsics")
-    for flag in ("save_flow", "save_trajectory", "rigid_only"):
+    if args.save_state and not args.stabilise:
+        p.error("--save-state needs --stabilise")
+    if not (0.0 <= args.stabilise_alpha < 1.0) or not args.stabilise_tol > 0.0:
+        p.error("--stabilise-alpha must lie in [0, 1) and --stabilise-tol must be positive")
+    for flag in ("save_flow", "save_trajectory", "rigid_only", "stabilise"):
         if getattr(args, flag) and not args.pairs:
             p.error(f"--{flag.replace('_', '-')} needs --pairs")
-    if args.pairs and (args.save_cloud or args.save_depth or args.no_frame):
-        p.error("--pairs does not combine with --save-cloud, --save-depth or --no-frame")
+    if args.pairs and args.no_frame:
+        p.error("--pairs does not combine with --no-frame")
     if args.cloud_step < 1:
         p.error("--cloud-step must be at least 1")
     return args
@@ -103,18 +120,28 @@ def run_pairs(args, cfg, files):
     from ..data.preprocess.loading import read_rgb
     from ..engine.predictor import PairPredictor
     from ..geometry.pose_utils import accumulate_poses, write_kitti_poses
+    from ..hip.cloud import as_records
     from ..hip.flow import write_flo
+    from ..hip.temporal import state_picture
     predictor = PairPredictor(cfg)
     fx, fy, cx, cy = args.intrinsics
     K = np.array([[fx, 0, cx], [0, fy, cy], [0, 0, 1]], dtype=np.float32)
     j = predictor.next_context[0]                    # the context whose flow is saved: the next frame, or the previous one
     kept = []
-    for res in predictor.stream((read_rgb(f) for f in files), K, rigid_only=args.rigid_only):
+    temporal = dict(alpha=args.stabilise_alpha, tol=args.stabilise_tol) if args.stabilise else None
+    cloud = dict(min_depth=float(cfg.MODEL.get("MIN_DEPTH", 0.0)), max_depth=float(cfg.MODEL.MAX_DEPTH), step=args.cloud_step) if args.save_cloud else None
+    for res in predictor.stream((read_rgb(f) for f in files), K, rigid_only=args.rigid_only, temporal=temporal, want_u16=args.save_depth, cloud=cloud):
         stem = os.path.splitext(os.path.basename(files[res["index"]]))[0]
         Image.fromarray(res["canvas"]).save(os.path.join(args.output, stem + ".png"), format="PNG", compress_level=3)
         if args.save_flow:
             Image.fromarray(res["flow_canvas"][j]).save(os.path.join(args.output, stem + "_flow.png"), format="PNG", compress_level=3)
             write_flo(os.path.join(args.output, stem + ".flo"), res["flow"][j])
+        if args.save_depth:
+            Image.fromarray(np.ascontiguousarray(res["depth_u16"])).save(os.path.join(args.output, stem + "_depth.png"), format="PNG", compress_level=3)
+        if args.save_cloud:
+            write_ply(os.path.join(args.output, stem + ".ply"), as_records(res["points"], res["count"])[0])
+        if args.save_state:
+            Image.fromarray(state_picture(res["temporal_state"])).save(os.path.join(args.output, stem + "_state.png"), format="PNG", compress_level=3)
         kept.append({"index": res["index"], "pose": res["pose"].copy(), "pose_next": res["pose_next"]})
     if not kept:
         raise SystemExit(f"--pairs: {len(files)} frame(s) are fewer than one window of the model (offsets {predictor.offsets})")
