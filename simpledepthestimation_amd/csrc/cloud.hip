@@ -19,6 +19,7 @@
 //
 // Built with -ffp-contract=off: the coordinates keep the operation order stated in include/sde_hip.h, which the tests' bound counts.
 #include "common.h"
+#include "pinhole.h"
 #include "sde_hip.h"
 
 namespace {
@@ -112,12 +113,8 @@ __global__ void __launch_bounds__(TILE) cloud_scatter(CloudP p) {
     if (!keep) return;
     int at = p.ws[(size_t)n * p.nblk + blockIdx.x] + __popcll(m & ((1ull << lane) - 1ull));
     for (int i = 0; i < wave; ++i) at += wsum[i];
-    // the reference's inv_intrinsics, then x = d * (Kinv00 * u + Kinv02): five roundings per coordinate, none fused
-    const float* K = p.K + (size_t)n * 9;
-    const float fx = K[0], cx = K[2], fy = K[4], cy = K[5];
-    const float k00 = 1.f / fx, k11 = 1.f / fy, k02 = (-1.f * cx) / fx, k12 = (-1.f * cy) / fy;
-    const float x = d * (k00 * (float)u + k02);
-    const float y = d * (k11 * (float)v + k12);
+    float x, y;
+    pinhole_lift(pinhole_load(p.K + (size_t)n * 9), (float)u, (float)v, d, x, y);
     uint32_t rgba = 0xffffffffu;
     if (p.frame) {
         const uint8_t* f = p.frame + (((size_t)n * p.H + v) * p.W + u) * 3;

@@ -13,6 +13,7 @@
 // the same for a whole workgroup.  The wheel sits in LDS as one packed dword per entry.  No atomics, no workspace, nothing read back: legal under
 // graph capture, the same bytes every run.
 #include "common.h"
+#include "pinhole.h"
 #include "sde_hip.h"
 #include "wide_io.h"
 
@@ -40,8 +41,8 @@ struct FlowP {
     float max_flow;
 };
 
-struct Cam {                     // what every pixel of one image shares
-    float k00, k02, k11, k12, fx, cx, fy, cy, R[9], t[3], xlim, ylim;
+struct Cam {                     // what every pixel of one image shares besides the intrinsics
+    float R[9], t[3], xlim, ylim;
 };
 
 __device__ __forceinline__ uint32_t channel(uint32_t w0, uint32_t w1, int shift, float f, float rad) {
@@ -68,18 +69,13 @@ __device__ __forceinline__ uint32_t flow_colour(float fx, float fy, float max_fl
 }
 
 // one pixel: depth d and translation (m0, m1, m2) = t + m already formed -> flow and validity bits
-__device__ __forceinline__ uint32_t project(const Cam& c, bool inside, int u, int v, float d, float m0, float m1, float m2, float& fx, float& fy) {
+__device__ __forceinline__ uint32_t project(const Pinhole& k, const Cam& c, bool inside, int u, int v, float d, float m0, float m1, float m2, float& fx,
+                                            float& fy) {
     const float fu = (float)u, fv = (float)v;
-    const float px = d * (c.k00 * fu + c.k02);
-    const float py = d * (c.k11 * fv + c.k12);
-    const float pz = d;
-    const float qx = c.R[0] * px + c.R[1] * py + c.R[2] * pz + m0;
-    const float qy = c.R[3] * px + c.R[4] * py + c.R[5] * pz + m1;
-    const float qz = c.R[6] * px + c.R[7] * py + c.R[8] * pz + m2;
-    const float nx = c.fx * qx + c.cx * qz;
-    const float ny = c.fy * qy + c.cy * qz;
-    const float den = qz + 1e-6f;
-    const float X = nx / den, Y = ny / den;
+    float px, py, qx, qy, qz, X, Y;
+    pinhole_lift(k, fu, fv, d, px, py);
+    pinhole_move<3>(c.R, px, py, d, m0, m1, m2, qx, qy, qz);
+    pinhole_project(k, qx, qy, qz, X, Y);
     const bool b0 = inside && fabsf(d) < INFINITY && d > 0.f && qz > 0.f && fabsf(X) < INFINITY && fabsf(Y) < INFINITY;   // a NaN fails a comparison
     const bool b1 = b0 && X >= 0.f && X < c.xlim && Y >= 0.f && Y < c.ylim;
     fx = b0 ? X - fu : 0.f;
@@ -98,12 +94,10 @@ __global__ void __launch_bounds__(TPB) pair_flow_kernel(FlowP p) {
     const int p0 = (blockIdx.x * TPB + threadIdx.x) * RUN;
     if (p0 >= npx) return;
     const int cnt = min(RUN, npx - p0);
+    const Pinhole k = pinhole_load(p.K + (size_t)n * 9);
     Cam c;
     {
-        const float* K = p.K + (size_t)n * 9;
         const float* T = p.T + (size_t)n * 16;
-        c.fx = K[0]; c.cx = K[2]; c.fy = K[4]; c.cy = K[5];
-        c.k00 = 1.f / c.fx; c.k11 = 1.f / c.fy; c.k02 = (-1.f * c.cx) / c.fx; c.k12 = (-1.f * c.cy) / c.fy;      // sde_depth_cloud's inv_intrinsics
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
             c.R[3 * i] = T[4 * i]; c.R[3 * i + 1] = T[4 * i + 1]; c.R[3 * i + 2] = T[4 * i + 2];
@@ -130,7 +124,7 @@ __global__ void __launch_bounds__(TPB) pair_flow_kernel(FlowP p) {
                 d = pr[at];
                 if (mo) { m0 = mo[at]; m1 = mo[plane + at]; m2 = mo[2 * plane + at]; }
             }
-            vb[j] = project(c, inside, x, y, d, c.t[0] + m0, c.t[1] + m1, c.t[2] + m2, fl[2 * j], fl[2 * j + 1]);
+            vb[j] = project(k, c, inside, x, y, d, c.t[0] + m0, c.t[1] + m1, c.t[2] + m2, fl[2 * j], fl[2 * j + 1]);
             if (p.canvas && (vb[j] & 1u)) col[j] = flow_colour(fl[2 * j], fl[2 * j + 1], p.max_flow, swheel, p.ncols);
             if (++x == p.W) { x = 0; ++y; r = y < p.H ? p.ymap[y] : -1; }
         }

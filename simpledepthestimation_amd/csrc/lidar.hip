@@ -3,22 +3,21 @@
 // pixel); the contract, with its one deviation, is stated in include/sde_hip.h.
 //
 // sde_lidar_depth, three launches ordered on the stream, one grid-stride grid each for all B scans:
-//   lidar_fill      every element of the output window <- the bit pattern of +inf;
-//   lidar_scatter   one point per thread: three dot products, two divisions, two v_rndne, then ONE no-return atomicMin on the pixel's bits.  Depths
-//                   that reach the map are positive finite floats, which order like their bit patterns, so the unsigned minimum is the float
-//                   minimum; a minimum does not depend on arrival order: the same bits run after run;
+//   zbuf_fill       every element of the output window <- the bit pattern of +inf (zbuf.h);
+//   lidar_scatter   one point per thread: three dot products, two divisions, the nearest pixel (pinhole.h), then the z-buffer's minimum (zbuf.h);
 //   lidar_finish    +inf -> 0 (no point), everything else min(d, max_depth).
 // Per frame at 120 k points and 375 x 1242: 1.4-1.9 MB of points read once, one 4-byte atomic per point that lands in the window, 1.9 MB of map
 // written twice and read once.
 //
 // Built with -ffp-contract=off: u, v, w keep the operation order the header states, which hip/lidar.py's host twin repeats bit for bit.
 #include "common.h"
+#include "pinhole.h"
 #include "sde_hip.h"
+#include "zbuf.h"
 
 namespace {
 
 constexpr int TILE = 256;
-constexpr unsigned EMPTY = 0x7f800000u;          // +inf: above every depth that is kept
 constexpr int MAX_BLOCKS = 2048;                 // 8 workgroups per compute unit; the grid-stride loops take the rest
 
 struct LidarP {
@@ -30,10 +29,6 @@ struct LidarP {
     int cap, stride, B, H, W, flags;
     float max_depth;
 };
-
-__global__ void __launch_bounds__(TILE) lidar_fill(unsigned* __restrict__ depth, size_t n) {
-    for (size_t i = (size_t)blockIdx.x * TILE + threadIdx.x; i < n; i += (size_t)gridDim.x * TILE) depth[i] = EMPTY;
-}
 
 __global__ void __launch_bounds__(TILE) lidar_scatter(LidarP p) {
     const size_t total = (size_t)p.B * p.cap;
@@ -50,24 +45,24 @@ __global__ void __launch_bounds__(TILE) lidar_scatter(LidarP p) {
         bool keep = fabsf(x) < INFINITY && fabsf(y) < INFINITY && fabsf(z) < INFINITY && w > 0.f;      // NaN fails every comparison
         keep = keep && d > 0.f && d < INFINITY;
         if ((p.flags & SDE_LIDAR_FRONT_ONLY) && !(x >= 0.f)) keep = false;
-        const float ru = rintf(u / w), rv = rintf(v / w);                    // round-half-even
-        if (!keep || !(fabsf(ru) < 1e9f) || !(fabsf(rv) < 1e9f)) continue;   // beyond any image (and the int conversion below stays defined)
-        const long px = (long)(int)ru - 1 - p.origin[2 * b], py = (long)(int)rv - 1 - p.origin[2 * b + 1];
+        int iu, iv;
+        if (!keep || !nearest_pixel(u / w, v / w, iu, iv)) continue;
+        const long px = (long)iu - 1 - p.origin[2 * b], py = (long)iv - 1 - p.origin[2 * b + 1];
         if (px < 0 || px >= p.W || py < 0 || py >= p.H) continue;
-        atomicMin(p.depth + ((size_t)b * p.H + (size_t)py) * p.W + (size_t)px, __float_as_uint(d));
+        zbuf_min(p.depth + ((size_t)b * p.H + (size_t)py) * p.W + (size_t)px, d);
     }
 }
 
 __global__ void __launch_bounds__(TILE) lidar_finish(unsigned* __restrict__ depth, size_t n, float max_depth) {
     for (size_t i = (size_t)blockIdx.x * TILE + threadIdx.x; i < n; i += (size_t)gridDim.x * TILE) {
         const unsigned bits = depth[i];
-        float d = bits == EMPTY ? 0.f : __uint_as_float(bits);
+        float d = bits == ZBUF_EMPTY ? 0.f : __uint_as_float(bits);
         if (max_depth > 0.f) d = fminf(d, max_depth);
         depth[i] = __float_as_uint(d);
     }
 }
 
-unsigned blocks_for(size_t n) { return (unsigned)(n / TILE >= (size_t)MAX_BLOCKS ? MAX_BLOCKS : (n + TILE - 1) / TILE); }
+unsigned blocks_for(size_t n) { return zbuf_blocks(n, TILE, MAX_BLOCKS); }
 
 }  // namespace
 
@@ -80,7 +75,7 @@ extern "C" int sde_lidar_depth(const float* pts, int cap, int stride, const int*
     SDE_CHECK_ARG(pts && count && proj && origin && depth, "sde_lidar_depth: null pointer");
     const size_t npx = (size_t)B * H * W;
     LidarP p{pts, count, proj, origin, (unsigned*)depth, cap, stride, B, H, W, flags, max_depth};
-    hipLaunchKernelGGL(lidar_fill, dim3(blocks_for(npx)), dim3(TILE), 0, (hipStream_t)stream, p.depth, npx);
+    hipLaunchKernelGGL(zbuf_fill<TILE>, dim3(blocks_for(npx)), dim3(TILE), 0, (hipStream_t)stream, p.depth, npx);
     hipLaunchKernelGGL(lidar_scatter, dim3(blocks_for((size_t)B * cap)), dim3(TILE), 0, (hipStream_t)stream, p);
     hipLaunchKernelGGL(lidar_finish, dim3(blocks_for(npx)), dim3(TILE), 0, (hipStream_t)stream, p.depth, npx, max_depth);
     SDE_CHECK_LAUNCH("sde_lidar_depth");

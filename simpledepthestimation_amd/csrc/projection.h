@@ -1,6 +1,7 @@
 // Projection helpers shared by the geometry kernels (photometric.hip, motion_loss.hip): pinhole back-projection / projection in the reference's fp32
 // operation order, the grid_sample tap set and the ReflectionPad2d(1) index map.  Every file that includes this header MUST be compiled with
 // -ffp-contract=off (see photometric.hip: floor() of the sample coordinate is bit-exact only with the explicit fmaf / mul / add order kept).
+// Not to be merged with pinhole.h: the inference-side operators keep another operation order (lift, move by [R | s], then project with K).
 #pragma once
 #include "common.h"
 

@@ -2,12 +2,10 @@
 // pose the model itself estimated, overlaps are resolved by a z-buffer, one-pixel holes are closed from the ring around them, and the result
 // is blended with the current prediction where the two agree.  The contract is written out in include/sde_hip.h.
 //
-// sde_depth_warp_fuse, three launches ordered on the stream, one grid-stride grid each for all N maps (the shape of lidar.hip):
-//   warp_fill      every element of the z-buffer <- the bit pattern of +inf;
-//   warp_scatter   one pixel of the PREVIOUS frame per thread: lifted through the intrinsics, moved by [R | t + m], projected again (the
-//                  operation order of sde_pair_flow, restated below), rounded to the nearest pixel (v_rndne), then ONE no-return atomicMin of
-//                  the new depth's bits.  Depths that reach the buffer are positive finite floats, which order like their bit patterns, so the
-//                  unsigned minimum is the float minimum; a minimum does not depend on arrival order: the same bits run after run;
+// sde_depth_warp_fuse, three launches ordered on the stream, one grid-stride grid each for all N maps:
+//   zbuf_fill      every element of the z-buffer <- the bit pattern of +inf (zbuf.h);
+//   warp_scatter   one pixel of the PREVIOUS frame per thread: lifted through the intrinsics, moved by [R | t + m], projected again, rounded
+//                  to the nearest pixel (pinhole.h), then the z-buffer's minimum of the new depth (zbuf.h);
 //   warp_fuse      one pixel of the CURRENT frame per thread: the z-buffer's entry, or -- where nothing landed -- the nearest entry of the up to
 //                  eight neighbours; the consistency test, the blend, the class.
 // Per pixel: 4 B of depth (+ 12 B of motion) read and one 4-byte atomic in the scatter; 4 B written by the fill; 4 B of z-buffer and 4 B of the
@@ -20,12 +18,13 @@
 // Built with -ffp-contract=off: the projection and the blend keep the operation order the header states, which hip/temporal.py's host twin
 // repeats bit for bit.
 #include "common.h"
+#include "pinhole.h"
 #include "sde_hip.h"
+#include "zbuf.h"
 
 namespace {
 
 constexpr int TILE = 256;
-constexpr unsigned EMPTY = 0x7f800000u;          // +inf: above every depth that is kept
 constexpr int MAX_BLOCKS = 2048;                 // 8 workgroups per compute unit; the grid-stride loops take the rest
 
 struct WarpP {
@@ -42,10 +41,6 @@ struct WarpP {
     float alpha, tol;
 };
 
-__global__ void __launch_bounds__(TILE) warp_fill(unsigned* __restrict__ zbuf, size_t n) {
-    for (size_t i = (size_t)blockIdx.x * TILE + threadIdx.x; i < n; i += (size_t)gridDim.x * TILE) zbuf[i] = EMPTY;
-}
-
 __global__ void __launch_bounds__(TILE) warp_scatter(WarpP p) {
     const size_t plane = (size_t)p.h * p.w, total = (size_t)p.N * plane;
     for (size_t i = (size_t)blockIdx.x * TILE + threadIdx.x; i < total; i += (size_t)gridDim.x * TILE) {
@@ -53,33 +48,22 @@ __global__ void __launch_bounds__(TILE) warp_scatter(WarpP p) {
         const size_t at = i - (size_t)n * plane;
         const int v = (int)(at / p.w), u = (int)(at - (size_t)v * p.w);
         const float d = p.prev[i];
-        const float* K = p.K + (size_t)n * 9;
+        const Pinhole c = pinhole_load(p.K + (size_t)n * 9);
         const float* T = p.T + (size_t)n * 16;
-        const float fx = K[0], cx = K[2], fy = K[4], cy = K[5];
-        const float k00 = 1.f / fx, k11 = 1.f / fy, k02 = (-1.f * cx) / fx, k12 = (-1.f * cy) / fy;      // sde_depth_cloud's inv_intrinsics
         float m0 = 0.f, m1 = 0.f, m2 = 0.f;
         if (p.motion) {
             const float* mo = p.motion + (size_t)n * 3 * plane + at;
             m0 = mo[0]; m1 = mo[plane]; m2 = mo[2 * plane];
         }
-        const float s0 = T[3] + m0, s1 = T[7] + m1, s2 = T[11] + m2;
-        const float fu = (float)u, fv = (float)v;
-        const float px = d * (k00 * fu + k02);
-        const float py = d * (k11 * fv + k12);
-        const float pz = d;
-        const float qx = T[0] * px + T[1] * py + T[2] * pz + s0;
-        const float qy = T[4] * px + T[5] * py + T[6] * pz + s1;
-        const float qz = T[8] * px + T[9] * py + T[10] * pz + s2;
-        const float nx = fx * qx + cx * qz;
-        const float ny = fy * qy + cy * qz;
-        const float den = qz + 1e-6f;
-        const float X = nx / den, Y = ny / den;
+        float px, py, qx, qy, qz, X, Y;
+        pinhole_lift(c, (float)u, (float)v, d, px, py);
+        pinhole_move<4>(T, px, py, d, T[3] + m0, T[7] + m1, T[11] + m2, qx, qy, qz);
+        pinhole_project(c, qx, qy, qz, X, Y);
         const bool keep = fabsf(d) < INFINITY && d > 0.f && qz > 0.f && qz < INFINITY && fabsf(X) < INFINITY && fabsf(Y) < INFINITY;   // a NaN fails a comparison
-        const float rx = rintf(X), ry = rintf(Y);                                  // round-half-even
-        if (!keep || !(fabsf(rx) < 1e9f) || !(fabsf(ry) < 1e9f)) continue;         // beyond any image (and the int conversion below stays defined)
-        const int ix = (int)rx, iy = (int)ry;
+        int ix, iy;
+        if (!keep || !nearest_pixel(X, Y, ix, iy)) continue;
         if (ix < 0 || ix >= p.w || iy < 0 || iy >= p.h) continue;
-        atomicMin(p.zbuf + (size_t)n * plane + (size_t)iy * p.w + (size_t)ix, __float_as_uint(qz));
+        zbuf_min(p.zbuf + (size_t)n * plane + (size_t)iy * p.w + (size_t)ix, qz);
     }
 }
 
@@ -90,7 +74,7 @@ __global__ void __launch_bounds__(TILE) warp_fuse(WarpP p) {
         const int y = (int)(at / p.w), x = (int)(at - (size_t)y * p.w);
         unsigned z = p.zbuf[i];
         bool filled = false;
-        if (z == EMPTY) {                                                           // nothing landed here: the nearest of the ring around it
+        if (z == ZBUF_EMPTY) {                                                           // nothing landed here: the nearest of the ring around it
             const unsigned* zn = p.zbuf + (i - at);
             for (int dy = -1; dy <= 1; ++dy) {
                 const int yy = y + dy;
@@ -98,12 +82,12 @@ __global__ void __launch_bounds__(TILE) warp_fuse(WarpP p) {
                 for (int dx = -1; dx <= 1; ++dx) {
                     const int xx = x + dx;
                     if (xx < 0 || xx >= p.w || (dx == 0 && dy == 0)) continue;
-                    z = min(z, zn[(size_t)yy * p.w + xx]);                          // EMPTY is above every entry: it never wins
+                    z = min(z, zn[(size_t)yy * p.w + xx]);                          // ZBUF_EMPTY is above every entry: it never wins
                 }
             }
-            filled = z != EMPTY;
+            filled = z != ZBUF_EMPTY;
         }
-        const bool hole = z == EMPTY;
+        const bool hole = z == ZBUF_EMPTY;
         const float wv = hole ? 0.f : __uint_as_float(z);
         const float c = p.cur[i];
         const bool c_ok = fabsf(c) < INFINITY && c > 0.f;
@@ -121,7 +105,7 @@ __global__ void __launch_bounds__(TILE) warp_fuse(WarpP p) {
     }
 }
 
-unsigned blocks_for(size_t n) { return (unsigned)(n / TILE >= (size_t)MAX_BLOCKS ? MAX_BLOCKS : (n + TILE - 1) / TILE); }
+unsigned blocks_for(size_t n) { return zbuf_blocks(n, TILE, MAX_BLOCKS); }
 
 }  // namespace
 
@@ -134,7 +118,7 @@ extern "C" int sde_depth_warp_fuse(const float* prev, const float* cur, const fl
     SDE_CHECK_ARG((long)h * w <= 0x7fffffffL, "sde_depth_warp_fuse: map too large (%dx%d)", h, w);
     const size_t npx = (size_t)N * h * w;
     WarpP p{prev, cur, K, T, motion, (unsigned*)zbuf, fused, state, warped, N, h, w, alpha, tol};
-    hipLaunchKernelGGL(warp_fill, dim3(blocks_for(npx)), dim3(TILE), 0, (hipStream_t)stream, p.zbuf, npx);
+    hipLaunchKernelGGL(zbuf_fill<TILE>, dim3(blocks_for(npx)), dim3(TILE), 0, (hipStream_t)stream, p.zbuf, npx);
     hipLaunchKernelGGL(warp_scatter, dim3(blocks_for(npx)), dim3(TILE), 0, (hipStream_t)stream, p);
     hipLaunchKernelGGL(warp_fuse, dim3(blocks_for(npx)), dim3(TILE), 0, (hipStream_t)stream, p);
     SDE_CHECK_LAUNCH("sde_depth_warp_fuse");

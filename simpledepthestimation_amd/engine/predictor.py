@@ -210,28 +210,27 @@ class _Predictor:
             self._slots[key] = _Slot(N, plan.Hs, plan.Ws, self.device)
         return self._slots[key]
 
-    def _set_intrinsics(self, slot, plan, intrinsics, N):
-        if intrinsics is None:
+    def _device_copy(self, slot, field, value, N):
+        """The slot's device copy `field` ("K": the intrinsics at the network's size, plan.intrinsics applied by the caller; "K_src": as given, at
+        the source size, for the point cloud and the flow) of the host intrinsics `value` ([3,3] or [N,3,3]), refreshed when they change;
+        None without any."""
+        if value is None:
             return None
-        K = np.asarray(plan.intrinsics(intrinsics), dtype=np.float32)
-        K = np.array(np.broadcast_to(K, (N, 3, 3)))          # a copy: broadcast views are read-only
-        if slot.K is None:
-            slot.K = torch.empty((N, 3, 3), dtype=torch.float32, device=self.device)
-        if slot.K_host is None or not np.array_equal(slot.K_host, K):
-            slot.K.copy_(torch.from_numpy(K))
-            slot.K_host = K
-        return slot.K
+        value = np.array(np.broadcast_to(np.asarray(value, dtype=np.float32), (N, 3, 3)))          # a copy: broadcast views are read-only
+        if getattr(slot, field) is None:
+            setattr(slot, field, torch.empty((N, 3, 3), dtype=torch.float32, device=self.device))
+        if getattr(slot, field + "_host") is None or not np.array_equal(getattr(slot, field + "_host"), value):
+            getattr(slot, field).copy_(torch.from_numpy(value))
+            setattr(slot, field + "_host", value)
+        return getattr(slot, field)
 
-    def _source_K(self, slot, K, N):
-        """The slot's device copy of the source-size intrinsics (the point cloud's, the flow's), refreshed when they change (None without any)."""
-        if K is None:
-            return None
-        if slot.K_src is None:
-            slot.K_src = torch.empty((N, 3, 3), dtype=torch.float32, device=self.device)
-        if slot.K_src_host is None or not np.array_equal(slot.K_src_host, K):
-            slot.K_src.copy_(torch.from_numpy(K))
-            slot.K_src_host = K
-        return slot.K_src
+    @staticmethod
+    def _host_K(name, intrinsics, N):
+        """intrinsics [3,3] or [N,3,3] (array or tensor) -> a float32 [N,3,3] host copy; ValueError unless finite with non-zero focal lengths."""
+        K = np.asarray(intrinsics.cpu().numpy() if torch.is_tensor(intrinsics) else intrinsics, dtype=np.float32)
+        if K.shape not in ((3, 3), (N, 3, 3)) or not (np.all(np.isfinite(K)) and np.all(K[..., 0, 0] != 0) and np.all(K[..., 1, 1] != 0)):
+            raise ValueError(f"{name}: intrinsics must be a finite [3,3] or [{N},3,3] matrix with non-zero focal lengths")
+        return np.array(np.broadcast_to(K, (N, 3, 3)))
 
     def _replay(self, slot, key, chain, persistent=()):
         """chain() on the current stream: eager, or the slot's graph of that key (captured at first use, after one eager run).  persistent:
@@ -376,11 +375,7 @@ class DepthPredictor(_Predictor):
         args = HC.check_range(cloud["min_depth"], cloud["max_depth"], cloud.get("step", 1))
         if intrinsics is None:
             raise ValueError("DepthPredictor: cloud needs intrinsics (the source-size K [3,3] or [N,3,3] of the frames)")
-        K = np.asarray(intrinsics.cpu().numpy() if torch.is_tensor(intrinsics) else intrinsics, dtype=np.float32)
-        K = np.array(np.broadcast_to(K, (N, 3, 3)))
-        if not (np.all(np.isfinite(K)) and np.all(K[:, 0, 0] != 0) and np.all(K[:, 1, 1] != 0)):
-            raise ValueError("DepthPredictor: cloud needs finite intrinsics with non-zero focal lengths")
-        return args, K
+        return args, _Predictor._host_K("DepthPredictor", intrinsics, N)
 
     def _run(self, slot, plan, K, flags, cloud=None, K_src=None):
         """The chain on the slot's buffers, on the current stream: eager, or the slot's graph (captured at first use, after one eager run)."""
@@ -401,8 +396,8 @@ class DepthPredictor(_Predictor):
         flags = (bool(present), bool(frame_in_canvas), bool(want_u16))
         with torch.cuda.device(self.device):
             self._upload(slot, t)
-            K = self._set_intrinsics(slot, plan, intrinsics, N)
-            out = self._run(slot, plan, K, flags, cloud, self._source_K(slot, K_cloud, N))
+            K = self._device_copy(slot, "K", None if intrinsics is None else plan.intrinsics(intrinsics), N)
+            out = self._run(slot, plan, K, flags, cloud, self._device_copy(slot, "K_src", K_cloud, N))
             # the slot's tensors are written again by the next call: hand out copies
             return {k: (v.clone() if v is not None else None) for k, v in out.items()}
 
@@ -433,8 +428,8 @@ class DepthPredictor(_Predictor):
                 yield t
 
         def run(slot, plan):
-            K = self._set_intrinsics(slot, plan, intrinsics, 1)
-            return self._run(slot, plan, K, flags, cloud, self._source_K(slot, K_cloud, 1))
+            K = self._device_copy(slot, "K", None if intrinsics is None else plan.intrinsics(intrinsics), 1)
+            return self._run(slot, plan, K, flags, cloud, self._device_copy(slot, "K_src", K_cloud, 1))
         yield from self._pump(items(), names, run, self._result)
 
 
@@ -625,15 +620,12 @@ class PairPredictor(_Predictor):
     def _source_intrinsics(self, intrinsics):
         if intrinsics is None:
             raise ValueError("PairPredictor: the flow needs intrinsics (the source-size K [3,3] of the frames)")
-        K = np.asarray(intrinsics.cpu().numpy() if torch.is_tensor(intrinsics) else intrinsics, dtype=np.float32)
-        if K.shape != (3, 3) or not (np.all(np.isfinite(K)) and K[0, 0] != 0 and K[1, 1] != 0):
-            raise ValueError("PairPredictor: intrinsics must be a finite [3,3] matrix with non-zero focal lengths")
-        return K
+        return self._host_K("PairPredictor", intrinsics, 1)[0]          # one K for the whole window
 
     def _run(self, slot, plan, intrinsics, K_host, present, rigid_only, max_flow, temporal=None, want_u16=False, cloud=None):
         N = 1 + self.n
-        K = self._set_intrinsics(slot, plan, intrinsics, N)
-        K_src = self._source_K(slot, np.array(np.broadcast_to(K_host, (self.n, 3, 3))), self.n)
+        K = self._device_copy(slot, "K", plan.intrinsics(intrinsics), N)
+        K_src =self._device_copy(slot, "K_src", K_host, self.n)
         max_flow = float(0.05 * plan.Ws if max_flow is None else max_flow)
         if not max_flow > 0:
             raise ValueError(f"PairPredictor: max_flow must be positive, got {max_flow}")

@@ -3,6 +3,7 @@
 import numpy as np
 import torch
 
+from . import args as A
 from . import lib as L
 from . import present as HP
 
@@ -33,42 +34,24 @@ def depth_cloud(pred, ymap, xmap, K, min_depth, max_depth, step=1, frame=None, o
     gives the structured view); what lies behind them is whatever the buffer held.  out: optional (points, count) destinations; workspace:
     optional int32 tensor of at least workspace_numel(N, H, W, step) elements.  No host synchronisation (device maps: see depth_present)."""
     min_depth, max_depth, step = check_range(min_depth, max_depth, step)
-    if pred.dim() == 2:
-        pred = pred[None]
-    elif pred.dim() == 4 and pred.shape[1] == 1:
-        pred = pred[:, 0]
-    if pred.dim() != 3 or pred.dtype != torch.float32 or not pred.is_cuda:
-        raise L.SdeHipError(f"depth_cloud: pred must be a float32 [N,ph,pw] device tensor, got {pred.dtype} {tuple(pred.shape)}")
-    pred = pred.contiguous()
+    pred = A.as_pred("depth_cloud", pred)
     N, ph, pw = pred.shape
     dev = pred.device
     ymap, xmap = HP.ensure_checked(ymap, xmap, ph, pw, dev)
     H, W = ymap.numel(), xmap.numel()
-    if K.dim() == 2:
-        K = K[None].expand(N, 3, 3)
-    if K.dtype != torch.float32 or tuple(K.shape) != (N, 3, 3) or not K.is_cuda:
-        raise L.SdeHipError(f"depth_cloud: K must be a float32 [{N},3,3] device tensor, got {K.dtype} {tuple(K.shape)}")
-    if frame is not None:
-        if frame.dim() == 3:
-            frame = frame[None]
-        if frame.dtype != torch.uint8 or tuple(frame.shape) != (N, H, W, 3) or not frame.is_cuda:
-            raise L.SdeHipError(f"depth_cloud: frame must be a uint8 [{N},{H},{W},3] device tensor, got {frame.dtype} {tuple(frame.shape)}")
+    K = A.as_K("depth_cloud", K, N, dev)
+    frame = A.as_frame("depth_cloud", frame, N, H, W, dev)
     cap = capacity(H, W, step)
     points, count = out if out is not None else (None, None)
-    if points is None:
-        points = torch.empty((N, cap, 16), dtype=torch.uint8, device=dev)
-    if count is None:
-        count = torch.empty((N,), dtype=torch.int32, device=dev)
-    if points.dtype != torch.uint8 or tuple(points.shape) != (N, cap, 16) or not points.is_cuda or count.dtype != torch.int32 or tuple(count.shape) != (N,):
-        raise L.SdeHipError(f"depth_cloud: destinations must be uint8 [{N},{cap},16] and int32 [{N}], got {tuple(points.shape)} and {tuple(count.shape)}")
+    points = A.dst("depth_cloud", points, (N, cap, 16), torch.uint8, True, dev)
+    count = A.dst("depth_cloud", count, (N,), torch.int32, True, dev)
     need = workspace_numel(N, H, W, step)
     if workspace is None:
         workspace = torch.empty((need,), dtype=torch.int32, device=dev)
-    if workspace.dtype != torch.int32 or not workspace.is_cuda:
-        raise L.SdeHipError("depth_cloud: the workspace must be an int32 device tensor")
-    L.check(L.lib().sde_depth_cloud(L.ptr(pred), N, ph, pw, L.ptr(ymap), L.ptr(xmap), H, W, L.ptr(frame.contiguous() if frame is not None else None),
-                                    L.ptr(K.contiguous()), min_depth, max_depth, step, L.ptr(workspace), workspace.numel() * 4, L.ptr(points), L.ptr(count),
-                                    L.stream()), "sde_depth_cloud")
+    if workspace.dtype != torch.int32 or workspace.device != dev:
+        raise L.SdeHipError(f"depth_cloud: workspace must be an int32 tensor on {dev}, got {workspace.dtype} on {workspace.device}")
+    L.check(L.lib().sde_depth_cloud(L.ptr(pred), N, ph, pw, L.ptr(ymap), L.ptr(xmap), H, W, L.ptr(frame), L.ptr(K), min_depth, max_depth, step,
+                                    L.ptr(workspace), workspace.numel() * 4, L.ptr(points), L.ptr(count), L.stream()), "sde_depth_cloud")
     return points, count
 
 

@@ -5,6 +5,7 @@ import struct
 import numpy as np
 import torch
 
+from . import args as A
 from . import lib as L
 from . import present as HP
 
@@ -48,48 +49,26 @@ def pair_flow(pred, ymap, xmap, K, T, motion=None, max_flow=10.0, frame=None, wa
         raise ValueError(f"pair_flow: max_flow must be positive, got {max_flow!r}")
     if not (want_canvas or want_flow or want_valid):
         raise ValueError("pair_flow: at least one of flow, valid and canvas must be asked for")
-    if pred.dim() == 2:
-        pred = pred[None]
-    elif pred.dim() == 4 and pred.shape[1] == 1:
-        pred = pred[:, 0]
-    if pred.dim() != 3 or pred.dtype != torch.float32 or not pred.is_cuda:
-        raise L.SdeHipError(f"pair_flow: pred must be a float32 [N,ph,pw] device tensor, got {pred.dtype} {tuple(pred.shape)}")
-    pred = pred.contiguous()
+    pred = A.as_pred("pair_flow", pred)
     N, ph, pw = pred.shape
     dev = pred.device
     ymap, xmap = HP.ensure_checked(ymap, xmap, ph, pw, dev)
     H, W = ymap.numel(), xmap.numel()
-    if K.dim() == 2:
-        K = K[None].expand(N, 3, 3)
-    for name, t, shape in (("K", K, (N, 3, 3)), ("T", T, (N, 4, 4)), ("motion", motion, (N, 3, ph, pw))):
-        if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_cuda):
-            raise L.SdeHipError(f"pair_flow: {name} must be a float32 {list(shape)} device tensor, got {t.dtype} {tuple(t.shape)}")
-    if frame is not None:
-        if frame.dim() == 3:
-            frame = frame[None]
-        if frame.dtype != torch.uint8 or tuple(frame.shape) != (N, H, W, 3) or not frame.is_cuda:
-            raise L.SdeHipError(f"pair_flow: frame must be a uint8 [{N},{H},{W},3] device tensor, got {frame.dtype} {tuple(frame.shape)}")
-    if wheel is None:
-        wheel = flow_wheel(dev)
-    if wheel.dtype != torch.uint8 or wheel.dim() != 2 or wheel.shape[1] != 3 or not 0 < wheel.shape[0] <= 256 or not wheel.is_cuda:
-        raise L.SdeHipError("pair_flow: wheel must be a uint8 [ncols,3] device tensor with at most 256 rows")
+    K = A.as_K("pair_flow", K, N, dev)
+    T = A.same_device_tensor("pair_flow", "T", T, torch.float32, (N, 4, 4), dev)
+    if motion is not None:
+        motion = A.same_device_tensor("pair_flow", "motion", motion, torch.float32, (N, 3, ph, pw), dev).contiguous()
+    frame = A.as_frame("pair_flow", frame, N, H, W, dev)
+    wheel = A.same_device_tensor("pair_flow", "wheel", flow_wheel(dev) if wheel is None else wheel, torch.uint8, (None, 3), dev)
+    if not 0 < wheel.shape[0] <= 256:
+        raise L.SdeHipError(f"pair_flow: wheel must have between 1 and 256 rows, got {wheel.shape[0]}")
     rows = 2 * H if frame is not None else H
     flow, valid, canvas = out if out is not None else (None, None, None)
-
-    def dst(t, shape, dtype, want):
-        if not want:
-            return None
-        if t is None:
-            return torch.empty(shape, dtype=dtype, device=dev)
-        if t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_cuda:
-            raise L.SdeHipError(f"pair_flow: destination must be {dtype} {tuple(shape)}, got {t.dtype} {tuple(t.shape)}")
-        return t
-    flow = dst(flow, (N, H, W, 2), torch.float32, want_flow)
-    valid = dst(valid, (N, H, W), torch.uint8, want_valid)
-    canvas = dst(canvas, (N, rows, W, 3), torch.uint8, want_canvas)
-    L.check(L.lib().sde_pair_flow(L.ptr(pred), N, ph, pw, L.ptr(ymap), L.ptr(xmap), H, W, L.ptr(K.contiguous()), L.ptr(T.contiguous()),
-                                  L.ptr(motion.contiguous() if motion is not None else None), L.ptr(wheel.contiguous()), int(wheel.shape[0]),
-                                  float(max_flow), L.ptr(frame.contiguous() if frame is not None else None), L.ptr(flow), L.ptr(valid), L.ptr(canvas),
+    flow = A.dst("pair_flow", flow, (N, H, W, 2), torch.float32, want_flow, dev)
+    valid = A.dst("pair_flow", valid, (N, H, W), torch.uint8, want_valid, dev)
+    canvas = A.dst("pair_flow", canvas, (N, rows, W, 3), torch.uint8, want_canvas, dev)
+    L.check(L.lib().sde_pair_flow(L.ptr(pred), N, ph, pw, L.ptr(ymap), L.ptr(xmap), H, W, L.ptr(K), L.ptr(T.contiguous()), L.ptr(motion),
+                                  L.ptr(wheel.contiguous()), int(wheel.shape[0]), float(max_flow), L.ptr(frame), L.ptr(flow), L.ptr(valid), L.ptr(canvas),
                                   L.stream()), "sde_pair_flow")
     return flow, valid, canvas
 

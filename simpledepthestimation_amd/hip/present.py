@@ -5,6 +5,7 @@ from ctypes import c_int, c_void_p
 import numpy as np
 import torch
 
+from . import args as A
 from . import lib as L
 
 _P, _I, _F = c_void_p, c_int, L.c_float
@@ -51,8 +52,8 @@ def ensure_checked(ymap, xmap, ph, pw, device):
     (one device -> host copy the first time the pair is seen, none after).  Shared by every binding that indexes a prediction through the maps."""
     if not (torch.is_tensor(ymap) and torch.is_tensor(xmap) and ymap.is_cuda and xmap.is_cuda):
         return device_maps(ymap, xmap, ph, pw, device)
-    if ymap.dtype != torch.int32 or xmap.dtype != torch.int32 or ymap.dim() != 1 or xmap.dim() != 1:
-        raise L.SdeHipError("the index maps must be 1-D int32")
+    for what, m in (("ymap", ymap), ("xmap", xmap)):
+        A.same_device_tensor("the index maps", what, m, torch.int32, (None,), torch.device(device))
     if _key(ymap, xmap, ph, pw) not in _checked:
         check_maps(ymap.cpu(), xmap.cpu(), ph, pw)
         _remember(ymap, xmap, ph, pw)
@@ -72,41 +73,18 @@ def depth_present(pred, ymap, xmap, vmax, gamma=0.8, lut=None, frame=None, want_
     CUDA tensors.  Returns (canvas [N, 2H or H, W, 3] uint8, depth_full [N,H,W] fp32 or None, depth_u16 [N,H,W] int16 bits of uint16 or None).
     Device maps are validated once per distinct pair (one device -> host copy the first time a pair is seen, none after: do that first call
     outside graph capture, or build the pair with device_maps()).  out: optional (canvas, depth_full, depth_u16) destinations.  No host sync."""
-    if pred.dim() == 2:
-        pred = pred[None]
-    elif pred.dim() == 4 and pred.shape[1] == 1:
-        pred = pred[:, 0]
-    if pred.dim() != 3 or pred.dtype != torch.float32 or not pred.is_cuda:
-        raise L.SdeHipError(f"depth_present: pred must be a float32 [N,ph,pw] device tensor, got {pred.dtype} {tuple(pred.shape)}")
-    pred = pred.contiguous()
+    pred = A.as_pred("depth_present", pred)
     N, ph, pw = pred.shape
-    ymap, xmap = ensure_checked(ymap, xmap, ph, pw, pred.device)
-    H, W = ymap.numel(), xmap.numel()
     dev = pred.device
-    if lut is None:
-        lut = default_lut(dev)
-    if lut.dtype != torch.uint8 or tuple(lut.shape) != (256, 3) or not lut.is_cuda:
-        raise L.SdeHipError("depth_present: lut must be a uint8 [256,3] device tensor")
-    if frame is not None:
-        if frame.dim() == 3:
-            frame = frame[None]
-        if frame.dtype != torch.uint8 or tuple(frame.shape) != (N, H, W, 3) or not frame.is_cuda:
-            raise L.SdeHipError(f"depth_present: frame must be a uint8 [{N},{H},{W},3] device tensor, got {frame.dtype} {tuple(frame.shape)}")
+    ymap, xmap = ensure_checked(ymap, xmap, ph, pw, dev)
+    H, W = ymap.numel(), xmap.numel()
+    lut = A.same_device_tensor("depth_present", "lut", default_lut(dev) if lut is None else lut, torch.uint8, (256, 3), dev)
+    frame = A.as_frame("depth_present", frame, N, H, W, dev)
     rows = 2 * H if frame is not None else H
     canvas, depth, u16 = out if out is not None else (None, None, None)
-
-    def dst(t, shape, dtype, want):
-        if not want:
-            return None
-        if t is None:
-            return torch.empty(shape, dtype=dtype, device=dev)
-        if t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_cuda:
-            raise L.SdeHipError(f"depth_present: destination must be {dtype} {tuple(shape)}, got {t.dtype} {tuple(t.shape)}")
-        return t
-    canvas = dst(canvas, (N, rows, W, 3), torch.uint8, True)
-    depth = dst(depth, (N, H, W), torch.float32, want_depth)
-    u16 = dst(u16, (N, H, W), torch.int16, want_u16)          # torch has no arithmetic on uint16: the bits; .cpu().numpy().view(np.uint16) on the host
+    canvas = A.dst("depth_present", canvas, (N, rows, W, 3), torch.uint8, True, dev)
+    depth = A.dst("depth_present", depth, (N, H, W), torch.float32, want_depth, dev)
+    u16 = A.dst("depth_present", u16, (N, H, W), torch.int16, want_u16, dev)          # torch has no arithmetic on uint16: the bits; .cpu().numpy().view(np.uint16) on the host
     L.check(L.lib().sde_depth_present(L.ptr(pred), N, ph, pw, L.ptr(ymap), L.ptr(xmap), H, W, float(vmax), float(gamma), L.ptr(lut.contiguous()),
-                                      L.ptr(frame.contiguous() if frame is not None else None), L.ptr(depth), L.ptr(u16), L.ptr(canvas), L.stream()),
-            "sde_depth_present")
+                                      L.ptr(frame), L.ptr(depth), L.ptr(u16), L.ptr(canvas), L.stream()), "sde_depth_present")
     return canvas, depth, u16

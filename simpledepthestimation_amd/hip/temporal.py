@@ -5,10 +5,11 @@ from the ring around them, and the result is blended with the current prediction
 import numpy as np
 import torch
 
+from . import args as A
 from . import lib as L
+from .twins import EMPTY as _EMPTY, pinhole_project_np, zbuffer_min_np
 
 NEW, FUSED, NEARER, FARTHER, FILLED = 0, 1, 2, 3, 4        # SDE_TEMPORAL_*: the class in bits 0-1 of `state`, FILLED is bit 2
-_EMPTY = np.uint32(0x7f800000)                              # +inf: above every depth that is kept
 STATE_COLOURS = np.array([[40, 40, 40], [60, 170, 90], [220, 120, 40], [70, 110, 220]], dtype=np.uint8)      # NEW, FUSED, NEARER, FARTHER
 
 
@@ -29,36 +30,22 @@ def warp_fuse(prev, cur, K, T, motion=None, alpha=0.5, tol=0.05, out=None, want_
     destination of `fused`; it may be `prev` or `cur` (a state buffer updated in place).  zbuf: an int32 [N,h,w] workspace (allocated when
     None); state / warped: optional destinations.  Three launches on the current stream, no host synchronisation."""
     alpha, tol = check_params(alpha, tol)
-    for name, t in (("prev", prev), ("cur", cur)):
-        if not torch.is_tensor(t) or t.dim() != 3 or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous():
-            raise L.SdeHipError(f"warp_fuse: {name} must be a contiguous float32 [N,h,w] device tensor")
-    N, h, w = prev.shape
-    dev = prev.device
-    if tuple(cur.shape) != (N, h, w):
-        raise L.SdeHipError(f"warp_fuse: prev {tuple(prev.shape)} and cur {tuple(cur.shape)} differ")
+    # prev and cur are not copied (`out` may be either of them): lib.ptr refuses a non-contiguous one
+    dev = prev.device if torch.is_tensor(prev) else None
+    N, h, w = A.same_device_tensor("warp_fuse", "prev", prev, torch.float32, (None, None, None), dev).shape
+    A.same_device_tensor("warp_fuse", "cur", cur, torch.float32, (N, h, w), dev)
     if N <= 0 or h <= 0 or w <= 0:
         raise L.SdeHipError(f"warp_fuse: N, h and w must be positive ({N}, {h}, {w})")
-    if K.dim() == 2:
-        K = K[None].expand(N, 3, 3)
-    for name, t, shape in (("K", K, (N, 3, 3)), ("T", T, (N, 4, 4)), ("motion", motion, (N, 3, h, w))):
-        if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != shape or t.device != dev):
-            raise L.SdeHipError(f"warp_fuse: {name} must be a float32 {list(shape)} tensor on {dev}, got {t.dtype} {tuple(t.shape)}")
-
-    def dst(t, dtype, want, name):
-        if not want:
-            return None
-        if t is None:
-            return torch.empty((N, h, w), dtype=dtype, device=dev)
-        if t.dtype != dtype or tuple(t.shape) != (N, h, w) or t.device != dev or not t.is_contiguous():
-            raise L.SdeHipError(f"warp_fuse: {name} must be a contiguous {dtype} [{N},{h},{w}] tensor on {dev}, got {t.dtype} {tuple(t.shape)}")
-        return t
-    fused = dst(out, torch.float32, True, "out")
-    state = dst(state, torch.uint8, want_state, "state")
-    warped = dst(warped, torch.float32, want_warped, "warped")
-    zbuf = dst(zbuf, torch.int32, True, "zbuf")
-    L.check(L.lib().sde_depth_warp_fuse(L.ptr(prev), L.ptr(cur), L.ptr(K.contiguous()), L.ptr(T.contiguous()),
-                                        L.ptr(motion.contiguous() if motion is not None else None), N, h, w, alpha, tol, L.ptr(zbuf), L.ptr(fused),
-                                        L.ptr(state), L.ptr(warped), L.stream()), "sde_depth_warp_fuse")
+    K = A.as_K("warp_fuse", K, N, dev)
+    T = A.same_device_tensor("warp_fuse", "T", T, torch.float32, (N, 4, 4), dev)
+    if motion is not None:
+        motion = A.same_device_tensor("warp_fuse", "motion", motion, torch.float32, (N, 3, h, w), dev).contiguous()
+    fused = A.dst("warp_fuse", out, (N, h, w), torch.float32, True, dev)
+    state = A.dst("warp_fuse", state, (N, h, w), torch.uint8, want_state, dev)
+    warped = A.dst("warp_fuse", warped, (N, h, w), torch.float32, want_warped, dev)
+    zbuf = A.dst("warp_fuse", zbuf, (N, h, w), torch.int32, True, dev)
+    L.check(L.lib().sde_depth_warp_fuse(L.ptr(prev), L.ptr(cur), L.ptr(K), L.ptr(T.contiguous()), L.ptr(motion), N, h, w, alpha, tol, L.ptr(zbuf),
+                                        L.ptr(fused), L.ptr(state), L.ptr(warped), L.stream()), "sde_depth_warp_fuse")
     return fused, state, warped
 
 
@@ -71,28 +58,13 @@ def warp_fuse_host(prev, cur, K, T, motion=None, alpha=0.5, tol=0.05):
     N, h, w = prev.shape
     K = np.array(np.broadcast_to(np.asarray(K, dtype=f32), (N, 3, 3)))
     T = np.asarray(T, dtype=f32).reshape(N, 4, 4)
-    fu, fv = np.arange(w, dtype=f32)[None, :], np.arange(h, dtype=f32)[:, None]
     fused, state, warped = np.empty((N, h, w), f32), np.empty((N, h, w), np.uint8), np.empty((N, h, w), f32)
     with np.errstate(all="ignore"):
         for n in range(N):
-            fx, cx, fy, cy = K[n, 0, 0], K[n, 0, 2], K[n, 1, 1], K[n, 1, 2]
-            k00, k11, k02, k12 = f32(1) / fx, f32(1) / fy, (f32(-1) * cx) / fx, (f32(-1) * cy) / fy
             d = prev[n]
-            m = np.asarray(motion[n], dtype=f32) if motion is not None else np.zeros((3, h, w), f32)
-            px, py, pz = d * (k00 * fu + k02), d * (k11 * fv + k12), d
-            q = [T[n, r, 0] * px + T[n, r, 1] * py + T[n, r, 2] * pz + (T[n, r, 3] + m[r]) for r in range(3)]        # fp32, left to right: the kernel's order
-            nx, ny = fx * q[0] + cx * q[2], fy * q[1] + cy * q[2]
-            den = q[2] + f32(1e-6)
-            X, Y = nx / den, ny / den
-            keep = np.isfinite(d) & (d > 0) & (q[2] > 0) & np.isfinite(q[2]) & np.isfinite(X) & np.isfinite(Y)
-            rx, ry = np.rint(X), np.rint(Y)                                                                           # round-half-even, as rintf
-            keep &= (np.abs(rx) < f32(1e9)) & (np.abs(ry) < f32(1e9))
-            sel = np.nonzero(keep.ravel())[0]
-            ix, iy = rx.ravel()[sel].astype(np.int64), ry.ravel()[sel].astype(np.int64)
-            inside = (ix >= 0) & (ix < w) & (iy >= 0) & (iy < h)
-            z = np.full(h * w, _EMPTY, dtype=np.uint32)
-            np.minimum.at(z, iy[inside] * w + ix[inside], np.ascontiguousarray(q[2], dtype=f32).ravel()[sel][inside].view(np.uint32))
-            z = z.reshape(h, w)
+            _, _, qz, X, Y = pinhole_project_np(d, K[n], T[n], motion[n] if motion is not None else None)
+            keep = np.isfinite(d) & (d > 0) & (qz > 0) & np.isfinite(qz) & np.isfinite(X) & np.isfinite(Y)
+            z = zbuffer_min_np(X, Y, qz, h, w, keep=keep)
             ring = np.full((h + 2, w + 2), _EMPTY, dtype=np.uint32)                                                  # outside the image: empty
             ring[1:-1, 1:-1] = z
             near = np.full((h, w), _EMPTY, dtype=np.uint32)

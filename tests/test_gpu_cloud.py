@@ -3,6 +3,8 @@
 Compacted cloud, per case: count, order, colours and z exact; x and y within the per-element bound of cloud_ref.py -- 2^-24 * k * |d| *
 (|Kinv00 u| + |Kinv02|) with k = K_BOUND = 5, the number of float32 roundings in the evaluation order include/sde_hip.h documents (1 / fx, * u,
 cx / fx, +, * d).  The order is checked against the (u, v) the restatement keeps, never against what the kernel wrote.
+The x, y, z bytes of every record are also compared with the host twin of the camera the geometry kernels share (hip/twins.py:
+pinhole_project_np): the bound would let a reordering pass, the twin does not.
 
 Dense mode: forward and the four gradients against the float64 restatement, relative to the maximum, within 4 x the restatement's own
 float32-vs-float64 deviation on the same inputs (printed), floor 2e-5: the rule of tests/test_gpu_bts_densenet.py."""
@@ -90,6 +92,32 @@ def test_depth_cloud(name):
         assert [(int(v), int(u)) for u, v in zip(want[0]["u"], want[0]["v"])] == [(0, 4), (1, 1), (1, 2), (2, 2)]
     if name == "no_frame":
         assert bool((want[0]["rgba"] == 255).all())
+
+
+@functools.lru_cache(maxsize=None)
+def twin(name):
+    """The kernel's own fp32 arithmetic on the host (hip/twins.py: pinhole_project_np, the camera every geometry kernel shares) -> per frame
+    the float32 [count,3] coordinates sde_depth_cloud must write, in raster order; the keep decision is the restatement's."""
+    from simpledepthestimation_amd.hip.twins import pinhole_project_np
+    inp, want = reference(name)
+    full = CR.restore(inp["pred"], inp["ymap"], inp["xmap"])
+    out = []
+    for n, w in enumerate(want):
+        px, py, _, _, _ = pinhole_project_np(full[n], inp["K"][n], np.eye(4, dtype=np.float32))
+        out.append(np.stack([px[w["v"], w["u"]], py[w["v"], w["u"]], full[n][w["v"], w["u"]]], 1).astype(np.float32))
+    return out
+
+
+@pytest.mark.parametrize("name", CR.CASES)
+def test_depth_cloud_equals_the_host_twin_bit_for_bit(name):
+    """count, and the x, y, z bytes of every record up to count, are those of the shared camera's fp32 operations in their order."""
+    want = twin(name)
+    recs, cnt, _ = run_cloud(reference(name)[0])
+    assert cnt.tolist() == [w.shape[0] for w in want]
+    for n, (r, w) in enumerate(zip(recs, want)):
+        got = np.stack([r["x"], r["y"], r["z"]], 1)
+        print(f"{name} frame {n}: {int((got.view(np.uint32) != w.view(np.uint32)).sum())} of {got.size} coordinates differ from the host twin")
+        assert got.tobytes() == w.tobytes(), f"frame {n}"
 
 
 def test_depth_cloud_is_deterministic_and_ignores_workspace_contents():

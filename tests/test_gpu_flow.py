@@ -3,7 +3,8 @@
 Kernel, per case: the validity map equal outside the edge band of flow_ref.py (at most 1 % of the pixels); the flow within the per-element
 bound wherever bit 0 is set -- first order in 2^-24 from the order of operations include/sde_hip.h documents, nothing measured from the kernel --
 and exactly (0, 0) elsewhere; the colours within +-1 per channel outside the pixels the restatement places next to the wheel's wrap or to
-radius 1 (at most 0.5 %); the frame on top bit for bit."""
+radius 1 (at most 0.5 %); the frame on top bit for bit.  And every pixel of the flow and of both validity bits, bit for bit, against the host
+twin of the camera the geometry kernels share (hip/twins.py: pinhole_project_np): the bound above would let a reordering pass, the twin does not."""
 import functools
 
 import numpy as np
@@ -99,6 +100,40 @@ def test_pair_flow(name):
     # the colours alone, without the frame
     _, _, alone = run(inp, with_frame=False, want=(False, False, True))
     assert np.array_equal(alone, colour_rows)
+
+
+@functools.lru_cache(maxsize=None)
+def twin(name):
+    """The kernel's own fp32 arithmetic on the host (hip/twins.py: pinhole_project_np, the camera every geometry kernel shares) on the restored
+    fp32 inputs of one case -> (flow [N,H,W,2] float32, valid [N,H,W] uint8), the bits sde_pair_flow must write."""
+    from simpledepthestimation_amd.hip.twins import pinhole_project_np
+    inp = FR.case_inputs(name)
+    d, inside = FR.restore(inp["pred"], inp["ymap"], inp["xmap"])
+    m = FR.restore(inp["motion"], inp["ymap"], inp["xmap"])[0] if inp["motion"] is not None else None
+    N, H, W = d.shape
+    f32 = np.float32
+    fu, fv = np.arange(W, dtype=f32)[None, :], np.arange(H, dtype=f32)[:, None]
+    flow, valid = np.zeros((N, H, W, 2), f32), np.zeros((N, H, W), np.uint8)
+    with np.errstate(all="ignore"):
+        for n in range(N):
+            _, _, qz, X, Y = pinhole_project_np(d[n], inp["K"][n], inp["T"][n], m[n] if m is not None else None)
+            b0 = inside & np.isfinite(d[n]) & (d[n] > 0) & (qz > 0) & np.isfinite(X) & np.isfinite(Y)
+            b1 = b0 & (X >= 0) & (X < f32(W - 1)) & (Y >= 0) & (Y < f32(H - 1))
+            flow[n, ..., 0], flow[n, ..., 1] = np.where(b0, X - fu, f32(0)), np.where(b0, Y - fv, f32(0))
+            valid[n] = b0.astype(np.uint8) | (b1.astype(np.uint8) << 1)
+    return flow, valid
+
+
+@pytest.mark.parametrize("name", FR.CASES)
+def test_pair_flow_equals_the_host_twin_bit_for_bit(name):
+    """Every pixel, no edge band: the flow's bytes and both validity bits are those of the shared camera's fp32 operations in their order."""
+    want_flow, want_valid = twin(name)
+    flow, valid, _ = run(reference(name)[0], want=(True, True, False))
+    differing = int((flow.view(np.uint32) != want_flow.view(np.uint32)).sum())
+    print(f"{name}: {differing} of {flow.size} flow values and {int((valid != want_valid).sum())} of {valid.size} validity bytes differ from the host twin")
+    assert np.array_equal(valid & 1, want_valid & 1), "bit 0"
+    assert np.array_equal(valid & 2, want_valid & 2), "bit 1"
+    assert flow.tobytes() == want_flow.tobytes()
 
 
 def test_two_runs_give_equal_bytes_and_unrequested_outputs_stay_untouched():
