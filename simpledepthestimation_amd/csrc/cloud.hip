@@ -143,7 +143,7 @@ __global__ void __launch_bounds__(TILE) i2p_fwd(const float* __restrict__ depth,
 
 __global__ void __launch_bounds__(TILE) i2p_bwd(const float* __restrict__ g, const float* __restrict__ depth, const float* __restrict__ R, int H, int W,
                                                 float* __restrict__ ddepth, float* __restrict__ part) {
-    __shared__ float red[16];
+    __shared__ float red[NSUM * WAVES];
     const int b = blockIdx.y, npx = H * W, i = blockIdx.x * TILE + threadIdx.x;
     float s[NSUM];
 #pragma unroll
@@ -166,12 +166,7 @@ __global__ void __launch_bounds__(TILE) i2p_bwd(const float* __restrict__ g, con
         ddepth[(size_t)b * npx + i] = dd;
     }
     if (!part) return;                                   // only ddepth was asked for (the same branch in every thread)
-    float* dst = part + ((size_t)b * gridDim.x + blockIdx.x) * NSUM;
-#pragma unroll
-    for (int k = 0; k < NSUM; ++k) {
-        const float r = sde_block_sum(s[k], red);
-        if (threadIdx.x == 0) dst[k] = r;
-    }
+    sde_block_sums<NSUM, WAVES>(s, red, part + ((size_t)b * gridDim.x + blockIdx.x) * NSUM);
 }
 
 // one wave per sample: lane k < 12 adds sum k of every workgroup, in workgroup order, in fp64

@@ -52,19 +52,6 @@ __device__ __forceinline__ void store_grid(const Proj& pr, int W, int H, float* 
     g[1] = (2.0f * ys) / hm1 - 1.0f;
 }
 
-// Sums of NV values over a 256-thread workgroup, written by threads 0..NV-1 to out[0..NV) (waves added in order: deterministic)
-template <int NV>
-__device__ __forceinline__ void block_sums(float (&v)[NV], float* red /*[4 * NV]*/, float* __restrict__ out) {
-#pragma unroll
-    for (int i = 0; i < NV; ++i) v[i] = sde_wave_sum(v[i]);
-    const int tid = threadIdx.x;
-    if ((tid & 63) == 0)
-#pragma unroll
-        for (int i = 0; i < NV; ++i) red[(tid >> 6) * NV + i] = v[i];
-    __syncthreads();
-    if (tid < NV) out[tid] = ((red[tid] + red[NV + tid]) + red[2 * NV + tid]) + red[3 * NV + tid];
-}
-
 // ------------------------------------------------------------------------------------------------
 // view_synthesis with t [B,3,H,W] (camera.py:L166-202): the outputs of view_synthesis_kernel
 // ------------------------------------------------------------------------------------------------
@@ -142,7 +129,7 @@ __global__ void __launch_bounds__(PB_N) rgbd_warp_kernel(const RgbdArgs a) {
         v[0] = occ; v[1] = (e * e) * occ; v[2] = l1; v[3] = fabsf(sD - Z) * occ;
     }
     const int blk = (n * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-    block_sums<4>(v, red, a.partial + 4 * (long)blk);
+    sde_block_sums<4, PB_N / 64>(v, red, a.partial + 4 * (long)blk);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -219,13 +206,12 @@ __device__ __forceinline__ float wssim_value(const float* __restrict__ xs, const
 
 // normalizer - 1 and the depth error's second moment of sample n from pass 1's partials: every workgroup of the sample adds them in the same order
 __device__ __forceinline__ float sample_m2(const float* __restrict__ part1, int n, int bps, float* red) {
-    float so = 0.f, se = 0.f;
-    for (int i = threadIdx.x; i < bps; i += PB_N) { so += part1[((long)n * bps + i) * 4]; se += part1[((long)n * bps + i) * 4 + 1]; }
-    so = sde_block_sum(so, red);
+    __shared__ float tot[2], m2s;
+    float v[2] = {0.f, 0.f};                                       // sum occ, sum err^2 occ: the first two of pass 1's four values
+    sde_partial_walk<2, PB_N>(v, part1, (long)n * bps, bps, threadIdx.x, 4);
+    sde_block_sums<2, PB_N / 64>(v, red, tot);
     __syncthreads();
-    se = sde_block_sum(se, red);
-    __shared__ float m2s;
-    if (threadIdx.x == 0) m2s = se / (so + 1.0f) + 1e-4f;
+    if (threadIdx.x == 0) m2s = tot[1] / (tot[0] + 1.0f) + 1e-4f;
     __syncthreads();
     return m2s;
 }
@@ -252,7 +238,6 @@ __global__ void __launch_bounds__(PB_N) wssim_fwd_kernel(const WssimArgs a) {
         if (a.wout) a.wout[n * hw + pix] = w.wc;
     }
     if (a.partial) {
-        __syncthreads();
         const float s = sde_block_sum(acc, red);
         if (threadIdx.x == 0) a.partial[(n * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = s;
     }
@@ -330,13 +315,10 @@ __global__ void __launch_bounds__(PB_N) rgbd_finalize_kernel(const float* __rest
     __shared__ float red[20];
     const int n = blockIdx.x;
     float v[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
-    for (int i = threadIdx.x; i < bps; i += PB_N) {
-        const float* p = part1 + ((long)n * bps + i) * 4;
-        v[0] += p[0]; v[1] += p[1]; v[2] += p[2]; v[3] += p[3];
-        if (part2) v[4] += part2[(long)n * bps + i];
-    }
+    sde_partial_walk<4, PB_N>(v, part1, (long)n * bps, bps, threadIdx.x);
+    if (part2) sde_partial_walk<1, PB_N>(v + 4, part2, (long)n * bps, bps, threadIdx.x);
     __shared__ float tot[5];
-    block_sums<5>(v, red, tot);
+    sde_block_sums<5, PB_N / 64>(v, red, tot);
     __syncthreads();
     if (threadIdx.x == 0) {
         const float nrm = tot[0] + 1.0f;
@@ -423,28 +405,24 @@ __global__ void __launch_bounds__(PB_N) rgbd_bwd_kernel(const RgbdBwdArgs a) {
         }
     }
     const int blk = (n * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-    block_sums<9>(acc9, red, a.dR_partial + 9 * (long)blk);
+    sde_block_sums<9, PB_N / 64>(acc9, red, a.dR_partial + 9 * (long)blk);
 }
 
-// d R [N,3,3] (+ optional second destination) from the per-workgroup partials: one wave per sample, lanes split the partials, fixed butterfly
+// the nine sums of sample n over its bps per-workgroup partials, in every lane: one wave per sample, lanes split the partials, fixed butterfly
+__device__ __forceinline__ void sample_sum9(const float* __restrict__ partial, int n, int bps, float (&acc)[9]) {
+#pragma unroll
+    for (int i = 0; i < 9; ++i) acc[i] = 0.f;
+    sde_partial_walk<9, 64>(acc, partial, (long)n * bps, bps, threadIdx.x);
+#pragma unroll
+    for (int i = 0; i < 9; ++i) acc[i] = sde_wave_sum(acc[i]);
+}
+
+// d R [N,3,3] from the per-workgroup partials
 __global__ void __launch_bounds__(64) sum9_finalize_kernel(const float* __restrict__ partial, int bps, float* __restrict__ dR) {
     const int n = blockIdx.x, lane = threadIdx.x;
     float acc[9];
-#pragma unroll
-    for (int i = 0; i < 9; ++i) acc[i] = 0.f;
-    for (int k = lane; k < bps; k += 64) {
-        const float* p = partial + ((long)n * bps + k) * 9;
-#pragma unroll
-        for (int i = 0; i < 9; ++i) acc[i] += p[i];
-    }
-#pragma unroll
-    for (int i = 0; i < 9; ++i) acc[i] = sde_wave_sum(acc[i]);
-    if (lane < 9) {
-        float s = 0.f;
-#pragma unroll
-        for (int i = 0; i < 9; ++i) s = lane == i ? acc[i] : s;
-        dR[n * 9 + lane] = s;
-    }
+    sample_sum9(partial, n, bps, acc);
+    if (lane < 9) dR[n * 9 + lane] = sde_lane_pick(acc, lane);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -529,7 +507,6 @@ __global__ void __launch_bounds__(PB_N) mc_finalize_kernel(const float* __restri
     for (int i = threadIdx.x; i < nblk; i += PB_N) s += partial[i];
     for (int n = threadIdx.x; n < N; n += PB_N) r += mc_rot(R1 + 9 * n, R2 + 9 * n, 0.f, nullptr, nullptr);
     s = sde_block_sum(s, red);
-    __syncthreads();
     r = sde_block_sum(r, red);
     if (threadIdx.x == 0) { out[0] = r / (float)N; out[1] = s * inv_pixels; }
 }
@@ -574,7 +551,7 @@ __global__ void __launch_bounds__(PB_N) mc_bwd_kernel(const float* __restrict__ 
         }
     }
     const int blk = (n * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-    block_sums<9>(acc9, red, dR_partial + 9 * (long)blk);
+    sde_block_sums<9, PB_N / 64>(acc9, red, dR_partial + 9 * (long)blk);
 }
 
 // d R_A2B = sum of the translation term's partials + rotation term, d R_B2A = rotation term: one wave per sample
@@ -582,15 +559,7 @@ __global__ void __launch_bounds__(64) mc_bwd_finalize_kernel(const float* __rest
                                                              const float* __restrict__ g_rot, int N, float* __restrict__ dR1, float* __restrict__ dR2) {
     const int n = blockIdx.x, lane = threadIdx.x;
     float acc[9];
-#pragma unroll
-    for (int i = 0; i < 9; ++i) acc[i] = 0.f;
-    for (int k = lane; k < bps; k += 64) {
-        const float* p = partial + ((long)n * bps + k) * 9;
-#pragma unroll
-        for (int i = 0; i < 9; ++i) acc[i] += p[i];
-    }
-#pragma unroll
-    for (int i = 0; i < 9; ++i) acc[i] = sde_wave_sum(acc[i]);
+    sample_sum9(partial, n, bps, acc);
     if (lane == 0) {
         float a[9], b[9];
         mc_rot(R1 + 9 * n, R2 + 9 * n, (g_rot ? g_rot[0] : 0.f) / (float)N, a, b);
@@ -604,19 +573,11 @@ __global__ void __launch_bounds__(64) mc_bwd_finalize_kernel(const float* __rest
 // arrives last (device-scope ticket, left at zero again) adds them up in index order.
 // ------------------------------------------------------------------------------------------------
 __device__ __forceinline__ void ticket_finalize(float s, float* __restrict__ partial, int nblk, int blk, float scale, float* __restrict__ out, int* __restrict__ ticket) {
-    __shared__ int last;
-    if (threadIdx.x == 0) {
-        __hip_atomic_store(partial + blk, s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __threadfence();
-        last = (__hip_atomic_fetch_add(ticket, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == nblk - 1);
-    }
-    __syncthreads();
-    if (last && threadIdx.x == 0) {
-        __threadfence();
+    if (threadIdx.x == 0) __hip_atomic_store(partial + blk, s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (sde_arrive_last(ticket, nblk) && threadIdx.x == 0) {
         float t = 0.f;
-        for (int i = 0; i < nblk; ++i) t += __hip_atomic_load(partial + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        for (int i = 0; i < nblk; ++i) t += ld_agent(partial + i);
         out[0] = t * scale;
-        __hip_atomic_store(ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 }
 
@@ -672,7 +633,6 @@ __global__ void __launch_bounds__(1024) msparse_fwd_kernel(const float* __restri
     const float m = ms, rm = 1.0f / (m + 1e-24f);
     v = 0.f;
     for (long i = threadIdx.x; i < hw; i += 1024) v += (2.0f * m) * sqrtf(fabsf(s[i]) * rm + 1.0f);
-    __syncthreads();
     v = sde_block_sum(v, red);
     ticket_finalize(v, partial, planes, p, scale, out, ticket);
 }
@@ -754,29 +714,17 @@ struct PrepArgs {
 template <int NV>
 __device__ __forceinline__ bool sample_sums_and_arrive(float* sums /*LDS [NV]*/, float* red /*LDS [4 * NV]*/, const float* __restrict__ partial, float* __restrict__ per,
                                                        int n, int N, int bps, int* __restrict__ ticket) {
-    __shared__ int last;
-    const int tid = threadIdx.x;
     float v[NV];
 #pragma unroll
     for (int k = 0; k < NV; ++k) v[k] = 0.f;
-    for (int i = tid; i < bps; i += PB_N)
-#pragma unroll
-        for (int k = 0; k < NV; ++k) v[k] += partial[((long)n * bps + i) * NV + k];
-    block_sums<NV>(v, red, sums);
+    sde_partial_walk<NV, PB_N>(v, partial, (long)n * bps, bps, threadIdx.x);
+    sde_block_sums<NV, PB_N / 64>(v, red, sums);
     __syncthreads();
-    if (tid == 0) {
+    if (threadIdx.x == 0)
 #pragma unroll
         for (int k = 0; k < NV; ++k) __hip_atomic_store(per + (long)n * NV + k, sums[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        last = (__hip_atomic_fetch_add(ticket, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == N - 1);
-        if (last) __hip_atomic_store(ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    __syncthreads();
-    if (!last) return false;
-    __threadfence();
-    return true;
+    return sde_arrive_last(ticket, N);
 }
-
-__device__ __forceinline__ float ld_agent(const float* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 __global__ void __launch_bounds__(PB_N) prep_pool_kernel(const PrepArgs a) {
     __shared__ float red[8];
@@ -811,7 +759,7 @@ __global__ void __launch_bounds__(PB_N) prep_pool_kernel(const PrepArgs a) {
             v[1] += t * t;
         }
     }
-    block_sums<2>(v, red, a.partial + 2 * (long)((blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x));
+    sde_block_sums<2, PB_N / 64>(v, red, a.partial + 2 * (long)((blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x));
 }
 
 // depth mean and per-sample motion scale from the partials of prep_pool_kernel: grid N
@@ -906,7 +854,7 @@ __global__ void __launch_bounds__(PB_N) prep_bwd_reduce_kernel(const PrepBwdArgs
             v[6 + c] = tv;
         }
     }
-    block_sums<9>(v, red, a.partial + 9 * (long)((blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x));
+    sde_block_sums<9, PB_N / 64>(v, red, a.partial + 9 * (long)((blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x));
 }
 
 // c_n, d t_pose and d depth_mean from the partials of prep_bwd_reduce_kernel: grid N

@@ -413,7 +413,8 @@ __device__ __forceinline__ void photo_bwd_body(const PhotoBwdArgs& a, const int 
                 acc12[9 + m] = kq;
             }
         }
-        // the 12 pose-gradient terms: wave sums now (every wave owns its slots of `red`: no barrier), the block sum once after the loop
+        // the 12 pose-gradient terms: wave sums now (every wave owns its slots of `red`: no barrier), the block sum once after the loop.  This is
+        // sde_block_sums<12, 4> (reduce.h) taken apart so that NCTX contexts share one barrier; kept open-coded because the kernel is register-bound
 #pragma unroll
         for (int i = 0; i < 12; ++i) acc12[i] = sde_wave_sum(acc12[i]);
         if ((lp & 63) == 0)
@@ -534,7 +535,7 @@ __global__ void __launch_bounds__(256) reduce_partials_kernel(const MultiReduce 
     __shared__ float red[16];
     const int k = blockIdx.x;
     float s = 0.f;
-    for (int i = threadIdx.x; i < r.n[k]; i += 256) s += r.partial[k][i];
+    sde_partial_walk<1, 256>(&s, r.partial[k], 0, r.n[k], threadIdx.x);
     s = sde_block_sum(s, red);
     if (threadIdx.x == 0) out[k] = r.accumulate ? out[k] + s * r.scale[k] : s * r.scale[k];
 }
@@ -553,19 +554,13 @@ __global__ void pose_grad_finalize_multi_kernel(const MultiPose mp, int nctx, in
 #pragma unroll
         for (int i = 0; i < 12; ++i) acc[i] = 0.f;
         const int bps = mp.blocks_per_sample[s];
-        for (int k = lane; k < bps; k += 64) {
-            const float* p = mp.partial[s] + (((long)b * bps + k) * nctx + j) * 12;
-#pragma unroll
-            for (int i = 0; i < 12; ++i) acc[i] += p[i];
-        }
+        sde_partial_walk<12, 64>(acc, mp.partial[s] + j * 12, (long)b * bps, bps, lane, nctx * 12);      // the slab interleaves the contexts
 #pragma unroll
         for (int i = 0; i < 12; ++i) tot[i] += sde_wave_sum(acc[i]);
     }
     float* dp = j == 0 ? dpose0 : (j == 1 ? dpose1 : (j == 2 ? dpose2 : dpose3));
     if (lane < 12) {
-        float s = 0.f;
-#pragma unroll
-        for (int i = 0; i < 12; ++i) s = lane == i ? tot[i] : s;
+        const float s = sde_lane_pick(tot, lane);
         const int r = lane < 9 ? lane / 3 : lane - 9, c = lane < 9 ? lane % 3 : 3;
         float* o = dp + b * 16 + r * 4 + c;
         *o = mp.accumulate ? (*o + s) : s;
@@ -594,7 +589,7 @@ __device__ __forceinline__ void smooth_fwd_body(const float* __restrict__ depth,
                                                 const float* __restrict__ mean_part, int B, int h, int w,
                                                 float* __restrict__ dn, float* __restrict__ loss_part /*[nblk]*/,
                                                 float* __restrict__ s_part /*[nblk]*/, const int bx, const int by, const int bz, const int gdx, const int gdy) {
-    __shared__ float red[16];
+    __shared__ float red[16], tot[2];
     const int b = bz;
     const int x = bx * 64 + (threadIdx.x & 63);
     const int y = by * 4 + (threadIdx.x >> 6);
@@ -658,10 +653,13 @@ __device__ __forceinline__ void smooth_fwd_body(const float* __restrict__ depth,
         sv = g * inv;
     }
     const int blk = (bz * gdy + by) * gdx + bx;
-    const float ls = sde_block_sum(loss, red);
-    if (threadIdx.x == 0) loss_part[blk] = ls;
-    const float ss = sde_block_sum(sv, red);
-    if (threadIdx.x == 0 && s_part) s_part[blk] = ss;
+    float v[2] = {loss, sv};
+    sde_block_sums<2, 4>(v, red, tot);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        loss_part[blk] = tot[0];
+        if (s_part) s_part[blk] = tot[1];
+    }
 }
 
 __device__ __forceinline__ void smooth_bwd_body(const float* __restrict__ depth, const float* __restrict__ dn,
@@ -675,7 +673,7 @@ __device__ __forceinline__ void smooth_bwd_body(const float* __restrict__ depth,
     // the sample's sum of the forward partials: every workgroup needs it, and a single thread walking the up to 480 partials one dependent load at a
     // time made this pass 6x its traffic time (61 us at 192x640); all 256 threads take a strided share, in the same fixed order in every workgroup
     float s = 0.f;
-    for (int i = threadIdx.x; i < blocks_per_sample; i += 256) s += s_part[(long)b * blocks_per_sample + i];
+    sde_partial_walk<1, 256>(&s, s_part, (long)b * blocks_per_sample, blocks_per_sample, threadIdx.x);
     s = sde_block_sum(s, red);
     if (threadIdx.x == 0) {
         float m = 0.f;
@@ -742,26 +740,18 @@ struct MonoReduce {
 };
 __global__ void __launch_bounds__(256) mono_loss_finalize_kernel(const MonoReduce r, float* __restrict__ per_scale, float* __restrict__ totals, int* __restrict__ ticket) {
     __shared__ float red[16];
-    __shared__ int last;
     const int k = blockIdx.x;
     float s = 0.f;
-    for (int i = threadIdx.x; i < r.n[k]; i += 256) s += r.partial[k][i];
+    sde_partial_walk<1, 256>(&s, r.partial[k], 0, r.n[k], threadIdx.x);
     s = sde_block_sum(s, red);
-    if (threadIdx.x == 0) {
-        __hip_atomic_store(per_scale + k, s * r.scale[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __threadfence();
-        last = (__hip_atomic_fetch_add(ticket, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == r.count - 1);
-    }
-    __syncthreads();
-    if (last && threadIdx.x == 0) {
-        __threadfence();
+    if (threadIdx.x == 0) __hip_atomic_store(per_scale + k, s * r.scale[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (sde_arrive_last(ticket, r.count) && threadIdx.x == 0) {
         float t0 = 0.f, t1 = 0.f;
         for (int j = 0; j < r.count; ++j) {
-            const float v = __hip_atomic_load(per_scale + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) * r.weight[j];
+            const float v = ld_agent(per_scale + j) * r.weight[j];
             if (j < r.nphoto) t0 += v; else t1 += v;
         }
         totals[0] = t0; totals[1] = t1;
-        __hip_atomic_store(ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 }
 
@@ -805,12 +795,8 @@ __global__ void __launch_bounds__(256) silog_multi_fwd_kernel(SilogScales a, con
             c += 1.f; s1 += d; s2 += d * d;
         }
     }
-    c = sde_block_sum(c, red);
-    if (threadIdx.x == 0) part[blockIdx.x * 3 + 0] = c;
-    s1 = sde_block_sum(s1, red);
-    if (threadIdx.x == 0) part[blockIdx.x * 3 + 1] = s1;
-    s2 = sde_block_sum(s2, red);
-    if (threadIdx.x == 0) part[blockIdx.x * 3 + 2] = s2;
+    float v[3] = {c, s1, s2};
+    sde_block_sums<3, 4>(v, red, part + blockIdx.x * 3);
 }
 
 // stats[k][0..3] = (count, mean d, mean d^2, loss) with loss = 10 * sqrt(E[d^2] - vf * E[d]^2); total[0] (optional) = sum_k weight[k] * loss[k] (scales in

@@ -215,6 +215,19 @@ def stream():
     return c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+_TICKET = {}
+
+
+def ticket(dev):
+    """Arrival counter of the loss kernels whose last workgroup finishes the reduction (csrc/reduce.h: sde_arrive_last): one int per device, zero between
+    launches (the last arriver resets it).  Every launch that is given it counts on this same int, so such launches must be ordered on ONE stream: two
+    of them that overlap on different streams would see each other's arrivals.  The current users: the mono loss' finalize, motion smoothness and
+    sparsity, and pair_prep's two finalize kernels."""
+    if dev not in _TICKET:
+        _TICKET[dev] = torch.zeros(1, dtype=torch.int32, device=dev)
+    return _TICKET[dev]
+
+
 _side = {}
 # Weight-gradient GEMMs run on ONE side stream, forked in groups and joined late (hip/nn.py: WGradReducer, wgrad_group_rule).  The values below
 # were each decided by an A/B run inside one gpurun call in round 1 (DESIGN.md 6.1 keeps the measurements); the environment switches that

@@ -23,16 +23,6 @@ def _shape(t, shape, name):
         raise L.SdeHipError(f"{name}: expected shape {tuple(shape)}, got {tuple(t.shape)}")
 
 
-_TICKET = {}
-
-
-def _ticket(dev):
-    """Arrival counter of the single-launch reductions: one device int per device, zero between launches (the kernel resets it)."""
-    if dev not in _TICKET:
-        _TICKET[dev] = torch.zeros(1, dtype=torch.int32, device=dev)
-    return _TICKET[dev]
-
-
 def view_synthesis_pp(image_B, depth_A, K, R, t):
     """camera.py:L166-202 with t [B,3,H,W], forward only (the parity surface): dict(sampled, Z, grid, valid)."""
     image_B, depth_A, K, R, t = _f32c(image_B), _f32c(depth_A), _f32c(K), _f32c(R), _f32c(t)
@@ -187,7 +177,7 @@ class _MotionSmooth(torch.autograd.Function):
         lib = L.lib()
         part = torch.empty(lib.sde_motion_smooth_num_blocks(B * C, H, W), device=f.device)
         out = torch.empty((), device=f.device)
-        L.check(lib.sde_motion_smooth_fwd(L.ptr(f), B * C, H, W, L.ptr(part), L.ptr(out), L.ptr(_ticket(f.device)), L.stream()), "sde_motion_smooth_fwd")
+        L.check(lib.sde_motion_smooth_fwd(L.ptr(f), B * C, H, W, L.ptr(part), L.ptr(out), L.ptr(L.ticket(f.device)), L.stream()), "sde_motion_smooth_fwd")
         ctx.save_for_backward(f)
         return out
 
@@ -212,7 +202,7 @@ class _MotionSparsity(torch.autograd.Function):
         B, C, H, W = f.shape
         mean, part = torch.empty(B * C, device=f.device), torch.empty(B * C, device=f.device)
         out = torch.empty((), device=f.device)
-        L.check(L.lib().sde_motion_sparsity_fwd(L.ptr(f), B * C, H * W, L.ptr(mean), L.ptr(part), L.ptr(out), L.ptr(_ticket(f.device)), L.stream()),
+        L.check(L.lib().sde_motion_sparsity_fwd(L.ptr(f), B * C, H * W, L.ptr(mean), L.ptr(part), L.ptr(out), L.ptr(L.ticket(f.device)), L.stream()),
                 "sde_motion_sparsity_fwd")
         ctx.save_for_backward(f, mean)
         return out
@@ -285,7 +275,7 @@ class _PairPrep(torch.autograd.Function):
         m_norm = e(N, 3, h, w) if motion is not None else None
         partial, stats = e(lib.sde_rgbd_num_blocks(N, h, w), 2), e(2 + 4 * N)
         L.check(lib.sde_motion_prep_fwd(L.ptr(depth), L.ptr(motion), L.ptr(t_pose), L.ptr(mask01), N, H0, W0, h, w, int(normalize), L.ptr(depth_r), L.ptr(depth_n),
-                                        L.ptr(t), L.ptr(overall), L.ptr(m_norm), L.ptr(dn_sw), L.ptr(t_sw), L.ptr(partial), L.ptr(stats), L.ptr(_ticket(dev)),
+                                        L.ptr(t), L.ptr(overall), L.ptr(m_norm), L.ptr(dn_sw), L.ptr(t_sw), L.ptr(partial), L.ptr(stats), L.ptr(L.ticket(dev)),
                                         L.stream()), "sde_motion_prep_fwd")
         ctx.save_for_backward(mask01, depth_n, t, m_norm, stats)
         ctx.cfg = (N, H0, W0, h, w, bool(normalize))
@@ -310,7 +300,7 @@ class _PairPrep(torch.autograd.Function):
         d_motion = e(N, 3, H0, W0) if m_norm is not None else None
         partial, bstats = e(lib.sde_rgbd_num_blocks(N, h, w), 9), e(1 + 10 * N)
         L.check(lib.sde_motion_prep_bwd(L.ptr(mask01), L.ptr(depth_n), L.ptr(t), L.ptr(m_norm), L.ptr(stats), L.ptr(g[0]), L.ptr(g[1]), L.ptr(g[2]), L.ptr(g[3]),
-                                        L.ptr(g[4]), N, H0, W0, h, w, int(normalize), L.ptr(partial), L.ptr(bstats), L.ptr(_ticket(dev)), L.ptr(d_depth),
+                                        L.ptr(g[4]), N, H0, W0, h, w, int(normalize), L.ptr(partial), L.ptr(bstats), L.ptr(L.ticket(dev)), L.ptr(d_depth),
                                         L.ptr(d_motion), L.ptr(d_tpose), L.stream()), "sde_motion_prep_bwd")
         return d_depth, d_motion, d_tpose, None, None, None, None
 
