@@ -799,6 +799,62 @@ int sde_depth_warp_fuse(const float* prev, const float* cur, const float* K, con
                         float alpha, float tol, uint32_t* zbuf, float* fused, uint8_t* state, float* warped, sde_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * A sequence's depth fused into one truncated-signed-distance (TSDF) volume (csrc/volume.hip; binding and host twins in hip/volume.py): every
+ * frame's depth is averaged into a voxel grid through its world-to-camera pose, and the zero crossings of the grid are the surface.  No
+ * counterpart in the reference.
+ *
+ * The volume: nx x ny x nz voxels, x fastest, linear index v = (k * ny + j) * nx + i; every dimension in [1, 1024], nx * ny * nz <= 2^30.
+ * Three device arrays: tsdf [nz,ny,nx] fp32, weight [nz,ny,nx] fp32, rgba [nz,ny,nx,4] uint8 (4-byte aligned; NULL: no colour).  A fresh volume
+ * is tsdf = 1, weight = 0, rgba = 0, written by the caller.  origin [3]: HOST memory, the corner of voxel (0,0,0) in world coordinates, read
+ * before the launch; voxel: the edge length.  The centre of voxel (i,j,k), in fp32, nothing fused:
+ *   wx = ox + ((float)i + 0.5f) * voxel;   wy = oy + ((float)j + 0.5f) * voxel;   wz = oz + ((float)k + 0.5f) * voxel.
+ *
+ * sde_pose_compose: C <- T * C for ONE rigid 4x4 fp32 transform, both row-major in device memory, in place.  For the rows r = 0, 1, 2:
+ *   C'_rc = (T_r0 * C_0c + T_r1 * C_1c) + T_r2 * C_2c          for c = 0, 1, 2;      C'_r3 = ((T_r0 * C_03 + T_r1 * C_13) + T_r2 * C_23) + T_r3;
+ * the bottom row is written as 0 0 0 1 (those of T and C are not read).  With C the world-to-camera pose of frame i (p_cam = C p_world, the
+ * first frame as the world: C_0 = I) and T_i the step i -> i+1 (p_{i+1} = T_i p_i, what the pose network predicts), C_{i+1} = T_i C_i: the
+ * inverse of the camera-to-world chain of accumulate_poses, and no inversion on the device.  One launch of one workgroup.  Refused: NULL T or C.
+ *
+ * sde_tsdf_integrate: ONE frame into the volume.  pred [ph,pw] fp32, ymap [H] / xmap [W] (the maps of sde_depth_present, same contract: -1 =
+ * outside; the caller validates the ranges), frame [H,W,3] uint8 RGB or NULL, K [3,3] fp32 at the restored (source) size (only fx = K[0],
+ * cx = K[2], fy = K[4], cy = K[5] are read), C [4,4] fp32 in device memory, world -> camera (only its top three rows are read).  For the voxel
+ * (i,j,k) with centre (wx,wy,wz), in fp32 in exactly this order, nothing fused (every division correctly rounded):
+ *   1. q_r = ((C_r0 * wx + C_r1 * wy) + C_r2 * wz) + C_r3  for the rows r = x, y, z;                       kept iff qz is finite and > 0;
+ *   2. nx = fx * qx + cx * qz;  ny = fy * qy + cy * qz;  den = qz + 1e-6f;  X = nx / den;  Y = ny / den;       (sde_pair_flow's projection)
+ *      rx = rintf(X), ry = rintf(Y) (round-half-even);      kept iff |rx|, |ry| < 1e9f and, with ix = (int)rx, iy = (int)ry, 0 <= ix < W, 0 <= iy < H;
+ *   3. my = ymap[iy];  mx = xmap[ix];                                                                         kept iff both >= 0;
+ *   4. d = pred[my * pw + mx];                              kept iff d is finite and min_depth < d <= max_depth  (sde_depth_cloud's rule);
+ *   5. sdf = d - qz;                                                                                          kept iff sdf >= -trunc;
+ *   6. t = fminf(1.f, sdf / trunc);   w0 = weight[v];   t0 = tsdf[v];
+ *      tsdf[v] = (t0 * w0 + t) / (w0 + 1.f);   weight[v] = fminf(w0 + 1.f, max_weight);
+ *   7. with frame and rgba both non-NULL, and only where sdf <= trunc: per channel, with c0 the stored byte and f the frame's at (iy, ix),
+ *      c = ((float)c0 * w0 + (float)f) / (w0 + 1.f), stored as (uint8)(c + 0.5f); the alpha byte becomes 255.
+ * A voxel that is not kept is neither read from nor written to the three arrays.  Voxels are independent: one launch (a grid-stride grid), no
+ * atomics, no workspace, no allocation, no host synchronisation: legal under graph capture, the same bytes every run.  frame without rgba and
+ * rgba without frame are allowed: colour is skipped.  Refused before any launch: H, W, ph, pw <= 0, dims outside the limits above, voxel, trunc
+ * or max_weight <= 0 (or a NaN), min_depth >= max_depth (or a NaN), NULL pred / maps / K / C / origin / tsdf / weight, rgba off a 4-byte boundary.
+ *
+ * sde_tsdf_points: the zero crossings of the volume as the 16-byte records { float x, y, z; uint8 r, g, b, a } of sde_depth_cloud, each written
+ * by one aligned 16-byte store.  A voxel is valid iff weight >= min_weight (min_weight >= 1).  For the voxel v and, in the order x, y, z, its +1
+ * neighbour n along that axis inside the grid: one record iff both are valid and (tsdf[v] < 0) != (tsdf[n] < 0).  With tv = tsdf[v], tn = tsdf[n]:
+ *   f = tv / (tv - tn);   the coordinate along the axis = (the centre of v along it) + f * voxel;   the other two are the centre's;
+ *   colour: rgba[v] if f < 0.5f, else rgba[n] (0, 0, 0 with rgba == NULL);   a = 255.
+ * Record order: ascending v, then axis.  points [cap][16 bytes], 16-byte aligned; count [1] int32: the total number of crossings, also when it
+ * exceeds cap (saturated at 2^31 - 1); records at positions >= cap are not written, and the bytes behind the written records are not touched.
+ * workspace: sde_tsdf_points_ws_bytes(nx, ny, nz) bytes of device memory, 4-byte aligned, contents irrelevant (0 for dims the entry points
+ * refuse).  Three launches ordered on the stream (crossings per tile of 256 voxels, exclusive scan, scatter); no workgroup waits for another, no
+ * atomics, no host synchronisation, no allocation: legal under graph capture, the same bytes every run.  Refused before any launch: dims outside
+ * the limits, voxel <= 0, min_weight < 1 (or a NaN), cap outside [1, 2^31), NULL tsdf / weight / origin / points / count, points off a 16-byte
+ * or rgba off a 4-byte boundary, a workspace that is NULL or smaller than the query reports. */
+int sde_pose_compose(const float* T, float* C, sde_stream_t stream);
+int sde_tsdf_integrate(const float* pred, int ph, int pw, const int* ymap, const int* xmap, int H, int W, const uint8_t* frame, const float* K,
+                       const float* C, const float* origin, float voxel, float trunc, float max_weight, float min_depth, float max_depth,
+                       float* tsdf, float* weight, uint8_t* rgba, int nx, int ny, int nz, sde_stream_t stream);
+size_t sde_tsdf_points_ws_bytes(int nx, int ny, int nz);
+int sde_tsdf_points(const float* tsdf, const float* weight, const uint8_t* rgba, int nx, int ny, int nz, const float* origin, float voxel,
+                    float min_weight, void* workspace, size_t workspace_bytes, void* points, long cap, int* count, sde_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * MotionLearning loss stack (csrc/motion_loss.hip; autograd wrappers in hip/motion_loss.py).  fp32, planar NCHW, no host synchronisation.
  *
  * sde_view_synthesis_pp: detectron2/geometry/camera.py:L166-202 with a per-pixel translation t [B,3,H,W] and a 3x3 rotation R [B,3,3]; the

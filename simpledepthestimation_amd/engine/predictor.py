@@ -509,6 +509,39 @@ class _TemporalState:
             self.motion.zero_()
 
 
+def volume_arg(volume, device=None):
+    """volume=None -> None; else the hip.volume.TsdfVolume itself, which must live on the predictor's device."""
+    if volume is None:
+        return None
+    from ..hip.volume import TsdfVolume
+    if not isinstance(volume, TsdfVolume):
+        raise ValueError(f"PairPredictor: volume must be None or a hip.volume.TsdfVolume, got {type(volume).__name__}")
+    if device is not None and volume.device != device:
+        raise ValueError(f"PairPredictor: the volume lives on {volume.device}, the predictor on {device}")
+    return volume
+
+
+class _VolumeState:
+    """What the volume fusion keeps on the device from one window to the next, beside the temporal state: C, the world-to-camera pose of the
+    window's target (the first target of a sequence is the world), and T, the step previous target -> this one that C is advanced by before the
+    window is integrated -- the form _TemporalState keeps its pose in, the identity until a window has run (`started`, for a model that only
+    looks back and so brings the step into its own window along).  The graphs of both slots read and write these tensors."""
+
+    def __init__(self, device):
+        self.eye = torch.eye(4, dtype=torch.float32, device=device)
+        self.C, self.T, self.inv = self.eye.clone(), self.eye.clone(), self.eye.clone()
+        self.started = torch.zeros((1,), dtype=torch.bool, device=device)
+
+    def tensors(self):
+        return [self.C, self.T, self.started]
+
+    def reset(self):
+        """The next window is the world, on the current stream.  The volume itself is the caller's and is left as it is."""
+        self.C.copy_(self.eye)
+        self.T.copy_(self.eye)
+        self.started.zero_()
+
+
 def as_window(frames, n):
     """A window of 1 + n frames (the target, then the contexts in `ctx_img` order; a list or one [1+n,H,W,3] array) -> uint8 [1+n,H,W,3] tensor."""
     if isinstance(frames, (list, tuple)):
@@ -543,7 +576,11 @@ class PairPredictor(_Predictor):
     the device for the warp of window k + 1; a model that only looks back inverts the current window's pose to the context at -1 on the device
     and warps rigidly, because its motion field lies on the current frame's grid, not on the previous one's.  The pictures come from the fused
     map; the flow, the pose network and the depth network keep the raw prediction.  The intrinsics of the warp are the network-size ones, so
-    the depth network's output must have the network's input size."""
+    the depth network's output must have the network's input size.
+
+    `stream(..., volume=vol)` fuses the sequence into one TSDF volume (hip/volume.py): sde_pose_compose chains the world-to-camera pose from the
+    model's step poses on the device and sde_tsdf_integrate averages every window's depth -- the one the pictures show -- into the caller's grid
+    through it, inside the same graph."""
     NAME = "PairPredictor"
 
     def __init__(self, cfg, model=None, chain=None, device="cuda", use_graph=None, vmax=None, gamma=0.8):
@@ -556,6 +593,7 @@ class PairPredictor(_Predictor):
         self.stacked = cfg.MODEL.POSE_NET.NAME in SINGLE_CONTEXT_NETS          # MotionLearning's both-directions input
         self.pose_use_depth = self.stacked and bool(cfg.MODEL.POSE_NET.USE_DEPTH)
         self._temporal = {}                                   # source size -> _TemporalState
+        self._volume = {}                                     # source size -> _VolumeState
 
     def pose_input(self, img, depth_all=None):
         """The pose network's input from the prepared window img [1+n,3,h,w] (and, with USE_DEPTH, the depth [2,1,h,w] of target and context)."""
@@ -570,7 +608,13 @@ class PairPredictor(_Predictor):
             self._temporal[key] = _TemporalState(plan.h, plan.w, self.stacked, self.device)
         return self._temporal[key]
 
-    def _chain(self, plan, frames, K, K_src, present, rigid_only, max_flow, temporal=None, want_u16=False, cloud=None):
+    def _volume_state(self, plan):
+        key = (plan.Hs, plan.Ws)
+        if key not in self._volume:
+            self._volume[key] = _VolumeState(self.device)
+        return self._volume[key]
+
+    def _chain(self, plan, frames, K, K_src, present, rigid_only, max_flow, temporal=None, want_u16=False, cloud=None, volume=None):
         N = 1 + self.n
         img, _ = self._aug.prep(frames, self._no_jitter(N), plan.h, plan.w, tabs=(plan.xtab, plan.ytab))
         nd = 2 if self.pose_use_depth else 1                   # frames the depth net sees
@@ -607,6 +651,20 @@ class PairPredictor(_Predictor):
                 st.T.copy_(pose[j:j + 1])
                 if carried:
                     st.motion.copy_(motion)
+        if volume is not None:                                  # the depth the pictures show, through the pose chained on the device
+            vol, vs = volume
+            j, inverted = temporal_context(self.offsets)
+            if inverted:                                        # previous -> current: this window's pose to the context at -1, inverted as above;
+                Rt, t = pose[j, :3, :3].t(), pose[j, :3, 3]       # the first window of a sequence is the world and takes no step
+                vs.inv[:3, :3].copy_(Rt)
+                vs.inv[:3, 3].copy_(-(Rt[:, 0] * t[0] + Rt[:, 1] * t[1] + Rt[:, 2] * t[2]))
+                vs.T.copy_(torch.where(vs.started, vs.inv, vs.eye))
+            vol.compose(vs.T, vs.C)
+            vol.integrate(shown, ymap, xmap, K_src[:1], vs.C, frame=frames[:1])
+            out["world_to_camera"] = vs.C.clone()               # the state moves on with the next window, on the other slot: this slot's copy
+            if not inverted:                                    # this window's pose to the frame at +1 is the next window's step
+                vs.T.copy_(pose[j])
+            vs.started.fill_(True)
         out["flow"], out["flow_valid"], out["flow_canvas"] = HF.pair_flow(pred.expand(self.n, -1, -1), ymap, xmap, K_src, pose,
                                                                           motion=None if rigid_only else motion, max_flow=max_flow, want_canvas=present)
         if present:
@@ -622,7 +680,7 @@ class PairPredictor(_Predictor):
             raise ValueError("PairPredictor: the flow needs intrinsics (the source-size K [3,3] of the frames)")
         return self._host_K("PairPredictor", intrinsics, 1)[0]          # one K for the whole window
 
-    def _run(self, slot, plan, intrinsics, K_host, present, rigid_only, max_flow, temporal=None, want_u16=False, cloud=None):
+    def _run(self, slot, plan, intrinsics, K_host, present, rigid_only, max_flow, temporal=None, want_u16=False, cloud=None, volume=None):
         N = 1 + self.n
         K = self._device_copy(slot, "K", plan.intrinsics(intrinsics), N)
         K_src =self._device_copy(slot, "K_src", K_host, self.n)
@@ -630,13 +688,18 @@ class PairPredictor(_Predictor):
         if not max_flow > 0:
             raise ValueError(f"PairPredictor: max_flow must be positive, got {max_flow}")
         key = ("pair", bool(present), bool(rigid_only), max_flow)
-        if temporal is None and not want_u16 and cloud is None:
+        if temporal is None and not want_u16 and cloud is None and volume is None:
             return self._replay(slot, key, lambda: self._chain(plan, slot.frames, K, K_src, bool(present), bool(rigid_only), max_flow))
         key += ((temporal[:2] if temporal is not None else None),) + ((bool(want_u16), cloud) if want_u16 or cloud is not None else ())
-        return self._replay(slot, key, lambda: self._chain(plan, slot.frames, K, K_src, bool(present), bool(rigid_only), max_flow, temporal, bool(want_u16), cloud),
-                            persistent=temporal[2].tensors() if temporal is not None else ())
+        persistent = temporal[2].tensors() if temporal is not None else []
+        if volume is not None:                                  # the volume's parameters and addresses are part of what the graph holds; its arrays move on
+            vol, vs = volume                                    # with every run, so the eager run before a capture is taken back like the states'
+            key += (("volume",) + vol.params(),)
+            persistent = persistent + vs.tensors() + [t for t in (vol.tsdf, vol.weight, vol.rgba) if t is not None]
+        return self._replay(slot, key, lambda: self._chain(plan, slot.frames, K, K_src, bool(present), bool(rigid_only), max_flow, temporal, bool(want_u16), cloud,
+                                                           volume), persistent=persistent)
 
-    def predict(self, frames, intrinsics, present=True, rigid_only=False, max_flow=None, temporal=None):
+    def predict(self, frames, intrinsics, present=True, rigid_only=False, max_flow=None, temporal=None, volume=None):
         """frames: the window, a list of 1 + n uint8 [H,W,3] RGB frames of one size -- the target, then the n context frames in the order the dataset
         emits `ctx_img` (self.offsets, ascending, e.g. the frames at -1 and +1).  intrinsics: the source-size K [3,3] of the frames.  Returns a
         dict of device tensors: `depth` [1,H,W], `canvas` [1,2H,W,3], `depth_net` [1,h,w] as DepthPredictor returns them for the target; `pose`
@@ -646,9 +709,11 @@ class PairPredictor(_Predictor):
         still returned).  max_flow: the flow length, in pixels, that reaches full saturation in `flow_canvas`; default 5 % of the frame's
         width -- a presentation constant, like gamma.  present=False skips the three pictures.  Translations, and with them the flow's share
         that comes from them, are up to the scale of the monocular depth.  No host synchronisation after the first call of a size.  predict keeps
-        nothing from call to call: temporal fusion is `stream`'s, and anything but temporal=None is refused."""
+        nothing from call to call: temporal fusion and volume fusion are `stream`'s, and anything but temporal=None, volume=None is refused."""
         if temporal is not None:
             raise ValueError("PairPredictor.predict is stateless: temporal fusion needs the frames in order, use stream(..., temporal=...)")
+        if volume is not None:
+            raise ValueError("PairPredictor.predict is stateless: volume fusion chains the poses of frames in order, use stream(..., volume=...)")
         t = as_window(frames, self.n)
         K_host = self._source_intrinsics(intrinsics)
         plan = self.plan(t.shape[1], t.shape[2])
@@ -670,7 +735,7 @@ class PairPredictor(_Predictor):
         res["pose_next"] = invert_pose_np(res["pose"][j]) if inverted else res["pose"][j].copy()
         return res
 
-    def stream(self, frames_iter, intrinsics, present=True, rigid_only=False, max_flow=None, temporal=None, want_u16=False, cloud=None):
+    def stream(self, frames_iter, intrinsics, present=True, rigid_only=False, max_flow=None, temporal=None, want_u16=False, cloud=None, volume=None):
         """Generator over host frames of a sequence (uint8 [H,W,3] RGB, one at a time, one size).  Keeps a sliding window and yields, in order, one
         dict of host arrays per target frame that has all its context frames: the outputs of `predict` (`depth` [H,W], `canvas` [2H,W,3], `pose`,
         `flow`, `flow_valid`, `flow_canvas`, `motion`; with present=False `depth_net` instead of the pictures), `index`, the target's position in
@@ -687,17 +752,25 @@ class PairPredictor(_Predictor):
         window is the raw prediction, with state 0 everywhere.  ValueError for a model without a context one frame away.
 
         want_u16 (with present) adds `depth_u16` [H,W] and cloud=dict(min_depth=, max_depth=, step=1) adds `points` [1,cap,16] and `count` [1] of
-        the target, as DepthPredictor.stream yields them, from the depth the pictures show (the fused one with temporal)."""
+        the target, as DepthPredictor.stream yields them, from the depth the pictures show (the fused one with temporal).
+
+        volume=vol (a hip.volume.TsdfVolume on this device): every window's depth -- the one the pictures show -- is integrated into the volume
+        (sde_tsdf_integrate, with the source-size intrinsics and the target's colours) through the world-to-camera pose chained on the device
+        from the model's own step poses (sde_pose_compose); every record then holds `world_to_camera` [4,4], the pose its depth went in with: the
+        identity for the first target, which is the world.  Every call, and every change of the frame size, starts a new chain; the volume is the
+        caller's and is never reset here, so several sequences may go into one.  ValueError for a model without a context one frame away."""
         K_host = self._source_intrinsics(intrinsics)
         fuse = temporal_args(temporal)
+        volume = volume_arg(volume, self.device)
         cloud, _ = DepthPredictor._cloud_args(cloud, K_host, 1)
         want_u16 = bool(want_u16 and present)
-        if fuse is not None:
+        if fuse is not None or volume is not None:
             temporal_context(self.offsets)
         names = [k for k, on in (("depth", present), ("canvas", present), ("depth_net", not present or fuse is not None), ("depth_net_raw", fuse is not None),
                                  ("temporal_state", fuse is not None), ("pose", True), ("flow", True), ("flow_valid", True), ("flow_canvas", present),
-                                 ("motion", True), ("depth_u16", want_u16), ("points", cloud is not None), ("count", cloud is not None)) if on]
-        live = []                                              # the state this call has reset and is advancing
+                                 ("motion", True), ("depth_u16", want_u16), ("points", cloud is not None), ("count", cloud is not None),
+                                 ("world_to_camera", volume is not None)) if on]
+        live, live_v = [], []                                  # the states this call has reset and is advancing
         lo, hi = min(self.offsets + (0,)), max(self.offsets + (0,))
         targets = []
 
@@ -720,11 +793,18 @@ class PairPredictor(_Predictor):
             return res
 
         def run(slot, plan):
+            vol = None
+            if volume is not None:
+                vs = self._volume_state(plan)
+                if not live_v or live_v[0] is not vs:          # the first window of this call, or frames of another size: that target is the world
+                    vs.reset()
+                    live_v[:] = [vs]
+                vol = (volume, vs)
             if fuse is None:
-                return self._run(slot, plan, intrinsics, K_host, present, rigid_only, max_flow, want_u16=want_u16, cloud=cloud)
+                return self._run(slot, plan, intrinsics, K_host, present, rigid_only, max_flow, want_u16=want_u16, cloud=cloud, volume=vol)
             st = self._temporal_state(plan)
             if not live or live[0] is not st:                  # the first window of this call, or frames of another size: an empty state
                 st.reset()
                 live[:] = [st]
-            return self._run(slot, plan, intrinsics, K_host, present, rigid_only, max_flow, temporal=fuse + (st,), want_u16=want_u16, cloud=cloud)
+            return self._run(slot, plan, intrinsics, K_host, present, rigid_only, max_flow, temporal=fuse + (st,), want_u16=want_u16, cloud=cloud, volume=vol)
         yield from self._pump(windows(), names, run, result)

@@ -139,6 +139,11 @@ _PROTOS = {
     "sde_pair_flow": ([_P, _I, _I, _I, _P, _P, _I, _I, _P, _P, _P, _P, _I, _F, _P, _P, _P, _P, _P], c_int),
     # temporally fused depth: forward warp, z-buffer, blend (csrc/temporal.hip; binding and host twin in hip/temporal.py)
     "sde_depth_warp_fuse": ([_P, _P, _P, _P, _P, _I, _I, _I, _F, _F, _P, _P, _P, _P, _P], c_int),
+    # a sequence's depth fused into one TSDF volume (csrc/volume.hip; binding and host twins in hip/volume.py); origin is a host float[3]
+    "sde_pose_compose": ([_P, _P, _P], c_int),
+    "sde_tsdf_integrate": ([_P, _I, _I, _P, _P, _I, _I, _P, _P, _P, POINTER(c_float), _F, _F, _F, _F, _F, _P, _P, _P, _I, _I, _I, _P], c_int),
+    "sde_tsdf_points_ws_bytes": ([_I, _I, _I], c_size_t),
+    "sde_tsdf_points": ([_P, _P, _P, _I, _I, _I, POINTER(c_float), _F, _F, _P, c_size_t, _P, ctypes.c_long, _P, _P], c_int),
 }
 
 _lib = None

@@ -24,6 +24,27 @@ def pinhole_project_np(d, K, T, m=None):
         return px, py, q[2], nx / den, ny / den
 
 
+def pinhole_move_project_np(K, T, px, py, pz):
+    """Camera-frame points (px, py, pz: float32 arrays of one shape) moved by T [4,4] (q = R p + t) and projected through K [3,3] ->
+    (qx, qy, qz, X, Y): pinhole_move<4> with s = t, then pinhole_project, the order of csrc/pinhole.h."""
+    f32 = np.float32
+    K, T = np.asarray(K, dtype=f32), np.asarray(T, dtype=f32)
+    with np.errstate(all="ignore"):
+        q = [T[r, 0] * px + T[r, 1] * py + T[r, 2] * pz + T[r, 3] for r in range(3)]
+        nx, ny = K[0, 0] * q[0] + K[0, 2] * q[2], K[1, 1] * q[1] + K[1, 2] * q[2]
+        den = q[2] + f32(1e-6)
+        return q[0], q[1], q[2], nx / den, ny / den
+
+
+def nearest_pixel_np(X, Y):
+    """nearest_pixel of csrc/pinhole.h: (ok, ix, iy) with ix = rint(X), iy = rint(Y) (round-half-even) as int64, ok False where a rounding is
+    not below 1e9 in magnitude (a NaN is not); ix, iy are 0 there."""
+    with np.errstate(all="ignore"):
+        rx, ry = np.rint(np.asarray(X, dtype=np.float32)), np.rint(np.asarray(Y, dtype=np.float32))
+        ok = (np.abs(rx) < np.float32(1e9)) & (np.abs(ry) < np.float32(1e9))
+        return ok, np.where(ok, rx, 0).astype(np.int64), np.where(ok, ry, 0).astype(np.int64)
+
+
 def zbuffer_min_np(px, py, values, H, W, keep=None, origin=(0, 0)):
     """px, py: float32 coordinates of the candidates, values: their float32 depths, keep: the candidates the caller admits (all of one shape;
     an admitted depth is positive and finite) -> uint32 [H,W], the smallest bit pattern that lands on each pixel, EMPTY where none does.  A

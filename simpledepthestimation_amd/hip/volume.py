@@ -1,0 +1,265 @@
+"""A sequence's depth fused into one truncated-signed-distance (TSDF) volume (include/sde_hip.h: sde_pose_compose, sde_tsdf_integrate,
+sde_tsdf_points; csrc/volume.hip).  `TsdfVolume` owns the three device arrays and binds the kernels; `compose_host`, `integrate_host` and
+`points_host` are their host twins -- the same fp32 operations in the same order in numpy, for machines without a GPU and for the tests,
+which compare the two bit for bit.  Every frame's depth is averaged into the voxel grid through its world-to-camera pose; the zero crossings
+of the grid are the surface, handed out as the 16-byte records of hip.cloud (as_records and the PLY writer take them as they are)."""
+import ctypes
+import warnings
+
+import numpy as np
+import torch
+
+from . import args as A
+from . import lib as L
+from . import present as HP
+from .cloud import RECORD, as_records
+from .twins import nearest_pixel_np, pinhole_move_project_np
+
+MAX_DIM, MAX_VOXELS = 1024, 1 << 30
+DEFAULT_CAP = 1 << 22           # records `points` makes room for when the caller names no cap (64 MiB), or 3 per voxel if that is fewer
+
+
+def check_params(dims, voxel, origin=None, trunc=None, max_weight=64.0, min_depth=0.0, max_depth=80.0):
+    """The argument errors the C side refuses, raised as ValueError before anything touches the device.  -> (dims, voxel, origin, trunc,
+    max_weight, min_depth, max_depth) as the kernels receive them (fp32 values as Python floats); origin=None puts the first camera at the
+    middle of the near face, (-nx * voxel / 2, -ny * voxel / 2, 0), trunc=None is 4 * voxel."""
+    try:
+        given = tuple(dims)
+        exact = len(given) == 3 and all(int(n) == n for n in given)
+        dims = tuple(int(n) for n in given)
+    except (TypeError, ValueError):
+        exact = False
+    if not exact or not all(1 <= n <= MAX_DIM for n in dims) or dims[0] * dims[1] * dims[2] > MAX_VOXELS:
+        raise ValueError(f"TsdfVolume: dims must be three integers in [1, {MAX_DIM}] with a product of at most 2^30, got {dims!r}")
+    f = lambda x: float(np.float32(x))
+    voxel = f(voxel)
+    if not voxel > 0.0 or not np.isfinite(voxel):
+        raise ValueError(f"TsdfVolume: voxel must be positive and finite, got {voxel!r}")
+    trunc = f(4.0 * voxel if trunc is None else trunc)
+    max_weight = f(max_weight)
+    if not trunc > 0.0 or not max_weight > 0.0:
+        raise ValueError(f"TsdfVolume: trunc and max_weight must be positive, got ({trunc!r}, {max_weight!r})")
+    min_depth, max_depth = f(min_depth), f(max_depth)
+    if not min_depth < max_depth:
+        raise ValueError(f"TsdfVolume: min_depth must lie below max_depth, got ({min_depth}, {max_depth})")
+    if origin is None:
+        origin = (-dims[0] * voxel / 2, -dims[1] * voxel / 2, 0.0)
+    origin = tuple(f(o) for o in np.asarray(origin, dtype=np.float64).reshape(-1))
+    if len(origin) != 3 or not all(np.isfinite(o) for o in origin):
+        raise ValueError(f"TsdfVolume: origin must be three finite numbers, got {origin!r}")
+    return dims, voxel, origin, trunc, max_weight, min_depth, max_depth
+
+
+def check_min_weight(min_weight):
+    min_weight = float(np.float32(min_weight))
+    if not min_weight >= 1.0:
+        raise ValueError(f"TsdfVolume: min_weight must be at least 1, got {min_weight!r}")
+    return min_weight
+
+
+def pose_compose(T, C):
+    """C <- T C in place: T, C [4,4] (or [1,4,4]) fp32 contiguous CUDA tensors, one rigid transform each.  One launch, no host synchronisation."""
+    dev = C.device if torch.is_tensor(C) else None
+    for what, t in (("C", C), ("T", T)):
+        if not torch.is_tensor(t) or t.dtype != torch.float32 or t.numel() != 16 or tuple(t.shape[-2:]) != (4, 4) or t.device != dev:
+            got = f"{t.dtype} {tuple(t.shape)} on {t.device}" if torch.is_tensor(t) else type(t).__name__
+            raise L.SdeHipError(f"pose_compose: {what} must be one float32 [4,4] tensor on {dev}, got {got}")
+    L.check(L.lib().sde_pose_compose(L.ptr(T), L.ptr(C), L.stream()), "sde_pose_compose")
+    return C
+
+
+class TsdfVolume:
+    """nx x ny x nz voxels of edge `voxel`, x fastest: `tsdf` and `weight` [nz,ny,nx] fp32 and, with colour, `rgba` [nz,ny,nx,4] uint8 on
+    `device`.  Extents are in the units of the depth that is integrated (a monocular model's depth is known up to one scale factor)."""
+
+    def __init__(self, dims, voxel, origin=None, trunc=None, max_weight=64.0, min_depth=0.0, max_depth=80.0, colour=True, device="cuda"):
+        self.dims, self.voxel, self.origin, self.trunc, self.max_weight, self.min_depth, self.max_depth = check_params(
+            dims, voxel, origin, trunc, max_weight, min_depth, max_depth)
+        self.colour = bool(colour)
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise L.SdeHipError("TsdfVolume: the volume lives on a GPU; there is no CPU fallback (the host twins are functions of this module)")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        nx, ny, nz = self.dims
+        self.tsdf = torch.empty((nz, ny, nx), dtype=torch.float32, device=self.device)
+        self.weight = torch.empty((nz, ny, nx), dtype=torch.float32, device=self.device)
+        self.rgba = torch.empty((nz, ny, nx, 4), dtype=torch.uint8, device=self.device) if self.colour else None
+        self._origin = (ctypes.c_float * 3)(*self.origin)
+        self.reset()
+
+    def params(self):
+        """What a captured launch depends on: the parameters and the addresses of ALL the arrays (a later volume may get one array of an earlier
+        one back from the allocator and the others elsewhere)."""
+        return (self.dims, self.voxel, self.origin, self.trunc, self.max_weight, self.min_depth, self.max_depth, self.colour, self.tsdf.data_ptr(),
+                self.weight.data_ptr(), self.rgba.data_ptr() if self.rgba is not None else 0)
+
+    def reset(self):
+        """A fresh volume, on the current stream: tsdf = 1, weight = 0, rgba = 0."""
+        self.tsdf.fill_(1.0)
+        self.weight.zero_()
+        if self.rgba is not None:
+            self.rgba.zero_()
+
+    def integrate(self, pred, ymap, xmap, K, C, frame=None):
+        """One frame into the volume.  pred [ph,pw] (or [1,ph,pw] / [1,1,ph,pw]) fp32, ymap [H] / xmap [W] int32 (hip.present's maps), K [3,3]
+        fp32 at the restored size, C [4,4] fp32 world -> camera, frame [H,W,3] uint8 or None (no colour): CUDA tensors on the volume's device.
+        One launch on the current stream, no host synchronisation (device maps: see depth_present)."""
+        pred = A.as_pred("tsdf_integrate", pred)
+        A.same_device_tensor("tsdf_integrate", "pred", pred, torch.float32, (1, None, None), self.device)
+        _, ph, pw = pred.shape
+        ymap, xmap = HP.ensure_checked(ymap, xmap, ph, pw, self.device)
+        H, W = ymap.numel(), xmap.numel()
+        K = A.as_K("tsdf_integrate", K, 1, self.device)
+        if torch.is_tensor(C) and C.dim() == 3:
+            C = C[0]
+        C = A.same_device_tensor("tsdf_integrate", "C", C, torch.float32, (4, 4), self.device)
+        frame = A.as_frame("tsdf_integrate", frame, 1, H, W, self.device)
+        nx, ny, nz = self.dims
+        L.check(L.lib().sde_tsdf_integrate(L.ptr(pred), ph, pw, L.ptr(ymap), L.ptr(xmap), H, W, L.ptr(frame), L.ptr(K), L.ptr(C), self._origin, self.voxel,
+                                           self.trunc, self.max_weight, self.min_depth, self.max_depth, L.ptr(self.tsdf), L.ptr(self.weight),
+                                           L.ptr(self.rgba), nx, ny, nz, L.stream()), "sde_tsdf_integrate")
+
+    def compose(self, T, C):
+        """C <- T C in place (pose_compose): the world-to-camera pose advanced by the step T, frame i -> frame i + 1."""
+        return pose_compose(T, C)
+
+    def default_cap(self):
+        return min(3 * self.dims[0] * self.dims[1] * self.dims[2], DEFAULT_CAP)
+
+    def workspace_numel(self):
+        """int32 elements of workspace sde_tsdf_points asks for."""
+        return int(L.lib().sde_tsdf_points_ws_bytes(*self.dims)) // 4
+
+    def points(self, min_weight=1, cap=None, out=None, workspace=None):
+        """The zero crossings between voxels of weight >= min_weight -> (points [cap,16] uint8, count [1] int32) on the device: the records are
+        points[:min(count, cap)], ascending voxel then axis (hip.cloud.as_records gives the structured view); count is the total, also when it
+        exceeds cap.  cap=None: default_cap().  out: optional (points, count) destinations; workspace: optional int32 tensor of at least
+        workspace_numel() elements.  Three launches on the current stream, no host synchronisation."""
+        min_weight = check_min_weight(min_weight)
+        cap = self.default_cap() if cap is None else int(cap)
+        if not 1 <= cap <= 0x7fffffff:
+            raise ValueError(f"TsdfVolume.points: cap must lie in [1, 2^31), got {cap}")
+        points, count = out if out is not None else (None, None)
+        points = A.dst("tsdf_points", points, (cap, 16), torch.uint8, True, self.device)
+        count = A.dst("tsdf_points", count, (1,), torch.int32, True, self.device)
+        need = self.workspace_numel()
+        if workspace is None:
+            workspace = torch.empty((need,), dtype=torch.int32, device=self.device)
+        if workspace.dtype != torch.int32 or workspace.device != self.device:
+            raise L.SdeHipError(f"tsdf_points: workspace must be an int32 tensor on {self.device}, got {workspace.dtype} on {workspace.device}")
+        nx, ny, nz = self.dims
+        L.check(L.lib().sde_tsdf_points(L.ptr(self.tsdf), L.ptr(self.weight), L.ptr(self.rgba), nx, ny, nz, self._origin, self.voxel, min_weight,
+                                        L.ptr(workspace), workspace.numel() * 4, L.ptr(points), cap, L.ptr(count), L.stream()), "sde_tsdf_points")
+        return points, count
+
+    def save_ply(self, path, min_weight=1, cap=None):
+        """The surface points as a binary PLY (the cloud's writer and record).  Synchronises.  Returns (records written, crossings found); when
+        the volume holds more crossings than `cap` records, the first `cap` are written and a warning says so."""
+        points, count = self.points(min_weight=min_weight, cap=cap)
+        return write_points_ply(path, points.cpu().numpy(), int(count.item()))
+
+
+def write_points_ply(path, points, count):
+    """points [cap,16] uint8 (host) and the count `points` / `points_host` reported -> the PLY file of the first min(count, cap) records."""
+    from ..tools.demo import write_ply
+    cap = points.shape[0]
+    if count > cap:
+        warnings.warn(f"TsdfVolume.save_ply: the volume holds {count} crossings, room was made for {cap}: the first {cap} are written "
+                      f"(pass cap={count} for all of them)")
+    n = min(count, cap)
+    write_ply(path, as_records(points, n))
+    return n, count
+
+
+# ---- host twins ---------------------------------------------------------------------------------------------------------------------------------
+def compose_host(T, C):
+    """The host twin of sde_pose_compose: T, C [4,4] float32 -> the new C (T C with the documented order of operations)."""
+    f32 = np.float32
+    T, C = np.asarray(T, dtype=f32).reshape(4, 4), np.asarray(C, dtype=f32).reshape(4, 4)
+    out = np.zeros((4, 4), f32)
+    out[3, 3] = 1
+    with np.errstate(all="ignore"):
+        for r in range(3):
+            row = T[r, 0] * C[0] + T[r, 1] * C[1] + T[r, 2] * C[2]
+            row[3] = row[3] + T[r, 3]
+            out[r] = row
+    return out
+
+
+def centres_np(n, o, voxel):
+    """The centres of n voxels along one axis: o + ((float)i + 0.5f) * voxel, float32."""
+    f32 = np.float32
+    return f32(o) + (np.arange(n, dtype=f32) + f32(0.5)) * f32(voxel)
+
+
+def integrate_host(tsdf, weight, rgba, pred, ymap, xmap, K, C, frame, origin, voxel, trunc, max_weight, min_depth, max_depth):
+    """The host twin of sde_tsdf_integrate.  tsdf, weight [nz,ny,nx] float32 and rgba [nz,ny,nx,4] uint8 (or None) are updated IN PLACE with
+    the bits the kernel writes; pred [ph,pw] float32, ymap [H] / xmap [W] int, K [3,3], C [4,4], frame [H,W,3] uint8 or None.  Returns the
+    bool [nz,ny,nx] mask of the voxels that were kept (the others are untouched)."""
+    f32 = np.float32
+    nz, ny, nx = tsdf.shape
+    pred, ymap, xmap = np.asarray(pred, dtype=f32), np.asarray(ymap), np.asarray(xmap)
+    H, W = ymap.size, xmap.size
+    voxel, trunc, max_weight, lo, hi = f32(voxel), f32(trunc), f32(max_weight), f32(min_depth), f32(max_depth)
+    wx = centres_np(nx, origin[0], voxel)[None, None, :]
+    wy = centres_np(ny, origin[1], voxel)[None, :, None]
+    wz = centres_np(nz, origin[2], voxel)[:, None, None]
+    with np.errstate(all="ignore"):
+        _, _, qz, X, Y = pinhole_move_project_np(K, C, wx, wy, wz)
+        keep = (qz > 0) & (qz < np.inf)
+        ok, ix, iy = nearest_pixel_np(X, Y)
+        keep = keep & ok & (ix >= 0) & (ix < W) & (iy >= 0) & (iy < H)
+        ix, iy = np.where(keep, ix, 0), np.where(keep, iy, 0)
+        my, mx = ymap[iy], xmap[ix]
+        keep &= (my >= 0) & (mx >= 0)
+        d = pred[np.where(keep, my, 0), np.where(keep, mx, 0)]
+        keep &= np.isfinite(d) & (lo < d) & (d <= hi)
+        sdf = d - qz
+        keep &= sdf >= -trunc
+        t = np.fmin(f32(1), sdf / trunc)
+        w0, t0 = weight[keep], tsdf[keep]
+        w1 = w0 + f32(1)
+        tsdf[keep] = (t0 * w0 + t[keep]) / w1
+        weight[keep] = np.fmin(w1, max_weight)
+        if frame is not None and rgba is not None:
+            sel = keep & (sdf <= trunc)
+            w0, w1 = w0[sel[keep]], w1[sel[keep]]
+            f = np.asarray(frame)[iy[sel], ix[sel]].astype(f32)                                  # [n,3]
+            c = (rgba[sel][:, :3].astype(f32) * w0[:, None] + f) / w1[:, None]
+            new = np.full((c.shape[0], 4), 255, np.uint8)
+            new[:, :3] = (c + f32(0.5)).astype(np.uint8)
+            rgba[sel] = new
+    return keep
+
+
+def points_host(tsdf, weight, rgba, origin, voxel, min_weight=1, cap=None):
+    """The host twin of sde_tsdf_points -> (records, count): the structured array (hip.cloud.RECORD) of the first min(count, cap) crossings in
+    the kernel's order (ascending voxel, then axis) with the bits it writes, and the total number of crossings."""
+    f32 = np.float32
+    tsdf, weight = np.asarray(tsdf, dtype=f32), np.asarray(weight, dtype=f32)
+    nz, ny, nx = tsdf.shape
+    voxel = f32(voxel)
+    valid, neg = weight >= f32(check_min_weight(min_weight)), tsdf < 0
+    cross = np.zeros((nz, ny, nx, 3), bool)
+    cross[:, :, :-1, 0] = valid[:, :, :-1] & valid[:, :, 1:] & (neg[:, :, :-1] != neg[:, :, 1:])
+    cross[:, :-1, :, 1] = valid[:, :-1] & valid[:, 1:] & (neg[:, :-1] != neg[:, 1:])
+    cross[:-1, :, :, 2] = valid[:-1] & valid[1:] & (neg[:-1] != neg[1:])
+    k, j, i, a = np.nonzero(cross)                                # C order: ascending voxel, then axis
+    count = int(k.size)
+    if cap is not None:
+        k, j, i, a = (x[:int(cap)] for x in (k, j, i, a))
+    kn, jn, in_ = k + (a == 2), j + (a == 1), i + (a == 0)
+    rec = np.zeros(k.size, RECORD)
+    with np.errstate(all="ignore"):
+        tv, tn = tsdf[k, j, i], tsdf[kn, jn, in_]
+        f = tv / (tv - tn)
+        along = f * voxel
+        cx, cy, cz = centres_np(nx, origin[0], voxel)[i], centres_np(ny, origin[1], voxel)[j], centres_np(nz, origin[2], voxel)[k]
+        rec["x"], rec["y"], rec["z"] = np.where(a == 0, cx + along, cx), np.where(a == 1, cy + along, cy), np.where(a == 2, cz + along, cz)
+        rec["alpha"] = 255
+        if rgba is not None:
+            own = f < f32(0.5)
+            col = np.asarray(rgba)[np.where(own, k, kn), np.where(own, j, jn), np.where(own, i, in_)]
+            rec["red"], rec["green"], rec["blue"] = col[:, 0], col[:, 1], col[:, 2]
+    return rec, count

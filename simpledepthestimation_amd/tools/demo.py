@@ -25,7 +25,15 @@ depth of the previous frame into the current camera with the pose the model esti
 agree within --stabilise-tol (relative; default 0.05), with weight --stabilise-alpha (default 0.5) for the warped depth.  The pictures then show
 the fused depth.  --save-state adds `<stem>_state.png`, the class of every pixel at the network's size in four fixed colours: dark grey where
 the pixel is new (nothing was warped there), green where the two depths were fused, orange / blue where the warped surface lies nearer / farther
-than the prediction, which is then kept.  The model needs a context one frame away."""
+than the prediction, which is then kept.  The model needs a context one frame away.
+
+--volume NX NY NZ --voxel V (with --pairs) fuses the whole sequence into one model of the scene: PairPredictor.stream(..., volume=TsdfVolume(...))
+averages every frame's depth (the fused one with --stabilise), in the range --save-cloud uses, into a truncated-signed-distance grid of NX x NY x
+NZ voxels of edge V through the camera pose chained from the model's own steps, and after the last frame `volume.ply` holds the grid's zero
+crossings as coloured points (the record and the PLY layout of --save-cloud), in the first frame's camera coordinates.  --volume-origin X Y Z is
+the corner of the first voxel (default: the first camera at the middle of the near face), --trunc M the truncation distance (default 4 V),
+--min-weight N the number of observations a voxel needs (default 1).  All lengths are in the model's depth units: a monocular model's scale is
+not aligned.  The model needs a context one frame away."""
 import argparse
 import os
 import sys
@@ -52,6 +60,13 @@ def parse_args(argv=None):
     p.add_argument("--stabilise-alpha", type=float, default=0.5, help="with --stabilise: weight of the warped depth in the blend, in [0, 1) (default 0.5)")
     p.add_argument("--stabilise-tol", type=float, default=0.05, help="with --stabilise: relative depth difference up to which the two are blended (default 0.05)")
     p.add_argument("--save-state", action="store_true", help="with --stabilise: also write <stem>_state.png, the class of every pixel in four colours")
+    p.add_argument("--volume", type=int, nargs=3, metavar=("NX", "NY", "NZ"), help="with --pairs: fuse the sequence into a TSDF volume of that many voxels and "
+                                                                                   "write volume.ply, its surface points (needs --voxel)")
+    p.add_argument("--voxel", type=float, help="with --volume: edge length of a voxel, in the model's depth units")
+    p.add_argument("--trunc", type=float, help="with --volume: truncation distance (default 4 voxels)")
+    p.add_argument("--volume-origin", type=float, nargs=3, metavar=("X", "Y", "Z"), help="with --volume: corner of the first voxel in the first camera's "
+                                                                                          "coordinates (default: the camera at the middle of the near face)")
+    p.add_argument("--min-weight", type=float, default=1.0, help="with --volume: observations a voxel needs to count as surface (default 1)")
     p.add_argument("--cloud-step", type=int, default=1, help="the cloud takes every N-th pixel of every N-th row (default 1: all)")
     p.add_argument("--opts", default=[], nargs=argparse.REMAINDER, help="config overrides as KEY VALUE pairs, e.g. MODEL.WEIGHTS model.pth")
     args = p.parse_args(argv)
@@ -63,8 +78,19 @@ def parse_args(argv=None):
         p.error("--save-state needs --stabilise")
     if not (0.0 <= args.stabilise_alpha < 1.0) or not args.stabilise_tol > 0.0:
         p.error("--stabilise-alpha must lie in [0, 1) and --stabilise-tol must be positive")
-    for flag in ("save_flow", "save_trajectory", "rigid_only", "stabilise"):
-        if getattr(args, flag) and not args.pairs:
+    if args.volume is not None:
+        if args.voxel is None:
+            p.error("--volume needs --voxel V")
+        from ..hip.volume import check_min_weight, check_params
+        try:
+            check_params(args.volume, args.voxel, args.volume_origin, args.trunc)
+            check_min_weight(args.min_weight)
+        except ValueError as e:
+            p.error(str(e))
+    elif any(v is not None for v in (args.voxel, args.trunc, args.volume_origin)):
+        p.error("--voxel, --trunc and --volume-origin need --volume NX NY NZ")
+    for flag in ("save_flow", "save_trajectory", "rigid_only", "stabilise", "volume"):
+        if getattr(args, flag) not in (None, False) and not args.pairs:
             p.error(f"--{flag.replace('_', '-')} needs --pairs")
     if args.pairs and args.no_frame:
         p.error("--pairs does not combine with --no-frame")
@@ -129,8 +155,14 @@ def run_pairs(args, cfg, files):
     j = predictor.next_context[0]                    # the context whose flow is saved: the next frame, or the previous one
     kept = []
     temporal = dict(alpha=args.stabilise_alpha, tol=args.stabilise_tol) if args.stabilise else None
-    cloud = dict(min_depth=float(cfg.MODEL.get("MIN_DEPTH", 0.0)), max_depth=float(cfg.MODEL.MAX_DEPTH), step=args.cloud_step) if args.save_cloud else None
-    for res in predictor.stream((read_rgb(f) for f in files), K, rigid_only=args.rigid_only, temporal=temporal, want_u16=args.save_depth, cloud=cloud):
+    depth_range = dict(min_depth=float(cfg.MODEL.get("MIN_DEPTH", 0.0)), max_depth=float(cfg.MODEL.MAX_DEPTH))
+    cloud = dict(depth_range, step=args.cloud_step) if args.save_cloud else None
+    volume = None
+    if args.volume is not None:
+        from ..hip.volume import TsdfVolume
+        volume = TsdfVolume(args.volume, args.voxel, origin=args.volume_origin, trunc=args.trunc, device=predictor.device, **depth_range)
+    for res in predictor.stream((read_rgb(f) for f in files), K, rigid_only=args.rigid_only, temporal=temporal, want_u16=args.save_depth, cloud=cloud,
+                                volume=volume):
         stem = os.path.splitext(os.path.basename(files[res["index"]]))[0]
         Image.fromarray(res["canvas"]).save(os.path.join(args.output, stem + ".png"), format="PNG", compress_level=3)
         if args.save_flow:
@@ -148,6 +180,9 @@ def run_pairs(args, cfg, files):
     if args.save_trajectory:
         steps, _ = trajectory_steps(kept, predictor.offsets)
         write_kitti_poses(os.path.join(args.output, "trajectory.txt"), accumulate_poses(np.stack(steps)))
+    if volume is not None:
+        written, found = volume.save_ply(os.path.join(args.output, "volume.ply"), min_weight=args.min_weight)
+        print(f"volume.ply: {written} of {found} surface point(s)")
     print(f"{len(kept)} picture(s) written to {args.output}")
     return 0
 
