@@ -845,7 +845,31 @@ int sde_depth_warp_fuse(const float* prev, const float* cur, const float* K, con
  * refuse).  Three launches ordered on the stream (crossings per tile of 256 voxels, exclusive scan, scatter); no workgroup waits for another, no
  * atomics, no host synchronisation, no allocation: legal under graph capture, the same bytes every run.  Refused before any launch: dims outside
  * the limits, voxel <= 0, min_weight < 1 (or a NaN), cap outside [1, 2^31), NULL tsdf / weight / origin / points / count, points off a 16-byte
- * or rgba off a 4-byte boundary, a workspace that is NULL or smaller than the query reports. */
+ * or rgba off a 4-byte boundary, a workspace that is NULL or smaller than the query reports.
+ *
+ * sde_tsdf_mesh: the surface as a triangle mesh by surface nets (no case table): ONE vertex per cell that holds a crossing, ONE quad (two
+ * triangles) per crossing edge -- the connectivity of the records of sde_tsdf_points.  A crossing edge (v, a) is exactly a record of
+ * sde_tsdf_points: the same validity (weight >= min_weight), the same sign rule, the same point (f, centre + f * voxel) and the same colour.
+ * Cell (i,j,k), i < nx-1, j < ny-1, k < nz-1, is named by its lowest corner and has the linear index of that voxel.  Its 12 edges in order:
+ * axis x, y, z; within an axis, with b < c the other two axes, the edge starts at the corner offset (db, dc) = (0,0), (1,0), (0,1), (1,1).
+ * A cell has a vertex iff m >= 1 of its edges cross.  The vertex is one 16-byte record { float x, y, z; uint8 r, g, b, a } (sde_depth_cloud's):
+ *   each coordinate: s = 0.f;  s = s + (the crossing point's coordinate) over the m crossing edges in edge order;  stored s / (float)m;  nothing fused;
+ *   each colour channel: the integer sum t of the m crossings' bytes, stored (uint8)((float)t / (float)m + 0.5f);   a = 255;   0, 0, 0 with rgba == NULL.
+ * Vertices are numbered from 0 in ascending cell index.  A crossing edge (v, a), v = (i,j,k), gives two triangles iff the four cells around it
+ * exist: v's coordinates along b and c lie in [1, n_b - 2] and [1, n_c - 2].  With q0..q3 the vertex numbers of the cells at the offsets (-1,-1),
+ * (0,-1), (0,0), (-1,0) in (b, c) from v, the quad is q0 q1 q2 q3 when (tsdf[v] < 0) != (a == y), else q0 q3 q2 q1 ((y, x, z) is left-handed);
+ * the triangles are (p0, p1, p2) and (p0, p2, p3) of the quad p.  Normals point from negative to positive tsdf: towards the camera that saw the
+ * surface.  faces [cap_faces][3] int32, 4-byte aligned: ascending v, then axis, the two triangles of a quad next to each other.
+ * vertices [cap_vertices][16 bytes], 16-byte aligned.  count [2] int32: count[0] the number of vertices, count[1] the number of triangles, also
+ * when they exceed the caps (each saturated at 2^31 - 1).  Records and triangles at positions >= their cap are not written, the bytes behind the
+ * written ones are not touched; a written triangle always holds the true vertex numbers, also those >= cap_vertices: with count[0] >
+ * cap_vertices the mesh is incomplete and the caller runs again with more room.  A grid with a dimension of 1 has no cells: both counts are 0.
+ * workspace: sde_tsdf_mesh_ws_bytes(nx, ny, nz) bytes of device memory (0 for dims the entry points refuse), 4-byte aligned, CONTENTS IRRELEVANT
+ * on entry: two counts per tile of 256 voxels and a cell -> vertex number map of 4 B per voxel, which is written for every cell that has a vertex
+ * and read only for such cells.  Four launches ordered on the stream (both counts per tile, one scan of both lists, vertices + map, faces); no
+ * workgroup waits for another, no atomics, no host synchronisation, no allocation: legal under graph capture, the same bytes every run.  Refused
+ * before any launch: dims outside the limits, voxel <= 0, min_weight < 1 (or a NaN), either cap outside [1, 2^31), NULL tsdf / weight / origin /
+ * vertices / faces / count, vertices off a 16-byte or faces / rgba off a 4-byte boundary, a workspace that is NULL, misaligned or too small. */
 int sde_pose_compose(const float* T, float* C, sde_stream_t stream);
 int sde_tsdf_integrate(const float* pred, int ph, int pw, const int* ymap, const int* xmap, int H, int W, const uint8_t* frame, const float* K,
                        const float* C, const float* origin, float voxel, float trunc, float max_weight, float min_depth, float max_depth,
@@ -853,6 +877,10 @@ int sde_tsdf_integrate(const float* pred, int ph, int pw, const int* ymap, const
 size_t sde_tsdf_points_ws_bytes(int nx, int ny, int nz);
 int sde_tsdf_points(const float* tsdf, const float* weight, const uint8_t* rgba, int nx, int ny, int nz, const float* origin, float voxel,
                     float min_weight, void* workspace, size_t workspace_bytes, void* points, long cap, int* count, sde_stream_t stream);
+size_t sde_tsdf_mesh_ws_bytes(int nx, int ny, int nz);
+int sde_tsdf_mesh(const float* tsdf, const float* weight, const uint8_t* rgba, int nx, int ny, int nz, const float* origin, float voxel,
+                  float min_weight, void* workspace, size_t workspace_bytes, void* vertices, long cap_vertices, int* faces, long cap_faces,
+                  int* count, sde_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------
  * MotionLearning loss stack (csrc/motion_loss.hip; autograd wrappers in hip/motion_loss.py).  fp32, planar NCHW, no host synchronisation.

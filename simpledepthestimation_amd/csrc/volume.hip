@@ -16,6 +16,8 @@
 //                   axes), wave bases through LDS, record index = ws[tile] + wave base + rank; records at or beyond cap are not written.
 // No workgroup waits for another, no atomics; the order is ascending voxel, then axis, run after run.  The scan is cloud.hip's, written again:
 // that file's bytes stay what they are.
+// sde_tsdf_mesh        the same crossings connected into triangles by surface nets (one vertex per cell with a crossing, one quad per crossing
+//                      edge): four launches, described in front of its kernels below.
 //
 // Built with -ffp-contract=off: the projection, the average and the interpolation keep the operation order the header states, which
 // hip/volume.py's host twins repeat bit for bit.
@@ -229,6 +231,241 @@ __global__ void __launch_bounds__(TILE) points_scatter(PointsP p) {
     }
 }
 
+// ---- sde_tsdf_mesh: surface nets -------------------------------------------------------------------------------------------------------------------
+// One thread per voxel, which stands for the cell whose lowest corner it is AND for its own three edges.  Four launches:
+//   mesh_count     the 8 corners of the cell (weight, and tsdf where valid: plain loads, neighbours in x share cache lines, the rows above come
+//                  from L2) -> the 12 edge bits; cells with a vertex and quads per tile -> ws_v[tile], ws_q[tile].  A quad belongs to the voxel
+//                  its edge starts at, and an edge with all four cells around it is edge 0, 4 or 8 of that voxel's own cell: one mask serves both;
+//   mesh_scan      both lists by one workgroup with a running carry, 8 rows of 256 counts per step; count[0] = vertices, count[1] = 2 * quads;
+//   mesh_vertices  the same masks, rank = ws_v[tile] + wave base + popcount below the lane: map[cell] = rank, and the record where rank < cap;
+//   mesh_faces     crossings() of the voxel's own edges as in points_scatter, the four vertex numbers from map, two triangles per quad.
+// map is written for every cell with a vertex and read only for cells around a crossing edge, which have one: it needs no clearing.
+struct MeshP {
+    PointsP pt;                  // the volume; ws = vertex counts / offsets per tile, points = the vertices, cap = cap_vertices, count [2]
+    unsigned* ws_q;              // [ntiles] quads per tile, then exclusive offsets
+    unsigned* map;               // [total] cell -> vertex number
+    int* faces;                  // [cap_faces][3]
+    size_t cap_faces;
+};
+
+// corner c = di + 2 dj + 4 dk of a cell; edge e = 4 a + (db + 2 dc) runs from corner edge_lo(a, db, dc) along axis a
+__device__ __forceinline__ constexpr int edge_lo(int a, int db, int dc) { return a == 0 ? 2 * db + 4 * dc : a == 1 ? db + 4 * dc : db + 2 * dc; }
+
+// the crossing edges of the cell at voxel v as bits 0..11 (0: no such cell); t: tsdf of the valid corners.  The tests are those of crossings().
+__device__ __forceinline__ unsigned cell_edges(const PointsP& p, size_t v, int i, int j, int k, float t[8]) {
+    if (v >= p.total || i + 1 >= p.g.nx || j + 1 >= p.g.ny || k + 1 >= p.g.nz) return 0u;
+    const size_t sy = (size_t)p.g.nx, sz = (size_t)p.g.nx * p.g.ny;
+    unsigned valid = 0u, neg = 0u;
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+        const size_t n = v + (c & 1) + ((c >> 1) & 1) * sy + (c >> 2) * sz;
+        if (!(p.weight[n] >= p.min_weight)) continue;
+        valid |= 1u << c;
+        t[c] = p.tsdf[n];
+        if (t[c] < 0.f) neg |= 1u << c;
+    }
+    unsigned m = 0u;
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int lo = edge_lo(a, e & 1, e >> 1), hi = lo + (1 << a);
+            if (((valid >> lo) & (valid >> hi) & 1u) && (((neg >> lo) ^ (neg >> hi)) & 1u)) m |= 1u << (4 * a + e);
+        }
+    return m;
+}
+
+// of the voxel's own crossings (bits 0..2 = axes), those with four cells around the edge
+__device__ __forceinline__ unsigned face_mask(const Grid& g, unsigned mc, int i, int j, int k) {
+    const bool bx = i >= 1 && i <= g.nx - 2, by = j >= 1 && j <= g.ny - 2, bz = k >= 1 && k <= g.nz - 2;
+    return mc & ((by && bz ? 1u : 0u) | (bx && bz ? 2u : 0u) | (bx && by ? 4u : 0u));
+}
+
+__global__ void __launch_bounds__(TILE) mesh_count(MeshP p) {
+    __shared__ unsigned wsum[2][WAVES];
+    for (size_t tile = blockIdx.x; tile < p.pt.ntiles; tile += gridDim.x) {             // the same trip count in every thread of the workgroup
+        const size_t v = tile * TILE + threadIdx.x;
+        int i = 0, j = 0, k = 0;
+        if (v < p.pt.total) split(p.pt.g, v, i, j, k);
+        float t[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        const unsigned m = cell_edges(p.pt, v, i, j, k, t);
+        const unsigned fb = face_mask(p.pt.g, (m & 1u) | ((m >> 3) & 2u) | ((m >> 6) & 4u), i, j, k);
+        const unsigned nv = (unsigned)__popcll(__ballot(m != 0u));
+        const unsigned nq = (unsigned)(__popcll(__ballot(fb & 1u)) + __popcll(__ballot(fb & 2u)) + __popcll(__ballot(fb & 4u)));
+        if ((threadIdx.x & 63) == 0) {
+            wsum[0][threadIdx.x >> 6] = nv;
+            wsum[1][threadIdx.x >> 6] = nq;
+        }
+        __syncthreads();
+        if (threadIdx.x < 2) {
+            unsigned s = 0;
+#pragma unroll
+            for (int w = 0; w < WAVES; ++w) s += wsum[threadIdx.x][w];
+            (threadIdx.x == 0 ? p.pt.ws : p.ws_q)[tile] = s;
+        }
+        __syncthreads();                                                                 // wsum is written again by the next tile
+    }
+}
+
+// points_scan's walk with a running carry, but a chunk is SCAN_ROWS rows of TILE counts of BOTH lists held in registers: sixteen independent
+// loads, their wave scans, ONE pair of barriers.  The walk is serial and every chunk costs a round trip to memory: 2 * ntiles / TILE of them
+// (a 256 x 256 x 128 grid: 256) took more time than the other three launches together; this way they are ntiles / (SCAN_ROWS * TILE) (16).
+constexpr int SCAN_ROWS = 8;
+
+__global__ void __launch_bounds__(TILE) mesh_scan(unsigned* ws_v, unsigned* ws_q, int* count, size_t ntiles) {
+    __shared__ unsigned wtot[2][SCAN_ROWS][WAVES];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    unsigned* const ws[2] = {ws_v, ws_q};
+    unsigned carry[2] = {0u, 0u};                                // entries in front of this chunk: the same values in every thread
+    for (size_t b0 = 0; b0 < ntiles; b0 += (size_t)SCAN_ROWS * TILE) {
+        unsigned c[2][SCAN_ROWS], inc[2][SCAN_ROWS];
+#pragma unroll
+        for (int l = 0; l < 2; ++l)
+#pragma unroll
+            for (int r = 0; r < SCAN_ROWS; ++r) {
+                const size_t b = b0 + (size_t)r * TILE + threadIdx.x;
+                inc[l][r] = c[l][r] = b < ntiles ? ws[l][b] : 0u;
+            }
+#pragma unroll
+        for (int s = 1; s < 64; s <<= 1) {                       // inclusive scans over the wave; the step outermost: sixteen shuffles in flight
+            unsigned o[2][SCAN_ROWS];
+#pragma unroll
+            for (int l = 0; l < 2; ++l)
+#pragma unroll
+                for (int r = 0; r < SCAN_ROWS; ++r) o[l][r] = (unsigned)__shfl_up((int)inc[l][r], s, 64);
+#pragma unroll
+            for (int l = 0; l < 2; ++l)
+#pragma unroll
+                for (int r = 0; r < SCAN_ROWS; ++r)
+                    if (lane >= s) inc[l][r] += o[l][r];
+        }
+        if (lane == 63) {
+#pragma unroll
+            for (int l = 0; l < 2; ++l)
+#pragma unroll
+                for (int r = 0; r < SCAN_ROWS; ++r) wtot[l][r][wave] = inc[l][r];
+        }
+        __syncthreads();
+#pragma unroll
+        for (int l = 0; l < 2; ++l) {
+            unsigned base = carry[l];
+#pragma unroll
+            for (int r = 0; r < SCAN_ROWS; ++r) {
+                unsigned mine = base;
+#pragma unroll
+                for (int w = 0; w < WAVES; ++w) {
+                    if (w < wave) mine += wtot[l][r][w];
+                    base += wtot[l][r][w];
+                }
+                const size_t b = b0 + (size_t)r * TILE + threadIdx.x;
+                if (b < ntiles) ws[l][b] = mine + inc[l][r] - c[l][r];               // exclusive
+            }
+            carry[l] = base;
+        }
+        __syncthreads();                                         // wtot is written again by the next chunk
+    }
+    if (threadIdx.x == 0) {
+        count[0] = (int)carry[0];                                // at most 2^30 cells
+        count[1] = carry[1] > 0x3fffffffu ? 0x7fffffff : (int)(2u * carry[1]);           // at most 3 * 2^30 quads: the offsets stay in quads
+    }
+}
+
+__global__ void __launch_bounds__(TILE) mesh_vertices(MeshP p) {
+    __shared__ unsigned wsum[WAVES];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    const Grid& g = p.pt.g;
+    const size_t step[3] = {(size_t)1, (size_t)g.nx, (size_t)g.nx * g.ny};
+    for (size_t tile = blockIdx.x; tile < p.pt.ntiles; tile += gridDim.x) {
+        const size_t v = tile * TILE + threadIdx.x;
+        int i = 0, j = 0, k = 0;
+        if (v < p.pt.total) split(g, v, i, j, k);
+        float t[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        const unsigned m = cell_edges(p.pt, v, i, j, k, t);
+        const unsigned long long has = __ballot(m != 0u);
+        if (lane == 0) wsum[wave] = (unsigned)__popcll(has);
+        __syncthreads();
+        if (m) {
+            unsigned at = p.pt.ws[tile] + (unsigned)__popcll(has & below);
+            for (int w = 0; w < wave; ++w) at += wsum[w];
+            p.map[v] = at;
+            if (at < p.pt.cap) {
+                const float cx[2] = {centre(g.ox, i, g.voxel), centre(g.ox, i + 1, g.voxel)};
+                const float cy[2] = {centre(g.oy, j, g.voxel), centre(g.oy, j + 1, g.voxel)};
+                const float cz[2] = {centre(g.oz, k, g.voxel), centre(g.oz, k + 1, g.voxel)};
+                uint32_t col[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};                    // the corners' colours: eight independent loads, not up to twelve in a chain
+                if (p.pt.rgba) {
+#pragma unroll
+                    for (int c = 0; c < 8; ++c) col[c] = p.pt.rgba[v + (c & 1) * step[0] + ((c >> 1) & 1) * step[1] + (c >> 2) * step[2]];
+                }
+                float sx = 0.f, sy = 0.f, sz = 0.f;
+                unsigned sr = 0u, sg = 0u, sb = 0u, n = 0u;
+#pragma unroll
+                for (int a = 0; a < 3; ++a)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        if (!(m & (1u << (4 * a + e)))) continue;
+                        const int lo = edge_lo(a, e & 1, e >> 1), hi = lo + (1 << a);
+                        const float f = t[lo] / (t[lo] - t[hi]);
+                        const float along = f * g.voxel;
+                        const float x = cx[lo & 1], y = cy[(lo >> 1) & 1], z = cz[lo >> 2];
+                        sx = sx + (a == 0 ? x + along : x);
+                        sy = sy + (a == 1 ? y + along : y);
+                        sz = sz + (a == 2 ? z + along : z);
+                        const uint32_t rgb = f < 0.5f ? col[lo] : col[hi];
+                        sr += rgb & 255u;
+                        sg += (rgb >> 8) & 255u;
+                        sb += (rgb >> 16) & 255u;
+                        ++n;
+                    }
+                const float fm = (float)n;
+                const uint32_t rgba = 0xff000000u | (uint32_t)(uint8_t)((float)sr / fm + 0.5f) | ((uint32_t)(uint8_t)((float)sg / fm + 0.5f) << 8) |
+                                      ((uint32_t)(uint8_t)((float)sb / fm + 0.5f) << 16);
+                p.pt.points[at] = make_uint4(__float_as_uint(sx / fm), __float_as_uint(sy / fm), __float_as_uint(sz / fm), rgba);
+            }
+        }
+        __syncthreads();                                                                 // wsum is written again by the next tile
+    }
+}
+
+__global__ void __launch_bounds__(TILE) mesh_faces(MeshP p) {
+    __shared__ unsigned wsum[WAVES];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    const Grid& g = p.pt.g;
+    const size_t step[3] = {(size_t)1, (size_t)g.nx, (size_t)g.nx * g.ny};
+    for (size_t tile = blockIdx.x; tile < p.pt.ntiles; tile += gridDim.x) {
+        const size_t v = tile * TILE + threadIdx.x;
+        int i = 0, j = 0, k = 0;
+        if (v < p.pt.total) split(g, v, i, j, k);
+        float tv = 0.f, tn[3] = {0.f, 0.f, 0.f};
+        const unsigned m = face_mask(g, crossings(p.pt, v, i, j, k, tv, tn), i, j, k);
+        const unsigned long long b0 = __ballot(m & 1u), b1 = __ballot(m & 2u), b2 = __ballot(m & 4u);
+        if (lane == 0) wsum[wave] = (unsigned)(__popcll(b0) + __popcll(b1) + __popcll(b2));
+        __syncthreads();
+        if (m) {
+            unsigned at = p.ws_q[tile] + (unsigned)(__popcll(b0 & below) + __popcll(b1 & below) + __popcll(b2 & below));
+            for (int w = 0; w < wave; ++w) at += wsum[w];
+#pragma unroll
+            for (int a = 0; a < 3; ++a) {
+                if (!(m & (1u << a))) continue;
+                const size_t sb = step[a == 0 ? 1 : 0], sc = step[a == 2 ? 1 : 2];       // b < c, the other two axes; face_mask: both >= 1 here
+                const size_t tri = 2 * (size_t)at;
+                if (tri < p.cap_faces) {
+                    const int q0 = (int)p.map[v - sb - sc], q1 = (int)p.map[v - sc], q2 = (int)p.map[v], q3 = (int)p.map[v - sb];
+                    const bool keep = (tv < 0.f) != (a == 1);
+                    const int p1 = keep ? q1 : q3, p3 = keep ? q3 : q1;
+                    int* f = p.faces + 3 * tri;
+                    f[0] = q0, f[1] = p1, f[2] = q2;
+                    if (tri + 1 < p.cap_faces) f[3] = q0, f[4] = q2, f[5] = p3;
+                }
+                ++at;
+            }
+        }
+        __syncthreads();                                                                 // wsum is written again by the next tile
+    }
+}
+
 bool dims_ok(int nx, int ny, int nz) {
     return nx >= 1 && ny >= 1 && nz >= 1 && nx <= MAX_DIM && ny <= MAX_DIM && nz <= MAX_DIM && (long)nx * ny * nz <= MAX_VOXELS;
 }
@@ -290,6 +527,41 @@ int sde_tsdf_points(const float* tsdf, const float* weight, const uint8_t* rgba,
     hipLaunchKernelGGL(points_scan, dim3(1), dim3(TILE), 0, (hipStream_t)stream, p.ws, count, p.ntiles);
     hipLaunchKernelGGL(points_scatter, dim3(grid), dim3(TILE), 0, (hipStream_t)stream, p);
     SDE_CHECK_LAUNCH("sde_tsdf_points");
+    return SDE_OK;
+}
+
+size_t sde_tsdf_mesh_ws_bytes(int nx, int ny, int nz) {
+    if (!dims_ok(nx, ny, nz)) return 0;
+    const size_t total = (size_t)nx * ny * nz;
+    return (2 * ((total + TILE - 1) / TILE) + total) * sizeof(unsigned);                 // vertex counts, quad counts, the cell -> vertex map
+}
+
+int sde_tsdf_mesh(const float* tsdf, const float* weight, const uint8_t* rgba, int nx, int ny, int nz, const float* origin, float voxel,
+                  float min_weight, void* workspace, size_t workspace_bytes, void* vertices, long cap_vertices, int* faces, long cap_faces,
+                  int* count, sde_stream_t stream) {
+    SDE_CHECK_ARG(dims_ok(nx, ny, nz), "sde_tsdf_mesh: every dimension must lie in [1, %d] and their product be at most 2^30 (%d x %d x %d)", MAX_DIM, nx, ny,
+                  nz);
+    SDE_CHECK_ARG(voxel > 0.f, "sde_tsdf_mesh: voxel must be positive (%g)", (double)voxel);
+    SDE_CHECK_ARG(min_weight >= 1.f, "sde_tsdf_mesh: min_weight must be at least 1 (%g)", (double)min_weight);
+    SDE_CHECK_ARG(cap_vertices >= 1 && cap_vertices <= 0x7fffffffL && cap_faces >= 1 && cap_faces <= 0x7fffffffL,
+                  "sde_tsdf_mesh: both caps must lie in [1, 2^31) (%ld, %ld)", cap_vertices, cap_faces);
+    SDE_CHECK_ARG(tsdf && weight && origin && vertices && faces && count, "sde_tsdf_mesh: null pointer");
+    SDE_CHECK_ARG(((uintptr_t)vertices & 15) == 0, "sde_tsdf_mesh: vertices must be 16-byte aligned");
+    SDE_CHECK_ARG(((uintptr_t)faces & 3) == 0 && ((uintptr_t)rgba & 3) == 0, "sde_tsdf_mesh: faces and rgba must be 4-byte aligned");
+    const size_t need = sde_tsdf_mesh_ws_bytes(nx, ny, nz);
+    SDE_CHECK_ARG(workspace && workspace_bytes >= need && ((uintptr_t)workspace & 3) == 0,
+                  "sde_tsdf_mesh: workspace of %zu bytes, sde_tsdf_mesh_ws_bytes asks for %zu (4-byte aligned)", workspace ? workspace_bytes : (size_t)0, need);
+    const size_t total = (size_t)nx * ny * nz, ntiles = (total + TILE - 1) / TILE;
+    unsigned* ws = (unsigned*)workspace;
+    MeshP p{PointsP{tsdf, weight, (const uint32_t*)rgba, ws, count, (uint4*)vertices, Grid{nx, ny, nz, origin[0], origin[1], origin[2], voxel}, total, ntiles,
+                    (unsigned)cap_vertices, min_weight},
+            ws + ntiles, ws + 2 * ntiles, faces, (size_t)cap_faces};
+    const unsigned grid = (unsigned)(ntiles < (size_t)MAX_BLOCKS ? ntiles : (size_t)MAX_BLOCKS);
+    hipLaunchKernelGGL(mesh_count, dim3(grid), dim3(TILE), 0, (hipStream_t)stream, p);
+    hipLaunchKernelGGL(mesh_scan, dim3(1), dim3(TILE), 0, (hipStream_t)stream, p.pt.ws, p.ws_q, count, ntiles);
+    hipLaunchKernelGGL(mesh_vertices, dim3(grid), dim3(TILE), 0, (hipStream_t)stream, p);
+    hipLaunchKernelGGL(mesh_faces, dim3(grid), dim3(TILE), 0, (hipStream_t)stream, p);
+    SDE_CHECK_LAUNCH("sde_tsdf_mesh");
     return SDE_OK;
 }
 

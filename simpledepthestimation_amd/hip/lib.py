@@ -144,6 +144,8 @@ _PROTOS = {
     "sde_tsdf_integrate": ([_P, _I, _I, _P, _P, _I, _I, _P, _P, _P, POINTER(c_float), _F, _F, _F, _F, _F, _P, _P, _P, _I, _I, _I, _P], c_int),
     "sde_tsdf_points_ws_bytes": ([_I, _I, _I], c_size_t),
     "sde_tsdf_points": ([_P, _P, _P, _I, _I, _I, POINTER(c_float), _F, _F, _P, c_size_t, _P, ctypes.c_long, _P, _P], c_int),
+    "sde_tsdf_mesh_ws_bytes": ([_I, _I, _I], c_size_t),
+    "sde_tsdf_mesh": ([_P, _P, _P, _I, _I, _I, POINTER(c_float), _F, _F, _P, c_size_t, _P, ctypes.c_long, _P, ctypes.c_long, _P, _P], c_int),
 }
 
 _lib = None

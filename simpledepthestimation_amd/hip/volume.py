@@ -2,7 +2,8 @@
 sde_tsdf_points; csrc/volume.hip).  `TsdfVolume` owns the three device arrays and binds the kernels; `compose_host`, `integrate_host` and
 `points_host` are their host twins -- the same fp32 operations in the same order in numpy, for machines without a GPU and for the tests,
 which compare the two bit for bit.  Every frame's depth is averaged into the voxel grid through its world-to-camera pose; the zero crossings
-of the grid are the surface, handed out as the 16-byte records of hip.cloud (as_records and the PLY writer take them as they are)."""
+of the grid are the surface, handed out as the 16-byte records of hip.cloud (as_records and the PLY writer take them as they are), or connected
+into a triangle mesh by surface nets (sde_tsdf_mesh: `TsdfVolume.mesh`, `save_mesh`, the twin `mesh_host`, `write_mesh_ply` / `read_mesh_ply`)."""
 import ctypes
 import warnings
 
@@ -153,6 +154,58 @@ class TsdfVolume:
                                         L.ptr(workspace), workspace.numel() * 4, L.ptr(points), cap, L.ptr(count), L.stream()), "sde_tsdf_points")
         return points, count
 
+    def default_mesh_caps(self):
+        """(cap_vertices, cap_faces) `mesh` makes room for when the caller names none: every cell a vertex and six triangles, or DEFAULT_CAP
+        vertices (64 MiB) and twice as many triangles (96 MiB) if that is fewer."""
+        cells = max((self.dims[0] - 1) * (self.dims[1] - 1) * (self.dims[2] - 1), 1)
+        return min(cells, DEFAULT_CAP), min(6 * cells, 2 * DEFAULT_CAP)
+
+    def mesh_workspace_numel(self):
+        """int32 elements of workspace sde_tsdf_mesh asks for."""
+        return int(L.lib().sde_tsdf_mesh_ws_bytes(*self.dims)) // 4
+
+    def mesh(self, min_weight=1, cap_vertices=None, cap_faces=None, out=None, workspace=None):
+        """The surface as triangles (surface nets: one vertex per cell that holds a crossing of `points`, two triangles per crossing edge with
+        four cells around it) -> (vertices [cap_vertices,16] uint8, faces [cap_faces,3] int32, count [2] int32) on the device.  The vertices are
+        the cloud's records (as_records), vertices[:min(count[0], cap_vertices)]; the triangles faces[:min(count[1], cap_faces)] hold vertex
+        numbers, counter-clockwise seen from the side of positive tsdf (the camera's).  count holds the totals, also beyond the caps: with
+        count[0] > cap_vertices or count[1] > cap_faces the mesh is incomplete (save_mesh runs again).  Caps None: default_mesh_caps().  out:
+        optional (vertices, faces, count) destinations; workspace: optional int32 tensor of at least mesh_workspace_numel() elements, whose
+        contents do not matter.  Four launches on the current stream, no host synchronisation."""
+        min_weight = check_min_weight(min_weight)
+        dv, df = self.default_mesh_caps()
+        cap_vertices, cap_faces = dv if cap_vertices is None else int(cap_vertices), df if cap_faces is None else int(cap_faces)
+        if not 1 <= cap_vertices <= 0x7fffffff or not 1 <= cap_faces <= 0x7fffffff:
+            raise ValueError(f"TsdfVolume.mesh: cap_vertices and cap_faces must lie in [1, 2^31), got {cap_vertices}, {cap_faces}")
+        vertices, faces, count = out if out is not None else (None, None, None)
+        vertices = A.dst("tsdf_mesh", vertices, (cap_vertices, 16), torch.uint8, True, self.device)
+        faces = A.dst("tsdf_mesh", faces, (cap_faces, 3), torch.int32, True, self.device)
+        count = A.dst("tsdf_mesh", count, (2,), torch.int32, True, self.device)
+        if workspace is None:
+            workspace = torch.empty((self.mesh_workspace_numel(),), dtype=torch.int32, device=self.device)
+        if not torch.is_tensor(workspace) or workspace.dtype != torch.int32 or workspace.device != self.device:
+            got = f"{workspace.dtype} on {workspace.device}" if torch.is_tensor(workspace) else type(workspace).__name__
+            raise L.SdeHipError(f"tsdf_mesh: workspace must be an int32 tensor on {self.device}, got {got}")
+        nx, ny, nz = self.dims
+        L.check(L.lib().sde_tsdf_mesh(L.ptr(self.tsdf), L.ptr(self.weight), L.ptr(self.rgba), nx, ny, nz, self._origin, self.voxel, min_weight,
+                                      L.ptr(workspace), workspace.numel() * 4, L.ptr(vertices), cap_vertices, L.ptr(faces), cap_faces, L.ptr(count),
+                                      L.stream()), "sde_tsdf_mesh")
+        return vertices, faces, count
+
+    def save_mesh(self, path, min_weight=1, cap_vertices=None, cap_faces=None):
+        """The mesh as a binary PLY (write_mesh_ply).  Synchronises.  When either cap was too small the mesh is taken once more with exactly the
+        counted room: a truncated mesh, whose triangles would name missing vertices, is never written.  Returns (vertices, triangles) written."""
+        vertices, faces, count = self.mesh(min_weight=min_weight, cap_vertices=cap_vertices, cap_faces=cap_faces)
+        nv, nf = (int(c) for c in count.cpu())
+        if nf == 0x7fffffff:
+            raise L.SdeHipError("TsdfVolume.save_mesh: the volume holds 2^31 - 1 triangles or more, beyond what sde_tsdf_mesh can hand out")
+        if nv > vertices.shape[0] or nf > faces.shape[0]:
+            del vertices, faces
+            vertices, faces, count = self.mesh(min_weight=min_weight, cap_vertices=max(nv, 1), cap_faces=max(nf, 1))
+            assert (nv, nf) == tuple(int(c) for c in count.cpu())
+        write_mesh_ply(path, as_records(vertices[:nv], nv), faces[:nf].cpu().numpy())
+        return nv, nf
+
     def save_ply(self, path, min_weight=1, cap=None):
         """The surface points as a binary PLY (the cloud's writer and record).  Synchronises.  Returns (records written, crossings found); when
         the volume holds more crossings than `cap` records, the first `cap` are written and a warning says so."""
@@ -170,6 +223,53 @@ def write_points_ply(path, points, count):
     n = min(count, cap)
     write_ply(path, as_records(points, n))
     return n, count
+
+
+PLY_FACE = np.dtype([("n", "u1"), ("v", "<i4", (3,))])               # one `property list uchar int vertex_indices` entry of a triangle: 13 bytes
+assert PLY_FACE.itemsize == 13
+
+
+def write_mesh_ply(path, vertices, faces):
+    """vertices: a 1-D array of hip.cloud.RECORD; faces [n,3] int32 vertex numbers, all in [0, vertices.size) -> a binary little-endian PLY with
+    the cloud's vertex properties and `element face n` / `property list uchar int vertex_indices`."""
+    from ..tools.demo import PLY_PROPERTIES
+    vertices, faces = np.asarray(vertices), np.asarray(faces)
+    if vertices.dtype != RECORD or vertices.ndim != 1:
+        raise ValueError(f"write_mesh_ply: a 1-D array of hip.cloud.RECORD expected, got {vertices.dtype} {vertices.shape}")
+    if faces.dtype != np.int32 or faces.ndim != 2 or faces.shape[1] != 3:
+        raise ValueError(f"write_mesh_ply: faces must be int32 [n,3], got {faces.dtype} {faces.shape}")
+    if faces.size and (int(faces.min()) < 0 or int(faces.max()) >= vertices.size):
+        raise ValueError(f"write_mesh_ply: a triangle names a vertex outside [0, {vertices.size}): the mesh is incomplete")
+    lines = (["ply", "format binary_little_endian 1.0", f"element vertex {vertices.size}"] + [f"property {t} {name}" for t, name in PLY_PROPERTIES]
+             + [f"element face {faces.shape[0]}", "property list uchar int vertex_indices", "end_header"])
+    body = np.zeros(faces.shape[0], PLY_FACE)
+    body["n"], body["v"] = 3, faces
+    with open(path, "wb") as f:
+        f.write(("\n".join(lines) + "\n").encode("ascii"))
+        vertices.tofile(f)
+        body.tofile(f)
+
+
+def read_mesh_ply(path):
+    """What write_mesh_ply wrote -> (vertices as hip.cloud.RECORD, faces [n,3] int32).  It reads this module's layout, not PLY in general."""
+    from ..tools.demo import PLY_PROPERTIES
+    with open(path, "rb") as f:
+        raw = f.read()
+    end = raw.index(b"end_header\n") + len(b"end_header\n")
+    lines = raw[:end].decode("ascii").split("\n")
+    want = ["ply", "format binary_little_endian 1.0", None] + [f"property {t} {name}" for t, name in PLY_PROPERTIES] + [
+        None, "property list uchar int vertex_indices", "end_header", ""]
+    if len(lines) != len(want) or any(w is not None and w != g for w, g in zip(want, lines)):
+        raise ValueError(f"read_mesh_ply: {path} does not have the header write_mesh_ply writes")
+    nv, nf = int(lines[2].removeprefix("element vertex ")), int(lines[len(PLY_PROPERTIES) + 3].removeprefix("element face "))
+    if len(raw) != end + nv * RECORD.itemsize + nf * PLY_FACE.itemsize:
+        raise ValueError(f"read_mesh_ply: {path} holds {len(raw) - end} bytes behind its header, {nv} vertices and {nf} triangles need "
+                         f"{nv * RECORD.itemsize + nf * PLY_FACE.itemsize}")
+    vertices = np.frombuffer(raw, RECORD, nv, end).copy()
+    body = np.frombuffer(raw, PLY_FACE, nf, end + nv * RECORD.itemsize)
+    if nf and not bool((body["n"] == 3).all()):
+        raise ValueError(f"read_mesh_ply: {path} holds a face that is no triangle")
+    return vertices, np.ascontiguousarray(body["v"], dtype=np.int32).reshape(nf, 3)
 
 
 # ---- host twins ---------------------------------------------------------------------------------------------------------------------------------
@@ -233,6 +333,17 @@ def integrate_host(tsdf, weight, rgba, pred, ymap, xmap, K, C, frame, origin, vo
     return keep
 
 
+def crossings_np(tsdf, weight, min_weight):
+    """bool [nz,ny,nx,3]: voxel v and its +1 neighbour along x, y, z are both valid and differ in (tsdf < 0)."""
+    nz, ny, nx = tsdf.shape
+    valid, neg = weight >= np.float32(check_min_weight(min_weight)), tsdf < 0
+    cross = np.zeros((nz, ny, nx, 3), bool)
+    cross[:, :, :-1, 0] = valid[:, :, :-1] & valid[:, :, 1:] & (neg[:, :, :-1] != neg[:, :, 1:])
+    cross[:, :-1, :, 1] = valid[:, :-1] & valid[:, 1:] & (neg[:, :-1] != neg[:, 1:])
+    cross[:-1, :, :, 2] = valid[:-1] & valid[1:] & (neg[:-1] != neg[1:])
+    return cross
+
+
 def points_host(tsdf, weight, rgba, origin, voxel, min_weight=1, cap=None):
     """The host twin of sde_tsdf_points -> (records, count): the structured array (hip.cloud.RECORD) of the first min(count, cap) crossings in
     the kernel's order (ascending voxel, then axis) with the bits it writes, and the total number of crossings."""
@@ -240,11 +351,7 @@ def points_host(tsdf, weight, rgba, origin, voxel, min_weight=1, cap=None):
     tsdf, weight = np.asarray(tsdf, dtype=f32), np.asarray(weight, dtype=f32)
     nz, ny, nx = tsdf.shape
     voxel = f32(voxel)
-    valid, neg = weight >= f32(check_min_weight(min_weight)), tsdf < 0
-    cross = np.zeros((nz, ny, nx, 3), bool)
-    cross[:, :, :-1, 0] = valid[:, :, :-1] & valid[:, :, 1:] & (neg[:, :, :-1] != neg[:, :, 1:])
-    cross[:, :-1, :, 1] = valid[:, :-1] & valid[:, 1:] & (neg[:, :-1] != neg[:, 1:])
-    cross[:-1, :, :, 2] = valid[:-1] & valid[1:] & (neg[:-1] != neg[1:])
+    cross = crossings_np(tsdf, weight, min_weight)
     k, j, i, a = np.nonzero(cross)                                # C order: ascending voxel, then axis
     count = int(k.size)
     if cap is not None:
@@ -263,3 +370,80 @@ def points_host(tsdf, weight, rgba, origin, voxel, min_weight=1, cap=None):
             col = np.asarray(rgba)[np.where(own, k, kn), np.where(own, j, jn), np.where(own, i, in_)]
             rec["red"], rec["green"], rec["blue"] = col[:, 0], col[:, 1], col[:, 2]
     return rec, count
+
+
+# the 12 edges of a cell in the order of include/sde_hip.h: (axis, corner offset (di, dj, dk) the edge starts at)
+CELL_EDGES = tuple((a, tuple(np.insert((db, dc), a, 0))) for a in range(3) for db, dc in ((0, 0), (1, 0), (0, 1), (1, 1)))
+
+
+def mesh_host(tsdf, weight, rgba, origin, voxel, min_weight=1, cap_vertices=None, cap_faces=None):
+    """The host twin of sde_tsdf_mesh -> (vertices, faces, count): the structured array (hip.cloud.RECORD) of the first min(count[0],
+    cap_vertices) vertices in ascending cell index, the first min(count[1], cap_faces) triangles as int32 [n,3] (ascending voxel, then axis, the
+    two triangles of a quad next to each other; vertex numbers are the true ones, also beyond cap_vertices) and count = int32 [vertices,
+    triangles], the totals: the bits the kernels write."""
+    f32 = np.float32
+    tsdf, weight = np.asarray(tsdf, dtype=f32), np.asarray(weight, dtype=f32)
+    nz, ny, nx = tsdf.shape
+    voxel = f32(voxel)
+    cross = crossings_np(tsdf, weight, min_weight)
+    cz, cy, cx = max(nz - 1, 0), max(ny - 1, 0), max(nx - 1, 0)                              # cells along each axis
+    edge = lambda a, d: cross[d[2]:d[2] + cz, d[1]:d[1] + cy, d[0]:d[0] + cx, a]             # that edge of every cell
+    has = np.zeros((cz, cy, cx), bool)
+    for a, d in CELL_EDGES:
+        has |= edge(a, d)
+    k, j, i = np.nonzero(has)                                     # C order: ascending cell index
+    nv = int(k.size)
+    number = np.full((nz, ny, nx), -1, np.int32)                  # cell -> vertex number
+    number[k, j, i] = np.arange(nv, dtype=np.int32)
+    if cap_vertices is not None:
+        k, j, i = (x[:int(cap_vertices)] for x in (k, j, i))
+    rec = np.zeros(k.size, RECORD)
+    cen = [centres_np(n, o, voxel) for n, o in zip((nx, ny, nz), origin)]
+    s = [np.zeros(k.size, f32) for _ in range(3)]
+    col = np.zeros((k.size, 3), np.int64)
+    m = np.zeros(k.size, np.int64)
+    with np.errstate(all="ignore"):
+        for a, d in CELL_EDGES:
+            lo = (i + d[0], j + d[1], k + d[2])
+            hi = tuple(lo[b] + (a == b) for b in range(3))
+            on = cross[lo[2], lo[1], lo[0], a]
+            tv, tn = tsdf[lo[2], lo[1], lo[0]], tsdf[hi[2], hi[1], hi[0]]
+            f = tv / (tv - tn)
+            along = f * voxel
+            for b in range(3):
+                c = cen[b][lo[b]]
+                s[b] = np.where(on, s[b] + (c + along if a == b else c), s[b])
+            if rgba is not None:
+                own = f < f32(0.5)
+                pick = [np.where(own, lo[b], hi[b]) for b in range(3)]
+                col += np.where(on[:, None], np.asarray(rgba)[pick[2], pick[1], pick[0], :3].astype(np.int64), 0)
+            m += on
+        fm = m.astype(f32)
+        rec["x"], rec["y"], rec["z"] = s[0] / fm, s[1] / fm, s[2] / fm
+        byte = (col.astype(f32) / fm[:, None] + f32(0.5)).astype(np.uint8)
+    rec["red"], rec["green"], rec["blue"], rec["alpha"] = byte[:, 0], byte[:, 1], byte[:, 2], 255
+
+    k, j, i, a = np.nonzero(cross)                                # C order: ascending voxel, then axis
+    inner = [(1 <= x) & (x <= n - 2) for x, n in zip((i, j, k), (nx, ny, nz))]
+    sel = np.where(a == 0, inner[1] & inner[2], np.where(a == 1, inner[0] & inner[2], inner[0] & inner[1]))
+    k, j, i, a = (x[sel] for x in (k, j, i, a))
+    nq = int(k.size)
+    nf = min(2 * nq, 0x7fffffff)
+    if cap_faces is not None:
+        k, j, i, a = (x[:(int(cap_faces) + 1) // 2] for x in (k, j, i, a))
+    b, c = np.where(a == 0, 1, 0), np.where(a == 2, 1, 2)         # b < c, the other two axes
+    pos = np.stack([i, j, k], 1)
+    rows = np.arange(k.size)
+
+    def q(db, dc):
+        p = pos.copy()
+        p[rows, b] += db
+        p[rows, c] += dc
+        return number[p[:, 2], p[:, 1], p[:, 0]]
+    q0, q1, q2, q3 = q(-1, -1), q(0, -1), q(0, 0), q(-1, 0)
+    keep = (tsdf[k, j, i] < 0) != (a == 1)
+    p1, p3 = np.where(keep, q1, q3), np.where(keep, q3, q1)
+    faces = np.stack([q0, p1, q2, q0, q2, p3], 1).astype(np.int32).reshape(-1, 3)
+    if cap_faces is not None:
+        faces = faces[:int(cap_faces)]
+    return rec, np.ascontiguousarray(faces), np.array([nv, nf], np.int32)

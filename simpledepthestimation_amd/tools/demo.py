@@ -32,7 +32,8 @@ averages every frame's depth (the fused one with --stabilise), in the range --sa
 NZ voxels of edge V through the camera pose chained from the model's own steps, and after the last frame `volume.ply` holds the grid's zero
 crossings as coloured points (the record and the PLY layout of --save-cloud), in the first frame's camera coordinates.  --volume-origin X Y Z is
 the corner of the first voxel (default: the first camera at the middle of the near face), --trunc M the truncation distance (default 4 V),
---min-weight N the number of observations a voxel needs (default 1).  All lengths are in the model's depth units: a monocular model's scale is
+--min-weight N the number of observations a voxel needs (default 1).  --save-mesh adds `volume_mesh.ply`, the same surface as a triangle mesh
+(TsdfVolume.save_mesh: one vertex per grid cell the surface passes through, two triangles per crossing, coloured like the points).  All lengths are in the model's depth units: a monocular model's scale is
 not aligned.  The model needs a context one frame away."""
 import argparse
 import os
@@ -67,6 +68,7 @@ def parse_args(argv=None):
     p.add_argument("--volume-origin", type=float, nargs=3, metavar=("X", "Y", "Z"), help="with --volume: corner of the first voxel in the first camera's "
                                                                                           "coordinates (default: the camera at the middle of the near face)")
     p.add_argument("--min-weight", type=float, default=1.0, help="with --volume: observations a voxel needs to count as surface (default 1)")
+    p.add_argument("--save-mesh", action="store_true", help="with --volume: also write volume_mesh.ply, the surface as a triangle mesh")
     p.add_argument("--cloud-step", type=int, default=1, help="the cloud takes every N-th pixel of every N-th row (default 1: all)")
     p.add_argument("--opts", default=[], nargs=argparse.REMAINDER, help="config overrides as KEY VALUE pairs, e.g. MODEL.WEIGHTS model.pth")
     args = p.parse_args(argv)
@@ -89,6 +91,8 @@ def parse_args(argv=None):
             p.error(str(e))
     elif any(v is not None for v in (args.voxel, args.trunc, args.volume_origin)):
         p.error("--voxel, --trunc and --volume-origin need --volume NX NY NZ")
+    elif args.save_mesh:
+        p.error("--save-mesh needs --volume NX NY NZ")
     for flag in ("save_flow", "save_trajectory", "rigid_only", "stabilise", "volume"):
         if getattr(args, flag) not in (None, False) and not args.pairs:
             p.error(f"--{flag.replace('_', '-')} needs --pairs")
@@ -183,6 +187,9 @@ def run_pairs(args, cfg, files):
     if volume is not None:
         written, found = volume.save_ply(os.path.join(args.output, "volume.ply"), min_weight=args.min_weight)
         print(f"volume.ply: {written} of {found} surface point(s)")
+        if args.save_mesh:
+            nv, nf = volume.save_mesh(os.path.join(args.output, "volume_mesh.ply"), min_weight=args.min_weight)
+            print(f"volume_mesh.ply: {nv} vertices, {nf} triangle(s)")
     print(f"{len(kept)} picture(s) written to {args.output}")
     return 0
 
