@@ -471,7 +471,10 @@ __global__ void __launch_bounds__(256) splitk_finish_kernel(const float* __restr
 //   Used for forward and data-gradient of every 3x3/1 layer whose output tiles well (see use_halo()).
 // ------------------------------------------------------------------------------------------------------------------
 constexpr int HT_H = 8, HT_W = 16, HALO_W = HT_W + 2, HALO_PIX = (HT_H + 2) * HALO_W;   // 10 x 18 = 180 halo pixels
-constexpr int HPIX_STRIDE = 144;                                                        // 128 B of channels + 16 B pad
+// 128 B of channels + 32 B pad.  ds_read_b128 serves a wave in four groups of 16 lanes; a group of the fragment read holds all 16 pixel columns,
+// eight of them one 16-byte chunk further on, so its 16-byte bank slots are (10 x + {0, 1}) mod 16: with ten slots per pixel all distinct.  Nine slots
+// (144 B) put seven pairs of lanes on the same banks: every fragment read of the tile took twice its LDS cycles.
+constexpr int HPIX_STRIDE = 160;
 constexpr int HALO_PASSES = (HALO_PIX * 8 + NTHREADS - 1) / NTHREADS;                   // 16-byte chunks per thread per block
 
 // byte offsets of halo pixel (ih, iw) of image n in source 0 / source 1 (channel 0), kOOB when it is padding
@@ -500,7 +503,7 @@ __global__ void __launch_bounds__(NTHREADS, 2) halo3_kernel(IGemmP p) {
     constexpr int CPAD = 4;
     static_assert(WM * WN == 4 && sizeof(T) == 2, "4 waves, 16-bit storage");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    unsigned char* sH = smem;                                   // [HALO_PIX][144 B]
+    unsigned char* sH = smem;                                   // [HALO_PIX][HPIX_STRIDE]
     unsigned char* sB = smem + HALO_PIX * HPIX_STRIDE;          // [2][BN][128 B]
 
     const Gather& g = p.g;
@@ -526,8 +529,7 @@ __global__ void __launch_bounds__(NTHREADS, 2) halo3_kernel(IGemmP p) {
         const int hy = hp / HALO_W, hx = hp - hy * HALO_W;
         halo_pix<T, SRC>(g, hp < HALO_PIX, img, oy0 - g.pad + hy, ox0 - g.pad + hx, hp0[j], hp1[j]);
     }
-    const int ncb = (g.Cin + BK - 1) / BK;          // 64-channel blocks
-    const int nst = ncb * 9;                        // pipeline stages: (channel block, tap)
+    const int ncb = (g.Cin + BK - 1) / BK;          // 64-channel blocks, nine pipeline stages (taps) each
     uint4 rh[HALO_PASSES];
     auto load_halo = [&](int cb) {
         const int ci = cb * BK + hc * V;
@@ -558,9 +560,8 @@ __global__ void __launch_bounds__(NTHREADS, 2) halo3_kernel(IGemmP p) {
     // ---- weight side: rows r0 + 32 i, chunk cc (as igemm_kernel); stage s = cb * 9 + tap reads k = tap*Cin + cb*64 + cc*8
     const int cc = tid & 7, r0 = tid >> 3;
     uint4 rb[3][B_PASSES];
-    auto load_b = [&](int s, auto SET) {
+    auto load_b = [&](int cb, int tap, auto SET) {
         constexpr int st = decltype(SET)::value;
-        const int cb = s / 9, tap = s - cb * 9;
         const int ci = cb * BK + cc * V;
         const int k = tap * g.Cin + ci;
 #pragma unroll
@@ -607,33 +608,42 @@ __global__ void __launch_bounds__(NTHREADS, 2) halo3_kernel(IGemmP p) {
                 for (int j = 0; j < FN; ++j) acc[i][j] = mma64<T>(a[i], b[j], acc[i][j]);
         }
     };
-    // one step: request weights of stage st+3, (at the first tap of a block) request the NEXT block's halo into registers,
-    // multiply stage st, publish weights of stage st+1; at a block boundary swap the halo tile (all waves are past their reads).
-    auto step = [&](int st, auto CUR, auto NXT) {
-        if (st >= nst) return;
-        const int cb = st / 9, tap = st - cb * 9;
-        if (st + 3 < nst) load_b(st + 3, CUR);
-        if (tap == 0 && cb + 1 < ncb) load_halo(cb + 1);
-        compute_stage(st & 1, tap);
-        if (st + 1 < nst) store_b((st + 1) & 1, NXT);
+    // one stage = (channel block cb, tap TAP): request the weights three stages ahead, (at tap HALO_TAP of a block) request the NEXT block's halo
+    // into registers, multiply this stage, publish the weights of the next one; at a block boundary swap the halo tile (all waves are past their
+    // reads).  The tap, the register set (TAP % 3: nine taps close the three-set rotation per block) and whether a next block exists are
+    // compile-time, so the stage holds no branch and hipcc counts the loads in flight: every wait in front of a store is a partial vmcnt(N).
+    // Weight ring slot of stage (cb, tap) = (cb * 9 + tap) & 1 = (cb + tap) & 1.
+    // HALO_TAP = 3: six stages of MFMAs still cover the halo's round trip, and the plain-source BN 64 kernel lands on 168 VGPRs = three waves per
+    // SIMD with no spill (requested at tap 0 it needs 169, at tap 5 or later 176; tests/test_halo3_loop_isa.py holds the budget).
+    constexpr int HALO_TAP = 3;
+    auto stage = [&](int cb, auto TAP, auto LAST) {
+        constexpr int tap = decltype(TAP)::value;
+        constexpr bool last = decltype(LAST)::value;
+        if constexpr (tap + 3 < 9) load_b(cb, tap + 3, IC<tap % 3>{});
+        else if constexpr (!last) load_b(cb + 1, tap + 3 - 9, IC<tap % 3>{});
+        if constexpr (tap == HALO_TAP && !last) load_halo(cb + 1);
+        compute_stage((cb + tap) & 1, tap);
+        if constexpr (tap < 8 || !last) store_b((cb + tap + 1) & 1, IC<(tap + 1) % 3>{});
         __syncthreads();
-        if (tap == 8 && cb + 1 < ncb) {
+        if constexpr (tap == 8 && !last) {
             store_halo();
             __syncthreads();
         }
     };
+    auto block = [&](int cb, auto LAST) {
+        stage(cb, IC<0>{}, LAST); stage(cb, IC<1>{}, LAST); stage(cb, IC<2>{}, LAST);
+        stage(cb, IC<3>{}, LAST); stage(cb, IC<4>{}, LAST); stage(cb, IC<5>{}, LAST);
+        stage(cb, IC<6>{}, LAST); stage(cb, IC<7>{}, LAST); stage(cb, IC<8>{}, LAST);
+    };
     load_halo(0);
-    load_b(0, IC<0>{});
-    if (nst > 1) load_b(1, IC<1>{});
-    if (nst > 2) load_b(2, IC<2>{});
+    load_b(0, 0, IC<0>{});
+    load_b(0, 1, IC<1>{});
+    load_b(0, 2, IC<2>{});
     store_halo();
     store_b(0, IC<0>{});
     __syncthreads();
-    for (int s = 0; s < nst; s += 3) {
-        step(s, IC<0>{}, IC<1>{});
-        step(s + 1, IC<1>{}, IC<2>{});
-        step(s + 2, IC<2>{}, IC<0>{});
-    }
+    for (int cb = 0; cb + 1 < ncb; ++cb) block(cb, std::false_type{});
+    block(ncb - 1, std::true_type{});       // peeled: no next halo, no weights past the last tap
 
     // ---- epilogue (as igemm_kernel; tile row r = ty*16 + tx -> output pixel (oy0+ty, ox0+tx))
     float* sC = reinterpret_cast<float*>(smem);   // [BM][BN + CPAD]
