@@ -18,23 +18,14 @@
 //
 // All of it is bandwidth-bound: 16 bytes per lane on the NHWC tensors.  The plane head keeps the reference's operation order in fp32
 // (this file is compiled without FMA contraction).
-#include "common.h"
-#include "sde_hip.h"
+#include "vec16.h"
+#include "launch.h"
 
 namespace {
 
-template <int ES> struct Bits;
-template <> struct Bits<2> { typedef unsigned short E; static constexpr int V = 8; };
-template <> struct Bits<4> { typedef unsigned int E; static constexpr int V = 4; };
-
-
-int grid_for(long n) {
-    long nb = (n + 255) / 256;
-    if (nb > 16384) nb = 16384;
-    return (int)(nb < 1 ? 1 : nb);
-}
-
-#define BTS_DISPATCH(dtype, F32, BF, HF) do { if ((dtype) == SDE_F32) { F32; } else if ((dtype) == SDE_BF16) { BF; } else { HF; } } while (0)
+typedef SdeTypes<float, bf16_t, half_t> Types;
+typedef SdeTypes<bf16_t, half_t, float> MoveTypes;      // the Bits<ES> kernels: the 2-byte instance comes first in the code object
+constexpr int GRID_CAP = SDE_GRID_CAP_16K;
 
 // ---------------------------------------------------------------------------------------------------------------------
 // space-to-batch for dilated convolutions (pure data movement, raw bits)
@@ -352,45 +343,49 @@ __global__ void __launch_bounds__(256) sigmoid_head_bwd_kernel(const T* __restri
 extern "C" {
 
 int sde_dilate_split(const void* x, int B, int H, int W, int C, int d, int dtype, void* out, sde_stream_t stream) {
-    const int V = SDE_IS16(dtype) ? 8 : 4;
-    SDE_CHECK_ARG(x && out && SDE_DTYPE_OK(dtype) && B > 0 && H > 0 && W > 0 && C > 0 && C % V == 0 && d >= 1, "sde_dilate_split: bad argument");
+    const int V = sde_vec_elems(dtype);
+    SDE_CHECK_ARG(x && out && Types::has(dtype) && B > 0 && H > 0 && W > 0 && C > 0 && C % V == 0 && d >= 1, "sde_dilate_split: bad argument (dtype %d)", dtype);
     const int Hs = (H + d - 1) / d, Ws = (W + d - 1) / d;
-    const int nb = grid_for((long)B * d * d * Hs * Ws * (C / V));
-    if (SDE_IS16(dtype)) hipLaunchKernelGGL((dilate_kernel<2, false>), dim3(nb), dim3(256), 0, (hipStream_t)stream, x, out, B, H, W, C, d, Hs, Ws);
-    else hipLaunchKernelGGL((dilate_kernel<4, false>), dim3(nb), dim3(256), 0, (hipStream_t)stream, x, out, B, H, W, C, d, Hs, Ws);
+    const int nb = sde_grid_for((long)B * d * d * Hs * Ws * (C / V), GRID_CAP);
+    MoveTypes::dispatch(dtype, [&](auto tag) {
+        hipLaunchKernelGGL((dilate_kernel<decltype(tag)::size, false>), dim3(nb), dim3(256), 0, (hipStream_t)stream, x, out, B, H, W, C, d, Hs, Ws);
+    });
     SDE_CHECK_LAUNCH("sde_dilate_split");
     return SDE_OK;
 }
 
 int sde_dilate_merge(const void* sub, int B, int H, int W, int C, int d, int dtype, void* out, sde_stream_t stream) {
-    const int V = SDE_IS16(dtype) ? 8 : 4;
-    SDE_CHECK_ARG(sub && out && SDE_DTYPE_OK(dtype) && B > 0 && H > 0 && W > 0 && C > 0 && C % V == 0 && d >= 1, "sde_dilate_merge: bad argument");
+    const int V = sde_vec_elems(dtype);
+    SDE_CHECK_ARG(sub && out && Types::has(dtype) && B > 0 && H > 0 && W > 0 && C > 0 && C % V == 0 && d >= 1, "sde_dilate_merge: bad argument (dtype %d)", dtype);
     const int Hs = (H + d - 1) / d, Ws = (W + d - 1) / d;
-    const int nb = grid_for((long)B * H * W * (C / V));
-    if (SDE_IS16(dtype)) hipLaunchKernelGGL((dilate_kernel<2, true>), dim3(nb), dim3(256), 0, (hipStream_t)stream, sub, out, B, H, W, C, d, Hs, Ws);
-    else hipLaunchKernelGGL((dilate_kernel<4, true>), dim3(nb), dim3(256), 0, (hipStream_t)stream, sub, out, B, H, W, C, d, Hs, Ws);
+    const int nb = sde_grid_for((long)B * H * W * (C / V), GRID_CAP);
+    MoveTypes::dispatch(dtype, [&](auto tag) {
+        hipLaunchKernelGGL((dilate_kernel<decltype(tag)::size, true>), dim3(nb), dim3(256), 0, (hipStream_t)stream, sub, out, B, H, W, C, d, Hs, Ws);
+    });
     SDE_CHECK_LAUNCH("sde_dilate_merge");
     return SDE_OK;
 }
 
 int sde_upsample2_fwd(const void* x, int B, int H, int W, int C, int dtype, void* out, sde_stream_t stream) {
-    const int V = SDE_IS16(dtype) ? 8 : 4;
-    SDE_CHECK_ARG(x && out && SDE_DTYPE_OK(dtype) && B > 0 && H > 0 && W > 0 && C > 0 && C % V == 0, "sde_upsample2_fwd: bad argument");
-    const int nb = grid_for((long)B * 4 * H * W * (C / V));
-    if (SDE_IS16(dtype)) hipLaunchKernelGGL(up2_fwd_kernel<2>, dim3(nb), dim3(256), 0, (hipStream_t)stream, x, out, B, H, W, C);
-    else hipLaunchKernelGGL(up2_fwd_kernel<4>, dim3(nb), dim3(256), 0, (hipStream_t)stream, x, out, B, H, W, C);
+    const int V = sde_vec_elems(dtype);
+    SDE_CHECK_ARG(x && out && Types::has(dtype) && B > 0 && H > 0 && W > 0 && C > 0 && C % V == 0, "sde_upsample2_fwd: bad argument (dtype %d)", dtype);
+    const int nb = sde_grid_for((long)B * 4 * H * W * (C / V), GRID_CAP);
+    MoveTypes::dispatch(dtype, [&](auto tag) {
+        hipLaunchKernelGGL(up2_fwd_kernel<decltype(tag)::size>, dim3(nb), dim3(256), 0, (hipStream_t)stream, x, out, B, H, W, C);
+    });
     SDE_CHECK_LAUNCH("sde_upsample2_fwd");
     return SDE_OK;
 }
 
 int sde_upsample2_bwd(const void* dout, int B, int H, int W, int C, int dtype, void* dx, sde_stream_t stream) {
-    const int V = SDE_IS16(dtype) ? 8 : 4;
-    SDE_CHECK_ARG(dout && dx && SDE_DTYPE_OK(dtype) && B > 0 && H > 0 && W > 0 && C > 0 && C % V == 0, "sde_upsample2_bwd: bad argument");
-    const int nb = grid_for((long)B * H * W * (C / V));
+    const int V = sde_vec_elems(dtype);
+    SDE_CHECK_ARG(dout && dx && Types::has(dtype) && B > 0 && H > 0 && W > 0 && C > 0 && C % V == 0, "sde_upsample2_bwd: bad argument (dtype %d)", dtype);
+    const int nb = sde_grid_for((long)B * H * W * (C / V), GRID_CAP);
     hipStream_t s = (hipStream_t)stream;
-    BTS_DISPATCH(dtype, hipLaunchKernelGGL(up2_bwd_kernel<float>, dim3(nb), dim3(256), 0, s, (const float*)dout, (float*)dx, B, H, W, C),
-                 hipLaunchKernelGGL(up2_bwd_kernel<bf16_t>, dim3(nb), dim3(256), 0, s, (const bf16_t*)dout, (bf16_t*)dx, B, H, W, C),
-                 hipLaunchKernelGGL(up2_bwd_kernel<half_t>, dim3(nb), dim3(256), 0, s, (const half_t*)dout, (half_t*)dx, B, H, W, C));
+    Types::dispatch(dtype, [&](auto tag) {
+        typedef typename decltype(tag)::type T;
+        hipLaunchKernelGGL(up2_bwd_kernel<T>, dim3(nb), dim3(256), 0, s, (const T*)dout, (T*)dx, B, H, W, C);
+    });
     SDE_CHECK_LAUNCH("sde_upsample2_bwd");
     return SDE_OK;
 }
@@ -411,33 +406,35 @@ static int cat_table(const sde_cat_piece* pieces, int n, int Ct, int V, CatTable
 }
 
 int sde_cat_fwd(const sde_cat_piece* pieces, int n, long P, int Ct, int dtype, void* out, sde_stream_t stream) {
-    const int V = SDE_IS16(dtype) ? 8 : 4;
-    SDE_CHECK_ARG(out && SDE_DTYPE_OK(dtype) && P > 0, "sde_cat_fwd: bad argument");
+    const int V = sde_vec_elems(dtype);
+    SDE_CHECK_ARG(out && Types::has(dtype) && P > 0, "sde_cat_fwd: bad argument (dtype %d)", dtype);
     CatTable t;
     const int rc = cat_table(pieces, n, Ct, V, t, "sde_cat_fwd");
     if (rc) return rc;
-    const int nb = grid_for(P * (Ct / V));
+    const int nb = sde_grid_for(P * (Ct / V), GRID_CAP);
     hipStream_t s = (hipStream_t)stream;
-    BTS_DISPATCH(dtype, hipLaunchKernelGGL(cat_fwd_kernel<float>, dim3(nb), dim3(256), 0, s, t, P, Ct, (float*)out),
-                 hipLaunchKernelGGL(cat_fwd_kernel<bf16_t>, dim3(nb), dim3(256), 0, s, t, P, Ct, (bf16_t*)out),
-                 hipLaunchKernelGGL(cat_fwd_kernel<half_t>, dim3(nb), dim3(256), 0, s, t, P, Ct, (half_t*)out));
+    Types::dispatch(dtype, [&](auto tag) {
+        typedef typename decltype(tag)::type T;
+        hipLaunchKernelGGL(cat_fwd_kernel<T>, dim3(nb), dim3(256), 0, s, t, P, Ct, (T*)out);
+    });
     SDE_CHECK_LAUNCH("sde_cat_fwd");
     return SDE_OK;
 }
 
 int sde_cat_bwd(const void* dout, long P, int Ct, int dtype, const sde_cat_piece* grads, int n, sde_stream_t stream) {
-    const int V = SDE_IS16(dtype) ? 8 : 4;
-    SDE_CHECK_ARG(dout && SDE_DTYPE_OK(dtype) && P > 0, "sde_cat_bwd: bad argument");
+    const int V = sde_vec_elems(dtype);
+    SDE_CHECK_ARG(dout && Types::has(dtype) && P > 0, "sde_cat_bwd: bad argument (dtype %d)", dtype);
     CatTable t;
     const int rc = cat_table(grads, n, Ct, V, t, "sde_cat_bwd");
     if (rc) return rc;
     int gtot = 0;
     for (int k = 0; k < n; ++k) gtot += grads[k].f32map ? 1 : grads[k].ld / V;
-    const int nb = grid_for(P * gtot);
+    const int nb = sde_grid_for(P * gtot, GRID_CAP);
     hipStream_t s = (hipStream_t)stream;
-    BTS_DISPATCH(dtype, hipLaunchKernelGGL(cat_bwd_kernel<float>, dim3(nb), dim3(256), 0, s, t, P, Ct, (const float*)dout, gtot),
-                 hipLaunchKernelGGL(cat_bwd_kernel<bf16_t>, dim3(nb), dim3(256), 0, s, t, P, Ct, (const bf16_t*)dout, gtot),
-                 hipLaunchKernelGGL(cat_bwd_kernel<half_t>, dim3(nb), dim3(256), 0, s, t, P, Ct, (const half_t*)dout, gtot));
+    Types::dispatch(dtype, [&](auto tag) {
+        typedef typename decltype(tag)::type T;
+        hipLaunchKernelGGL(cat_bwd_kernel<T>, dim3(nb), dim3(256), 0, s, t, P, Ct, (const T*)dout, gtot);
+    });
     SDE_CHECK_LAUNCH("sde_cat_bwd");
     return SDE_OK;
 }
@@ -445,74 +442,80 @@ int sde_cat_bwd(const void* dout, long P, int Ct, int dtype, const sde_cat_piece
 int sde_channel_stats_tiles(long M) { return M > 0 ? sde_cdiv(M, SDE_STATS_ROWS) : 0; }
 
 int sde_channel_stats(const void* x, long M, int C, int dtype, float* part, sde_stream_t stream) {
-    const int V = SDE_IS16(dtype) ? 8 : 4;
-    SDE_CHECK_ARG(x && part && SDE_DTYPE_OK(dtype) && M > 0 && C > 0 && C % V == 0, "sde_channel_stats: bad argument");
+    const int V = sde_vec_elems(dtype);
+    SDE_CHECK_ARG(x && part && Types::has(dtype) && M > 0 && C > 0 && C % V == 0, "sde_channel_stats: bad argument (dtype %d)", dtype);
     const dim3 grid(sde_channel_stats_tiles(M), sde_cdiv(C / V, STATS_GROUPS));
     hipStream_t s = (hipStream_t)stream;
-    BTS_DISPATCH(dtype, hipLaunchKernelGGL(channel_stats_kernel<float>, grid, dim3(256), 0, s, (const float*)x, M, C, part),
-                 hipLaunchKernelGGL(channel_stats_kernel<bf16_t>, grid, dim3(256), 0, s, (const bf16_t*)x, M, C, part),
-                 hipLaunchKernelGGL(channel_stats_kernel<half_t>, grid, dim3(256), 0, s, (const half_t*)x, M, C, part));
+    Types::dispatch(dtype, [&](auto tag) {
+        typedef typename decltype(tag)::type T;
+        hipLaunchKernelGGL(channel_stats_kernel<T>, grid, dim3(256), 0, s, (const T*)x, M, C, part);
+    });
     SDE_CHECK_LAUNCH("sde_channel_stats");
     return SDE_OK;
 }
 
 int sde_relu_fwd(const void* x, long n, int dtype, void* y, sde_stream_t stream) {
-    const int V = SDE_IS16(dtype) ? 8 : 4;
-    SDE_CHECK_ARG(x && y && SDE_DTYPE_OK(dtype) && n > 0 && n % V == 0, "sde_relu_fwd: bad argument");
-    const int nb = grid_for(n / V);
+    const int V = sde_vec_elems(dtype);
+    SDE_CHECK_ARG(x && y && Types::has(dtype) && n > 0 && n % V == 0, "sde_relu_fwd: bad argument (dtype %d)", dtype);
+    const int nb = sde_grid_for(n / V, GRID_CAP);
     hipStream_t s = (hipStream_t)stream;
-    BTS_DISPATCH(dtype, hipLaunchKernelGGL(relu_kernel<float>, dim3(nb), dim3(256), 0, s, (const float*)x, (float*)y, n),
-                 hipLaunchKernelGGL(relu_kernel<bf16_t>, dim3(nb), dim3(256), 0, s, (const bf16_t*)x, (bf16_t*)y, n),
-                 hipLaunchKernelGGL(relu_kernel<half_t>, dim3(nb), dim3(256), 0, s, (const half_t*)x, (half_t*)y, n));
+    Types::dispatch(dtype, [&](auto tag) {
+        typedef typename decltype(tag)::type T;
+        hipLaunchKernelGGL(relu_kernel<T>, dim3(nb), dim3(256), 0, s, (const T*)x, (T*)y, n);
+    });
     SDE_CHECK_LAUNCH("sde_relu_fwd");
     return SDE_OK;
 }
 
 int sde_lpg_fwd(const void* y, int B, int h, int w, int ld, int r, float max_depth, int ds, int dtype, float* full, float* down, sde_stream_t stream) {
-    SDE_CHECK_ARG(y && full && SDE_DTYPE_OK(dtype) && B > 0 && h > 0 && w > 0 && ld >= 3 && r >= 1 && max_depth > 0.f, "sde_lpg_fwd: bad argument");
+    SDE_CHECK_ARG(y && full && Types::has(dtype) && B > 0 && h > 0 && w > 0 && ld >= 3 && r >= 1 && max_depth > 0.f, "sde_lpg_fwd: bad argument (dtype %d)", dtype);
     SDE_CHECK_ARG(ds == 0 || (down && (h * r) % ds == 0 && (w * r) % ds == 0), "sde_lpg_fwd: bad down-sampling (%d)", ds);
-    const int nb = grid_for((long)B * h * r * w * r);
+    const int nb = sde_grid_for((long)B * h * r * w * r, GRID_CAP);
     hipStream_t s = (hipStream_t)stream;
-    BTS_DISPATCH(dtype, hipLaunchKernelGGL(lpg_fwd_kernel<float>, dim3(nb), dim3(256), 0, s, (const float*)y, B, h, w, ld, r, max_depth, ds, full, down),
-                 hipLaunchKernelGGL(lpg_fwd_kernel<bf16_t>, dim3(nb), dim3(256), 0, s, (const bf16_t*)y, B, h, w, ld, r, max_depth, ds, full, down),
-                 hipLaunchKernelGGL(lpg_fwd_kernel<half_t>, dim3(nb), dim3(256), 0, s, (const half_t*)y, B, h, w, ld, r, max_depth, ds, full, down));
+    Types::dispatch(dtype, [&](auto tag) {
+        typedef typename decltype(tag)::type T;
+        hipLaunchKernelGGL(lpg_fwd_kernel<T>, dim3(nb), dim3(256), 0, s, (const T*)y, B, h, w, ld, r, max_depth, ds, full, down);
+    });
     SDE_CHECK_LAUNCH("sde_lpg_fwd");
     return SDE_OK;
 }
 
 int sde_lpg_bwd(const void* y, const float* dfull, const float* ddown, int B, int h, int w, int ld, int r, float max_depth, int ds, int dtype, void* dy,
                 sde_stream_t stream) {
-    SDE_CHECK_ARG(y && dy && SDE_DTYPE_OK(dtype) && B > 0 && h > 0 && w > 0 && ld >= 3 && r >= 1 && max_depth > 0.f, "sde_lpg_bwd: bad argument");
+    SDE_CHECK_ARG(y && dy && Types::has(dtype) && B > 0 && h > 0 && w > 0 && ld >= 3 && r >= 1 && max_depth > 0.f, "sde_lpg_bwd: bad argument (dtype %d)", dtype);
     SDE_CHECK_ARG(!ddown || (ds > 0 && (h * r) % ds == 0 && (w * r) % ds == 0), "sde_lpg_bwd: bad down-sampling (%d)", ds);
-    const int nb = grid_for((long)B * h * w);
+    const int nb = sde_grid_for((long)B * h * w, GRID_CAP);
     hipStream_t s = (hipStream_t)stream;
-    BTS_DISPATCH(dtype, hipLaunchKernelGGL(lpg_bwd_kernel<float>, dim3(nb), dim3(256), 0, s, (const float*)y, dfull, ddown, B, h, w, ld, r, max_depth, ds, (float*)dy),
-                 hipLaunchKernelGGL(lpg_bwd_kernel<bf16_t>, dim3(nb), dim3(256), 0, s, (const bf16_t*)y, dfull, ddown, B, h, w, ld, r, max_depth, ds, (bf16_t*)dy),
-                 hipLaunchKernelGGL(lpg_bwd_kernel<half_t>, dim3(nb), dim3(256), 0, s, (const half_t*)y, dfull, ddown, B, h, w, ld, r, max_depth, ds, (half_t*)dy));
+    Types::dispatch(dtype, [&](auto tag) {
+        typedef typename decltype(tag)::type T;
+        hipLaunchKernelGGL(lpg_bwd_kernel<T>, dim3(nb), dim3(256), 0, s, (const T*)y, dfull, ddown, B, h, w, ld, r, max_depth, ds, (T*)dy);
+    });
     SDE_CHECK_LAUNCH("sde_lpg_bwd");
     return SDE_OK;
 }
 
 int sde_sigmoid_head_fwd(const void* y, int B, int H, int W, int ld, float scale, const float* focal, float focal_div, int flip, int dtype, float* out,
                          sde_stream_t stream) {
-    SDE_CHECK_ARG(y && out && SDE_DTYPE_OK(dtype) && B > 0 && H > 0 && W > 0 && ld >= 1 && (!focal || focal_div != 0.f), "sde_sigmoid_head_fwd: bad argument");
-    const int nb = grid_for((long)B * H * W);
+    SDE_CHECK_ARG(y && out && Types::has(dtype) && B > 0 && H > 0 && W > 0 && ld >= 1 && (!focal || focal_div != 0.f), "sde_sigmoid_head_fwd: bad argument (dtype %d)", dtype);
+    const int nb = sde_grid_for((long)B * H * W, GRID_CAP);
     hipStream_t s = (hipStream_t)stream;
-    BTS_DISPATCH(dtype, hipLaunchKernelGGL(sigmoid_head_fwd_kernel<float>, dim3(nb), dim3(256), 0, s, (const float*)y, B, H, W, ld, scale, focal, focal_div, flip, out),
-                 hipLaunchKernelGGL(sigmoid_head_fwd_kernel<bf16_t>, dim3(nb), dim3(256), 0, s, (const bf16_t*)y, B, H, W, ld, scale, focal, focal_div, flip, out),
-                 hipLaunchKernelGGL(sigmoid_head_fwd_kernel<half_t>, dim3(nb), dim3(256), 0, s, (const half_t*)y, B, H, W, ld, scale, focal, focal_div, flip, out));
+    Types::dispatch(dtype, [&](auto tag) {
+        typedef typename decltype(tag)::type T;
+        hipLaunchKernelGGL(sigmoid_head_fwd_kernel<T>, dim3(nb), dim3(256), 0, s, (const T*)y, B, H, W, ld, scale, focal, focal_div, flip, out);
+    });
     SDE_CHECK_LAUNCH("sde_sigmoid_head_fwd");
     return SDE_OK;
 }
 
 int sde_sigmoid_head_bwd(const void* y, const float* dout, int B, int H, int W, int ld, float scale, const float* focal, float focal_div, int flip, int dtype,
                          void* dy, sde_stream_t stream) {
-    SDE_CHECK_ARG(y && dout && dy && SDE_DTYPE_OK(dtype) && B > 0 && H > 0 && W > 0 && ld >= 1 && (!focal || focal_div != 0.f), "sde_sigmoid_head_bwd: bad argument");
-    const int nb = grid_for((long)B * H * W);
+    SDE_CHECK_ARG(y && dout && dy && Types::has(dtype) && B > 0 && H > 0 && W > 0 && ld >= 1 && (!focal || focal_div != 0.f), "sde_sigmoid_head_bwd: bad argument (dtype %d)", dtype);
+    const int nb = sde_grid_for((long)B * H * W, GRID_CAP);
     hipStream_t s = (hipStream_t)stream;
-    BTS_DISPATCH(dtype, hipLaunchKernelGGL(sigmoid_head_bwd_kernel<float>, dim3(nb), dim3(256), 0, s, (const float*)y, dout, B, H, W, ld, scale, focal, focal_div, flip, (float*)dy),
-                 hipLaunchKernelGGL(sigmoid_head_bwd_kernel<bf16_t>, dim3(nb), dim3(256), 0, s, (const bf16_t*)y, dout, B, H, W, ld, scale, focal, focal_div, flip, (bf16_t*)dy),
-                 hipLaunchKernelGGL(sigmoid_head_bwd_kernel<half_t>, dim3(nb), dim3(256), 0, s, (const half_t*)y, dout, B, H, W, ld, scale, focal, focal_div, flip, (half_t*)dy));
+    Types::dispatch(dtype, [&](auto tag) {
+        typedef typename decltype(tag)::type T;
+        hipLaunchKernelGGL(sigmoid_head_bwd_kernel<T>, dim3(nb), dim3(256), 0, s, (const T*)y, dout, B, H, W, ld, scale, focal, focal_div, flip, (T*)dy);
+    });
     SDE_CHECK_LAUNCH("sde_sigmoid_head_bwd");
     return SDE_OK;
 }

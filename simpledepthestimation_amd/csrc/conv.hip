@@ -21,7 +21,7 @@
 //     over pixel ranges into fp32 slabs that a second kernel sums in fixed order (bit-reproducible gradients).
 #include <type_traits>
 
-#include "common.h"
+#include "vec16.h"      // VecOf
 #include "sde_hip.h"
 #include "conv_common.h"
 
@@ -34,11 +34,6 @@ typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) short s16x4;
 typedef __attribute__((ext_vector_type(8))) short s16x8;
-
-template <typename T> struct VecOf;
-template <> struct VecOf<float> { static constexpr int V = 4; };
-template <> struct VecOf<bf16_t> { static constexpr int V = 8; };
-template <> struct VecOf<half_t> { static constexpr int V = 8; };
 
 template <typename T>
 __device__ __forceinline__ uint4 gather16(const Gather& g, int n, int ih, int iw, int ci) {

@@ -16,8 +16,8 @@
 //
 // A workgroup owns up to 8 sixteen-byte channel groups (64 bf16 / 32 fp32 channels) of a range of rows: a lane keeps its channel group for the
 // whole launch, so the piece it reads is looked up once.  No atomics, every sum has one order: two runs give the same bits.
-#include "common.h"
-#include "sde_hip.h"
+#include "vec16.h"
+#include "launch.h"
 
 namespace {
 
@@ -35,8 +35,6 @@ struct GatherTab {
 
 constexpr int DCW = 8;               // sixteen-byte channel groups per workgroup
 constexpr int DENSE_ROWS = 64;       // most partial rows of the backward reduction
-
-template <typename T> struct VOf { static constexpr int V = 16 / sizeof(T); };
 
 // the lane's place: channel group cv (of cch), row lane rl (of rp); lanes beyond rp * cw or beyond the last channel group idle
 struct Lane { int cw, rp, cl, rl, cv; bool on; };
@@ -113,7 +111,7 @@ __global__ void __launch_bounds__(256) dense_params_kernel(const float* __restri
 
 template <typename T>
 __global__ void __launch_bounds__(256) dense_fwd_kernel(const DenseTab t, long M, int Cin, const float* __restrict__ bnp, T* __restrict__ out, long rpb) {
-    constexpr int V = VOf<T>::V;
+    constexpr int V = VecOf<T>::V;
     const Lane l = lane_of(Cin / V);
     if (!l.on) return;
     const int c0 = l.cv * V;
@@ -138,7 +136,7 @@ __global__ void __launch_bounds__(256) dense_fwd_kernel(const DenseTab t, long M
 template <typename T>
 __global__ void __launch_bounds__(256) dense_bwd_reduce_kernel(const DenseTab t, long M, int Cin, const T* __restrict__ g, const float* __restrict__ bnp,
                                                                float* __restrict__ part, long rpb) {
-    constexpr int V = VOf<T>::V;
+    constexpr int V = VecOf<T>::V;
     __shared__ float sh[256 * 2 * V];
     const int cch = Cin / V;
     const Lane l = lane_of(cch);
@@ -185,7 +183,7 @@ template <typename T>
 __global__ void __launch_bounds__(256) dense_bwd_apply_kernel(const DenseTab t, long M, int Cin, const T* __restrict__ g, const float* __restrict__ bnp,
                                                               const float* __restrict__ part, int R, float* __restrict__ dgamma, float* __restrict__ dbeta,
                                                               int accumulate, T* __restrict__ dx, long rpb) {
-    constexpr int V = VOf<T>::V;
+    constexpr int V = VecOf<T>::V;
     __shared__ float coef[DCW * 2 * V];
     const int cch = Cin / V;
     const Lane l = lane_of(cch);
@@ -234,7 +232,7 @@ __global__ void __launch_bounds__(256) dense_bwd_apply_kernel(const DenseTab t, 
 
 template <typename T>
 __global__ void __launch_bounds__(256) dense_gather_kernel(const GatherTab t, long M, int off, int g, const T* __restrict__ outside, T* __restrict__ out) {
-    constexpr int V = VOf<T>::V;
+    constexpr int V = VecOf<T>::V;
     const int cg = g / V;
     const long total = M * cg;
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
@@ -264,7 +262,7 @@ __global__ void __launch_bounds__(256) dense_gather_kernel(const GatherTab t, lo
 
 template <typename T>
 __global__ void __launch_bounds__(256) avgpool2_fwd_kernel(const T* __restrict__ x, T* __restrict__ out, int B, int H, int W, int C) {
-    constexpr int V = VOf<T>::V;
+    constexpr int V = VecOf<T>::V;
     const int cg = C / V, OH = H / 2, OW = W / 2;
     const long total = (long)B * OH * OW * cg;
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
@@ -290,7 +288,7 @@ __global__ void __launch_bounds__(256) avgpool2_fwd_kernel(const T* __restrict__
 
 template <typename T>
 __global__ void __launch_bounds__(256) avgpool2_bwd_kernel(const T* __restrict__ dout, T* __restrict__ dx, int B, int H, int W, int C) {
-    constexpr int V = VOf<T>::V;
+    constexpr int V = VecOf<T>::V;
     const int cg = C / V, OH = H / 2, OW = W / 2;
     const long total = (long)B * H * W * cg;
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
@@ -310,17 +308,12 @@ __global__ void __launch_bounds__(256) avgpool2_bwd_kernel(const T* __restrict__
     }
 }
 
-int grid_for(long n) {
-    long nb = (n + 255) / 256;
-    if (nb > 16384) nb = 16384;
-    return (int)(nb < 1 ? 1 : nb);
-}
-
-bool dense_dtype_ok(int dtype) { return dtype == SDE_F32 || dtype == SDE_BF16; }
+typedef SdeTypes<bf16_t, float> Types;
+constexpr int GRID_CAP = SDE_GRID_CAP_16K;
 
 int build_tab(const sde_dense_desc* d, int dtype, DenseTab& t, const char* who) {
     SDE_CHECK_ARG(d, "%s: null descriptor", who);
-    SDE_CHECK_ARG(dense_dtype_ok(dtype), "%s: fp32 and bf16 only (dtype %d)", who, dtype);
+    SDE_CHECK_ARG(Types::has(dtype), "%s: fp32 and bf16 only (dtype %d)", who, dtype);
     SDE_CHECK_ARG(d->n >= 1 && d->n <= SDE_DENSE_MAX, "%s: 1..%d pieces, got %d", who, SDE_DENSE_MAX, d->n);
     t.n = d->n;
     t.off[0] = 0;
@@ -335,7 +328,7 @@ int build_tab(const sde_dense_desc* d, int dtype, DenseTab& t, const char* who) 
 
 // rows a lane pass covers, channel-group columns of the grid
 void dense_geometry(int Cin, int dtype, int& rp, int& ny) {
-    const int V = dtype == SDE_F32 ? 4 : 8;
+    const int V = sde_vec_elems(dtype);
     const int cch = Cin / V;
     const int cw = cch < DCW ? cch : DCW;
     rp = 256 / cw;
@@ -361,7 +354,7 @@ int sde_dense_stats(const float* slab, int rows, int C, long count, float* table
 }
 
 int sde_dense_bwd_rows(long M, int Cin, int dtype) {
-    SDE_CHECK_ARG(dense_dtype_ok(dtype), "sde_dense_bwd_rows: fp32 and bf16 only (dtype %d)", dtype);
+    SDE_CHECK_ARG(Types::has(dtype), "sde_dense_bwd_rows: fp32 and bf16 only (dtype %d)", dtype);
     SDE_CHECK_ARG(M > 0 && Cin > 0 && Cin % 8 == 0, "sde_dense_bwd_rows: M > 0 and a channel count that is a multiple of 8 (M=%ld Cin=%d)", M, Cin);
     int rp, ny;
     dense_geometry(Cin, dtype, rp, ny);
@@ -385,10 +378,10 @@ int sde_dense_bn_relu_fwd(const sde_dense_desc* d, long M, int dtype, const floa
     const long nx = row_blocks(M, rp, 1024);
     const long rpb = (M + nx - 1) / nx;
     const dim3 grid((unsigned)nx, (unsigned)ny);
-    if (dtype == SDE_BF16)
-        hipLaunchKernelGGL(dense_fwd_kernel<bf16_t>, grid, dim3(256), 0, s, t, M, Cin, bnp, (bf16_t*)out, rpb);
-    else
-        hipLaunchKernelGGL(dense_fwd_kernel<float>, grid, dim3(256), 0, s, t, M, Cin, bnp, (float*)out, rpb);
+    Types::dispatch(dtype, [&](auto tag) {
+        typedef typename decltype(tag)::type T;
+        hipLaunchKernelGGL(dense_fwd_kernel<T>, grid, dim3(256), 0, s, t, M, Cin, bnp, (T*)out, rpb);
+    });
     SDE_CHECK_LAUNCH("sde_dense_bn_relu_fwd");
     return SDE_OK;
 }
@@ -407,22 +400,19 @@ int sde_dense_bn_relu_bwd(const sde_dense_desc* d, long M, int dtype, const void
     const long nx = row_blocks(M, rp, 256);
     const long rpa = (M + nx - 1) / nx;
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == SDE_BF16) {
-        hipLaunchKernelGGL(dense_bwd_reduce_kernel<bf16_t>, dim3(R, ny), dim3(256), 0, s, t, M, Cin, (const bf16_t*)g, bnp, part, rpb);
-        hipLaunchKernelGGL(dense_bwd_apply_kernel<bf16_t>, dim3((unsigned)nx, ny), dim3(256), 0, s, t, M, Cin, (const bf16_t*)g, bnp, part, R, dgamma, dbeta,
-                           accumulate_params, (bf16_t*)dx, rpa);
-    } else {
-        hipLaunchKernelGGL(dense_bwd_reduce_kernel<float>, dim3(R, ny), dim3(256), 0, s, t, M, Cin, (const float*)g, bnp, part, rpb);
-        hipLaunchKernelGGL(dense_bwd_apply_kernel<float>, dim3((unsigned)nx, ny), dim3(256), 0, s, t, M, Cin, (const float*)g, bnp, part, R, dgamma, dbeta,
-                           accumulate_params, (float*)dx, rpa);
-    }
+    Types::dispatch(dtype, [&](auto tag) {
+        typedef typename decltype(tag)::type T;
+        hipLaunchKernelGGL(dense_bwd_reduce_kernel<T>, dim3(R, ny), dim3(256), 0, s, t, M, Cin, (const T*)g, bnp, part, rpb);
+        hipLaunchKernelGGL(dense_bwd_apply_kernel<T>, dim3((unsigned)nx, ny), dim3(256), 0, s, t, M, Cin, (const T*)g, bnp, part, R, dgamma, dbeta, accumulate_params,
+                           (T*)dx, rpa);
+    });
     SDE_CHECK_LAUNCH("sde_dense_bn_relu_bwd");
     return SDE_OK;
 }
 
 int sde_dense_grad_gather(const sde_dense_desc* dxs, long M, int off, int g, int dtype, const void* outside, void* out, sde_stream_t stream) {
     SDE_CHECK_ARG(dxs && out, "sde_dense_grad_gather: null pointer");
-    SDE_CHECK_ARG(dense_dtype_ok(dtype), "sde_dense_grad_gather: fp32 and bf16 only (dtype %d)", dtype);
+    SDE_CHECK_ARG(Types::has(dtype), "sde_dense_grad_gather: fp32 and bf16 only (dtype %d)", dtype);
     SDE_CHECK_ARG(dxs->n >= 0 && dxs->n <= SDE_DENSE_MAX && (dxs->n > 0 || outside), "sde_dense_grad_gather: 0..%d sources (none only with an outside gradient), got %d",
                   SDE_DENSE_MAX, dxs->n);
     SDE_CHECK_ARG(M > 0 && off >= 0 && off % 8 == 0 && g > 0 && g % 8 == 0, "sde_dense_grad_gather: offset and width must be multiples of 8 (off=%d g=%d)", off, g);
@@ -434,41 +424,41 @@ int sde_dense_grad_gather(const sde_dense_desc* dxs, long M, int off, int g, int
         t.p[k] = k < dxs->n ? dxs->p[k] : nullptr;
         t.ld[k] = k < dxs->n ? dxs->C[k] : 0;
     }
-    const int V = dtype == SDE_F32 ? 4 : 8;
-    const int nb = grid_for(M * (g / V));
+    const int V = sde_vec_elems(dtype);
+    const int nb = sde_grid_for(M * (g / V), GRID_CAP);
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == SDE_BF16)
-        hipLaunchKernelGGL(dense_gather_kernel<bf16_t>, dim3(nb), dim3(256), 0, s, t, M, off, g, (const bf16_t*)outside, (bf16_t*)out);
-    else
-        hipLaunchKernelGGL(dense_gather_kernel<float>, dim3(nb), dim3(256), 0, s, t, M, off, g, (const float*)outside, (float*)out);
+    Types::dispatch(dtype, [&](auto tag) {
+        typedef typename decltype(tag)::type T;
+        hipLaunchKernelGGL(dense_gather_kernel<T>, dim3(nb), dim3(256), 0, s, t, M, off, g, (const T*)outside, (T*)out);
+    });
     SDE_CHECK_LAUNCH("sde_dense_grad_gather");
     return SDE_OK;
 }
 
 int sde_avgpool2x2_fwd(const void* x, int B, int H, int W, int C, int dtype, void* out, sde_stream_t stream) {
-    SDE_CHECK_ARG(dense_dtype_ok(dtype), "sde_avgpool2x2_fwd: fp32 and bf16 only (dtype %d)", dtype);
+    SDE_CHECK_ARG(Types::has(dtype), "sde_avgpool2x2_fwd: fp32 and bf16 only (dtype %d)", dtype);
     SDE_CHECK_ARG(x && out && B > 0 && H >= 2 && W >= 2 && C > 0 && C % 8 == 0, "sde_avgpool2x2_fwd: bad argument (H=%d W=%d C=%d)", H, W, C);
-    const int V = dtype == SDE_F32 ? 4 : 8;
-    const int nb = grid_for((long)B * (H / 2) * (W / 2) * (C / V));
+    const int V = sde_vec_elems(dtype);
+    const int nb = sde_grid_for((long)B * (H / 2) * (W / 2) * (C / V), GRID_CAP);
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == SDE_BF16)
-        hipLaunchKernelGGL(avgpool2_fwd_kernel<bf16_t>, dim3(nb), dim3(256), 0, s, (const bf16_t*)x, (bf16_t*)out, B, H, W, C);
-    else
-        hipLaunchKernelGGL(avgpool2_fwd_kernel<float>, dim3(nb), dim3(256), 0, s, (const float*)x, (float*)out, B, H, W, C);
+    Types::dispatch(dtype, [&](auto tag) {
+        typedef typename decltype(tag)::type T;
+        hipLaunchKernelGGL(avgpool2_fwd_kernel<T>, dim3(nb), dim3(256), 0, s, (const T*)x, (T*)out, B, H, W, C);
+    });
     SDE_CHECK_LAUNCH("sde_avgpool2x2_fwd");
     return SDE_OK;
 }
 
 int sde_avgpool2x2_bwd(const void* dout, int B, int H, int W, int C, int dtype, void* dx, sde_stream_t stream) {
-    SDE_CHECK_ARG(dense_dtype_ok(dtype), "sde_avgpool2x2_bwd: fp32 and bf16 only (dtype %d)", dtype);
+    SDE_CHECK_ARG(Types::has(dtype), "sde_avgpool2x2_bwd: fp32 and bf16 only (dtype %d)", dtype);
     SDE_CHECK_ARG(dout && dx && B > 0 && H >= 2 && W >= 2 && C > 0 && C % 8 == 0, "sde_avgpool2x2_bwd: bad argument (H=%d W=%d C=%d)", H, W, C);
-    const int V = dtype == SDE_F32 ? 4 : 8;
-    const int nb = grid_for((long)B * H * W * (C / V));
+    const int V = sde_vec_elems(dtype);
+    const int nb = sde_grid_for((long)B * H * W * (C / V), GRID_CAP);
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == SDE_BF16)
-        hipLaunchKernelGGL(avgpool2_bwd_kernel<bf16_t>, dim3(nb), dim3(256), 0, s, (const bf16_t*)dout, (bf16_t*)dx, B, H, W, C);
-    else
-        hipLaunchKernelGGL(avgpool2_bwd_kernel<float>, dim3(nb), dim3(256), 0, s, (const float*)dout, (float*)dx, B, H, W, C);
+    Types::dispatch(dtype, [&](auto tag) {
+        typedef typename decltype(tag)::type T;
+        hipLaunchKernelGGL(avgpool2_bwd_kernel<T>, dim3(nb), dim3(256), 0, s, (const T*)dout, (T*)dx, B, H, W, C);
+    });
     SDE_CHECK_LAUNCH("sde_avgpool2x2_bwd");
     return SDE_OK;
 }

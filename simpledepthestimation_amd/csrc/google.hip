@@ -14,48 +14,16 @@
 //   softplus_head F.softplus(out_conv(x)) (L103): channel 0 -> planar [B,1,H,W] fp32, flip folded in
 //
 // No atomics anywhere: every sum has one owner and a fixed order, so repeated runs give identical bits.
-#include "common.h"
-#include "sde_hip.h"
+#include "vec16.h"
+#include "launch.h"
 
 namespace {
 
+typedef SdeTypes<float, bf16_t> Types;
+constexpr int GRID_CAP = SDE_GRID_CAP_16K;
+
 constexpr int RLN_CHUNKS = SDE_RLN_CHUNKS;
 constexpr int RLN_MAXC = 2048;      // LDS holds [2][RLN_MAXC] floats
-
-template <typename T> struct Vec;
-template <> struct Vec<float> { static constexpr int V = 4; };
-template <> struct Vec<bf16_t> { static constexpr int V = 8; };
-
-template <typename T> __device__ __forceinline__ void ld_vec(const T* p, float* v);
-template <> __device__ __forceinline__ void ld_vec<float>(const float* p, float* v) {
-    const float4 t = *reinterpret_cast<const float4*>(p);
-    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-}
-template <> __device__ __forceinline__ void ld_vec<bf16_t>(const bf16_t* p, float* v) {
-    const uint4 t = *reinterpret_cast<const uint4*>(p);
-    const uint32_t w[4] = {t.x, t.y, t.z, t.w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        v[2 * i] = __uint_as_float(w[i] << 16);
-        v[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
-    }
-}
-template <typename T> __device__ __forceinline__ void st_vec(T* p, const float* v);
-template <> __device__ __forceinline__ void st_vec<float>(float* p, const float* v) {
-    *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-}
-template <> __device__ __forceinline__ void st_vec<bf16_t>(bf16_t* p, const float* v) {
-    bf16_t o[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) o[i] = (bf16_t)v[i];
-    *reinterpret_cast<uint4*>(p) = *reinterpret_cast<uint4*>(o);
-}
-
-int grid_for(long n) {
-    long nb = (n + 255) / 256;
-    if (nb > 16384) nb = 16384;
-    return (int)(nb < 1 ? 1 : nb);
-}
 
 __host__ __device__ __forceinline__ int rln_chunks(int HW) {
     const int n = HW / 64;
@@ -101,7 +69,7 @@ __device__ void fold_rows(const Layout& l, int C, const float (&acc1)[2][V], con
 // forward stage 1: part[b][chunk][c] = (sum, sum^2) of x[b, p, c] - x[b, 0, c] over the chunk's pixels
 template <typename T>
 __global__ void __launch_bounds__(256) rln_stats_kernel(const T* __restrict__ x, int HW, int C, float* __restrict__ part) {
-    constexpr int V = Vec<T>::V;
+    constexpr int V = VecOf<T>::V;
     __shared__ float sh[2 * RLN_MAXC];
     const int b = blockIdx.y, ch = blockIdx.x, nch = gridDim.x;
     const Layout l(C, V);
@@ -119,10 +87,10 @@ __global__ void __launch_bounds__(256) rln_stats_kernel(const T* __restrict__ x,
             const int g = l.tx + gi * 256;
             if (g >= l.cch) continue;
             float k[V];
-            ld_vec<T>(xb + g * V, k);
+            load_vec<T>(xb + g * V, k);
             for (int p = p0 + l.ty; p < p1; p += l.TY) {
                 float v[V];
-                ld_vec<T>(xb + (long)p * C + g * V, v);
+                load_vec<T>(xb + (long)p * C + g * V, v);
 #pragma unroll
                 for (int e = 0; e < V; ++e) { const float d = v[e] - k[e]; a1[gi][e] += d; a2[gi][e] += d * d; }
             }
@@ -137,7 +105,7 @@ __global__ void __launch_bounds__(256) rln_apply_kernel(const T* __restrict__ y,
                                                         const float* __restrict__ gamma, const float* __restrict__ beta, const float* __restrict__ z,
                                                         const float* __restrict__ stddev, int train, int B, int HW, int C, int Cr, float eps, int relu,
                                                         float* __restrict__ rlnp, T* __restrict__ out) {
-    constexpr int V = Vec<T>::V;
+    constexpr int V = VecOf<T>::V;
     __shared__ float sm[RLN_MAXC], sr[RLN_MAXC];
     const int b = blockIdx.y, ch = blockIdx.x, nch = gridDim.x;
     const T* yb = y + (long)b * HW * C;
@@ -180,9 +148,9 @@ __global__ void __launch_bounds__(256) rln_apply_kernel(const T* __restrict__ y,
         const int c0 = (int)(i % cch) * V;
         const long off = base + i * V;
         float v[V];
-        ld_vec<T>(y + off, v);
+        load_vec<T>(y + off, v);
         float rv[V];
-        if (res) ld_vec<T>(res + off, rv);
+        if (res) load_vec<T>(res + off, rv);
 #pragma unroll
         for (int e = 0; e < V; ++e) {
             const int c = c0 + e;
@@ -194,7 +162,7 @@ __global__ void __launch_bounds__(256) rln_apply_kernel(const T* __restrict__ y,
             }
             v[e] = o;
         }
-        st_vec<T>(out + off, v);
+        store_vec<T>(out + off, v);
     }
 }
 
@@ -204,7 +172,7 @@ template <typename T>
 __global__ void __launch_bounds__(256) rln_bwd_kernel(const T* __restrict__ d0, const T* __restrict__ d1, const T* __restrict__ d2, const T* __restrict__ out,
                                                       const T* __restrict__ y, const float* __restrict__ rlnp, const float* __restrict__ gamma, int relu,
                                                       int HW, int C, int Cr, float* __restrict__ part, T* __restrict__ gm_out, T* __restrict__ dx) {
-    constexpr int V = Vec<T>::V;
+    constexpr int V = VecOf<T>::V;
     __shared__ float sh[2 * RLN_MAXC];
     const int b = blockIdx.y, ch = blockIdx.x, nch = gridDim.x;
     const Layout l(C, V);
@@ -232,31 +200,31 @@ __global__ void __launch_bounds__(256) rln_bwd_kernel(const T* __restrict__ d0, 
             for (int p = p0 + l.ty; p < p1; p += l.TY) {
                 const long off = sb + (long)p * C + g * V;
                 float gv[V], t[V];
-                ld_vec<T>(d0 + off, gv);
+                load_vec<T>(d0 + off, gv);
                 if (d1) {
-                    ld_vec<T>(d1 + off, t);
+                    load_vec<T>(d1 + off, t);
 #pragma unroll
                     for (int e = 0; e < V; ++e) gv[e] += t[e];
                 }
                 if (d2) {
-                    ld_vec<T>(d2 + off, t);
+                    load_vec<T>(d2 + off, t);
 #pragma unroll
                     for (int e = 0; e < V; ++e) gv[e] += t[e];
                 }
                 if (relu) {
-                    ld_vec<T>(out + off, t);
+                    load_vec<T>(out + off, t);
 #pragma unroll
                     for (int e = 0; e < V; ++e) gv[e] = t[e] > 0.f ? gv[e] : 0.f;
                 }
-                if (gm_out) st_vec<T>(gm_out + off, gv);
-                ld_vec<T>(y + off, t);
+                if (gm_out) store_vec<T>(gm_out + off, gv);
+                load_vec<T>(y + off, t);
 #pragma unroll
                 for (int e = 0; e < V; ++e) {
                     a1[gi][e] += gv[e];
                     a2[gi][e] += gv[e] * ((t[e] - m[e]) * r[e]);
                     t[e] = gv[e] * k[e];
                 }
-                st_vec<T>(dx + off, t);
+                store_vec<T>(dx + off, t);
             }
         }
     fold_rows<V>(l, C, a1, a2, sh, part + ((long)b * RLN_CHUNKS + ch) * C * 2);
@@ -301,7 +269,7 @@ __device__ __forceinline__ float up_scale(int in) { return (float)(in - 1) / (fl
 
 template <typename T>
 __global__ void __launch_bounds__(256) bilinear2_fwd_kernel(const T* __restrict__ x, T* __restrict__ out, int B, int H, int W, int C) {
-    constexpr int V = Vec<T>::V;
+    constexpr int V = VecOf<T>::V;
     const int cch = C / V, OH = 2 * H, OW = 2 * W;
     const float sh = up_scale(H), sw = up_scale(W);
     const long total = (long)B * OH * OW * cch;
@@ -312,14 +280,14 @@ __global__ void __launch_bounds__(256) bilinear2_fwd_kernel(const T* __restrict_
         const Tap ty = tap(oy, H, sh), tx = tap(ox, W, sw);
         const T* xb = x + (long)b * H * W * C + g * V;
         float v00[V], v01[V], v10[V], v11[V], o[V];
-        ld_vec<T>(xb + ((long)ty.i0 * W + tx.i0) * C, v00);
-        ld_vec<T>(xb + ((long)ty.i0 * W + tx.i1) * C, v01);
-        ld_vec<T>(xb + ((long)ty.i1 * W + tx.i0) * C, v10);
-        ld_vec<T>(xb + ((long)ty.i1 * W + tx.i1) * C, v11);
+        load_vec<T>(xb + ((long)ty.i0 * W + tx.i0) * C, v00);
+        load_vec<T>(xb + ((long)ty.i0 * W + tx.i1) * C, v01);
+        load_vec<T>(xb + ((long)ty.i1 * W + tx.i0) * C, v10);
+        load_vec<T>(xb + ((long)ty.i1 * W + tx.i1) * C, v11);
 #pragma unroll
         for (int e = 0; e < V; ++e)
             o[e] = ty.l0 * (tx.l0 * v00[e] + tx.l1 * v01[e]) + ty.l1 * (tx.l0 * v10[e] + tx.l1 * v11[e]);
-        st_vec<T>(out + i * V, o);
+        store_vec<T>(out + i * V, o);
     }
 }
 
@@ -339,7 +307,7 @@ __device__ __forceinline__ int gather_taps(int i, int in, float scale, int* pos,
 
 template <typename T>
 __global__ void __launch_bounds__(256) bilinear2_bwd_kernel(const T* __restrict__ dout, T* __restrict__ dx, int B, int H, int W, int C) {
-    constexpr int V = Vec<T>::V;
+    constexpr int V = VecOf<T>::V;
     const int cch = C / V, OW = 2 * W;
     const float sh = up_scale(H), sw = up_scale(W);
     const long total = (long)B * H * W * cch;
@@ -357,12 +325,12 @@ __global__ void __launch_bounds__(256) bilinear2_bwd_kernel(const T* __restrict_
         for (int a = 0; a < ny; ++a)
             for (int c = 0; c < nx; ++c) {
                 float v[V];
-                ld_vec<T>(db + ((long)py[a] * OW + px[c]) * C, v);
+                load_vec<T>(db + ((long)py[a] * OW + px[c]) * C, v);
                 const float w = wy[a] * wx[c];
 #pragma unroll
                 for (int e = 0; e < V; ++e) acc[e] += w * v[e];
             }
-        st_vec<T>(dx + i * V, acc);
+        store_vec<T>(dx + i * V, acc);
     }
 }
 
@@ -402,9 +370,6 @@ __global__ void __launch_bounds__(256) softplus_head_bwd_kernel(const T* __restr
     }
 }
 
-#define GOOGLE_DISPATCH(dtype, F32, BF) do { if ((dtype) == SDE_F32) { F32; } else { BF; } } while (0)
-#define GOOGLE_DTYPE_OK(dtype) ((dtype) == SDE_F32 || (dtype) == SDE_BF16)
-
 }  // namespace
 
 extern "C" {
@@ -413,38 +378,39 @@ int sde_randln_chunks(int HW) { return rln_chunks(HW); }
 
 int sde_randln_fwd(const void* y, const void* res, const float* gamma, const float* beta, const float* z, const float* stddev, int train, int B, int HW,
                    int C, int Cr, float eps, int relu, int dtype, float* part, float* rlnp, void* out, sde_stream_t stream) {
-    const int V = dtype == SDE_F32 ? 4 : 8;
-    SDE_CHECK_ARG(y && gamma && beta && part && rlnp && out && GOOGLE_DTYPE_OK(dtype) && B > 0 && HW >= 2 && C > 0 && C % V == 0 && C <= RLN_MAXC &&
+    const int V = sde_vec_elems(dtype);
+    SDE_CHECK_ARG(y && gamma && beta && part && rlnp && out && Types::has(dtype) && B > 0 && HW >= 2 && C > 0 && C % V == 0 && C <= RLN_MAXC &&
                       Cr > 0 && Cr <= C && (!train || (z && stddev)),
                   "sde_randln_fwd: bad argument (B=%d HW=%d C=%d Cr=%d dtype=%d train=%d)", B, HW, C, Cr, dtype, train);
     const int nch = rln_chunks(HW);
     hipStream_t s = (hipStream_t)stream;
-    GOOGLE_DISPATCH(dtype,
-                    hipLaunchKernelGGL(rln_stats_kernel<float>, dim3(nch, B), dim3(256), 0, s, (const float*)y, HW, C, part),
-                    hipLaunchKernelGGL(rln_stats_kernel<bf16_t>, dim3(nch, B), dim3(256), 0, s, (const bf16_t*)y, HW, C, part));
+    Types::dispatch(dtype, [&](auto tag) {
+        typedef typename decltype(tag)::type T;
+        hipLaunchKernelGGL(rln_stats_kernel<T>, dim3(nch, B), dim3(256), 0, s, (const T*)y, HW, C, part);
+    });
     SDE_CHECK_LAUNCH("sde_randln_fwd(stats)");
-    GOOGLE_DISPATCH(dtype,
-                    hipLaunchKernelGGL(rln_apply_kernel<float>, dim3(nch, B), dim3(256), 0, s, (const float*)y, (const float*)res, part, gamma, beta, z, stddev,
-                                       train, B, HW, C, Cr, eps, relu, rlnp, (float*)out),
-                    hipLaunchKernelGGL(rln_apply_kernel<bf16_t>, dim3(nch, B), dim3(256), 0, s, (const bf16_t*)y, (const bf16_t*)res, part, gamma, beta, z,
-                                       stddev, train, B, HW, C, Cr, eps, relu, rlnp, (bf16_t*)out));
+    Types::dispatch(dtype, [&](auto tag) {
+        typedef typename decltype(tag)::type T;
+        hipLaunchKernelGGL(rln_apply_kernel<T>, dim3(nch, B), dim3(256), 0, s, (const T*)y, (const T*)res, part, gamma, beta, z, stddev, train, B, HW, C, Cr, eps, relu, rlnp,
+                           (T*)out);
+    });
     SDE_CHECK_LAUNCH("sde_randln_fwd(apply)");
     return SDE_OK;
 }
 
 int sde_randln_bwd(const void* d0, const void* d1, const void* d2, const void* out, const void* y, const float* rlnp, const float* gamma, int relu, int B,
                    int HW, int C, int Cr, int dtype, float* part, float* dgamma, float* dbeta, int accumulate, void* gm, void* dx, sde_stream_t stream) {
-    const int V = dtype == SDE_F32 ? 4 : 8;
-    SDE_CHECK_ARG(d0 && y && rlnp && gamma && part && dgamma && dbeta && dx && (!relu || out) && GOOGLE_DTYPE_OK(dtype) && B > 0 && HW >= 2 && C > 0 &&
+    const int V = sde_vec_elems(dtype);
+    SDE_CHECK_ARG(d0 && y && rlnp && gamma && part && dgamma && dbeta && dx && (!relu || out) && Types::has(dtype) && B > 0 && HW >= 2 && C > 0 &&
                       C % V == 0 && C <= RLN_MAXC && Cr > 0 && Cr <= C,
                   "sde_randln_bwd: bad argument (B=%d HW=%d C=%d Cr=%d dtype=%d)", B, HW, C, Cr, dtype);
     const int nch = rln_chunks(HW);
     hipStream_t s = (hipStream_t)stream;
-    GOOGLE_DISPATCH(dtype,
-                    hipLaunchKernelGGL(rln_bwd_kernel<float>, dim3(nch, B), dim3(256), 0, s, (const float*)d0, (const float*)d1, (const float*)d2,
-                                       (const float*)out, (const float*)y, rlnp, gamma, relu, HW, C, Cr, part, (float*)gm, (float*)dx),
-                    hipLaunchKernelGGL(rln_bwd_kernel<bf16_t>, dim3(nch, B), dim3(256), 0, s, (const bf16_t*)d0, (const bf16_t*)d1, (const bf16_t*)d2,
-                                       (const bf16_t*)out, (const bf16_t*)y, rlnp, gamma, relu, HW, C, Cr, part, (bf16_t*)gm, (bf16_t*)dx));
+    Types::dispatch(dtype, [&](auto tag) {
+        typedef typename decltype(tag)::type T;
+        hipLaunchKernelGGL(rln_bwd_kernel<T>, dim3(nch, B), dim3(256), 0, s, (const T*)d0, (const T*)d1, (const T*)d2, (const T*)out, (const T*)y, rlnp, gamma, relu, HW, C, Cr,
+                           part, (T*)gm, (T*)dx);
+    });
     SDE_CHECK_LAUNCH("sde_randln_bwd");
     hipLaunchKernelGGL(rln_bwd_final_kernel, dim3((Cr + 255) / 256), dim3(256), 0, s, part, B, nch, C, Cr, dgamma, dbeta, accumulate);
     SDE_CHECK_LAUNCH("sde_randln_bwd(final)");
@@ -452,43 +418,51 @@ int sde_randln_bwd(const void* d0, const void* d1, const void* d2, const void* o
 }
 
 int sde_bilinear2_fwd(const void* x, int B, int H, int W, int C, int dtype, void* out, sde_stream_t stream) {
-    const int V = dtype == SDE_F32 ? 4 : 8;
-    SDE_CHECK_ARG(x && out && GOOGLE_DTYPE_OK(dtype) && B > 0 && H > 0 && W > 0 && C > 0 && C % V == 0, "sde_bilinear2_fwd: bad argument");
-    const int nb = grid_for((long)B * 4 * H * W * (C / V));
+    const int V = sde_vec_elems(dtype);
+    SDE_CHECK_ARG(x && out && Types::has(dtype) && B > 0 && H > 0 && W > 0 && C > 0 && C % V == 0, "sde_bilinear2_fwd: bad argument (dtype %d)", dtype);
+    const int nb = sde_grid_for((long)B * 4 * H * W * (C / V), GRID_CAP);
     hipStream_t s = (hipStream_t)stream;
-    GOOGLE_DISPATCH(dtype, hipLaunchKernelGGL(bilinear2_fwd_kernel<float>, dim3(nb), dim3(256), 0, s, (const float*)x, (float*)out, B, H, W, C),
-                    hipLaunchKernelGGL(bilinear2_fwd_kernel<bf16_t>, dim3(nb), dim3(256), 0, s, (const bf16_t*)x, (bf16_t*)out, B, H, W, C));
+    Types::dispatch(dtype, [&](auto tag) {
+        typedef typename decltype(tag)::type T;
+        hipLaunchKernelGGL(bilinear2_fwd_kernel<T>, dim3(nb), dim3(256), 0, s, (const T*)x, (T*)out, B, H, W, C);
+    });
     SDE_CHECK_LAUNCH("sde_bilinear2_fwd");
     return SDE_OK;
 }
 
 int sde_bilinear2_bwd(const void* dout, int B, int H, int W, int C, int dtype, void* dx, sde_stream_t stream) {
-    const int V = dtype == SDE_F32 ? 4 : 8;
-    SDE_CHECK_ARG(dout && dx && GOOGLE_DTYPE_OK(dtype) && B > 0 && H > 0 && W > 0 && C > 0 && C % V == 0, "sde_bilinear2_bwd: bad argument");
-    const int nb = grid_for((long)B * H * W * (C / V));
+    const int V = sde_vec_elems(dtype);
+    SDE_CHECK_ARG(dout && dx && Types::has(dtype) && B > 0 && H > 0 && W > 0 && C > 0 && C % V == 0, "sde_bilinear2_bwd: bad argument (dtype %d)", dtype);
+    const int nb = sde_grid_for((long)B * H * W * (C / V), GRID_CAP);
     hipStream_t s = (hipStream_t)stream;
-    GOOGLE_DISPATCH(dtype, hipLaunchKernelGGL(bilinear2_bwd_kernel<float>, dim3(nb), dim3(256), 0, s, (const float*)dout, (float*)dx, B, H, W, C),
-                    hipLaunchKernelGGL(bilinear2_bwd_kernel<bf16_t>, dim3(nb), dim3(256), 0, s, (const bf16_t*)dout, (bf16_t*)dx, B, H, W, C));
+    Types::dispatch(dtype, [&](auto tag) {
+        typedef typename decltype(tag)::type T;
+        hipLaunchKernelGGL(bilinear2_bwd_kernel<T>, dim3(nb), dim3(256), 0, s, (const T*)dout, (T*)dx, B, H, W, C);
+    });
     SDE_CHECK_LAUNCH("sde_bilinear2_bwd");
     return SDE_OK;
 }
 
 int sde_softplus_head_fwd(const void* y, int B, int H, int W, int ld, int flip, int dtype, float* out, sde_stream_t stream) {
-    SDE_CHECK_ARG(y && out && GOOGLE_DTYPE_OK(dtype) && B > 0 && H > 0 && W > 0 && ld >= 1, "sde_softplus_head_fwd: bad argument");
-    const int nb = grid_for((long)B * H * W);
+    SDE_CHECK_ARG(y && out && Types::has(dtype) && B > 0 && H > 0 && W > 0 && ld >= 1, "sde_softplus_head_fwd: bad argument (dtype %d)", dtype);
+    const int nb = sde_grid_for((long)B * H * W, GRID_CAP);
     hipStream_t s = (hipStream_t)stream;
-    GOOGLE_DISPATCH(dtype, hipLaunchKernelGGL(softplus_head_fwd_kernel<float>, dim3(nb), dim3(256), 0, s, (const float*)y, B, H, W, ld, flip, out),
-                    hipLaunchKernelGGL(softplus_head_fwd_kernel<bf16_t>, dim3(nb), dim3(256), 0, s, (const bf16_t*)y, B, H, W, ld, flip, out));
+    Types::dispatch(dtype, [&](auto tag) {
+        typedef typename decltype(tag)::type T;
+        hipLaunchKernelGGL(softplus_head_fwd_kernel<T>, dim3(nb), dim3(256), 0, s, (const T*)y, B, H, W, ld, flip, out);
+    });
     SDE_CHECK_LAUNCH("sde_softplus_head_fwd");
     return SDE_OK;
 }
 
 int sde_softplus_head_bwd(const void* y, const float* dout, int B, int H, int W, int ld, int flip, int dtype, void* dy, sde_stream_t stream) {
-    SDE_CHECK_ARG(y && dout && dy && GOOGLE_DTYPE_OK(dtype) && B > 0 && H > 0 && W > 0 && ld >= 1, "sde_softplus_head_bwd: bad argument");
-    const int nb = grid_for((long)B * H * W);
+    SDE_CHECK_ARG(y && dout && dy && Types::has(dtype) && B > 0 && H > 0 && W > 0 && ld >= 1, "sde_softplus_head_bwd: bad argument (dtype %d)", dtype);
+    const int nb = sde_grid_for((long)B * H * W, GRID_CAP);
     hipStream_t s = (hipStream_t)stream;
-    GOOGLE_DISPATCH(dtype, hipLaunchKernelGGL(softplus_head_bwd_kernel<float>, dim3(nb), dim3(256), 0, s, (const float*)y, dout, B, H, W, ld, flip, (float*)dy),
-                    hipLaunchKernelGGL(softplus_head_bwd_kernel<bf16_t>, dim3(nb), dim3(256), 0, s, (const bf16_t*)y, dout, B, H, W, ld, flip, (bf16_t*)dy));
+    Types::dispatch(dtype, [&](auto tag) {
+        typedef typename decltype(tag)::type T;
+        hipLaunchKernelGGL(softplus_head_bwd_kernel<T>, dim3(nb), dim3(256), 0, s, (const T*)y, dout, B, H, W, ld, flip, (T*)dy);
+    });
     SDE_CHECK_LAUNCH("sde_softplus_head_bwd");
     return SDE_OK;
 }

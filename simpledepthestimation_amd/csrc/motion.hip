@@ -15,45 +15,13 @@
 //   prep_bwd     the gradient of sde_prep_input without mean / std / flip: NHWC compute dtype -> planar fp32 NCHW, two gradients summed.
 //
 // No atomics anywhere: every sum has one owner and a fixed order, so repeated runs give identical bits.
-#include "common.h"
-#include "sde_hip.h"
+#include "vec16.h"
+#include "launch.h"
 
 namespace {
 
-template <typename T> struct Vec;
-template <> struct Vec<float> { static constexpr int V = 4; };
-template <> struct Vec<bf16_t> { static constexpr int V = 8; };
-
-template <typename T> __device__ __forceinline__ void ld_vec(const T* p, float* v);
-template <> __device__ __forceinline__ void ld_vec<float>(const float* p, float* v) {
-    const float4 t = *reinterpret_cast<const float4*>(p);
-    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-}
-template <> __device__ __forceinline__ void ld_vec<bf16_t>(const bf16_t* p, float* v) {
-    const uint4 t = *reinterpret_cast<const uint4*>(p);
-    const uint32_t w[4] = {t.x, t.y, t.z, t.w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        v[2 * i] = __uint_as_float(w[i] << 16);
-        v[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
-    }
-}
-template <typename T> __device__ __forceinline__ void st_vec(T* p, const float* v);
-template <> __device__ __forceinline__ void st_vec<float>(float* p, const float* v) {
-    *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-}
-template <> __device__ __forceinline__ void st_vec<bf16_t>(bf16_t* p, const float* v) {
-    bf16_t o[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) o[i] = (bf16_t)v[i];
-    *reinterpret_cast<uint4*>(p) = *reinterpret_cast<uint4*>(o);
-}
-
-int grid_for(long n) {
-    long nb = (n + 255) / 256;
-    if (nb > 16384) nb = 16384;
-    return (int)(nb < 1 ? 1 : nb);
-}
+typedef SdeTypes<float, bf16_t> Types;
+constexpr int GRID_CAP = SDE_GRID_CAP_16K;
 
 // ---------------------------------------------------------------------------------------------------------------------
 // resize (align_corners=True, any ratio) + cat
@@ -79,7 +47,7 @@ __device__ __forceinline__ Tap tap(int o, int in, float scale) {
 template <typename T>
 __global__ void __launch_bounds__(256) resize_cat_fwd_kernel(const float* __restrict__ field, int h, int w, const T* __restrict__ skip, int B, int H, int W,
                                                              int Cs, int Cr, int Cx, T* __restrict__ X, float* __restrict__ up) {
-    constexpr int V = Vec<T>::V;
+    constexpr int V = VecOf<T>::V;
     const int cch = Cx / V;
     const float sh = ac_scale(h, H), sw = ac_scale(w, W);
     const long total = (long)B * H * W * cch;
@@ -106,7 +74,7 @@ __global__ void __launch_bounds__(256) resize_cat_fwd_kernel(const float* __rest
             o[2] = ty.l0 * (tx.l0 * v00.z + tx.l1 * v01.z) + ty.l1 * (tx.l0 * v10.z + tx.l1 * v11.z);
             *reinterpret_cast<float4*>(up + pix * 4) = make_float4(o[0], o[1], o[2], 0.f);
         }
-        st_vec<T>(X + i * V, o);
+        store_vec<T>(X + i * V, o);
     }
 }
 
@@ -122,7 +90,7 @@ template <typename T>
 __global__ void __launch_bounds__(256) resize_cat_bwd_kernel(const T* __restrict__ d0, const T* __restrict__ d1, const float* __restrict__ dup, int B, int H,
                                                              int W, int Cx, int Cr, int Cs, int h, int w, float* __restrict__ dfield,
                                                              T* __restrict__ dskip) {
-    constexpr int V = Vec<T>::V;
+    constexpr int V = VecOf<T>::V;
     // 1. the skip's gradient: channels 3 .. 3 + Cr of the summed gradient, dense with zero pad channels
     if (dskip) {
         const int cch = Cs / V;
@@ -139,18 +107,18 @@ __global__ void __launch_bounds__(256) resize_cat_bwd_kernel(const T* __restrict
                 const T* d = k ? d1 : d0;
                 if (!d || !first) continue;
                 float v[V];
-                ld_vec<T>(d + pix * Cx + g * V, v);
+                load_vec<T>(d + pix * Cx + g * V, v);
 #pragma unroll
                 for (int e = 0; e < V; ++e) two[e] += v[e];
                 if (second) {
-                    ld_vec<T>(d + pix * Cx + (g + 1) * V, v);
+                    load_vec<T>(d + pix * Cx + (g + 1) * V, v);
 #pragma unroll
                     for (int e = 0; e < V; ++e) two[V + e] += v[e];
                 }
             }
 #pragma unroll
             for (int e = 0; e < V; ++e) o[e] = (g * V + e < Cr) ? two[3 + e] : 0.f;
-            st_vec<T>(dskip + i * V, o);
+            store_vec<T>(dskip + i * V, o);
         }
     }
     // 2. the field's gradient: gather form
@@ -195,7 +163,7 @@ int tail_tpp(int groups2) {
 template <typename T>
 __global__ void __launch_bounds__(256) tail_fwd_kernel(const T* __restrict__ o1, const T* __restrict__ o2, const float* __restrict__ w3,
                                                        const float* __restrict__ up, long P, int ld, int mid, int tpp, float* __restrict__ out) {
-    constexpr int V = Vec<T>::V;
+    constexpr int V = VecOf<T>::V;
     const int groups = ld / V, groups2 = 2 * groups;
     const int ppb = 256 / tpp;                     // pixels per workgroup and sweep
     const int sub = threadIdx.x % tpp, slot = threadIdx.x / tpp;
@@ -206,7 +174,7 @@ __global__ void __launch_bounds__(256) tail_fwd_kernel(const T* __restrict__ o1,
             for (int g2 = sub; g2 < groups2; g2 += tpp) {
                 const int half = g2 >= groups, g = half ? g2 - groups : g2;
                 float v[V];
-                ld_vec<T>((half ? o2 : o1) + pix * ld + g * V, v);
+                load_vec<T>((half ? o2 : o1) + pix * ld + g * V, v);
                 const int c0 = g * V;
 #pragma unroll
                 for (int e = 0; e < V; ++e) {
@@ -246,7 +214,7 @@ template <typename T>
 __global__ void __launch_bounds__(256) tail_bwd_kernel(const float* __restrict__ dout, const T* __restrict__ o1, const T* __restrict__ o2,
                                                        const float* __restrict__ w3, long P, int ld, int mid, int CH, T* __restrict__ do1,
                                                        T* __restrict__ do2, float* __restrict__ part) {
-    constexpr int V = Vec<T>::V;
+    constexpr int V = VecOf<T>::V;
     __shared__ float red[256 * 3 * V];
     const int groups = ld / V, groups2 = 2 * groups;
     const int slots = 256 / CH;
@@ -274,7 +242,7 @@ __global__ void __launch_bounds__(256) tail_bwd_kernel(const float* __restrict__
             for (long pix = (long)blockIdx.x * slots + slot; pix < P; pix += (long)gridDim.x * slots) {
                 const float4 d = *reinterpret_cast<const float4*>(dout + pix * 4);
                 float v[V], o[V];
-                ld_vec<T>(src + pix * ld + c0, v);
+                load_vec<T>(src + pix * ld + c0, v);
 #pragma unroll
                 for (int e = 0; e < V; ++e) {
                     o[e] = d.x * wv[0][e] + d.y * wv[1][e] + d.z * wv[2][e];
@@ -282,7 +250,7 @@ __global__ void __launch_bounds__(256) tail_bwd_kernel(const float* __restrict__
                     acc[1][e] += d.y * v[e];
                     acc[2][e] += d.z * v[e];
                 }
-                st_vec<T>(dst + pix * ld + c0, o);
+                store_vec<T>(dst + pix * ld + c0, o);
             }
         }
         __syncthreads();
@@ -424,85 +392,79 @@ __global__ void __launch_bounds__(256) prep_bwd_kernel(const T* __restrict__ d0,
     }
 }
 
-#define MOTION_DISPATCH(dtype, F32, BF) do { if ((dtype) == SDE_F32) { F32; } else { BF; } } while (0)
-#define MOTION_DTYPE_OK(dtype) ((dtype) == SDE_F32 || (dtype) == SDE_BF16)
-
 }  // namespace
 
 extern "C" {
 
 int sde_motion_resize_cat_fwd(const float* field, int h, int w, const void* skip, int B, int H, int W, int Cs, int Cr, int Cx, int dtype, void* X,
                               float* up, sde_stream_t stream) {
-    const int V = dtype == SDE_F32 ? 4 : 8;
-    SDE_CHECK_ARG(field && skip && X && up && MOTION_DTYPE_OK(dtype) && B > 0 && h > 0 && w > 0 && H > 0 && W > 0 && Cr > 0 && Cr <= Cs && Cs % V == 0 &&
+    const int V = sde_vec_elems(dtype);
+    SDE_CHECK_ARG(field && skip && X && up && Types::has(dtype) && B > 0 && h > 0 && w > 0 && H > 0 && W > 0 && Cr > 0 && Cr <= Cs && Cs % V == 0 &&
                       Cx % V == 0 && Cx >= Cr + 3,
                   "sde_motion_resize_cat_fwd: bad argument (B=%d %dx%d -> %dx%d Cs=%d Cr=%d Cx=%d dtype=%d)", B, h, w, H, W, Cs, Cr, Cx, dtype);
-    const int nb = grid_for((long)B * H * W * (Cx / V));
+    const int nb = sde_grid_for((long)B * H * W * (Cx / V), GRID_CAP);
     hipStream_t s = (hipStream_t)stream;
-    MOTION_DISPATCH(dtype,
-                    hipLaunchKernelGGL(resize_cat_fwd_kernel<float>, dim3(nb), dim3(256), 0, s, field, h, w, (const float*)skip, B, H, W, Cs, Cr, Cx,
-                                       (float*)X, up),
-                    hipLaunchKernelGGL(resize_cat_fwd_kernel<bf16_t>, dim3(nb), dim3(256), 0, s, field, h, w, (const bf16_t*)skip, B, H, W, Cs, Cr, Cx,
-                                       (bf16_t*)X, up));
+    Types::dispatch(dtype, [&](auto tag) {
+        typedef typename decltype(tag)::type T;
+        hipLaunchKernelGGL(resize_cat_fwd_kernel<T>, dim3(nb), dim3(256), 0, s, field, h, w, (const T*)skip, B, H, W, Cs, Cr, Cx, (T*)X, up);
+    });
     SDE_CHECK_LAUNCH("sde_motion_resize_cat_fwd");
     return SDE_OK;
 }
 
 int sde_motion_resize_cat_bwd(const void* dX0, const void* dX1, const float* dup, int B, int H, int W, int Cx, int Cr, int Cs, int h, int w, int dtype,
                               float* dfield, void* dskip, sde_stream_t stream) {
-    const int V = dtype == SDE_F32 ? 4 : 8;
-    SDE_CHECK_ARG(dfield && MOTION_DTYPE_OK(dtype) && B > 0 && h > 0 && w > 0 && H > 0 && W > 0 && Cr > 0 && Cr <= Cs && Cs % V == 0 && Cx % V == 0 &&
+    const int V = sde_vec_elems(dtype);
+    SDE_CHECK_ARG(dfield && Types::has(dtype) && B > 0 && h > 0 && w > 0 && H > 0 && W > 0 && Cr > 0 && Cr <= Cs && Cs % V == 0 && Cx % V == 0 &&
                       Cx >= Cr + 3,
                   "sde_motion_resize_cat_bwd: bad argument (B=%d %dx%d -> %dx%d Cs=%d Cr=%d Cx=%d dtype=%d)", B, h, w, H, W, Cs, Cr, Cx, dtype);
     const long work = dskip ? (long)B * H * W * (Cs / V) : (long)B * h * w;
-    const int nb = grid_for(work);
+    const int nb = sde_grid_for(work, GRID_CAP);
     hipStream_t s = (hipStream_t)stream;
-    MOTION_DISPATCH(dtype,
-                    hipLaunchKernelGGL(resize_cat_bwd_kernel<float>, dim3(nb), dim3(256), 0, s, (const float*)dX0, (const float*)dX1, dup, B, H, W, Cx, Cr, Cs,
-                                       h, w, dfield, (float*)dskip),
-                    hipLaunchKernelGGL(resize_cat_bwd_kernel<bf16_t>, dim3(nb), dim3(256), 0, s, (const bf16_t*)dX0, (const bf16_t*)dX1, dup, B, H, W, Cx, Cr,
-                                       Cs, h, w, dfield, (bf16_t*)dskip));
+    Types::dispatch(dtype, [&](auto tag) {
+        typedef typename decltype(tag)::type T;
+        hipLaunchKernelGGL(resize_cat_bwd_kernel<T>, dim3(nb), dim3(256), 0, s, (const T*)dX0, (const T*)dX1, dup, B, H, W, Cx, Cr, Cs, h, w, dfield, (T*)dskip);
+    });
     SDE_CHECK_LAUNCH("sde_motion_resize_cat_bwd");
     return SDE_OK;
 }
 
 int sde_motion_tail_fwd(const void* o1, const void* o2, const float* w3, const float* up, long P, int ld, int mid, int dtype, float* out,
                         sde_stream_t stream) {
-    const int V = dtype == SDE_F32 ? 4 : 8;
-    SDE_CHECK_ARG(o1 && o2 && w3 && up && out && MOTION_DTYPE_OK(dtype) && P > 0 && mid > 0 && mid <= ld && ld % V == 0,
+    const int V = sde_vec_elems(dtype);
+    SDE_CHECK_ARG(o1 && o2 && w3 && up && out && Types::has(dtype) && P > 0 && mid > 0 && mid <= ld && ld % V == 0,
                   "sde_motion_tail_fwd: bad argument (P=%ld ld=%d mid=%d dtype=%d)", P, ld, mid, dtype);
     const int tpp = tail_tpp(2 * (ld / V));
     const int ppb = 256 / tpp;
     long nb = (P + ppb - 1) / ppb;
-    if (nb > 16384) nb = 16384;
+    if (nb > GRID_CAP) nb = GRID_CAP;
     hipStream_t s = (hipStream_t)stream;
-    MOTION_DISPATCH(dtype,
-                    hipLaunchKernelGGL(tail_fwd_kernel<float>, dim3((int)nb), dim3(256), 0, s, (const float*)o1, (const float*)o2, w3, up, P, ld, mid, tpp, out),
-                    hipLaunchKernelGGL(tail_fwd_kernel<bf16_t>, dim3((int)nb), dim3(256), 0, s, (const bf16_t*)o1, (const bf16_t*)o2, w3, up, P, ld, mid, tpp,
-                                       out));
+    Types::dispatch(dtype, [&](auto tag) {
+        typedef typename decltype(tag)::type T;
+        hipLaunchKernelGGL(tail_fwd_kernel<T>, dim3((int)nb), dim3(256), 0, s, (const T*)o1, (const T*)o2, w3, up, P, ld, mid, tpp, out);
+    });
     SDE_CHECK_LAUNCH("sde_motion_tail_fwd");
     return SDE_OK;
 }
 
 int sde_motion_tail_blocks(long P, int ld, int dtype) {
-    const int V = dtype == SDE_F32 ? 4 : 8;
+    const int V = sde_vec_elems(dtype);
     if (P <= 0 || ld <= 0 || ld % V) return 0;
     return tail_bwd_blocks(P, 2 * (ld / V));
 }
 
 int sde_motion_tail_bwd(const float* dout, const void* o1, const void* o2, const float* w3, long P, int ld, int mid, int dtype, void* do1, void* do2,
                         float* part, float* dw3, sde_stream_t stream) {
-    const int V = dtype == SDE_F32 ? 4 : 8;
-    SDE_CHECK_ARG(dout && o1 && o2 && w3 && do1 && do2 && part && dw3 && MOTION_DTYPE_OK(dtype) && P > 0 && mid > 0 && mid <= ld && ld % V == 0,
+    const int V = sde_vec_elems(dtype);
+    SDE_CHECK_ARG(dout && o1 && o2 && w3 && do1 && do2 && part && dw3 && Types::has(dtype) && P > 0 && mid > 0 && mid <= ld && ld % V == 0,
                   "sde_motion_tail_bwd: bad argument (P=%ld ld=%d mid=%d dtype=%d)", P, ld, mid, dtype);
     const int groups2 = 2 * (ld / V);
     const int CH = tail_bwd_ch(groups2), nb = tail_bwd_blocks(P, groups2);
     hipStream_t s = (hipStream_t)stream;
-    MOTION_DISPATCH(dtype,
-                    hipLaunchKernelGGL(tail_bwd_kernel<float>, dim3(nb), dim3(256), 0, s, dout, (const float*)o1, (const float*)o2, w3, P, ld, mid, CH,
-                                       (float*)do1, (float*)do2, part),
-                    hipLaunchKernelGGL(tail_bwd_kernel<bf16_t>, dim3(nb), dim3(256), 0, s, dout, (const bf16_t*)o1, (const bf16_t*)o2, w3, P, ld, mid, CH,
-                                       (bf16_t*)do1, (bf16_t*)do2, part));
+    Types::dispatch(dtype, [&](auto tag) {
+        typedef typename decltype(tag)::type T;
+        hipLaunchKernelGGL(tail_bwd_kernel<T>, dim3(nb), dim3(256), 0, s, dout, (const T*)o1, (const T*)o2, w3, P, ld, mid, CH, (T*)do1, (T*)do2, part);
+    });
     SDE_CHECK_LAUNCH("sde_motion_tail_bwd");
     const int n = 6 * mid;
     hipLaunchKernelGGL(tail_bwd_final_kernel, dim3((n + 3) / 4), dim3(256), 0, s, part, nb, n, dw3);
@@ -523,7 +485,7 @@ int sde_motion_head_fwd(const float* field, const float* scale, const float* wei
         hipLaunchKernelGGL(head_sum_kernel, dim3(nb), dim3(256), 0, s, field, scale, P, part);
         SDE_CHECK_LAUNCH("sde_motion_head_fwd(sum)");
     }
-    hipLaunchKernelGGL(head_apply_kernel, dim3(grid_for(P)), dim3(256), 0, s, field, scale, weight, mask ? part : nullptr, nb, B, (long)H * W,
+    hipLaunchKernelGGL(head_apply_kernel, dim3(sde_grid_for(P, GRID_CAP)), dim3(256), 0, s, field, scale, weight, mask ? part : nullptr, nb, B, (long)H * W,
                        mask ? keep : nullptr, out);
     SDE_CHECK_LAUNCH("sde_motion_head_fwd(apply)");
     return SDE_OK;
@@ -540,12 +502,13 @@ int sde_motion_head_bwd(const float* dout, const float* field, const float* scal
 }
 
 int sde_prep_input_bwd(const void* d0, const void* d1, int B, int C, int H, int W, int Cp, int dtype, float* dimg, sde_stream_t stream) {
-    SDE_CHECK_ARG(d0 && dimg && MOTION_DTYPE_OK(dtype) && B > 0 && C > 0 && C <= Cp && H > 0 && W > 0, "sde_prep_input_bwd: bad argument");
-    const int nb = grid_for((long)B * C * H * W);
+    SDE_CHECK_ARG(d0 && dimg && Types::has(dtype) && B > 0 && C > 0 && C <= Cp && H > 0 && W > 0, "sde_prep_input_bwd: bad argument (dtype %d)", dtype);
+    const int nb = sde_grid_for((long)B * C * H * W, GRID_CAP);
     hipStream_t s = (hipStream_t)stream;
-    MOTION_DISPATCH(dtype,
-                    hipLaunchKernelGGL(prep_bwd_kernel<float>, dim3(nb), dim3(256), 0, s, (const float*)d0, (const float*)d1, B, C, (long)H * W, Cp, dimg),
-                    hipLaunchKernelGGL(prep_bwd_kernel<bf16_t>, dim3(nb), dim3(256), 0, s, (const bf16_t*)d0, (const bf16_t*)d1, B, C, (long)H * W, Cp, dimg));
+    Types::dispatch(dtype, [&](auto tag) {
+        typedef typename decltype(tag)::type T;
+        hipLaunchKernelGGL(prep_bwd_kernel<T>, dim3(nb), dim3(256), 0, s, (const T*)d0, (const T*)d1, B, C, (long)H * W, Cp, dimg);
+    });
     SDE_CHECK_LAUNCH("sde_prep_input_bwd");
     return SDE_OK;
 }

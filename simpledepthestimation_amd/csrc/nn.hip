@@ -12,54 +12,14 @@
 // the channel-fastest axis (full 1 KiB per wave instruction).  Channel reductions write per-workgroup partial slabs that a
 // small second kernel sums in fixed order (fp64) -- no float atomics, bit-reproducible statistics and gradients.
 #include <stdlib.h>
-#include "common.h"
-#include "sde_hip.h"
+#include "vec16.h"
+#include "launch.h"
 
 namespace {
 
-template <typename T> struct VecOf;
-template <> struct VecOf<float> { static constexpr int V = 4; };
-template <> struct VecOf<bf16_t> { static constexpr int V = 8; };
-template <> struct VecOf<half_t> { static constexpr int V = 8; };
-
-template <typename T> __device__ __forceinline__ void load_vec(const T* p, float* v);
-template <> __device__ __forceinline__ void load_vec<float>(const float* p, float* v) {
-    const float4 t = *reinterpret_cast<const float4*>(p);
-    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-}
-template <> __device__ __forceinline__ void load_vec<bf16_t>(const bf16_t* p, float* v) {
-    const uint4 t = *reinterpret_cast<const uint4*>(p);
-    const uint32_t w[4] = {t.x, t.y, t.z, t.w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        v[2 * i] = __uint_as_float(w[i] << 16);
-        v[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
-    }
-}
-template <> __device__ __forceinline__ void load_vec<half_t>(const half_t* p, float* v) {
-    typedef __attribute__((ext_vector_type(8))) _Float16 h8;
-    const h8 t = *reinterpret_cast<const h8*>(p);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) v[i] = (float)t[i];
-}
-template <typename T> __device__ __forceinline__ void store_vec(T* p, const float* v);
-template <> __device__ __forceinline__ void store_vec<float>(float* p, const float* v) {
-    *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-}
-template <> __device__ __forceinline__ void store_vec<bf16_t>(bf16_t* p, const float* v) {
-    bf16_t o[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) o[i] = (bf16_t)v[i];
-    *reinterpret_cast<uint4*>(p) = *reinterpret_cast<uint4*>(o);
-}
-
-template <> __device__ __forceinline__ void store_vec<half_t>(half_t* p, const float* v) {
-    typedef __attribute__((ext_vector_type(8))) _Float16 h8;
-    h8 o;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) o[i] = (_Float16)v[i];
-    *reinterpret_cast<h8*>(p) = o;
-}
+typedef SdeTypes<bf16_t, half_t, float> Types;
+typedef SdeTypes<bf16_t, half_t> Types16;      // the kernels that exist for 16-bit storage only
+constexpr int GRID_CAP = SDE_GRID_CAP_8K;
 
 // ------------------------------------------------------------------------------------------------------------------
 // Input: NCHW fp32 image -> normalised NHWC T, channels zero-padded to Cpad, optional horizontal flip
@@ -1389,33 +1349,21 @@ const float* pre_reduce(const float* part, int& rows, int width, hipStream_t s) 
     return out;
 }
 
-int grid_for(long n_items) {
-    long nb = (n_items + 255) / 256;
-    if (nb < 1) nb = 1;
-    if (nb > 8192) nb = 8192;
-    return (int)nb;
-}
-
 }  // namespace
-
-#define DISPATCH_T(dtype, CALL_F32, CALL_BF16, CALL_F16) \
-    do {                                        \
-        if ((dtype) == SDE_BF16) { CALL_BF16; }  \
-        else if ((dtype) == SDE_F16) { CALL_F16; } \
-        else { CALL_F32; }                      \
-    } while (0)
 
 extern "C" {
 
 int sde_prep_input(const float* img, const float* mean, const float* std_, int B, int C, int H, int W, int Cpad, int flip, int dtype, void* out,
                    sde_stream_t stream) {
+    SDE_CHECK_ARG(Types::has(dtype), "sde_prep_input: unsupported dtype %d", dtype);
     SDE_CHECK_ARG(img && out && B > 0 && C > 0 && H > 0 && W > 0 && Cpad >= C, "sde_prep_input: bad argument");
     SDE_CHECK_ARG((mean == nullptr) == (std_ == nullptr), "sde_prep_input: mean/std must both be given or both be null");
     hipStream_t s = (hipStream_t)stream;
-    const int nb = grid_for((long)B * H * W);
-    DISPATCH_T(dtype, hipLaunchKernelGGL(prep_input_kernel<float>, dim3(nb), dim3(256), 0, s, img, mean, std_, B, C, H, W, Cpad, flip, (float*)out),
-               hipLaunchKernelGGL(prep_input_kernel<bf16_t>, dim3(nb), dim3(256), 0, s, img, mean, std_, B, C, H, W, Cpad, flip, (bf16_t*)out),
-               hipLaunchKernelGGL(prep_input_kernel<half_t>, dim3(nb), dim3(256), 0, s, img, mean, std_, B, C, H, W, Cpad, flip, (half_t*)out));
+    const int nb = sde_grid_for((long)B * H * W, GRID_CAP);
+    Types::dispatch(dtype, [&](auto tag) {
+        typedef typename decltype(tag)::type T;
+        hipLaunchKernelGGL(prep_input_kernel<T>, dim3(nb), dim3(256), 0, s, img, mean, std_, B, C, H, W, Cpad, flip, (T*)out);
+    });
     SDE_CHECK_LAUNCH("sde_prep_input");
     return SDE_OK;
 }
@@ -1457,12 +1405,11 @@ int sde_bn_finalize_apply(const float* part, int tiles, int C, long count, const
     chunks = (M + rpw - 1) / rpw;
     const dim3 grid((unsigned)strips, (unsigned)chunks);
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == SDE_BF16)
-        hipLaunchKernelGGL(bn_finalize_apply_kernel<bf16_t>, grid, dim3(256), 0, s, part, tiles, C, (float)count, gamma, beta, running_mean, running_var, momentum, eps,
-                           bnp, (const bf16_t*)y, (const bf16_t*)residual, relu, M, rpw, (bf16_t*)out);
-    else
-        hipLaunchKernelGGL(bn_finalize_apply_kernel<half_t>, grid, dim3(256), 0, s, part, tiles, C, (float)count, gamma, beta, running_mean, running_var, momentum, eps,
-                           bnp, (const half_t*)y, (const half_t*)residual, relu, M, rpw, (half_t*)out);
+    Types16::dispatch(dtype, [&](auto tag) {
+        typedef typename decltype(tag)::type T;
+        hipLaunchKernelGGL(bn_finalize_apply_kernel<T>, grid, dim3(256), 0, s, part, tiles, C, (float)count, gamma, beta, running_mean, running_var, momentum, eps, bnp,
+                           (const T*)y, (const T*)residual, relu, M, rpw, (T*)out);
+    });
     SDE_CHECK_LAUNCH("sde_bn_finalize_apply");
     return SDE_OK;
 }
@@ -1476,13 +1423,15 @@ int sde_bn_eval_params(const float* gamma, const float* beta, const float* runni
 }
 
 int sde_bn_apply(const void* y, const float* bnp, const void* residual, int relu, long M, int C, int dtype, void* out, sde_stream_t stream) {
-    const int V = SDE_IS16(dtype) ? 8 : 4;
+    SDE_CHECK_ARG(Types::has(dtype), "sde_bn_apply: unsupported dtype %d", dtype);
+    const int V = sde_vec_elems(dtype);
     SDE_CHECK_ARG(y && bnp && out && M > 0 && C > 0 && C % V == 0, "sde_bn_apply: bad argument (C=%d)", C);
     hipStream_t s = (hipStream_t)stream;
-    const int nb = grid_for(M * (C / V));
-    DISPATCH_T(dtype, hipLaunchKernelGGL(bn_apply_kernel<float>, dim3(nb), dim3(256), 0, s, (const float*)y, bnp, (const float*)residual, relu, M, C, (float*)out),
-               hipLaunchKernelGGL(bn_apply_kernel<bf16_t>, dim3(nb), dim3(256), 0, s, (const bf16_t*)y, bnp, (const bf16_t*)residual, relu, M, C, (bf16_t*)out),
-               hipLaunchKernelGGL(bn_apply_kernel<half_t>, dim3(nb), dim3(256), 0, s, (const half_t*)y, bnp, (const half_t*)residual, relu, M, C, (half_t*)out));
+    const int nb = sde_grid_for(M * (C / V), GRID_CAP);
+    Types::dispatch(dtype, [&](auto tag) {
+        typedef typename decltype(tag)::type T;
+        hipLaunchKernelGGL(bn_apply_kernel<T>, dim3(nb), dim3(256), 0, s, (const T*)y, bnp, (const T*)residual, relu, M, C, (T*)out);
+    });
     SDE_CHECK_LAUNCH("sde_bn_apply");
     return SDE_OK;
 }
@@ -1499,7 +1448,8 @@ int sde_reduce_num_blocks(long M, int C) {
 int sde_bn_bwd(const void* dout, const void* dout1, const void* dout2, const void* out, const void* y, const float* bnp, const float* gamma, int relu,
                long M, int C, int dtype, float* part, float* coef, float* dgamma, float* dbeta, int accumulate_params, void* gm, void* dy,
                sde_stream_t stream) {
-    const int V = SDE_IS16(dtype) ? 8 : 4;
+    SDE_CHECK_ARG(Types::has(dtype), "sde_bn_bwd: unsupported dtype %d", dtype);
+    const int V = sde_vec_elems(dtype);
     SDE_CHECK_ARG(dout && y && bnp && part && coef && dgamma && dbeta && dy && M > 0 && C > 0 && C % V == 0, "sde_bn_bwd: bad argument");
     if (relu && !out) relu = 2;          // BatchNorm + ReLU without a residual: the mask is re-derived from y and the BN parameters
     SDE_CHECK_ARG(gm || (!relu && !dout1 && !dout2), "sde_bn_bwd: a masked or summed gradient needs the gm buffer");
@@ -1514,17 +1464,18 @@ int sde_bn_bwd(const void* dout, const void* dout1, const void* dout2, const voi
     if (wide) {
         // big layers: 1024-thread workgroups, a quarter as many of them -> at most 256 partial rows, and finalize + apply become one launch below
         nblk = (nblk + 3) / 4;
-        if (dtype == SDE_BF16)
-            hipLaunchKernelGGL((bn_bwd_reduce_kernel<bf16_t, 1024>), dim3(nblk), dim3(1024), 1024 * 16 * sizeof(float), s, (const bf16_t*)dout, (const bf16_t*)dout1,
-                               (const bf16_t*)dout2, (const bf16_t*)out, (const bf16_t*)y, bnp, relu, M, C, rpb, part, (bf16_t*)gm);
-        else
-            hipLaunchKernelGGL((bn_bwd_reduce_kernel<half_t, 1024>), dim3(nblk), dim3(1024), 1024 * 16 * sizeof(float), s, (const half_t*)dout, (const half_t*)dout1,
-                               (const half_t*)dout2, (const half_t*)out, (const half_t*)y, bnp, relu, M, C, rpb, part, (half_t*)gm);
-    } else
-    DISPATCH_T(dtype,
-               hipLaunchKernelGGL(bn_bwd_reduce_kernel<float>, dim3(nblk), dim3(256), lds, s, (const float*)dout, (const float*)dout1, (const float*)dout2, (const float*)out, (const float*)y, bnp, relu, M, C, rpb, part, (float*)gm),
-               hipLaunchKernelGGL(bn_bwd_reduce_kernel<bf16_t>, dim3(nblk), dim3(256), lds, s, (const bf16_t*)dout, (const bf16_t*)dout1, (const bf16_t*)dout2, (const bf16_t*)out, (const bf16_t*)y, bnp, relu, M, C, rpb, part, (bf16_t*)gm),
-               hipLaunchKernelGGL(bn_bwd_reduce_kernel<half_t>, dim3(nblk), dim3(256), lds, s, (const half_t*)dout, (const half_t*)dout1, (const half_t*)dout2, (const half_t*)out, (const half_t*)y, bnp, relu, M, C, rpb, part, (half_t*)gm));
+        Types16::dispatch(dtype, [&](auto tag) {
+            typedef typename decltype(tag)::type T;
+            hipLaunchKernelGGL((bn_bwd_reduce_kernel<T, 1024>), dim3(nblk), dim3(1024), 1024 * 16 * sizeof(float), s, (const T*)dout, (const T*)dout1, (const T*)dout2,
+                               (const T*)out, (const T*)y, bnp, relu, M, C, rpb, part, (T*)gm);
+        });
+    } else {
+        Types::dispatch(dtype, [&](auto tag) {
+            typedef typename decltype(tag)::type T;
+            hipLaunchKernelGGL(bn_bwd_reduce_kernel<T>, dim3(nblk), dim3(256), lds, s, (const T*)dout, (const T*)dout1, (const T*)dout2, (const T*)out, (const T*)y, bnp, relu,
+                               M, C, rpb, part, (T*)gm);
+        });
+    }
     SDE_CHECK_LAUNCH("sde_bn_bwd/reduce");
     const void* dz = gm ? gm : dout;
     if (g_bn_fuse && SDE_IS16(dtype) && C % 64 == 0 && nblk <= BNFA_MAX_ROWS) {       // short slab: finalize + apply in one launch
@@ -1534,12 +1485,11 @@ int sde_bn_bwd(const void* dout, const void* dout1, const void* dout2, const voi
         rpw = (rpw + 31) / 32 * 32;
         chunks = (M + rpw - 1) / rpw;
         const dim3 grid((unsigned)strips, (unsigned)chunks);
-        if (dtype == SDE_BF16)
-            hipLaunchKernelGGL(bn_bwd_finalize_apply_kernel<bf16_t>, grid, dim3(256), 0, s, part, nblk, C, (float)M, dgamma, dbeta, accumulate_params, (const bf16_t*)dz,
-                               (const bf16_t*)y, bnp, M, rpw, (bf16_t*)dy);
-        else
-            hipLaunchKernelGGL(bn_bwd_finalize_apply_kernel<half_t>, grid, dim3(256), 0, s, part, nblk, C, (float)M, dgamma, dbeta, accumulate_params, (const half_t*)dz,
-                               (const half_t*)y, bnp, M, rpw, (half_t*)dy);
+        Types16::dispatch(dtype, [&](auto tag) {
+            typedef typename decltype(tag)::type T;
+            hipLaunchKernelGGL(bn_bwd_finalize_apply_kernel<T>, grid, dim3(256), 0, s, part, nblk, C, (float)M, dgamma, dbeta, accumulate_params, (const T*)dz, (const T*)y, bnp,
+                               M, rpw, (T*)dy);
+        });
         SDE_CHECK_LAUNCH("sde_bn_bwd/finalize+apply");
         return SDE_OK;
     }
@@ -1547,18 +1497,19 @@ int sde_bn_bwd(const void* dout, const void* dout1, const void* dout2, const voi
     const float* src = pre_reduce(part, rows, 2 * C, s);
     hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(sde_cdiv(C, 8)), dim3(SLAB_T), 0, s, src, rows, C, (float)M, dgamma, dbeta, accumulate_params, coef);
     SDE_CHECK_LAUNCH("sde_bn_bwd/finalize");
-    const int nb = grid_for(M * (C / V));
-    DISPATCH_T(dtype,
-               hipLaunchKernelGGL(bn_bwd_apply_kernel<float>, dim3(nb), dim3(256), 0, s, (const float*)dz, (const float*)y, bnp, coef, M, C, (float*)dy),
-               hipLaunchKernelGGL(bn_bwd_apply_kernel<bf16_t>, dim3(nb), dim3(256), 0, s, (const bf16_t*)dz, (const bf16_t*)y, bnp, coef, M, C, (bf16_t*)dy),
-               hipLaunchKernelGGL(bn_bwd_apply_kernel<half_t>, dim3(nb), dim3(256), 0, s, (const half_t*)dz, (const half_t*)y, bnp, coef, M, C, (half_t*)dy));
+    const int nb = sde_grid_for(M * (C / V), GRID_CAP);
+    Types::dispatch(dtype, [&](auto tag) {
+        typedef typename decltype(tag)::type T;
+        hipLaunchKernelGGL(bn_bwd_apply_kernel<T>, dim3(nb), dim3(256), 0, s, (const T*)dz, (const T*)y, bnp, coef, M, C, (T*)dy);
+    });
     SDE_CHECK_LAUNCH("sde_bn_bwd/apply");
     return SDE_OK;
 }
 
 int sde_bn_bwd_from_part(const float* part, int rows, const void* gm, const void* y, const float* bnp, long M, int C, int dtype, float* coef,
                          float* dgamma, float* dbeta, int accumulate_params, void* dy, sde_stream_t stream) {
-    const int V = SDE_IS16(dtype) ? 8 : 4;
+    SDE_CHECK_ARG(Types::has(dtype), "sde_bn_bwd_from_part: unsupported dtype %d", dtype);
+    const int V = sde_vec_elems(dtype);
     SDE_CHECK_ARG(part && gm && y && bnp && coef && dgamma && dbeta && dy && rows > 0 && M > 0 && C > 0 && C % V == 0, "sde_bn_bwd_from_part: bad argument");
     hipStream_t s = (hipStream_t)stream;
     if (g_bn_fuse && SDE_IS16(dtype) && C % 64 == 0 && rows <= BNFA_MAX_ROWS) {       // short slab: finalize + apply in one launch
@@ -1568,12 +1519,11 @@ int sde_bn_bwd_from_part(const float* part, int rows, const void* gm, const void
         rpw = (rpw + 31) / 32 * 32;
         chunks = (M + rpw - 1) / rpw;
         const dim3 grid((unsigned)strips, (unsigned)chunks);
-        if (dtype == SDE_BF16)
-            hipLaunchKernelGGL(bn_bwd_finalize_apply_kernel<bf16_t>, grid, dim3(256), 0, s, part, rows, C, (float)M, dgamma, dbeta, accumulate_params, (const bf16_t*)gm,
-                               (const bf16_t*)y, bnp, M, rpw, (bf16_t*)dy);
-        else
-            hipLaunchKernelGGL(bn_bwd_finalize_apply_kernel<half_t>, grid, dim3(256), 0, s, part, rows, C, (float)M, dgamma, dbeta, accumulate_params, (const half_t*)gm,
-                               (const half_t*)y, bnp, M, rpw, (half_t*)dy);
+        Types16::dispatch(dtype, [&](auto tag) {
+            typedef typename decltype(tag)::type T;
+            hipLaunchKernelGGL(bn_bwd_finalize_apply_kernel<T>, grid, dim3(256), 0, s, part, rows, C, (float)M, dgamma, dbeta, accumulate_params, (const T*)gm, (const T*)y, bnp,
+                               M, rpw, (T*)dy);
+        });
         SDE_CHECK_LAUNCH("sde_bn_bwd_from_part/finalize+apply");
         return SDE_OK;
     }
@@ -1581,24 +1531,26 @@ int sde_bn_bwd_from_part(const float* part, int rows, const void* gm, const void
     const float* src = pre_reduce(part, r, 2 * C, s);
     hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(sde_cdiv(C, 8)), dim3(SLAB_T), 0, s, src, r, C, (float)M, dgamma, dbeta, accumulate_params, coef);
     SDE_CHECK_LAUNCH("sde_bn_bwd_from_part/finalize");
-    const int nb = grid_for(M * (C / V));
-    DISPATCH_T(dtype,
-               hipLaunchKernelGGL(bn_bwd_apply_kernel<float>, dim3(nb), dim3(256), 0, s, (const float*)gm, (const float*)y, bnp, coef, M, C, (float*)dy),
-               hipLaunchKernelGGL(bn_bwd_apply_kernel<bf16_t>, dim3(nb), dim3(256), 0, s, (const bf16_t*)gm, (const bf16_t*)y, bnp, coef, M, C, (bf16_t*)dy),
-               hipLaunchKernelGGL(bn_bwd_apply_kernel<half_t>, dim3(nb), dim3(256), 0, s, (const half_t*)gm, (const half_t*)y, bnp, coef, M, C, (half_t*)dy));
+    const int nb = sde_grid_for(M * (C / V), GRID_CAP);
+    Types::dispatch(dtype, [&](auto tag) {
+        typedef typename decltype(tag)::type T;
+        hipLaunchKernelGGL(bn_bwd_apply_kernel<T>, dim3(nb), dim3(256), 0, s, (const T*)gm, (const T*)y, bnp, coef, M, C, (T*)dy);
+    });
     SDE_CHECK_LAUNCH("sde_bn_bwd_from_part/apply");
     return SDE_OK;
 }
 
 int sde_maxpool_fwd(const void* x, int B, int H, int W, int C, int dtype, void* out, uint8_t* idx, sde_stream_t stream) {
-    const int V = SDE_IS16(dtype) ? 8 : 4;
+    SDE_CHECK_ARG(Types::has(dtype), "sde_maxpool_fwd: unsupported dtype %d", dtype);
+    const int V = sde_vec_elems(dtype);
     SDE_CHECK_ARG(x && out && idx && B > 0 && H > 1 && W > 1 && C % V == 0, "sde_maxpool_fwd: bad argument");
     const int OH = (H + 2 - 3) / 2 + 1, OW = (W + 2 - 3) / 2 + 1;
     hipStream_t s = (hipStream_t)stream;
-    const int nb = grid_for((long)B * OH * OW * (C / V));
-    DISPATCH_T(dtype, hipLaunchKernelGGL(maxpool_fwd_kernel<float>, dim3(nb), dim3(256), 0, s, (const float*)x, B, H, W, C, OH, OW, (float*)out, idx),
-               hipLaunchKernelGGL(maxpool_fwd_kernel<bf16_t>, dim3(nb), dim3(256), 0, s, (const bf16_t*)x, B, H, W, C, OH, OW, (bf16_t*)out, idx),
-               hipLaunchKernelGGL(maxpool_fwd_kernel<half_t>, dim3(nb), dim3(256), 0, s, (const half_t*)x, B, H, W, C, OH, OW, (half_t*)out, idx));
+    const int nb = sde_grid_for((long)B * OH * OW * (C / V), GRID_CAP);
+    Types::dispatch(dtype, [&](auto tag) {
+        typedef typename decltype(tag)::type T;
+        hipLaunchKernelGGL(maxpool_fwd_kernel<T>, dim3(nb), dim3(256), 0, s, (const T*)x, B, H, W, C, OH, OW, (T*)out, idx);
+    });
     SDE_CHECK_LAUNCH("sde_maxpool_fwd");
     return SDE_OK;
 }
@@ -1608,14 +1560,16 @@ int sde_maxpool_bwd(const void* dout, const uint8_t* idx, int B, int H, int W, i
 }
 
 int sde_maxpool_bwd_sum(const void* dout, const void* dout1, const uint8_t* idx, int B, int H, int W, int C, int dtype, void* dx, sde_stream_t stream) {
-    const int V = SDE_IS16(dtype) ? 8 : 4;
+    SDE_CHECK_ARG(Types::has(dtype), "sde_maxpool_bwd: unsupported dtype %d", dtype);
+    const int V = sde_vec_elems(dtype);
     SDE_CHECK_ARG(dout && idx && dx && B > 0 && H > 1 && W > 1 && C % V == 0, "sde_maxpool_bwd: bad argument");
     const int OH = (H + 2 - 3) / 2 + 1, OW = (W + 2 - 3) / 2 + 1;
     hipStream_t s = (hipStream_t)stream;
-    const int nb = grid_for((long)B * H * W * (C / V));
-    DISPATCH_T(dtype, hipLaunchKernelGGL(maxpool_bwd_kernel<float>, dim3(nb), dim3(256), 0, s, (const float*)dout, (const float*)dout1, idx, B, H, W, C, OH, OW, (float*)dx),
-               hipLaunchKernelGGL(maxpool_bwd_kernel<bf16_t>, dim3(nb), dim3(256), 0, s, (const bf16_t*)dout, (const bf16_t*)dout1, idx, B, H, W, C, OH, OW, (bf16_t*)dx),
-               hipLaunchKernelGGL(maxpool_bwd_kernel<half_t>, dim3(nb), dim3(256), 0, s, (const half_t*)dout, (const half_t*)dout1, idx, B, H, W, C, OH, OW, (half_t*)dx));
+    const int nb = sde_grid_for((long)B * H * W * (C / V), GRID_CAP);
+    Types::dispatch(dtype, [&](auto tag) {
+        typedef typename decltype(tag)::type T;
+        hipLaunchKernelGGL(maxpool_bwd_kernel<T>, dim3(nb), dim3(256), 0, s, (const T*)dout, (const T*)dout1, idx, B, H, W, C, OH, OW, (T*)dx);
+    });
     SDE_CHECK_LAUNCH("sde_maxpool_bwd");
     return SDE_OK;
 }
@@ -1627,7 +1581,8 @@ int sde_act_bwd_bias(const void* dout, const void* out, int act, long M, int C, 
 
 int sde_act_bwd_bias_sum(const void* dout, const void* dout1, const void* out, int act, long M, int C, int dtype, void* dz, float* part, float* dbias, int Cbias,
                          int accumulate, sde_stream_t stream) {
-    const int V = SDE_IS16(dtype) ? 8 : 4;
+    SDE_CHECK_ARG(Types::has(dtype), "sde_act_bwd_bias: unsupported dtype %d", dtype);
+    const int V = sde_vec_elems(dtype);
     SDE_CHECK_ARG(dout && M > 0 && C > 0 && C % V == 0, "sde_act_bwd_bias: bad argument");
     SDE_CHECK_ARG(act == SDE_ACT_NONE || out, "sde_act_bwd_bias: activation backward needs the saved output");
     SDE_CHECK_ARG((dbias == nullptr) || (part && Cbias > 0 && Cbias <= C), "sde_act_bwd_bias: bias gradient needs a partial slab");
@@ -1636,10 +1591,10 @@ int sde_act_bwd_bias_sum(const void* dout, const void* dout1, const void* out, i
     const long rpb = (M + nblk - 1) / nblk;
     float* p = part;                    // (part without dbias: the column partials only -- the caller sums them later, sde_colsum_finalize_batched)
     const size_t lds = ((size_t)C > 256 * 8 ? (size_t)C : 256 * 8) * sizeof(float);
-    DISPATCH_T(dtype,
-               hipLaunchKernelGGL(act_bwd_bias_kernel<float>, dim3(nblk), dim3(256), lds, s, (const float*)dout, (const float*)dout1, (const float*)out, act, M, C, rpb, (float*)dz, p),
-               hipLaunchKernelGGL(act_bwd_bias_kernel<bf16_t>, dim3(nblk), dim3(256), lds, s, (const bf16_t*)dout, (const bf16_t*)dout1, (const bf16_t*)out, act, M, C, rpb, (bf16_t*)dz, p),
-               hipLaunchKernelGGL(act_bwd_bias_kernel<half_t>, dim3(nblk), dim3(256), lds, s, (const half_t*)dout, (const half_t*)dout1, (const half_t*)out, act, M, C, rpb, (half_t*)dz, p));
+    Types::dispatch(dtype, [&](auto tag) {
+        typedef typename decltype(tag)::type T;
+        hipLaunchKernelGGL(act_bwd_bias_kernel<T>, dim3(nblk), dim3(256), lds, s, (const T*)dout, (const T*)dout1, (const T*)out, act, M, C, rpb, (T*)dz, p);
+    });
     SDE_CHECK_LAUNCH("sde_act_bwd_bias");
     if (dbias) {
         int rows = nblk;
@@ -1673,27 +1628,31 @@ int sde_colsum_finalize_batched(const sde_colsum_item* items, int n, sde_stream_
 }
 
 int sde_refl_fold(const void* dxp, int B, int H, int W, int C, int C0, int upcat, int dtype, void* dx0, void* dx1, sde_stream_t stream) {
-    const int V = SDE_IS16(dtype) ? 8 : 4;
+    SDE_CHECK_ARG(Types::has(dtype), "sde_refl_fold: unsupported dtype %d", dtype);
+    const int V = sde_vec_elems(dtype);
     SDE_CHECK_ARG(dxp && dx0 && B > 0 && H >= 2 && W >= 2 && C % V == 0, "sde_refl_fold: bad argument (B=%d H=%d W=%d C=%d)", B, H, W, C);
     SDE_CHECK_ARG(!upcat || (C0 > 0 && C0 <= C && C0 % V == 0 && H % 2 == 0 && W % 2 == 0 && (C0 == C || dx1)), "sde_refl_fold: bad upcat argument");
     hipStream_t s = (hipStream_t)stream;
     const long items = upcat ? (long)B * (H / 2) * (W / 2) * (C0 / V) + (long)B * H * W * ((C - C0) / V) : (long)B * H * W * (C / V);
-    const int nb = grid_for(items);
-    DISPATCH_T(dtype, hipLaunchKernelGGL(refl_fold_kernel<float>, dim3(nb), dim3(256), 0, s, (const float*)dxp, B, H, W, C, C0, upcat, (float*)dx0, (float*)dx1),
-               hipLaunchKernelGGL(refl_fold_kernel<bf16_t>, dim3(nb), dim3(256), 0, s, (const bf16_t*)dxp, B, H, W, C, C0, upcat, (bf16_t*)dx0, (bf16_t*)dx1),
-               hipLaunchKernelGGL(refl_fold_kernel<half_t>, dim3(nb), dim3(256), 0, s, (const half_t*)dxp, B, H, W, C, C0, upcat, (half_t*)dx0, (half_t*)dx1));
+    const int nb = sde_grid_for(items, GRID_CAP);
+    Types::dispatch(dtype, [&](auto tag) {
+        typedef typename decltype(tag)::type T;
+        hipLaunchKernelGGL(refl_fold_kernel<T>, dim3(nb), dim3(256), 0, s, (const T*)dxp, B, H, W, C, C0, upcat, (T*)dx0, (T*)dx1);
+    });
     SDE_CHECK_LAUNCH("sde_refl_fold");
     return SDE_OK;
 }
 
 int sde_depth_head_fwd(const void* y, int B, int H, int W, int ld, float min_depth, float max_depth, int flip, int dtype, float* depth, sde_stream_t stream) {
+    SDE_CHECK_ARG(Types::has(dtype), "sde_depth_head_fwd: unsupported dtype %d", dtype);
     SDE_CHECK_ARG(y && depth && B > 0 && H > 0 && W > 0 && ld > 0 && min_depth > 0 && max_depth > min_depth, "sde_depth_head_fwd: bad argument");
     hipStream_t s = (hipStream_t)stream;
     const float mind = 1.0f / max_depth, maxd = 1.0f / min_depth;
-    const int nb = grid_for((long)B * H * W);
-    DISPATCH_T(dtype, hipLaunchKernelGGL(depth_head_fwd_kernel<float>, dim3(nb), dim3(256), 0, s, (const float*)y, B, H, W, ld, mind, maxd, flip, depth),
-               hipLaunchKernelGGL(depth_head_fwd_kernel<bf16_t>, dim3(nb), dim3(256), 0, s, (const bf16_t*)y, B, H, W, ld, mind, maxd, flip, depth),
-               hipLaunchKernelGGL(depth_head_fwd_kernel<half_t>, dim3(nb), dim3(256), 0, s, (const half_t*)y, B, H, W, ld, mind, maxd, flip, depth));
+    const int nb = sde_grid_for((long)B * H * W, GRID_CAP);
+    Types::dispatch(dtype, [&](auto tag) {
+        typedef typename decltype(tag)::type T;
+        hipLaunchKernelGGL(depth_head_fwd_kernel<T>, dim3(nb), dim3(256), 0, s, (const T*)y, B, H, W, ld, mind, maxd, flip, depth);
+    });
     SDE_CHECK_LAUNCH("sde_depth_head_fwd");
     return SDE_OK;
 }
@@ -1703,18 +1662,20 @@ int sde_depth_head_bwd(const void* y, const float* ddepth, int B, int H, int W, 
     return sde_depth_head_bwd_bias(y, ddepth, B, H, W, ld, min_depth, max_depth, flip, dtype, dy, nullptr, nullptr, 0, stream);
 }
 
-int sde_depth_head_bias_blocks(int B, int H, int W) { return grid_for((long)B * H * W); }
+int sde_depth_head_bias_blocks(int B, int H, int W) { return sde_grid_for((long)B * H * W, GRID_CAP); }
 
 int sde_depth_head_bwd_bias(const void* y, const float* ddepth, int B, int H, int W, int ld, float min_depth, float max_depth, int flip, int dtype, void* dy,
                             float* part, float* dbias, int accumulate, sde_stream_t stream) {
+    SDE_CHECK_ARG(Types::has(dtype), "sde_depth_head_bwd: unsupported dtype %d", dtype);
     SDE_CHECK_ARG(y && ddepth && dy && B > 0 && H > 0 && W > 0 && ld > 0, "sde_depth_head_bwd: bad argument");
     SDE_CHECK_ARG((part == nullptr) == (dbias == nullptr), "sde_depth_head_bwd_bias: the bias gradient needs both the partial buffer and the output");
     hipStream_t s = (hipStream_t)stream;
     const float mind = 1.0f / max_depth, maxd = 1.0f / min_depth;
-    const int nb = grid_for((long)B * H * W);
-    DISPATCH_T(dtype, hipLaunchKernelGGL(depth_head_bwd_kernel<float>, dim3(nb), dim3(256), 0, s, (const float*)y, ddepth, B, H, W, ld, mind, maxd, flip, (float*)dy, part),
-               hipLaunchKernelGGL(depth_head_bwd_kernel<bf16_t>, dim3(nb), dim3(256), 0, s, (const bf16_t*)y, ddepth, B, H, W, ld, mind, maxd, flip, (bf16_t*)dy, part),
-               hipLaunchKernelGGL(depth_head_bwd_kernel<half_t>, dim3(nb), dim3(256), 0, s, (const half_t*)y, ddepth, B, H, W, ld, mind, maxd, flip, (half_t*)dy, part));
+    const int nb = sde_grid_for((long)B * H * W, GRID_CAP);
+    Types::dispatch(dtype, [&](auto tag) {
+        typedef typename decltype(tag)::type T;
+        hipLaunchKernelGGL(depth_head_bwd_kernel<T>, dim3(nb), dim3(256), 0, s, (const T*)y, ddepth, B, H, W, ld, mind, maxd, flip, (T*)dy, part);
+    });
     SDE_CHECK_LAUNCH("sde_depth_head_bwd");
     if (dbias) {
         hipLaunchKernelGGL(head_bias_finalize_kernel, dim3(1), dim3(256), 0, s, part, nb, dbias, accumulate);
@@ -1728,25 +1689,28 @@ int sde_gn_relu_fwd(const void* x, const float* gamma, const float* beta, int B,
     return sde_gn_relu_res_fwd(x, nullptr, gamma, beta, B, HW, C, G, eps, relu, dtype, part, gnp, out, stream);
 }
 
-static bool gn_vector_path(int C, int dtype) { const int V = SDE_IS16(dtype) ? 8 : 4; return C % V == 0 && 256 % (C / V) == 0; }
+static bool gn_vector_path(int C, int dtype) { const int V = sde_vec_elems(dtype); return C % V == 0 && 256 % (C / V) == 0; }
 
 int sde_gn_relu_res_fwd(const void* x, const void* res, const float* gamma, const float* beta, int B, int HW, int C, int G, float eps, int relu, int dtype,
                         float* part, float* gnp, void* out, sde_stream_t stream) {
+    SDE_CHECK_ARG(Types::has(dtype), "sde_gn_relu_fwd: unsupported dtype %d", dtype);
     SDE_CHECK_ARG(x && gamma && beta && part && gnp && out && B > 0 && HW > 0 && C > 0 && G > 0 && C % G == 0, "sde_gn_relu_fwd: bad argument");
-    SDE_CHECK_ARG(C % (SDE_IS16(dtype) ? 8 : 4) == 0, "sde_gn_relu_fwd: C=%d must be a multiple of the 16-byte group", C);
+    SDE_CHECK_ARG(C % sde_vec_elems(dtype) == 0, "sde_gn_relu_fwd: C=%d must be a multiple of the 16-byte group", C);
     SDE_CHECK_ARG(!res || gn_vector_path(C, dtype), "sde_gn_relu_res_fwd: the residual form needs C / (16-byte group) to divide 256 (C=%d)", C);
     hipStream_t s = (hipStream_t)stream;
     const size_t lds = 2 * (size_t)C * sizeof(float);
-    DISPATCH_T(dtype, hipLaunchKernelGGL(gn_stats_kernel<float>, dim3(GN_CHUNKS, B), dim3(256), lds, s, (const float*)x, (const float*)res, HW, C, part),
-               hipLaunchKernelGGL(gn_stats_kernel<bf16_t>, dim3(GN_CHUNKS, B), dim3(256), lds, s, (const bf16_t*)x, (const bf16_t*)res, HW, C, part),
-               hipLaunchKernelGGL(gn_stats_kernel<half_t>, dim3(GN_CHUNKS, B), dim3(256), lds, s, (const half_t*)x, (const half_t*)res, HW, C, part));
+    Types::dispatch(dtype, [&](auto tag) {
+        typedef typename decltype(tag)::type T;
+        hipLaunchKernelGGL(gn_stats_kernel<T>, dim3(GN_CHUNKS, B), dim3(256), lds, s, (const T*)x, (const T*)res, HW, C, part);
+    });
     SDE_CHECK_LAUNCH("sde_gn_relu_fwd/stats");
     hipLaunchKernelGGL(gn_finalize_kernel, dim3(B * G), dim3(64), 0, s, part, B, C, G, HW, eps, gnp);
     SDE_CHECK_LAUNCH("sde_gn_relu_fwd/finalize");
-    const int nb = grid_for((long)B * HW * (C / (SDE_IS16(dtype) ? 8 : 4)));
-    DISPATCH_T(dtype, hipLaunchKernelGGL(gn_apply_kernel<float>, dim3(nb), dim3(256), 0, s, (const float*)x, (const float*)res, gnp, gamma, beta, B, HW, C, G, relu, (float*)out),
-               hipLaunchKernelGGL(gn_apply_kernel<bf16_t>, dim3(nb), dim3(256), 0, s, (const bf16_t*)x, (const bf16_t*)res, gnp, gamma, beta, B, HW, C, G, relu, (bf16_t*)out),
-               hipLaunchKernelGGL(gn_apply_kernel<half_t>, dim3(nb), dim3(256), 0, s, (const half_t*)x, (const half_t*)res, gnp, gamma, beta, B, HW, C, G, relu, (half_t*)out));
+    const int nb = sde_grid_for((long)B * HW * (C / sde_vec_elems(dtype)), GRID_CAP);
+    Types::dispatch(dtype, [&](auto tag) {
+        typedef typename decltype(tag)::type T;
+        hipLaunchKernelGGL(gn_apply_kernel<T>, dim3(nb), dim3(256), 0, s, (const T*)x, (const T*)res, gnp, gamma, beta, B, HW, C, G, relu, (T*)out);
+    });
     SDE_CHECK_LAUNCH("sde_gn_relu_fwd/apply");
     return SDE_OK;
 }
@@ -1758,23 +1722,25 @@ int sde_gn_relu_bwd(const void* dout, const void* out, const void* x, const floa
 
 int sde_gn_relu_res_bwd(const void* dout, const void* out, const void* x, const void* res, const float* gnp, const float* gamma, int B, int HW, int C, int G, int relu,
                         int dtype, float* part, float* coef, float* dgamma, float* dbeta, int accumulate_params, void* dx, sde_stream_t stream) {
+    SDE_CHECK_ARG(Types::has(dtype), "sde_gn_relu_bwd: unsupported dtype %d", dtype);
     SDE_CHECK_ARG(dout && out && x && gnp && gamma && part && coef && dgamma && dbeta && dx && C % G == 0, "sde_gn_relu_bwd: bad argument");
     SDE_CHECK_ARG(!res || gn_vector_path(C, dtype), "sde_gn_relu_res_bwd: the residual form needs C / (16-byte group) to divide 256 (C=%d)", C);
-    SDE_CHECK_ARG(C % (SDE_IS16(dtype) ? 8 : 4) == 0, "sde_gn_relu_bwd: C=%d must be a multiple of the 16-byte group", C);
+    SDE_CHECK_ARG(C % sde_vec_elems(dtype) == 0, "sde_gn_relu_bwd: C=%d must be a multiple of the 16-byte group", C);
     hipStream_t s = (hipStream_t)stream;
     const size_t lds = 2 * (size_t)C * sizeof(float);
-    DISPATCH_T(dtype,
-               hipLaunchKernelGGL(gn_bwd_stats_kernel<float>, dim3(GN_CHUNKS, B), dim3(256), lds, s, (const float*)dout, (const float*)out, (const float*)x, (const float*)res, gnp, HW, C, G, relu, part),
-               hipLaunchKernelGGL(gn_bwd_stats_kernel<bf16_t>, dim3(GN_CHUNKS, B), dim3(256), lds, s, (const bf16_t*)dout, (const bf16_t*)out, (const bf16_t*)x, (const bf16_t*)res, gnp, HW, C, G, relu, part),
-               hipLaunchKernelGGL(gn_bwd_stats_kernel<half_t>, dim3(GN_CHUNKS, B), dim3(256), lds, s, (const half_t*)dout, (const half_t*)out, (const half_t*)x, (const half_t*)res, gnp, HW, C, G, relu, part));
+    Types::dispatch(dtype, [&](auto tag) {
+        typedef typename decltype(tag)::type T;
+        hipLaunchKernelGGL(gn_bwd_stats_kernel<T>, dim3(GN_CHUNKS, B), dim3(256), lds, s, (const T*)dout, (const T*)out, (const T*)x, (const T*)res, gnp, HW, C, G, relu, part);
+    });
     SDE_CHECK_LAUNCH("sde_gn_relu_bwd/stats");
     hipLaunchKernelGGL(gn_bwd_finalize_kernel, dim3(B * G + C), dim3(64), 0, s, part, gamma, B, C, G, HW, coef, dgamma, dbeta, accumulate_params);
     SDE_CHECK_LAUNCH("sde_gn_relu_bwd/finalize");
-    const int nb = grid_for((long)B * HW * (C / (SDE_IS16(dtype) ? 8 : 4)));
-    DISPATCH_T(dtype,
-               hipLaunchKernelGGL(gn_bwd_apply_kernel<float>, dim3(nb), dim3(256), 0, s, (const float*)dout, (const float*)out, (const float*)x, (const float*)res, gnp, coef, gamma, B, HW, C, G, relu, (float*)dx),
-               hipLaunchKernelGGL(gn_bwd_apply_kernel<bf16_t>, dim3(nb), dim3(256), 0, s, (const bf16_t*)dout, (const bf16_t*)out, (const bf16_t*)x, (const bf16_t*)res, gnp, coef, gamma, B, HW, C, G, relu, (bf16_t*)dx),
-               hipLaunchKernelGGL(gn_bwd_apply_kernel<half_t>, dim3(nb), dim3(256), 0, s, (const half_t*)dout, (const half_t*)out, (const half_t*)x, (const half_t*)res, gnp, coef, gamma, B, HW, C, G, relu, (half_t*)dx));
+    const int nb = sde_grid_for((long)B * HW * (C / sde_vec_elems(dtype)), GRID_CAP);
+    Types::dispatch(dtype, [&](auto tag) {
+        typedef typename decltype(tag)::type T;
+        hipLaunchKernelGGL(gn_bwd_apply_kernel<T>, dim3(nb), dim3(256), 0, s, (const T*)dout, (const T*)out, (const T*)x, (const T*)res, gnp, coef, gamma, B, HW, C, G, relu,
+                           (T*)dx);
+    });
     SDE_CHECK_LAUNCH("sde_gn_relu_bwd/apply");
     return SDE_OK;
 }
@@ -1793,7 +1759,7 @@ static int adam_check(const char* who, float* p, const float* g, float* m, float
 int sde_adam_step(float* p, const float* g, float* m, float* v, long n, const sde_adam_desc* d, sde_stream_t stream) {
     const int rc = adam_check("sde_adam_step", p, g, m, v, n, d);
     if (rc != SDE_OK) return rc;
-    hipLaunchKernelGGL(adam_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, *d);
+    hipLaunchKernelGGL(adam_kernel, dim3(sde_grid_for(n, GRID_CAP)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, *d);
     SDE_CHECK_LAUNCH("sde_adam_step");
     return SDE_OK;
 }
@@ -1806,8 +1772,10 @@ int sde_adam_step_twin(float* p, const float* g, float* m, float* v, long n, con
                   "sde_adam_step_twin: p, g, m, v must be 16-byte aligned and the twin 8-byte aligned");
     SDE_CHECK_ARG(n < (1L << 39), "sde_adam_step_twin: n too large");
     const dim3 grid((unsigned)(((n >> 2) + 256) / 256));       // one group of four per lane (+ block 0's tail lanes)
-    if (twin_dtype == SDE_BF16) hipLaunchKernelGGL(adam_twin_kernel<bf16_t>, grid, dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, (bf16_t*)twin, *d);
-    else hipLaunchKernelGGL(adam_twin_kernel<half_t>, grid, dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, (half_t*)twin, *d);
+    Types16::dispatch(twin_dtype, [&](auto tag) {
+        typedef typename decltype(tag)::type T;
+        hipLaunchKernelGGL(adam_twin_kernel<T>, grid, dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, (T*)twin, *d);
+    });
     SDE_CHECK_LAUNCH("sde_adam_step_twin");
     return SDE_OK;
 }
@@ -1815,7 +1783,7 @@ int sde_adam_step_twin(float* p, const float* g, float* m, float* v, long n, con
 int sde_grad_check(const float* g, long n, float* scale_state, sde_stream_t stream) {
     SDE_CHECK_ARG(g && scale_state && n > 0 && ((uintptr_t)g & 15) == 0, "sde_grad_check: bad argument");
     const long n4 = n / 4;
-    hipLaunchKernelGGL(grad_check_kernel, dim3(grid_for(n4 > 0 ? n4 : 1)), dim3(256), 0, (hipStream_t)stream, (const float4*)g, n4, g + n4 * 4, (int)(n - n4 * 4), scale_state);
+    hipLaunchKernelGGL(grad_check_kernel, dim3(sde_grid_for(n4 > 0 ? n4 : 1, GRID_CAP)), dim3(256), 0, (hipStream_t)stream, (const float4*)g, n4, g + n4 * 4, (int)(n - n4 * 4), scale_state);
     SDE_CHECK_LAUNCH("sde_grad_check");
     return SDE_OK;
 }

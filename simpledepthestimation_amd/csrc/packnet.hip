@@ -9,15 +9,14 @@
 //   inv_depth_head  inv = sigmoid(logit) / min_depth_head ; depth = 1 / (1/max_depth + (1/min_depth - 1/max_depth) * inv)  (+ horizontal flip)
 //
 // HBM-bound: algorithmic bytes = one read + one write of the tensor (2 x 2 B per element in 16-bit storage).
-#include "common.h"
-#include "sde_hip.h"
+#include "vec16.h"
+#include "launch.h"
 
 namespace {
 
-// 16 bytes of elements, as raw bits (these kernels only move / zero / add elements)
-template <int ES> struct Bits;
-template <> struct Bits<2> { typedef unsigned short E; static constexpr int V = 8; };
-template <> struct Bits<4> { typedef unsigned int E; static constexpr int V = 4; };
+typedef SdeTypes<float, bf16_t, half_t> Types;
+typedef SdeTypes<bf16_t, half_t, float> MoveTypes;      // the Bits<ES> kernels: the 2-byte instance comes first in the code object
+constexpr int GRID_CAP = SDE_GRID_CAP_8K;
 
 template <int ES>
 __global__ void __launch_bounds__(256) space_to_depth_kernel(const void* __restrict__ in_, void* __restrict__ out_, int B, int H, int W, int C) {
@@ -74,11 +73,6 @@ __global__ void __launch_bounds__(256) depth_to_space_kernel(const void* __restr
         }
     }
 }
-
-template <typename T> struct VecOf;
-template <> struct VecOf<float> { static constexpr int V = 4; };
-template <> struct VecOf<bf16_t> { static constexpr int V = 8; };
-template <> struct VecOf<half_t> { static constexpr int V = 8; };
 
 // out [B,H,W,Ct]: groups [0, C0/V) from p0 (+ p1 when add), then C1/V groups from p1 (concat mode), then -- when inv is given -- one group whose first
 // element is inv[b, y/2, x/2] (nearest x2 of the [B,H/2,W/2] fp32 map) and whose rest is zero
@@ -182,77 +176,74 @@ __global__ void __launch_bounds__(256) inv_depth_head_bwd_kernel(const T* __rest
     }
 }
 
-int grid_for(long n) {
-    long nb = (n + 255) / 256;
-    if (nb > 8192) nb = 8192;
-    return (int)(nb < 1 ? 1 : nb);
-}
-
 }  // namespace
-
-#define PK_DISPATCH(dtype, F32, BF, HF)  do { if ((dtype) == SDE_F32) { F32; } else if ((dtype) == SDE_BF16) { BF; } else { HF; } } while (0)
 
 extern "C" {
 
 int sde_space_to_depth(const void* x, int B, int H, int W, int C, int dtype, void* y, sde_stream_t stream) {
-    const int V = SDE_IS16(dtype) ? 8 : 4;
-    SDE_CHECK_ARG(x && y && SDE_DTYPE_OK(dtype) && B > 0 && H > 0 && W > 0 && H % 2 == 0 && W % 2 == 0 && C > 0 && C % V == 0,
+    SDE_CHECK_ARG(Types::has(dtype), "sde_space_to_depth: unsupported dtype %d", dtype);
+    const int V = sde_vec_elems(dtype);
+    SDE_CHECK_ARG(x && y && B > 0 && H > 0 && W > 0 && H % 2 == 0 && W % 2 == 0 && C > 0 && C % V == 0,
                   "sde_space_to_depth: bad argument (H=%d W=%d must be even, C=%d a multiple of %d)", H, W, C, V);
-    const int nb = grid_for((long)B * (H / 2) * (W / 2) * (C / V));
-    if (SDE_IS16(dtype)) hipLaunchKernelGGL(space_to_depth_kernel<2>, dim3(nb), dim3(256), 0, (hipStream_t)stream, x, y, B, H, W, C);
-    else hipLaunchKernelGGL(space_to_depth_kernel<4>, dim3(nb), dim3(256), 0, (hipStream_t)stream, x, y, B, H, W, C);
+    const int nb = sde_grid_for((long)B * (H / 2) * (W / 2) * (C / V), GRID_CAP);
+    MoveTypes::dispatch(dtype, [&](auto tag) {
+        hipLaunchKernelGGL(space_to_depth_kernel<decltype(tag)::size>, dim3(nb), dim3(256), 0, (hipStream_t)stream, x, y, B, H, W, C);
+    });
     SDE_CHECK_LAUNCH("sde_space_to_depth");
     return SDE_OK;
 }
 
 int sde_depth_to_space(const void* x, int B, int H, int W, int C4, int dtype, void* y, sde_stream_t stream) {
-    const int V = SDE_IS16(dtype) ? 8 : 4;
-    SDE_CHECK_ARG(x && y && SDE_DTYPE_OK(dtype) && B > 0 && H > 0 && W > 0 && C4 > 0 && C4 % (4 * V) == 0,
-                  "sde_depth_to_space: bad argument (C=%d must be a multiple of %d)", C4, 4 * V);
-    const int nb = grid_for((long)B * H * W * (C4 / 4 / V));
-    if (SDE_IS16(dtype)) hipLaunchKernelGGL(depth_to_space_kernel<2>, dim3(nb), dim3(256), 0, (hipStream_t)stream, x, y, B, H, W, C4);
-    else hipLaunchKernelGGL(depth_to_space_kernel<4>, dim3(nb), dim3(256), 0, (hipStream_t)stream, x, y, B, H, W, C4);
+    SDE_CHECK_ARG(Types::has(dtype), "sde_depth_to_space: unsupported dtype %d", dtype);
+    const int V = sde_vec_elems(dtype);
+    SDE_CHECK_ARG(x && y && B > 0 && H > 0 && W > 0 && C4 > 0 && C4 % (4 * V) == 0, "sde_depth_to_space: bad argument (C=%d must be a multiple of %d)", C4, 4 * V);
+    const int nb = sde_grid_for((long)B * H * W * (C4 / 4 / V), GRID_CAP);
+    MoveTypes::dispatch(dtype, [&](auto tag) {
+        hipLaunchKernelGGL(depth_to_space_kernel<decltype(tag)::size>, dim3(nb), dim3(256), 0, (hipStream_t)stream, x, y, B, H, W, C4);
+    });
     SDE_CHECK_LAUNCH("sde_depth_to_space");
     return SDE_OK;
 }
 
 int sde_concat_fwd(const void* p0, const void* p1, const float* inv, int add, int B, int H, int W, int C0, int C1, int Ct, int dtype, void* out,
                    sde_stream_t stream) {
-    const int V = SDE_IS16(dtype) ? 8 : 4;
+    SDE_CHECK_ARG(Types::has(dtype), "sde_concat_fwd: unsupported dtype %d", dtype);
+    const int V = sde_vec_elems(dtype);
     const int used = C0 + (add ? 0 : C1) + (inv ? 1 : 0);
-    SDE_CHECK_ARG(p0 && out && SDE_DTYPE_OK(dtype) && B > 0 && H > 0 && W > 0 && C0 > 0 && C0 % V == 0 && C1 >= 0 && C1 % V == 0 && Ct % V == 0 && Ct >= used && Ct < used + V,
+    SDE_CHECK_ARG(p0 && out && B > 0 && H > 0 && W > 0 && C0 > 0 && C0 % V == 0 && C1 >= 0 && C1 % V == 0 && Ct % V == 0 && Ct >= used && Ct < used + V,
                   "sde_concat_fwd: bad channel counts (C0=%d C1=%d Ct=%d)", C0, C1, Ct);
     SDE_CHECK_ARG((C1 == 0) == (p1 == nullptr) && (!add || C1 == C0), "sde_concat_fwd: second source / add mode mismatch");
     SDE_CHECK_ARG(!inv || (H % 2 == 0 && W % 2 == 0), "sde_concat_fwd: the inverse-depth map is up-sampled x2: H, W must be even");
-    const int nb = grid_for((long)B * H * W * (Ct / V));
+    const int nb = sde_grid_for((long)B * H * W * (Ct / V), GRID_CAP);
     hipStream_t s = (hipStream_t)stream;
-    PK_DISPATCH(dtype,
-                hipLaunchKernelGGL(concat_fwd_kernel<float>, dim3(nb), dim3(256), 0, s, (const float*)p0, (const float*)p1, inv, add, B, H, W, C0, C1, Ct, (float*)out),
-                hipLaunchKernelGGL(concat_fwd_kernel<bf16_t>, dim3(nb), dim3(256), 0, s, (const bf16_t*)p0, (const bf16_t*)p1, inv, add, B, H, W, C0, C1, Ct, (bf16_t*)out),
-                hipLaunchKernelGGL(concat_fwd_kernel<half_t>, dim3(nb), dim3(256), 0, s, (const half_t*)p0, (const half_t*)p1, inv, add, B, H, W, C0, C1, Ct, (half_t*)out));
+    Types::dispatch(dtype, [&](auto tag) {
+        typedef typename decltype(tag)::type T;
+        hipLaunchKernelGGL(concat_fwd_kernel<T>, dim3(nb), dim3(256), 0, s, (const T*)p0, (const T*)p1, inv, add, B, H, W, C0, C1, Ct, (T*)out);
+    });
     SDE_CHECK_LAUNCH("sde_concat_fwd");
     return SDE_OK;
 }
 
 int sde_concat_bwd(const void* dout, int add, int B, int H, int W, int C0, int C1, int Ct, int dtype, void* d0, void* d1, float* d_inv, sde_stream_t stream) {
-    const int V = SDE_IS16(dtype) ? 8 : 4;
-    SDE_CHECK_ARG(dout && d0 && SDE_DTYPE_OK(dtype) && B > 0 && H > 0 && W > 0 && C0 > 0 && C0 % V == 0 && C1 % V == 0 && Ct % V == 0, "sde_concat_bwd: bad argument");
+    SDE_CHECK_ARG(Types::has(dtype), "sde_concat_bwd: unsupported dtype %d", dtype);
+    const int V = sde_vec_elems(dtype);
+    SDE_CHECK_ARG(dout && d0 && B > 0 && H > 0 && W > 0 && C0 > 0 && C0 % V == 0 && C1 % V == 0 && Ct % V == 0, "sde_concat_bwd: bad argument");
     SDE_CHECK_ARG(add ? d1 == nullptr : ((C1 == 0) == (d1 == nullptr)), "sde_concat_bwd: d1 is written in concat mode only");
     hipStream_t s = (hipStream_t)stream;
     const int C1c = add ? 0 : C1;
-    const int nb = grid_for((long)B * H * W * ((C0 + C1c) / V));
-    PK_DISPATCH(dtype,
-                hipLaunchKernelGGL(concat_bwd_kernel<float>, dim3(nb), dim3(256), 0, s, (const float*)dout, B, H, W, C0, C1c, Ct, (float*)d0, (float*)d1),
-                hipLaunchKernelGGL(concat_bwd_kernel<bf16_t>, dim3(nb), dim3(256), 0, s, (const bf16_t*)dout, B, H, W, C0, C1c, Ct, (bf16_t*)d0, (bf16_t*)d1),
-                hipLaunchKernelGGL(concat_bwd_kernel<half_t>, dim3(nb), dim3(256), 0, s, (const half_t*)dout, B, H, W, C0, C1c, Ct, (half_t*)d0, (half_t*)d1));
+    const int nb = sde_grid_for((long)B * H * W * ((C0 + C1c) / V), GRID_CAP);
+    Types::dispatch(dtype, [&](auto tag) {
+        typedef typename decltype(tag)::type T;
+        hipLaunchKernelGGL(concat_bwd_kernel<T>, dim3(nb), dim3(256), 0, s, (const T*)dout, B, H, W, C0, C1c, Ct, (T*)d0, (T*)d1);
+    });
     SDE_CHECK_LAUNCH("sde_concat_bwd");
     if (d_inv) {
         SDE_CHECK_ARG(H % 2 == 0 && W % 2 == 0 && C0 + C1c < Ct, "sde_concat_bwd: no inverse-depth channel in this layout");
-        const int nb2 = grid_for((long)B * (H / 2) * (W / 2));
-        PK_DISPATCH(dtype,
-                    hipLaunchKernelGGL(concat_bwd_inv_kernel<float>, dim3(nb2), dim3(256), 0, s, (const float*)dout, B, H / 2, W / 2, Ct, C0 + C1c, d_inv),
-                    hipLaunchKernelGGL(concat_bwd_inv_kernel<bf16_t>, dim3(nb2), dim3(256), 0, s, (const bf16_t*)dout, B, H / 2, W / 2, Ct, C0 + C1c, d_inv),
-                    hipLaunchKernelGGL(concat_bwd_inv_kernel<half_t>, dim3(nb2), dim3(256), 0, s, (const half_t*)dout, B, H / 2, W / 2, Ct, C0 + C1c, d_inv));
+        const int nb2 = sde_grid_for((long)B * (H / 2) * (W / 2), GRID_CAP);
+        Types::dispatch(dtype, [&](auto tag) {
+            typedef typename decltype(tag)::type T;
+            hipLaunchKernelGGL(concat_bwd_inv_kernel<T>, dim3(nb2), dim3(256), 0, s, (const T*)dout, B, H / 2, W / 2, Ct, C0 + C1c, d_inv);
+        });
         SDE_CHECK_LAUNCH("sde_concat_bwd/inv");
     }
     return SDE_OK;
@@ -260,30 +251,32 @@ int sde_concat_bwd(const void* dout, int add, int B, int H, int W, int C0, int C
 
 int sde_inv_depth_head_fwd(const void* y, int B, int H, int W, int ld, float min_depth_head, float min_depth, float max_depth, int flip, int dtype, float* inv,
                            float* depth, sde_stream_t stream) {
-    SDE_CHECK_ARG(y && inv && depth && SDE_DTYPE_OK(dtype) && B > 0 && H > 0 && W > 0 && ld > 0 && min_depth_head > 0.f && min_depth > 0.f && max_depth > min_depth,
+    SDE_CHECK_ARG(Types::has(dtype), "sde_inv_depth_head_fwd: unsupported dtype %d", dtype);
+    SDE_CHECK_ARG(y && inv && depth && B > 0 && H > 0 && W > 0 && ld > 0 && min_depth_head > 0.f && min_depth > 0.f && max_depth > min_depth,
                   "sde_inv_depth_head_fwd: bad argument");
-    const int nb = grid_for((long)B * H * W);
+    const int nb = sde_grid_for((long)B * H * W, GRID_CAP);
     hipStream_t s = (hipStream_t)stream;
     const float lo = 1.0f / max_depth, hi = 1.0f / min_depth;
-    PK_DISPATCH(dtype,
-                hipLaunchKernelGGL(inv_depth_head_fwd_kernel<float>, dim3(nb), dim3(256), 0, s, (const float*)y, B, H, W, ld, min_depth_head, lo, hi, flip, inv, depth),
-                hipLaunchKernelGGL(inv_depth_head_fwd_kernel<bf16_t>, dim3(nb), dim3(256), 0, s, (const bf16_t*)y, B, H, W, ld, min_depth_head, lo, hi, flip, inv, depth),
-                hipLaunchKernelGGL(inv_depth_head_fwd_kernel<half_t>, dim3(nb), dim3(256), 0, s, (const half_t*)y, B, H, W, ld, min_depth_head, lo, hi, flip, inv, depth));
+    Types::dispatch(dtype, [&](auto tag) {
+        typedef typename decltype(tag)::type T;
+        hipLaunchKernelGGL(inv_depth_head_fwd_kernel<T>, dim3(nb), dim3(256), 0, s, (const T*)y, B, H, W, ld, min_depth_head, lo, hi, flip, inv, depth);
+    });
     SDE_CHECK_LAUNCH("sde_inv_depth_head_fwd");
     return SDE_OK;
 }
 
 int sde_inv_depth_head_bwd(const void* y, const float* d_inv, const float* d_depth, int B, int H, int W, int ld, float min_depth_head, float min_depth,
                            float max_depth, int flip, int dtype, void* dy, sde_stream_t stream) {
-    SDE_CHECK_ARG(y && dy && (d_inv || d_depth) && SDE_DTYPE_OK(dtype) && B > 0 && H > 0 && W > 0 && ld > 0 && min_depth_head > 0.f && min_depth > 0.f && max_depth > min_depth,
+    SDE_CHECK_ARG(Types::has(dtype), "sde_inv_depth_head_bwd: unsupported dtype %d", dtype);
+    SDE_CHECK_ARG(y && dy && (d_inv || d_depth) && B > 0 && H > 0 && W > 0 && ld > 0 && min_depth_head > 0.f && min_depth > 0.f && max_depth > min_depth,
                   "sde_inv_depth_head_bwd: bad argument");
-    const int nb = grid_for((long)B * H * W);
+    const int nb = sde_grid_for((long)B * H * W, GRID_CAP);
     hipStream_t s = (hipStream_t)stream;
     const float lo = 1.0f / max_depth, hi = 1.0f / min_depth;
-    PK_DISPATCH(dtype,
-                hipLaunchKernelGGL(inv_depth_head_bwd_kernel<float>, dim3(nb), dim3(256), 0, s, (const float*)y, d_inv, d_depth, B, H, W, ld, min_depth_head, lo, hi, flip, (float*)dy),
-                hipLaunchKernelGGL(inv_depth_head_bwd_kernel<bf16_t>, dim3(nb), dim3(256), 0, s, (const bf16_t*)y, d_inv, d_depth, B, H, W, ld, min_depth_head, lo, hi, flip, (bf16_t*)dy),
-                hipLaunchKernelGGL(inv_depth_head_bwd_kernel<half_t>, dim3(nb), dim3(256), 0, s, (const half_t*)y, d_inv, d_depth, B, H, W, ld, min_depth_head, lo, hi, flip, (half_t*)dy));
+    Types::dispatch(dtype, [&](auto tag) {
+        typedef typename decltype(tag)::type T;
+        hipLaunchKernelGGL(inv_depth_head_bwd_kernel<T>, dim3(nb), dim3(256), 0, s, (const T*)y, d_inv, d_depth, B, H, W, ld, min_depth_head, lo, hi, flip, (T*)dy);
+    });
     SDE_CHECK_LAUNCH("sde_inv_depth_head_bwd");
     return SDE_OK;
 }
