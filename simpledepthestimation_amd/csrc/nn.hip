@@ -1543,7 +1543,7 @@ int sde_bn_bwd_from_part(const float* part, int rows, const void* gm, const void
 int sde_maxpool_fwd(const void* x, int B, int H, int W, int C, int dtype, void* out, uint8_t* idx, sde_stream_t stream) {
     SDE_CHECK_ARG(Types::has(dtype), "sde_maxpool_fwd: unsupported dtype %d", dtype);
     const int V = sde_vec_elems(dtype);
-    SDE_CHECK_ARG(x && out && idx && B > 0 && H > 1 && W > 1 && C % V == 0, "sde_maxpool_fwd: bad argument");
+    SDE_CHECK_ARG(x && out && idx && B > 0 && H > 0 && W > 0 && C % V == 0, "sde_maxpool_fwd: bad argument");
     const int OH = (H + 2 - 3) / 2 + 1, OW = (W + 2 - 3) / 2 + 1;
     hipStream_t s = (hipStream_t)stream;
     const int nb = sde_grid_for((long)B * OH * OW * (C / V), GRID_CAP);
@@ -1562,7 +1562,7 @@ int sde_maxpool_bwd(const void* dout, const uint8_t* idx, int B, int H, int W, i
 int sde_maxpool_bwd_sum(const void* dout, const void* dout1, const uint8_t* idx, int B, int H, int W, int C, int dtype, void* dx, sde_stream_t stream) {
     SDE_CHECK_ARG(Types::has(dtype), "sde_maxpool_bwd: unsupported dtype %d", dtype);
     const int V = sde_vec_elems(dtype);
-    SDE_CHECK_ARG(dout && idx && dx && B > 0 && H > 1 && W > 1 && C % V == 0, "sde_maxpool_bwd: bad argument");
+    SDE_CHECK_ARG(dout && idx && dx && B > 0 && H > 0 && W > 0 && C % V == 0, "sde_maxpool_bwd: bad argument");
     const int OH = (H + 2 - 3) / 2 + 1, OW = (W + 2 - 3) / 2 + 1;
     hipStream_t s = (hipStream_t)stream;
     const int nb = sde_grid_for((long)B * H * W * (C / V), GRID_CAP);

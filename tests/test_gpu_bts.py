@@ -65,7 +65,7 @@ def dilated_conv_case(dtype, d, shape):
     from simpledepthestimation_amd.hip import nn as HN
     from simpledepthestimation_amd.layers.hip_modules import HipConv2d
     B, H, W, Cin, Cout = shape
-    dt = DT[dtype]
+    dt = REF_DT[dtype]
     # (the large shape's reference is used once: not kept)
     ref = dilated_reference(dtype, d, shape) if shape in BOUNDED_DILATED else dilated_reference.__wrapped__(dtype, d, shape)
     x, w, gy = ref["x"], ref["w"], ref["gy"]
@@ -78,7 +78,7 @@ def dilated_conv_case(dtype, d, shape):
     gyh = nhwc(gy, y.shape[3], dt)
     y.backward(gyh)
     torch.cuda.synchronize()
-    tol = 2e-5 if dt == torch.float32 else 2e-2
+    tol = {"fp32": 2e-5, "bf16": 2e-2, "fp16": 2e-2 * 2.0 ** -3}[dtype]      # fp16: the bf16 value scaled by the ratio of the unit roundoffs
     yo = y[..., :Cout].permute(0, 3, 1, 2)
     assert rel(yo, ref["y"]) < tol
     assert rel(xh.grad[..., :Cin].permute(0, 3, 1, 2), ref["dx"]) < tol
@@ -90,16 +90,19 @@ def dilated_conv_case(dtype, d, shape):
         CB.assert_within(conv.weight.grad.cpu(), ref["bw"]["dW"], torch.float32, f"{dtype} dilated dW", l2_tol=float("inf"))
 
 
-@pytest.mark.parametrize("dtype", ["fp32", "bf16"])
-@pytest.mark.parametrize("d", [1, 3, 6, 12, 18, 24])
-@pytest.mark.parametrize("shape", [(2, 44, 88, 256, 128), (2, 5, 7, 37, 21)], ids=["44x88_256to128", "small_odd"])
+# (one list with explicit ids -- "<shape>-<d>-<dtype>", what the stacked decorators produced -- so that fp16 can join for small_odd alone)
+DILATED = [pytest.param(shape, d, dtype, id=f"{sid}-{d}-{dtype}") for dtype in ("fp32", "bf16", "fp16") for d in (1, 3, 6, 12, 18, 24)
+           for sid, shape in (("44x88_256to128", (2, 44, 88, 256, 128)), ("small_odd", (2, 5, 7, 37, 21))) if dtype != "fp16" or sid == "small_odd"]
+
+
+@pytest.mark.parametrize("shape,d,dtype", DILATED)
 def test_dilated_conv_fwd_dgrad_wgrad(dtype, d, shape):
-    """small_odd: also element by element (tests/conv_bounds.py).  The 44 x 88 shape keeps the whole-tensor assertion alone: its fp64 adjoints take
-    too long on the CPU."""
+    """small_odd: also element by element (tests/conv_bounds.py), and in fp16.  The 44 x 88 shape keeps the whole-tensor assertion alone: its fp64
+    adjoints take too long on the CPU."""
     dilated_conv_case(dtype, d, shape)
 
 
-@pytest.mark.parametrize("dtype", ["fp32", "bf16"])
+@pytest.mark.parametrize("dtype", ["fp32", "bf16", "fp16"])
 @pytest.mark.parametrize("d", [3, 6])
 def test_dilated_conv_unequal_subgrids(dtype, d):
     """d smaller than H and W and dividing neither: sub-grids of unequal size, the last row and column of some of them missing."""
@@ -124,11 +127,11 @@ def lpg_torch(a, r, max_depth, ds):
     return full, (F.interpolate(full, scale_factor=1.0 / ds, mode="nearest") if ds else None)
 
 
-@pytest.mark.parametrize("dtype", ["fp32", "bf16"])
+@pytest.mark.parametrize("dtype", ["fp32", "bf16", "fp16"])
 @pytest.mark.parametrize("r,ds", [(8, 4), (4, 2), (2, 0)])
 def test_lpg_head_fwd_bwd(dtype, r, ds):
     from simpledepthestimation_amd.hip import bts as HB
-    dt = DT[dtype]
+    dt = REF_DT[dtype]
     B, h, w, md = 2, 6, 10, 80.0
     g = torch.Generator().manual_seed(r)
     a = (torch.randn(B, 3, h, w, generator=g) * 1.5).to(dt).float()
@@ -150,7 +153,8 @@ def test_lpg_head_fwd_bwd(dtype, r, ds):
     assert rel(full, full_r.detach()) < 1e-4
     if ds:
         assert rel(down, down_r.detach()) < 1e-4
-    assert rel(y.grad[..., :3].permute(0, 3, 1, 2), ad.grad) < (1e-3 if dt == torch.float32 else 1e-2)     # bf16: the stored logit gradient
+    # bf16: the stored logit gradient; fp16: the bf16 value scaled by the ratio of the unit roundoffs, not below the fp32 one
+    assert rel(y.grad[..., :3].permute(0, 3, 1, 2), ad.grad) < {"fp32": 1e-3, "bf16": 1e-2, "fp16": max(1e-3, 1e-2 * 2.0 ** -3)}[dtype]
     assert float(y.grad[..., 3:].abs().max()) == 0.0
 
 

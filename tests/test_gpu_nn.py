@@ -45,8 +45,8 @@ def check(a, b, dtype, name, f32_tol=2e-5, bf16_tol=1.5e-2, bound=None):
     if bound is not None:
         CB.assert_within(a, bound, dtype, name, l2_tol=float("inf"))          # (the relative-L2 line is the one below)
     e = relerr(a, b)
-    # fp16: the bf16 tolerance scaled by the ratio of the unit roundoffs, 2^-11 / 2^-8
-    tol = f32_tol if dtype == torch.float32 else bf16_tol if dtype == torch.bfloat16 else bf16_tol * 2.0 ** -3
+    # fp16: the bf16 tolerance scaled by the ratio of the unit roundoffs, 2^-11 / 2^-8, and not below the fp32 one
+    tol = f32_tol if dtype == torch.float32 else bf16_tol if dtype == torch.bfloat16 else max(f32_tol, bf16_tol * 2.0 ** -3)
     assert e < tol, f"{name}: relative L2 error {e:.3e} > {tol}"
     mx = (a.double() - b.double()).abs().max().item()
     scale = b.abs().max().item() + 1e-30
@@ -250,14 +250,14 @@ def test_batchnorm_several_consumers(NN, dtype, n_out, with_res, relu):
         check(nchw(rd.grad, C), rr.grad, dtype, "dres", 5e-5, 2e-2)
 
 
-@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["f32", "bf16"])
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.float16], ids=["f32", "bf16", "fp16"])
 def test_maxpool(NN, dtype):
     g = torch.Generator().manual_seed(1)
     V = 4 if dtype == torch.float32 else 8
     for (B, C, H, W) in [(2, 64, 16, 24), (1, 16, 13, 21)]:
         x = torch.randn(B, C, H, W, generator=g)
-        if dtype == torch.bfloat16:
-            x = x.bfloat16().float()
+        if dtype != torch.float32:
+            x = x.to(dtype).float()
         xr = x.clone().requires_grad_(True)
         yr = F.max_pool2d(xr, 3, 2, 1)
         gy = torch.randn(yr.shape, generator=g)
@@ -269,7 +269,7 @@ def test_maxpool(NN, dtype):
         check(nchw(xd.grad, C), xr.grad.to(dtype).float(), dtype, "maxpool dx", 1e-6, 1e-2)
 
 
-@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["f32", "bf16"])
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.float16], ids=["f32", "bf16", "fp16"])
 @pytest.mark.parametrize("flip", [False, True])
 def test_depth_head(NN, dtype, flip):
     g = torch.Generator().manual_seed(2)
@@ -277,8 +277,8 @@ def test_depth_head(NN, dtype, flip):
     B, H, W = 2, 12, 20
     y = torch.randn(B, 1, H, W, generator=g) * 3
     y[0, 0, 0, 0] = 25.0   # softplus threshold branch
-    if dtype == torch.bfloat16:
-        y = y.bfloat16().float()
+    if dtype != torch.float32:
+        y = y.to(dtype).float()
     yr = y.clone().requires_grad_(True)
     sd = 1 / 80 + (1 / 0.1 - 1 / 80) * F.softplus(yr)
     dr = 1 / sd
@@ -452,7 +452,7 @@ def test_prep_input(NN):
     img = torch.rand(2, 3, 10, 14, generator=g)
     mean = torch.tensor([0.485, 0.456, 0.406]); std = torch.tensor([0.229, 0.224, 0.225])
     ref = (img - mean.view(1, 3, 1, 1)) / std.view(1, 3, 1, 1)
-    for dtype, V in [(torch.float32, 4), (torch.bfloat16, 8)]:
+    for dtype, V in [(torch.float32, 4), (torch.bfloat16, 8), (torch.float16, 8)]:
         for flip in (False, True):
             out = NN.prep_input(img.to(dev), mean.to(dev), std.to(dev), dtype, flip)
             assert out.shape == (2, 10, 14, V) and (out[..., 3:] == 0).all()
@@ -602,7 +602,7 @@ def test_space_to_depth_and_depth_to_space(NN, dtype):
         NN.space_to_depth(torch.zeros(1, 5, 6, 16, device=dev, dtype=dtype))            # odd height
 
 
-@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["f32", "bf16"])
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.float16], ids=["f32", "bf16", "fp16"])
 @pytest.mark.parametrize("add,with_inv,with_p1", [(False, True, True), (False, False, True), (True, True, True), (True, False, True), (False, True, False)])
 def test_concat_with_upsampled_inverse_depth(NN, dtype, add, with_inv, with_p1):
     """PackNet01.py:L150-199: cat([unpacked, skip(, nearest_x2(inv depth))], 1) / [unpacked + skip(, ...)] in one pass, zero-filled to the 16-byte group;
@@ -638,7 +638,7 @@ def test_concat_with_upsampled_inverse_depth(NN, dtype, add, with_inv, with_p1):
         check(invd.grad.cpu(), invr.grad, dtype, "d inv", 1e-6, 1e-6)
 
 
-@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["f32", "bf16"])
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.float16], ids=["f32", "bf16", "fp16"])
 @pytest.mark.parametrize("flip", [False, True])
 def test_inv_depth_head(NN, dtype, flip):
     """layers01.py:L105-133 (sigmoid / min_depth) + PackNet01.py:L120-123,L199 (disp_to_depth, flip back) in one kernel, both outputs with gradients."""
@@ -977,19 +977,19 @@ def test_conv_output_with_two_consumers(NN, dtype, act, has_bias):
     check(nchw(xd2.grad, Cin), xr.grad, dtype, "dX one consumer")
 
 
-@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["f32", "bf16"])
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.float16], ids=["f32", "bf16", "fp16"])
 def test_maxpool_two_consumers(NN, dtype):
     g = torch.Generator().manual_seed(3)
     V = 4 if dtype == torch.float32 else 8
     B, C, H, W = 2, 64, 16, 24
     x = torch.randn(B, C, H, W, generator=g)
-    if dtype == torch.bfloat16:
-        x = x.bfloat16().float()
+    if dtype != torch.float32:
+        x = x.to(dtype).float()
     xr = x.clone().requires_grad_(True)
     yr = F.max_pool2d(xr, 3, 2, 1)
     g0, g1 = torch.randn(yr.shape, generator=g), torch.randn(yr.shape, generator=g)
-    if dtype == torch.bfloat16:
-        g0, g1 = g0.bfloat16().float(), g1.bfloat16().float()
+    if dtype != torch.float32:
+        g0, g1 = g0.to(dtype).float(), g1.to(dtype).float()
     yr.backward(g0 + g1)
     xd = nhwc(x, dtype, V).requires_grad_(True)
     ya, yb = NN.max_pool_3x3_s2(xd, n_out=2)
