@@ -94,7 +94,8 @@ int sde_photo_fwd(const sde_photo_desc* d, float* const* sampled, uint8_t* sel, 
                   float loss_scale, int accumulate, sde_stream_t stream);
 
 /* Backward w.r.t. depth and poses.  gout: device scalar (upstream gradient), multiplied by gscale.
- * d_depth [B,1,h,w]; pose_partial [sde_photo_num_blocks(...,1) * nctx * 12] workspace; d_pose[j] [B,4,4]. */
+ * d_depth [B,1,h,w]; pose_partial [sde_photo_num_blocks(...,1) * nctx * 12] workspace; d_pose[j] [B,4,4].
+ * sel may be NULL only with the 'mean' reduce and no clip thresholds (nothing is read from it then); h, w >= 4 as in the forward. */
 int sde_photo_bwd(const sde_photo_desc* d, const float* const* sampled, const uint8_t* sel, const float* gout, float gscale, float* d_depth,
                   int accumulate_depth, float* pose_partial, float* const* d_pose, int accumulate_pose, sde_stream_t stream);
 /* Every scale of the loss (MonoDepth2.py:L78-112 loops over the four decoder scales) in ONE launch per phase: d [n] descriptors (n <= 4, same batch and
@@ -146,7 +147,7 @@ int sde_smooth_bwd(const float* depth, const float* dn, const float* mean_part, 
                    int h, int w, float* d_depth, int accumulate, sde_stream_t stream);
 
 /* detectron2/modeling/losses/losses.py:L5-13 silog_loss against resize_img(depth_gt, 'nearest') (Supervised.py:L44-45), fused:
- * est [B,1,h,w], gt [B,1,H,W] full resolution (nearest-sampled in-kernel), mask gt > 1.  No compaction, no host sync.
+ * est [B,1,h,w], gt [B,1,H,W] full resolution (nearest-sampled in-kernel), mask gt > 1; H >= h, W >= w (both entries check it).  No compaction, no host sync.
  * part [sde_silog_num_blocks*3] workspace; stats[4] = (count, E[d], E[d^2], loss).  These two entries are the n = 1, weight 1 case of the launches behind
  * sde_silog_multi_fwd/_bwd. */
 int sde_silog_num_blocks(int B, int h, int w);

@@ -299,7 +299,7 @@ __device__ __forceinline__ void photo_bwd_body(const PhotoBwdArgs& a, const int 
     const int nmaps = a.automask ? 2 * NCTX : NCTX;
     const float g = a.gout[0] * a.gscale;
     const float g_mean = g / (float)nmaps;        // 'mean' reduce: every map's share
-    const int mysel = inimg ? a.sel[b * hw + pix] : 254;
+    const int mysel = (inimg && a.sel) ? a.sel[b * hw + pix] : 254;      // sel may be null with mean reduce and no clip (the host checks): mysel is unused then
 #pragma unroll
     for (int c = 0; c < 3; ++c) sA[c * BT_N + lp] = usable ? a.A[((long)b * 3 + c) * hw + pix] : 0.f;
     const float d = usable ? a.depth[b * hw + pix] : 1.f;
@@ -1007,7 +1007,8 @@ static int photo_multi_bwd_launch(const char* who, bool single, const sde_photo_
         SDE_CHECK_ARG(ds.nctx >= 1 && ds.nctx <= SDE_MAX_CTX, "%s: nctx=%d out of range", who, ds.nctx);
         SDE_CHECK_ARG(ds.nctx == d[0].nctx && ds.B == d[0].B && (single || !ds.clip_thr) && ds.A && ds.depth && ds.K && d_depth[s] && pose_partial[s],
                       "%s: scale %d: bad descriptor", who, s);
-        SDE_CHECK_ARG(ds.reduce_mean || sel[s], "%s: sel required for min reduce", who);
+        SDE_CHECK_ARG(ds.B > 0 && ds.h >= 4 && ds.w >= 4, "%s: bad shape B=%d h=%d w=%d", who, ds.B, ds.h, ds.w);
+        SDE_CHECK_ARG(sel[s] || (ds.reduce_mean && !ds.clip_thr), "%s: sel required for min reduce and with clip thresholds", who);
         PhotoBwdArgs& a = m.a[s];
         a.A = ds.A; a.depth = ds.depth; a.K = ds.K; a.sel = sel[s]; a.gout = gout + s * gout_stride; a.d_depth = d_depth[s]; a.pose_partial = pose_partial[s];
         for (int j = 0; j < SDE_MAX_CTX; ++j) {
@@ -1236,15 +1237,15 @@ int sde_silog_num_blocks(int B, int h, int w) {
     return (int)(nb < 1 ? 1 : (nb > 1024 ? 1024 : nb));
 }
 
-// the launch table of n scales; shapes: check them (sde_silog_bwd never did: it takes what its forward accepted)
-static int silog_scales(const char* who, bool shapes, const float* const* est, float* const* d_est, const int* h, const int* w, const float* weight, int n, int B, int H,
+// the launch table of n scales, shapes checked (every entry, forward and backward alike)
+static int silog_scales(const char* who, const float* const* est, float* const* d_est, const int* h, const int* w, const float* weight, int n, int B, int H,
                         int W, SilogScales& a) {
-    SDE_CHECK_ARG(est && h && w && weight && n >= 1 && n <= SDE_SILOG_MAX_SCALES && (!shapes || B > 0), "%s: bad scale table (n=%d)", who, n);
+    SDE_CHECK_ARG(est && h && w && weight && n >= 1 && n <= SDE_SILOG_MAX_SCALES && B > 0, "%s: bad scale table (n=%d)", who, n);
     a.n = n; a.accumulate = 0;
     int end = 0;
     for (int k = 0; k < n; ++k) {
         SDE_CHECK_ARG(est[k] && (!d_est || d_est[k]), "%s: null pointer (scale %d)", who, k);
-        SDE_CHECK_ARG(!shapes || (h[k] > 0 && w[k] > 0 && H >= h[k] && W >= w[k]), "%s: bad shape (scale %d)", who, k);
+        SDE_CHECK_ARG(h[k] > 0 && w[k] > 0 && H >= h[k] && W >= w[k], "%s: bad shape (scale %d)", who, k);
         a.est[k] = est[k]; a.d_est[k] = d_est ? d_est[k] : nullptr; a.h[k] = h[k]; a.w[k] = w[k]; a.weight[k] = weight[k];
         a.sh[k] = (float)((double)H / (double)h[k]); a.sw[k] = (float)((double)W / (double)w[k]);
         end += sde_silog_num_blocks(B, h[k], w[k]);
@@ -1267,7 +1268,7 @@ int sde_silog_fwd(const float* est, const float* gt, int B, int h, int w, int H,
     SDE_CHECK_ARG(est && gt && part && stats, "sde_silog_fwd: null pointer");
     const float one = 1.0f;
     SilogScales a;
-    const int rc = silog_scales("sde_silog_fwd", true, &est, nullptr, &h, &w, &one, 1, B, H, W, a);
+    const int rc = silog_scales("sde_silog_fwd", &est, nullptr, &h, &w, &one, 1, B, H, W, a);
     if (rc != SDE_OK) return rc;
     return silog_fwd_launch("sde_silog_fwd", a, gt, B, H, W, variance_focus, part, stats, nullptr, (hipStream_t)stream);
 }
@@ -1277,7 +1278,7 @@ int sde_silog_bwd(const float* est, const float* gt, const float* stats, const f
     SDE_CHECK_ARG(est && gt && stats && gout && d_est, "sde_silog_bwd: null pointer");
     const float one = 1.0f;
     SilogScales a;
-    const int rc = silog_scales("sde_silog_bwd", false, &est, &d_est, &h, &w, &one, 1, B, H, W, a);
+    const int rc = silog_scales("sde_silog_bwd", &est, &d_est, &h, &w, &one, 1, B, H, W, a);
     if (rc != SDE_OK) return rc;
     a.accumulate = accumulate;
     hipLaunchKernelGGL(silog_multi_bwd_kernel, dim3(a.blk_end[0]), dim3(256), 0, (hipStream_t)stream, a, gt, stats, gout, gscale, variance_focus, B, H, W);
@@ -1295,7 +1296,7 @@ int sde_silog_multi_fwd(const float* const* est, const float* gt, int B, const i
                         float variance_focus, float* part, float* stats, float* total, sde_stream_t stream) {
     SDE_CHECK_ARG(gt && part && stats && total, "sde_silog_multi_fwd: null pointer");
     SilogScales a;
-    const int rc = silog_scales("sde_silog_multi_fwd", true, est, nullptr, h, w, weight, n, B, H, W, a);
+    const int rc = silog_scales("sde_silog_multi_fwd", est, nullptr, h, w, weight, n, B, H, W, a);
     if (rc != SDE_OK) return rc;
     return silog_fwd_launch("sde_silog_multi_fwd", a, gt, B, H, W, variance_focus, part, stats, total, (hipStream_t)stream);
 }
@@ -1304,7 +1305,7 @@ int sde_silog_multi_bwd(const float* const* est, const float* gt, const float* s
                         const int* h, const int* w, const float* weight, int n, int H, int W, float* const* d_est, sde_stream_t stream) {
     SDE_CHECK_ARG(gt && stats && gout && d_est, "sde_silog_multi_bwd: null pointer");
     SilogScales a;
-    const int rc = silog_scales("sde_silog_multi_bwd", true, est, d_est, h, w, weight, n, B, H, W, a);
+    const int rc = silog_scales("sde_silog_multi_bwd", est, d_est, h, w, weight, n, B, H, W, a);
     if (rc != SDE_OK) return rc;
     hipLaunchKernelGGL(silog_multi_bwd_kernel, dim3(a.blk_end[n - 1]), dim3(256), 0, (hipStream_t)stream, a, gt, stats, gout, gscale, variance_focus, B, H, W);
     SDE_CHECK_LAUNCH("sde_silog_multi_bwd");
