@@ -11,6 +11,7 @@ import torch
 import torch.nn.functional as F
 
 import conv_bounds as CB
+import norm_bounds as NB
 
 pytestmark = pytest.mark.gpu
 dev = "cuda"
@@ -159,7 +160,7 @@ def test_conv_upsample_concat(NN, dtype, C0, C1, Cout):
         check(nchw(x1d.grad, C1), x1r.grad, dtype, "dx1 (skip)", bound=lim["dSkip"])
 
 
-@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["f32", "bf16"])
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.float16], ids=["f32", "bf16", "fp16"])
 @pytest.mark.parametrize("C,with_res,relu", [(64, False, True), (128, True, True), (256, False, False)])
 def test_conv_batchnorm(NN, dtype, C, with_res, relu):
     """conv (stats in the GEMM epilogue) -> training-mode BatchNorm [+ residual] [+ ReLU], forward and backward."""
@@ -170,23 +171,23 @@ def test_conv_batchnorm(NN, dtype, C, with_res, relu):
     w = torch.randn(C, Cin, 3, 3, generator=g) / math.sqrt(Cin * 9)
     gamma = torch.rand(C, generator=g) + 0.5; beta = torch.randn(C, generator=g) * 0.2
     res = torch.randn(B, C, H, W, generator=g) if with_res else None
-    if dtype == torch.bfloat16:
-        x = x.bfloat16().float(); w = w.bfloat16().float()
-        res = res.bfloat16().float() if with_res else None
+    if dtype != torch.float32:
+        x = x.to(dtype).float(); w = w.to(dtype).float()
+        res = res.to(dtype).float() if with_res else None
     xr, wr, gr, br = (t.clone().requires_grad_(True) for t in (x, w, gamma, beta))
     rr = res.clone().requires_grad_(True) if with_res else None
     rm, rv = torch.zeros(C), torch.ones(C)
     yc = F.conv2d(xr, wr, None, 1, 1)
-    if dtype == torch.bfloat16:   # the GPU path stores the conv output in bf16 before normalising
-        yc = yc + (yc.detach().bfloat16().float() - yc.detach())
+    if dtype != torch.float32:   # the GPU path stores the conv output in the 16-bit type before normalising
+        yc = yc + (yc.detach().to(dtype).float() - yc.detach())
     o = F.batch_norm(yc, rm, rv, gr, br, True, 0.1, 1e-5)
     if with_res:
         o = o + rr
     if relu:
         o = F.relu(o)
     go = torch.randn(o.shape, generator=g)
-    if dtype == torch.bfloat16:
-        go = go.bfloat16().float()
+    if dtype != torch.float32:
+        go = go.to(dtype).float()
     o.backward(go)
     xd = nhwc(x, dtype, V).requires_grad_(True)
     wd, gd, bd = (t.clone().to(dev).requires_grad_(True) for t in (w, gamma, beta))
@@ -194,9 +195,15 @@ def test_conv_batchnorm(NN, dtype, C, with_res, relu):
     rmd, rvd = torch.zeros(C, device=dev), torch.ones(C, device=dev)
     y, stats = NN.conv2d(xd, wd, None, stride=1, pad=1, bn_stats=True)
     out = NN.batch_norm_act(y, stats, gd, bd, rmd, rvd, residual=rd, relu=relu)
-    check(nchw(out, C), o.detach(), dtype, "bn out")
-    check(rmd.cpu(), rm, dtype, "running_mean", 1e-5, 1e-2)
-    check(rvd.cpu(), rv, dtype, "running_var", 1e-5, 1e-2)
+    # per element: the fp64 BatchNorm of the convolution output AS STORED, on the slab the epilogue left (norm_bounds.BNForward)
+    M = B * H * W
+    fwd = NB.BNForward(stats[:stats.shape[0] - NN.REDUCE_ROWS].cpu(), M, gamma, beta, 1e-5)
+    lim = fwd.out(y.detach().float().cpu().view(M, C), rd.detach().float().cpu().view(M, C) if with_res else None, relu, dtype)
+    to_nchw = lambda t: t.view(B, H, W, C).permute(0, 3, 1, 2)
+    check(nchw(out, C), o.detach(), dtype, "bn out", bound=CB.Bound(to_nchw(lim.ref), to_nchw(lim.lim)))
+    brm, brv = fwd.running(torch.zeros(C), torch.ones(C))
+    check(rmd.cpu(), rm, dtype, "running_mean", 1e-5, 1e-2, bound=brm)
+    check(rvd.cpu(), rv, dtype, "running_var", 1e-5, 1e-2, bound=brv)
     out.backward(nhwc(go, dtype, V))
     check(gd.grad.cpu(), gr.grad, dtype, "dgamma", 5e-5, 3e-2)
     check(bd.grad.cpu(), br.grad, dtype, "dbeta", 5e-5, 3e-2)
@@ -206,7 +213,7 @@ def test_conv_batchnorm(NN, dtype, C, with_res, relu):
         check(nchw(rd.grad, C), rr.grad, dtype, "dres")
 
 
-@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["f32", "bf16"])
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.float16], ids=["f32", "bf16", "fp16"])
 @pytest.mark.parametrize("n_out,with_res,relu", [(3, True, True), (2, False, True), (2, False, False), (3, True, False)])
 def test_batchnorm_several_consumers(NN, dtype, n_out, with_res, relu):
     """The block output feeds up to three consumers (next conv1, residual / down-sampling path, decoder skip): batch_norm_act(n_out) hands
@@ -220,14 +227,14 @@ def test_batchnorm_several_consumers(NN, dtype, n_out, with_res, relu):
     gamma = torch.rand(C, generator=g) + 0.5; beta = torch.randn(C, generator=g) * 0.2
     res = torch.randn(B, C, H, W, generator=g) if with_res else None
     cw = [torch.randn(B, C, H, W, generator=g) for _ in range(n_out)]          # consumer k: weighted sum of the output, scaled by (k + 1)
-    if dtype == torch.bfloat16:
-        x, w = x.bfloat16().float(), w.bfloat16().float()
-        res = res.bfloat16().float() if with_res else None
+    if dtype != torch.float32:
+        x, w = x.to(dtype).float(), w.to(dtype).float()
+        res = res.to(dtype).float() if with_res else None
     xr, wr, gr, br = (t.clone().requires_grad_(True) for t in (x, w, gamma, beta))
     rr = res.clone().requires_grad_(True) if with_res else None
     yc = F.conv2d(xr, wr)
-    if dtype == torch.bfloat16:
-        yc = yc + (yc.detach().bfloat16().float() - yc.detach())
+    if dtype != torch.float32:
+        yc = yc + (yc.detach().to(dtype).float() - yc.detach())
     o = F.batch_norm(yc, torch.zeros(C), torch.ones(C), gr, br, True, 0.1, 1e-5)
     o = o + rr if with_res else o
     o = F.relu(o) if relu else o
@@ -248,6 +255,13 @@ def test_batchnorm_several_consumers(NN, dtype, n_out, with_res, relu):
     check(wd.grad.cpu(), wr.grad, dtype, "dW", 5e-5, 3e-2)
     if with_res:
         check(nchw(rd.grad, C), rr.grad, dtype, "dres", 5e-5, 2e-2)
+
+
+def gn_bound(x, gamma, beta, act, dtype, groups=16, eps=1e-5):
+    """The per-element limit of GroupNorm's output (norm_bounds.GNForward) for an NCHW input holding storage values, as an NCHW Bound."""
+    B, C, H, W = x.shape
+    b = NB.GNForward(x.permute(0, 2, 3, 1).reshape(B, H * W, C), None, gamma, beta, groups, eps, act, dtype).out
+    return CB.Bound(b.ref.view(B, H, W, C).permute(0, 3, 1, 2), b.lim.view(B, H, W, C).permute(0, 3, 1, 2))
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.float16], ids=["f32", "bf16", "fp16"])
@@ -295,7 +309,7 @@ def test_depth_head(NN, dtype, flip):
     check(nchw(yd.grad, 1), yr.grad, dtype, "d logit", 2e-5, 1e-2)
 
 
-@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["f32", "bf16"])
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.float16], ids=["f32", "bf16", "fp16"])
 @pytest.mark.parametrize("C,H,W", [(16, 24, 40), (32, 12, 20), (256, 3, 5), (256, 2, 5)])
 def test_group_norm_relu(NN, dtype, C, H, W):
     g = torch.Generator().manual_seed(C + H)
@@ -303,8 +317,8 @@ def test_group_norm_relu(NN, dtype, C, H, W):
     B = 3
     x = torch.randn(B, C, H, W, generator=g) * 2 + 0.5
     gamma = torch.rand(C, generator=g) + 0.5; beta = torch.randn(C, generator=g) * 0.3
-    if dtype == torch.bfloat16:
-        x = x.bfloat16().float()
+    if dtype != torch.float32:
+        x = x.to(dtype).float()
     xr, gr, br = (t.clone().requires_grad_(True) for t in (x, gamma, beta))
     o = F.relu(F.group_norm(xr, 16, gr, br, 1e-5))
     go = torch.randn(o.shape, generator=g)
@@ -312,14 +326,14 @@ def test_group_norm_relu(NN, dtype, C, H, W):
     xd = nhwc(x, dtype, V).requires_grad_(True)
     gd, bd = (t.clone().to(dev).requires_grad_(True) for t in (gamma, beta))
     out = NN.group_norm_relu(xd, gd, bd, 16, 1e-5)
-    check(nchw(out, C), o.detach(), dtype, "gn out")
+    check(nchw(out, C), o.detach(), dtype, "gn out", bound=gn_bound(x, gamma, beta, NB.ACT_RELU, dtype))
     out.backward(nhwc(go, dtype, V))
     check(nchw(xd.grad, C), xr.grad, dtype, "gn dx", 5e-5, 3e-2)
     check(gd.grad.cpu(), gr.grad, dtype, "gn dgamma", 5e-5, 3e-2)
     check(bd.grad.cpu(), br.grad, dtype, "gn dbeta", 5e-5, 3e-2)
 
 
-@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.float16])
 @pytest.mark.parametrize("C,H,W", [(64, 12, 20), (512, 6, 10)])
 def test_group_norm_elu(NN, dtype, C, H, W):
     """PackNet's Conv2D tail: GroupNorm(16) + ELU (layers01.py:L33-40)."""
@@ -328,8 +342,8 @@ def test_group_norm_elu(NN, dtype, C, H, W):
     B = 2
     x = torch.randn(B, C, H, W, generator=g) * 2 + 0.3
     gamma = torch.rand(C, generator=g) + 0.5; beta = torch.randn(C, generator=g) * 0.3
-    if dtype == torch.bfloat16:
-        x = x.bfloat16().float()
+    if dtype != torch.float32:
+        x = x.to(dtype).float()
     xr, gr, br = (t.clone().requires_grad_(True) for t in (x, gamma, beta))
     o = F.elu(F.group_norm(xr, 16, gr, br, 1e-5))
     go = torch.randn(o.shape, generator=g)
@@ -337,7 +351,7 @@ def test_group_norm_elu(NN, dtype, C, H, W):
     xd = nhwc(x, dtype, V).requires_grad_(True)
     gd, bd = (t.clone().to(dev).requires_grad_(True) for t in (gamma, beta))
     out = NN.group_norm_relu(xd, gd, bd, 16, 1e-5, "elu")
-    check(nchw(out, C), o.detach(), dtype, "gn-elu out")
+    check(nchw(out, C), o.detach(), dtype, "gn-elu out", bound=gn_bound(x, gamma, beta, NB.ACT_ELU, dtype))
     out.backward(nhwc(go, dtype, V))
     check(nchw(xd.grad, C), xr.grad, dtype, "gn-elu dx", 5e-5, 3e-2)
     check(gd.grad.cpu(), gr.grad, dtype, "gn-elu dgamma", 5e-5, 3e-2)
