@@ -870,7 +870,40 @@ int sde_depth_warp_fuse(const float* prev, const float* cur, const float* K, con
  * and read only for such cells.  Four launches ordered on the stream (both counts per tile, one scan of both lists, vertices + map, faces); no
  * workgroup waits for another, no atomics, no host synchronisation, no allocation: legal under graph capture, the same bytes every run.  Refused
  * before any launch: dims outside the limits, voxel <= 0, min_weight < 1 (or a NaN), either cap outside [1, 2^31), NULL tsdf / weight / origin /
- * vertices / faces / count, vertices off a 16-byte or faces / rgba off a 4-byte boundary, a workspace that is NULL, misaligned or too small. */
+ * vertices / faces / count, vertices off a 16-byte or faces / rgba off a 4-byte boundary, a workspace that is NULL, misaligned or too small.
+ *
+ * sde_tsdf_render: the volume seen from a camera, by ray casting: ONE launch renders ONE picture of H x W pixels from the arrays as they are.
+ * K [3,3] fp32 (fx = K[0], cx = K[2], fy = K[4], cy = K[5] are read) and C [4,4] fp32, world -> camera (its top three rows are read: R = the 3x3
+ * block, t = the last column) are DEVICE pointers: the pose comes straight from the chain of sde_pose_compose.  C is taken as rigid, camera ->
+ * world being R^T (p - t): that is the CALLER's responsibility, a C that is not rigid renders a sheared volume.  Destinations:
+ *   depth   [H,W]   fp32: the z-depth of the surface, 0 where the ray finds none (a miss);
+ *   normal  [H,W,3] fp32, or NULL (not wanted): the unit normal in camera coordinates, towards positive tsdf; 0, 0, 0 on a miss;
+ *   picture [H,W,4] uint8, 4-byte aligned, or NULL; refused with rgba == NULL: the voxel colour with alpha 255; 0, 0, 0, 0 on a miss.
+ * near, step (fp32) and the sample count n are host arguments.  For the pixel (u, v), in fp32 in exactly this order, nothing fused, every division
+ * and the square root correctly rounded:
+ *   0. with k00 = 1 / fx, k02 = (-1 * cx) / fx, k11 = 1 / fy, k12 = (-1 * cy) / fy:  rx = k00 * (float)u + k02;  ry = k11 * (float)v + k12;  the ray
+ *      is (rx, ry, 1).  If one of the twelve entries of C that are read or one of fx, cx, fy, cy is not finite, EVERY pixel is a miss.
+ *   1. sample i = 0 .. n-1 lies at the z-depth s_i = near + (float)i * step (from i, never accumulated);   p = (s * rx, s * ry, s);
+ *      d_k = p_k - t_k;   w_r = (R_0r * d_0 + R_1r * d_1) + R_2r * d_2   for r = x, y, z;   g_r = (w_r - origin_r) / voxel - 0.5f;
+ *      b_r = floorf(g_r);   f_r = g_r - b_r.
+ *   2. the sample is VALID iff every g_r is finite (compared first: no integer conversion is undefined), 0 <= b_r <= n_r - 2 on every axis and all
+ *      eight voxels (bx + dx, by + dy, bz + dz), dx, dy, dz in {0, 1}, have weight >= min_weight.  With T_zyx their tsdf:
+ *   3. c_zy = T_zy0 + fx * (T_zy1 - T_zy0);   e_z = c_z0 + fy * (c_z1 - c_z0);   the sample's value t = e_0 + fz * (e_1 - e_0).
+ *   4. the march: a valid sample becomes prev, an invalid one clears prev.  The FIRST i with prev set, t_prev > 0 and t_i <= 0 is the hit; a
+ *      crossing from negative to positive is none and the march goes on; no hit in n samples is a miss.
+ *      depth = s_{i-1} + step * (t_prev / (t_prev - t_i)),   s_{i-1} = near + (float)(i - 1) * step.
+ *   5. normal and colour come from sample i's cell (valid by construction), up to one step behind the surface: the gradient of the interpolant at f,
+ *      X_zy = T_zy1 - T_zy0;   x_z = X_z0 + fy * (X_z1 - X_z0);   gx = x_0 + fz * (x_1 - x_0);
+ *      y_z = c_z1 - c_z0;      gy = y_0 + fz * (y_1 - y_0);       gz = e_1 - e_0;
+ *      m_r = (R_r0 * gx + R_r1 * gy) + R_r2 * gz;   len = sqrtf((gx * gx + gy * gy) + gz * gz);   normal_r = m_r / len, or 0, 0, 0 when len is 0
+ *      or not finite.  colour: rgba of the voxel (bx + (fx >= 0.5f), by + (fy >= 0.5f), bz + (fz >= 0.5f)), alpha replaced by 255.
+ * The result is that of the full march.  Because an invalid sample only clears prev and s_i does not depend on history, the kernel skips runs of
+ * samples it has PROVED invalid without touching memory (the ray against the box of valid grid coordinates, widened by a bound on the rounding
+ * of step 1) and no others; a ray that never enters the box reads nothing of the volume.  A grid with a dimension of 1 has no cells: every pixel
+ * is a miss.  One launch, one thread per pixel, no atomics, no workspace, no allocation, no host synchronisation: legal under graph capture, the
+ * same bytes every run; nothing but the three destinations is written.  Refused before any launch: dims outside the limits, voxel <= 0,
+ * min_weight < 1 (or a NaN), H or W outside [1, 32768], n outside [1, 65536], step <= 0, near or step not finite, NULL tsdf / weight / origin /
+ * K / C / depth, a picture with rgba == NULL, rgba or picture off a 4-byte boundary. */
 int sde_pose_compose(const float* T, float* C, sde_stream_t stream);
 int sde_tsdf_integrate(const float* pred, int ph, int pw, const int* ymap, const int* xmap, int H, int W, const uint8_t* frame, const float* K,
                        const float* C, const float* origin, float voxel, float trunc, float max_weight, float min_depth, float max_depth,
@@ -882,6 +915,9 @@ size_t sde_tsdf_mesh_ws_bytes(int nx, int ny, int nz);
 int sde_tsdf_mesh(const float* tsdf, const float* weight, const uint8_t* rgba, int nx, int ny, int nz, const float* origin, float voxel,
                   float min_weight, void* workspace, size_t workspace_bytes, void* vertices, long cap_vertices, int* faces, long cap_faces,
                   int* count, sde_stream_t stream);
+int sde_tsdf_render(const float* tsdf, const float* weight, const uint8_t* rgba, int nx, int ny, int nz, const float* origin, float voxel,
+                    float min_weight, const float* K, const float* C, int H, int W, float near, float step, int n, float* depth, float* normal,
+                    uint8_t* picture, sde_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------
  * MotionLearning loss stack (csrc/motion_loss.hip; autograd wrappers in hip/motion_loss.py).  fp32, planar NCHW, no host synchronisation.

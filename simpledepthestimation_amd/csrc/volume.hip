@@ -18,6 +18,8 @@
 // that file's bytes stay what they are.
 // sde_tsdf_mesh        the same crossings connected into triangles by surface nets (one vertex per cell with a crossing, one quad per crossing
 //                      edge): four launches, described in front of its kernels below.
+// sde_tsdf_render      the volume seen from a camera pose (depth, normal, colour) by ray casting: one launch, one thread per pixel, described in
+//                      front of its kernel below.
 //
 // Built with -ffp-contract=off: the projection, the average and the interpolation keep the operation order the header states, which
 // hip/volume.py's host twins repeat bit for bit.
@@ -466,6 +468,158 @@ __global__ void __launch_bounds__(TILE) mesh_faces(MeshP p) {
     }
 }
 
+// ---- sde_tsdf_render: ray casting -------------------------------------------------------------------------------------------------------------------
+// One thread per pixel, one launch.  A wave is an 8 x 8 pixel tile, a workgroup four of them side by side (32 x 8 pixels): neighbouring rays walk
+// neighbouring cells, so the eight corner loads of a sample fall into few cache lines per wave.  Per sample 8 weights and 8 tsdf values, all
+// sixteen loads issued before the first is used; the march is a chain of such round trips to the cache, and the kernel is bound by their latency.
+//
+// Skipping.  The result is defined by the full march over i = 0 .. n-1, but only VALID samples can matter, and a valid sample has
+// 0 <= g_r < n_r - 1 on every axis.  In exact arithmetic g_r is affine in s: g_r(s) = s * a_r + c_r with a_r = D_r / voxel,
+// c_r = (O_r - origin_r) / voxel - 0.5, D_r = R_0r rx + R_1r ry + R_2r, O_r = -(R_0r t_0 + R_1r t_1 + R_2r t_2), which fp64 gives from the fp32
+// inputs with a relative error of 2^-50.  The fp32 value the march computes differs from it, counted to first order with EPS = 2^-24:
+//   p_k = s ray_k, d_k = p_k - t_k, R_kr d_k, two sums:      |w_r - exact| <= EPS sum_k |R_kr| (5 |p_k| + 4 |t_k|) <= 5 EPS (A_r |s| + B_r),
+//   (w - o), / voxel, - 0.5 on a result in [0, 1024):        + 3 EPS (|g| + 0.5) <= 2e-4 grid units,
+// with A_r = sum_k |R_kr ray_k|, B_r = sum_k |R_kr t_k|.  The box is widened by m_r = 8 EPS (A_r smax + B_r) / voxel + 1e-3, smax = |near| + n step:
+// beyond twice the first-order count.  s_i itself is two roundings from near + i step, at most 2 EPS smax: the interval in s is widened by
+// 4 EPS smax before it becomes an index range, and that range by one index on either side.  Every sample outside the range is invalid whatever
+// the memory holds, the sample in front of the range among them: the march starts at its first index with prev cleared and ends at its last.
+constexpr int RENDER_TW = 32, RENDER_TH = 8;      // pixels per workgroup: four 8 x 8 waves side by side
+constexpr int MAX_SAMPLES = 65536;
+constexpr int MAX_PICTURE = 32768;                // pixels along either side
+
+struct RenderP {
+    const float* tsdf;
+    const float* weight;
+    const uint32_t* rgba;        // or null
+    const float* K;              // [3][3]
+    const float* C;              // [4][4]
+    float* depth;                // [H][W]
+    float* normal;               // [H][W][3] or null
+    uint32_t* picture;           // [H][W] or null
+    Grid g;
+    int H, W, n;
+    float near, step, min_weight;
+};
+
+__device__ __forceinline__ bool finite_f(float x) { return fabsf(x) < INFINITY; }       // a NaN fails the comparison
+
+__device__ __forceinline__ void render_miss(const RenderP& p, size_t px) {
+    p.depth[px] = 0.f;
+    if (p.normal) p.normal[3 * px] = 0.f, p.normal[3 * px + 1] = 0.f, p.normal[3 * px + 2] = 0.f;
+    if (p.picture) p.picture[px] = 0u;
+}
+
+__global__ void __launch_bounds__(RENDER_TW * RENDER_TH) tsdf_render(RenderP p) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int u = blockIdx.x * RENDER_TW + wave * 8 + (lane & 7), v = blockIdx.y * RENDER_TH + (lane >> 3);
+    if (u >= p.W || v >= p.H) return;
+    const size_t px = (size_t)v * p.W + u;
+    const Grid& g = p.g;
+    float R[3][3], t[3];
+    bool ok = g.nx >= 2 && g.ny >= 2 && g.nz >= 2;                                        // a dimension of 1: no cells
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) R[r][c] = p.C[4 * r + c], ok = ok && finite_f(R[r][c]);
+        t[r] = p.C[4 * r + 3], ok = ok && finite_f(t[r]);
+    }
+    const Pinhole cam = pinhole_load(p.K);
+    ok = ok && finite_f(cam.fx) && finite_f(cam.cx) && finite_f(cam.fy) && finite_f(cam.cy);
+    const float rx = cam.k00 * (float)u + cam.k02, ry = cam.k11 * (float)v + cam.k12;
+    // a ray component that is not finite makes d_0 or d_1, and with it every w_r, not finite at every s: no sample is valid
+    if (!ok || !finite_f(rx) || !finite_f(ry)) { render_miss(p, px); return; }
+
+    const float o[3] = {g.ox, g.oy, g.oz};
+    const int dim[3] = {g.nx, g.ny, g.nz};
+    const double ray[3] = {(double)rx, (double)ry, 1.0};
+    const double smax = fabs((double)p.near) + (double)p.n * (double)p.step, eps = 1.0 / 16777216.0, voxel = (double)g.voxel;
+    double slo = -(double)INFINITY, shi = (double)INFINITY;
+    bool empty = false;
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        double D = 0.0, O = 0.0, A = 0.0, B = 0.0;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const double Rk = (double)R[k][r];
+            D += Rk * ray[k], O -= Rk * (double)t[k], A += fabs(Rk * ray[k]), B += fabs(Rk * (double)t[k]);
+        }
+        const double a = D / voxel, c = (O - (double)o[r]) / voxel - 0.5, m = 8.0 * eps * (A * smax + B) / voxel + 1e-3;
+        const double lo = -m - c, hi = (double)(dim[r] - 1) + m - c;                   // lo <= s * a <= hi
+        if (a == 0.0) {
+            if (!(lo <= 0.0 && 0.0 <= hi)) empty = true;
+        } else {
+            const double s0 = lo / a, s1 = hi / a;
+            slo = fmax(slo, fmin(s0, s1)), shi = fmin(shi, fmax(s0, s1));
+        }
+    }
+    const double ds = 4.0 * eps * smax;
+    const double flo = floor((slo - ds - (double)p.near) / (double)p.step) - 1.0, fhi = ceil((shi + ds - (double)p.near) / (double)p.step) + 1.0;
+    if (empty || !(flo <= fhi) || !(fhi >= 0.0) || !(flo <= (double)(p.n - 1))) { render_miss(p, px); return; }
+    const int i0 = flo > 0.0 ? (int)flo : 0, i1 = fhi < (double)(p.n - 1) ? (int)fhi : p.n - 1;
+
+    const size_t sy = (size_t)g.nx, sz = (size_t)g.nx * g.ny;
+    const float top[3] = {(float)(g.nx - 2), (float)(g.ny - 2), (float)(g.nz - 2)};
+    bool prev = false;
+    float tp = 0.f;
+    for (int i = i0; i <= i1; ++i) {
+        const float s = p.near + (float)i * p.step;
+        const float d0 = s * rx - t[0], d1 = s * ry - t[1], d2 = s - t[2];
+        float gr[3], b[3];
+        bool valid = true;
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+            const float w = R[0][r] * d0 + R[1][r] * d1 + R[2][r] * d2;
+            gr[r] = (w - o[r]) / g.voxel - 0.5f;
+            b[r] = floorf(gr[r]);
+            valid = valid && finite_f(gr[r]) && b[r] >= 0.f && b[r] <= top[r];
+        }
+        if (!valid) { prev = false; continue; }
+        const float fx = gr[0] - b[0], fy = gr[1] - b[1], fz = gr[2] - b[2];
+        const int bx = (int)b[0], by = (int)b[1], bz = (int)b[2];
+        const size_t base = (size_t)bz * sz + (size_t)by * sy + (size_t)bx;
+        float wt[8], T[8];                                                               // corner c = dx + 2 dy + 4 dz
+#pragma unroll
+        for (int c = 0; c < 8; ++c) {
+            const size_t at = base + (c & 1) + ((c >> 1) & 1) * sy + (c >> 2) * sz;
+            wt[c] = p.weight[at];
+            T[c] = p.tsdf[at];
+        }
+#pragma unroll
+        for (int c = 0; c < 8; ++c) valid = valid && wt[c] >= p.min_weight;
+        if (!valid) { prev = false; continue; }
+        float cz[4], e[2];                                                               // c_zy at 2 z + y
+#pragma unroll
+        for (int q = 0; q < 4; ++q) cz[q] = T[2 * q] + fx * (T[2 * q + 1] - T[2 * q]);
+        e[0] = cz[0] + fy * (cz[1] - cz[0]);
+        e[1] = cz[2] + fy * (cz[3] - cz[2]);
+        const float ti = e[0] + fz * (e[1] - e[0]);
+        if (prev && tp > 0.f && ti <= 0.f) {
+            const float sp = p.near + (float)(i - 1) * p.step;
+            p.depth[px] = sp + p.step * (tp / (tp - ti));
+            if (p.normal) {
+                float X[4];
+#pragma unroll
+                for (int q = 0; q < 4; ++q) X[q] = T[2 * q + 1] - T[2 * q];
+                const float x0 = X[0] + fy * (X[1] - X[0]), x1 = X[2] + fy * (X[3] - X[2]);
+                const float gx = x0 + fz * (x1 - x0);
+                const float y0 = cz[1] - cz[0], y1 = cz[3] - cz[2];
+                const float gy = y0 + fz * (y1 - y0);
+                const float gz = e[1] - e[0];
+                const float len = sqrtf(gx * gx + gy * gy + gz * gz);
+                const bool unit = len > 0.f && len < INFINITY;
+#pragma unroll
+                for (int r = 0; r < 3; ++r) p.normal[3 * px + r] = unit ? (R[r][0] * gx + R[r][1] * gy + R[r][2] * gz) / len : 0.f;
+            }
+            if (p.picture)
+                p.picture[px] = (p.rgba[base + (fx >= 0.5f ? 1 : 0) + (fy >= 0.5f ? sy : 0) + (fz >= 0.5f ? sz : 0)] & 0x00ffffffu) | 0xff000000u;
+            return;
+        }
+        prev = true;
+        tp = ti;
+    }
+    render_miss(p, px);
+}
+
 bool dims_ok(int nx, int ny, int nz) {
     return nx >= 1 && ny >= 1 && nz >= 1 && nx <= MAX_DIM && ny <= MAX_DIM && nz <= MAX_DIM && (long)nx * ny * nz <= MAX_VOXELS;
 }
@@ -562,6 +716,28 @@ int sde_tsdf_mesh(const float* tsdf, const float* weight, const uint8_t* rgba, i
     hipLaunchKernelGGL(mesh_vertices, dim3(grid), dim3(TILE), 0, (hipStream_t)stream, p);
     hipLaunchKernelGGL(mesh_faces, dim3(grid), dim3(TILE), 0, (hipStream_t)stream, p);
     SDE_CHECK_LAUNCH("sde_tsdf_mesh");
+    return SDE_OK;
+}
+
+int sde_tsdf_render(const float* tsdf, const float* weight, const uint8_t* rgba, int nx, int ny, int nz, const float* origin, float voxel,
+                    float min_weight, const float* K, const float* C, int H, int W, float near, float step, int n, float* depth, float* normal,
+                    uint8_t* picture, sde_stream_t stream) {
+    SDE_CHECK_ARG(dims_ok(nx, ny, nz), "sde_tsdf_render: every dimension must lie in [1, %d] and their product be at most 2^30 (%d x %d x %d)", MAX_DIM, nx, ny,
+                  nz);
+    SDE_CHECK_ARG(voxel > 0.f, "sde_tsdf_render: voxel must be positive (%g)", (double)voxel);
+    SDE_CHECK_ARG(min_weight >= 1.f, "sde_tsdf_render: min_weight must be at least 1 (%g)", (double)min_weight);
+    SDE_CHECK_ARG(H >= 1 && W >= 1 && H <= MAX_PICTURE && W <= MAX_PICTURE, "sde_tsdf_render: H and W must lie in [1, %d] (%d x %d)", MAX_PICTURE, H, W);
+    SDE_CHECK_ARG(n >= 1 && n <= MAX_SAMPLES, "sde_tsdf_render: the sample count must lie in [1, %d] (%d)", MAX_SAMPLES, n);
+    SDE_CHECK_ARG(step > 0.f && step < INFINITY && fabsf(near) < INFINITY, "sde_tsdf_render: near must be finite, step positive and finite (%g, %g)",
+                  (double)near, (double)step);                                                           // a NaN fails the comparison
+    SDE_CHECK_ARG(tsdf && weight && origin && K && C && depth, "sde_tsdf_render: null pointer");
+    SDE_CHECK_ARG(!picture || rgba, "sde_tsdf_render: a picture needs a volume with rgba");
+    SDE_CHECK_ARG(((uintptr_t)rgba & 3) == 0 && ((uintptr_t)picture & 3) == 0, "sde_tsdf_render: rgba and picture must be 4-byte aligned");
+    RenderP p{tsdf, weight, (const uint32_t*)rgba, K, C, depth, normal, (uint32_t*)picture, Grid{nx, ny, nz, origin[0], origin[1], origin[2], voxel},
+              H, W, n, near, step, min_weight};
+    const dim3 grid((unsigned)((W + RENDER_TW - 1) / RENDER_TW), (unsigned)((H + RENDER_TH - 1) / RENDER_TH));
+    hipLaunchKernelGGL(tsdf_render, grid, dim3(RENDER_TW * RENDER_TH), 0, (hipStream_t)stream, p);
+    SDE_CHECK_LAUNCH("sde_tsdf_render");
     return SDE_OK;
 }
 

@@ -521,6 +521,26 @@ def volume_arg(volume, device=None):
     return volume
 
 
+def render_arg(render, volume):
+    """render=None -> None; else dict(normals=True, picture=True, min_weight=1, near=None, far=None, step=None), the arguments of
+    hip.volume.TsdfVolume.render, checked against the volume -> (normals, picture, min_weight, near, far, step): part of the replay key."""
+    if render is None:
+        return None
+    if volume is None:
+        raise ValueError("PairPredictor: render= shows the volume the sequence is fused into, it needs volume=TsdfVolume(...)")
+    known = ("normals", "picture", "min_weight", "near", "far", "step")
+    if not isinstance(render, dict) or set(render) - set(known):
+        raise ValueError(f"PairPredictor: render must be None or a dict with keys from {known}, got {render!r}")
+    from ..hip.volume import check_min_weight, check_render
+    normals, picture = bool(render.get("normals", True)), bool(render.get("picture", True))
+    if picture and not volume.colour:
+        raise ValueError("PairPredictor: render=dict(picture=True) needs a volume with colour; pass picture=False")
+    near, far, step = (float(np.float32(d if render.get(k) is None else render[k])) for k, d in (("near", volume.min_depth), ("far", volume.max_depth),
+                                                                                                ("step", volume.voxel)))
+    check_render((1, 1), near, far, step)                     # the sample count; the picture's size is checked when the first frame is seen
+    return normals, picture, check_min_weight(render.get("min_weight", 1)), near, far, step
+
+
 class _VolumeState:
     """What the volume fusion keeps on the device from one window to the next, beside the temporal state: C, the world-to-camera pose of the
     window's target (the first target of a sequence is the world), and T, the step previous target -> this one that C is advanced by before the
@@ -580,7 +600,8 @@ class PairPredictor(_Predictor):
 
     `stream(..., volume=vol)` fuses the sequence into one TSDF volume (hip/volume.py): sde_pose_compose chains the world-to-camera pose from the
     model's step poses on the device and sde_tsdf_integrate averages every window's depth -- the one the pictures show -- into the caller's grid
-    through it, inside the same graph."""
+    through it, inside the same graph.  With `render=dict(...)` as well, sde_tsdf_render then shows the volume from the window's own camera, and
+    the record holds the model's depth, normal and colour for the frame."""
     NAME = "PairPredictor"
 
     def __init__(self, cfg, model=None, chain=None, device="cuda", use_graph=None, vmax=None, gamma=0.8):
@@ -614,7 +635,7 @@ class PairPredictor(_Predictor):
             self._volume[key] = _VolumeState(self.device)
         return self._volume[key]
 
-    def _chain(self, plan, frames, K, K_src, present, rigid_only, max_flow, temporal=None, want_u16=False, cloud=None, volume=None):
+    def _chain(self, plan, frames, K, K_src, present, rigid_only, max_flow, temporal=None, want_u16=False, cloud=None, volume=None, render=None):
         N = 1 + self.n
         img, _ = self._aug.prep(frames, self._no_jitter(N), plan.h, plan.w, tabs=(plan.xtab, plan.ytab))
         nd = 2 if self.pose_use_depth else 1                   # frames the depth net sees
@@ -662,6 +683,10 @@ class PairPredictor(_Predictor):
             vol.compose(vs.T, vs.C)
             vol.integrate(shown, ymap, xmap, K_src[:1], vs.C, frame=frames[:1])
             out["world_to_camera"] = vs.C.clone()               # the state moves on with the next window, on the other slot: this slot's copy
+            if render is not None:                              # the model as this camera sees it, this window's depth included
+                normals, picture, min_weight, near, far, step = render
+                out["model_depth"], out["model_normal"], out["model_picture"] = vol.render(
+                    K_src[:1], vs.C, (plan.Hs, plan.Ws), near=near, far=far, step=step, min_weight=min_weight, normals=normals, picture=picture)
             if not inverted:                                    # this window's pose to the frame at +1 is the next window's step
                 vs.T.copy_(pose[j])
             vs.started.fill_(True)
@@ -680,7 +705,7 @@ class PairPredictor(_Predictor):
             raise ValueError("PairPredictor: the flow needs intrinsics (the source-size K [3,3] of the frames)")
         return self._host_K("PairPredictor", intrinsics, 1)[0]          # one K for the whole window
 
-    def _run(self, slot, plan, intrinsics, K_host, present, rigid_only, max_flow, temporal=None, want_u16=False, cloud=None, volume=None):
+    def _run(self, slot, plan, intrinsics, K_host, present, rigid_only, max_flow, temporal=None, want_u16=False, cloud=None, volume=None, render=None):
         N = 1 + self.n
         K = self._device_copy(slot, "K", plan.intrinsics(intrinsics), N)
         K_src =self._device_copy(slot, "K_src", K_host, self.n)
@@ -695,11 +720,13 @@ class PairPredictor(_Predictor):
         if volume is not None:                                  # the volume's parameters and addresses are part of what the graph holds; its arrays move on
             vol, vs = volume                                    # with every run, so the eager run before a capture is taken back like the states'
             key += (("volume",) + vol.params(),)
+            if render is not None:
+                key += (("render",) + render,)
             persistent = persistent + vs.tensors() + [t for t in (vol.tsdf, vol.weight, vol.rgba) if t is not None]
         return self._replay(slot, key, lambda: self._chain(plan, slot.frames, K, K_src, bool(present), bool(rigid_only), max_flow, temporal, bool(want_u16), cloud,
-                                                           volume), persistent=persistent)
+                                                           volume, render), persistent=persistent)
 
-    def predict(self, frames, intrinsics, present=True, rigid_only=False, max_flow=None, temporal=None, volume=None):
+    def predict(self, frames, intrinsics, present=True, rigid_only=False, max_flow=None, temporal=None, volume=None, render=None):
         """frames: the window, a list of 1 + n uint8 [H,W,3] RGB frames of one size -- the target, then the n context frames in the order the dataset
         emits `ctx_img` (self.offsets, ascending, e.g. the frames at -1 and +1).  intrinsics: the source-size K [3,3] of the frames.  Returns a
         dict of device tensors: `depth` [1,H,W], `canvas` [1,2H,W,3], `depth_net` [1,h,w] as DepthPredictor returns them for the target; `pose`
@@ -709,11 +736,14 @@ class PairPredictor(_Predictor):
         still returned).  max_flow: the flow length, in pixels, that reaches full saturation in `flow_canvas`; default 5 % of the frame's
         width -- a presentation constant, like gamma.  present=False skips the three pictures.  Translations, and with them the flow's share
         that comes from them, are up to the scale of the monocular depth.  No host synchronisation after the first call of a size.  predict keeps
-        nothing from call to call: temporal fusion and volume fusion are `stream`'s, and anything but temporal=None, volume=None is refused."""
+        nothing from call to call: temporal fusion and volume fusion are `stream`'s, and anything but temporal=None, volume=None, render=None is
+        refused."""
         if temporal is not None:
             raise ValueError("PairPredictor.predict is stateless: temporal fusion needs the frames in order, use stream(..., temporal=...)")
         if volume is not None:
             raise ValueError("PairPredictor.predict is stateless: volume fusion chains the poses of frames in order, use stream(..., volume=...)")
+        if render is not None:
+            raise ValueError("PairPredictor.predict is stateless: render= shows the volume a sequence is fused into, use stream(..., volume=..., render=...)")
         t = as_window(frames, self.n)
         K_host = self._source_intrinsics(intrinsics)
         plan = self.plan(t.shape[1], t.shape[2])
@@ -735,7 +765,8 @@ class PairPredictor(_Predictor):
         res["pose_next"] = invert_pose_np(res["pose"][j]) if inverted else res["pose"][j].copy()
         return res
 
-    def stream(self, frames_iter, intrinsics, present=True, rigid_only=False, max_flow=None, temporal=None, want_u16=False, cloud=None, volume=None):
+    def stream(self, frames_iter, intrinsics, present=True, rigid_only=False, max_flow=None, temporal=None, want_u16=False, cloud=None, volume=None,
+               render=None):
         """Generator over host frames of a sequence (uint8 [H,W,3] RGB, one at a time, one size).  Keeps a sliding window and yields, in order, one
         dict of host arrays per target frame that has all its context frames: the outputs of `predict` (`depth` [H,W], `canvas` [2H,W,3], `pose`,
         `flow`, `flow_valid`, `flow_canvas`, `motion`; with present=False `depth_net` instead of the pictures), `index`, the target's position in
@@ -758,10 +789,18 @@ class PairPredictor(_Predictor):
         (sde_tsdf_integrate, with the source-size intrinsics and the target's colours) through the world-to-camera pose chained on the device
         from the model's own step poses (sde_pose_compose); every record then holds `world_to_camera` [4,4], the pose its depth went in with: the
         identity for the first target, which is the world.  Every call, and every change of the frame size, starts a new chain; the volume is the
-        caller's and is never reset here, so several sequences may go into one.  ValueError for a model without a context one frame away."""
+        caller's and is never reset here, so several sequences may go into one.  ValueError for a model without a context one frame away.
+
+        render=dict(normals=True, picture=True, min_weight=1) (with volume=; also near=, far=, step=, default the volume's min_depth, max_depth
+        and voxel): after the window's depth has gone in, the volume is rendered from the window's own camera (sde_tsdf_render, hip.volume.
+        TsdfVolume.render: the source-size intrinsics, the chained pose, the frame's size) inside the same graph.  Every record then holds
+        `model_depth` [H,W] float32, the z-depth of the fused model's surface along every pixel's ray, 0 where there is none -- the depth that
+        is consistent over the whole sequence -- and, unless switched off, `model_normal` [H,W,3] float32 in camera coordinates and
+        `model_picture` [H,W,4] uint8."""
         K_host = self._source_intrinsics(intrinsics)
         fuse = temporal_args(temporal)
         volume = volume_arg(volume, self.device)
+        render = render_arg(render, volume)
         cloud, _ = DepthPredictor._cloud_args(cloud, K_host, 1)
         want_u16 = bool(want_u16 and present)
         if fuse is not None or volume is not None:
@@ -769,7 +808,8 @@ class PairPredictor(_Predictor):
         names = [k for k, on in (("depth", present), ("canvas", present), ("depth_net", not present or fuse is not None), ("depth_net_raw", fuse is not None),
                                  ("temporal_state", fuse is not None), ("pose", True), ("flow", True), ("flow_valid", True), ("flow_canvas", present),
                                  ("motion", True), ("depth_u16", want_u16), ("points", cloud is not None), ("count", cloud is not None),
-                                 ("world_to_camera", volume is not None)) if on]
+                                 ("world_to_camera", volume is not None), ("model_depth", render is not None),
+                                 ("model_normal", render is not None and render[0]), ("model_picture", render is not None and render[1])) if on]
         live, live_v = [], []                                  # the states this call has reset and is advancing
         lo, hi = min(self.offsets + (0,)), max(self.offsets + (0,))
         targets = []
@@ -800,11 +840,14 @@ class PairPredictor(_Predictor):
                     vs.reset()
                     live_v[:] = [vs]
                 vol = (volume, vs)
+                if render is not None:
+                    from ..hip.volume import check_render
+                    check_render((plan.Hs, plan.Ws), render[3], render[4], render[5])
             if fuse is None:
-                return self._run(slot, plan, intrinsics, K_host, present, rigid_only, max_flow, want_u16=want_u16, cloud=cloud, volume=vol)
+                return self._run(slot, plan, intrinsics, K_host, present, rigid_only, max_flow, want_u16=want_u16, cloud=cloud, volume=vol, render=render)
             st = self._temporal_state(plan)
             if not live or live[0] is not st:                  # the first window of this call, or frames of another size: an empty state
                 st.reset()
                 live[:] = [st]
-            return self._run(slot, plan, intrinsics, K_host, present, rigid_only, max_flow, temporal=fuse + (st,), want_u16=want_u16, cloud=cloud, volume=vol)
+            return self._run(slot, plan, intrinsics, K_host, present, rigid_only, max_flow, temporal=fuse + (st,), want_u16=want_u16, cloud=cloud, volume=vol, render=render)
         yield from self._pump(windows(), names, run, result)

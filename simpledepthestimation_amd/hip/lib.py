@@ -146,6 +146,7 @@ _PROTOS = {
     "sde_tsdf_points": ([_P, _P, _P, _I, _I, _I, POINTER(c_float), _F, _F, _P, c_size_t, _P, ctypes.c_long, _P, _P], c_int),
     "sde_tsdf_mesh_ws_bytes": ([_I, _I, _I], c_size_t),
     "sde_tsdf_mesh": ([_P, _P, _P, _I, _I, _I, POINTER(c_float), _F, _F, _P, c_size_t, _P, ctypes.c_long, _P, ctypes.c_long, _P, _P], c_int),
+    "sde_tsdf_render": ([_P, _P, _P, _I, _I, _I, POINTER(c_float), _F, _F, _P, _P, _I, _I, _F, _F, _I, _P, _P, _P, _P], c_int),
 }
 
 _lib = None

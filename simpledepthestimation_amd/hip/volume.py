@@ -3,7 +3,8 @@ sde_tsdf_points; csrc/volume.hip).  `TsdfVolume` owns the three device arrays an
 `points_host` are their host twins -- the same fp32 operations in the same order in numpy, for machines without a GPU and for the tests,
 which compare the two bit for bit.  Every frame's depth is averaged into the voxel grid through its world-to-camera pose; the zero crossings
 of the grid are the surface, handed out as the 16-byte records of hip.cloud (as_records and the PLY writer take them as they are), or connected
-into a triangle mesh by surface nets (sde_tsdf_mesh: `TsdfVolume.mesh`, `save_mesh`, the twin `mesh_host`, `write_mesh_ply` / `read_mesh_ply`)."""
+into a triangle mesh by surface nets (sde_tsdf_mesh: `TsdfVolume.mesh`, `save_mesh`, the twin `mesh_host`, `write_mesh_ply` / `read_mesh_ply`), or
+seen from a camera pose by ray casting (sde_tsdf_render: `TsdfVolume.render`, the twin `render_host`)."""
 import ctypes
 import warnings
 
@@ -56,6 +57,28 @@ def check_min_weight(min_weight):
     if not min_weight >= 1.0:
         raise ValueError(f"TsdfVolume: min_weight must be at least 1, got {min_weight!r}")
     return min_weight
+
+
+MAX_SAMPLES, MAX_PICTURE = 65536, 32768
+
+
+def check_render(size, near, far, step):
+    """The argument errors sde_tsdf_render refuses, raised as ValueError before anything touches the device.  -> (H, W, near, step, n): near and
+    step as the kernel receives them (fp32 values as Python floats) and the sample count n = ceil((far - near) / step), from the fp32 values."""
+    try:
+        H, W = (int(s) for s in size)
+        exact = len(tuple(size)) == 2 and all(int(s) == s for s in size)
+    except (TypeError, ValueError):
+        exact = False
+    if not exact or not (1 <= H <= MAX_PICTURE and 1 <= W <= MAX_PICTURE):
+        raise ValueError(f"TsdfVolume.render: size must be (H, W), integers in [1, {MAX_PICTURE}], got {size!r}")
+    near, far, step = (float(np.float32(x)) for x in (near, far, step))
+    if not (np.isfinite(near) and np.isfinite(far) and np.isfinite(step)) or not step > 0.0:
+        raise ValueError(f"TsdfVolume.render: near and far must be finite, step positive and finite, got ({near!r}, {far!r}, {step!r})")
+    n = int(np.ceil((far - near) / step))
+    if not 1 <= n <= MAX_SAMPLES:
+        raise ValueError(f"TsdfVolume.render: ceil((far - near) / step) samples must lie in [1, {MAX_SAMPLES}], got {n} (near {near}, far {far}, step {step})")
+    return H, W, near, step, n
 
 
 def pose_compose(T, C):
@@ -191,6 +214,33 @@ class TsdfVolume:
                                       L.ptr(workspace), workspace.numel() * 4, L.ptr(vertices), cap_vertices, L.ptr(faces), cap_faces, L.ptr(count),
                                       L.stream()), "sde_tsdf_mesh")
         return vertices, faces, count
+
+    def render(self, K, C, size, near=None, far=None, step=None, min_weight=1, normals=True, picture=True, out=None):
+        """The volume seen from a camera (sde_tsdf_render: ray casting) -> (depth [H,W] fp32, normal [H,W,3] fp32 or None, picture [H,W,4] uint8
+        or None) on the device.  K [3,3] fp32 at the picture's size and C [4,4] fp32, world -> camera (rigid: the caller's responsibility), are
+        CUDA tensors on the volume's device -- the pose `compose` chains goes in as it is.  size = (H, W).  The ray of every pixel is sampled at
+        the z-depths near + i * step, i < n = ceil((far - near) / step); defaults: near = min_depth, far = max_depth, step = voxel.  depth is the
+        z-depth of the first crossing from positive to negative tsdf between two valid samples (all eight voxels around a sample have weight >=
+        min_weight), 0 where there is none; normal the unit normal in camera coordinates, towards the side the surface was seen from; picture
+        the voxel colour with alpha 255 (picture=True needs a volume with colour); both zeros on a miss.  out: optional (depth, normal,
+        picture) destinations (None for those not wanted).  One launch on the current stream, no host synchronisation."""
+        min_weight = check_min_weight(min_weight)
+        H, W, near, step, n = check_render(size, self.min_depth if near is None else near, self.max_depth if far is None else far,
+                                           self.voxel if step is None else step)
+        if picture and self.rgba is None:
+            raise ValueError("TsdfVolume.render: picture=True needs a volume with colour (colour=True); pass picture=False")
+        K = A.as_K("tsdf_render", K, 1, self.device)
+        if torch.is_tensor(C) and C.dim() == 3:
+            C = C[0]
+        C = A.same_device_tensor("tsdf_render", "C", C, torch.float32, (4, 4), self.device).contiguous()
+        depth, normal, pic = out if out is not None else (None, None, None)
+        depth = A.dst("tsdf_render", depth, (H, W), torch.float32, True, self.device)
+        normal = A.dst("tsdf_render", normal, (H, W, 3), torch.float32, bool(normals), self.device)
+        pic = A.dst("tsdf_render", pic, (H, W, 4), torch.uint8, bool(picture), self.device)
+        nx, ny, nz = self.dims
+        L.check(L.lib().sde_tsdf_render(L.ptr(self.tsdf), L.ptr(self.weight), L.ptr(self.rgba), nx, ny, nz, self._origin, self.voxel, min_weight,
+                                        L.ptr(K), L.ptr(C), H, W, near, step, n, L.ptr(depth), L.ptr(normal), L.ptr(pic), L.stream()), "sde_tsdf_render")
+        return depth, normal, pic
 
     def save_mesh(self, path, min_weight=1, cap_vertices=None, cap_faces=None):
         """The mesh as a binary PLY (write_mesh_ply).  Synchronises.  When either cap was too small the mesh is taken once more with exactly the
@@ -447,3 +497,90 @@ def mesh_host(tsdf, weight, rgba, origin, voxel, min_weight=1, cap_vertices=None
     if cap_faces is not None:
         faces = faces[:int(cap_faces)]
     return rec, np.ascontiguousarray(faces), np.array([nv, nf], np.int32)
+
+
+def render_host(tsdf, weight, rgba, K, C, size, origin, voxel, near, step, n, min_weight=1):
+    """The host twin of sde_tsdf_render -> (depth [H,W] float32, normal [H,W,3] float32, picture [H,W,4] uint8 or None without rgba): the bits the
+    kernel writes.  The same fp32 operations in the same order, vectorised over the pixels with a loop over the n samples: the FULL march, no
+    sample is skipped."""
+    f32 = np.float32
+    tsdf, weight = np.asarray(tsdf, dtype=f32), np.asarray(weight, dtype=f32)
+    nz, ny, nx = tsdf.shape
+    H, W = (int(s) for s in size)
+    K, C = np.asarray(K, dtype=f32).reshape(3, 3), np.asarray(C, dtype=f32).reshape(4, 4)
+    R, t = C[:3, :3], C[:3, 3]
+    voxel, near, step, min_weight = f32(voxel), f32(near), f32(step), f32(check_min_weight(min_weight))
+    o = [f32(x) for x in origin]
+    depth, normal = np.zeros((H, W), f32), np.zeros((H, W, 3), f32)
+    picture = np.zeros((H, W, 4), np.uint8) if rgba is not None else None
+    fx, cx, fy, cy = K[0, 0], K[0, 2], K[1, 1], K[1, 2]
+    if not (np.isfinite(C[:3]).all() and np.isfinite([fx, cx, fy, cy]).all()) or min(nx, ny, nz) < 2:
+        return depth, normal, picture
+    flat_t, flat_w = tsdf.reshape(-1), weight.reshape(-1)
+    flat_c = np.asarray(rgba).reshape(-1, 4) if rgba is not None else None
+    sy, sz = nx, nx * ny
+    corner = [(c & 1) + ((c >> 1) & 1) * sy + (c >> 2) * sz for c in range(8)]
+    with np.errstate(all="ignore"):
+        k00, k11, k02, k12 = f32(1) / fx, f32(1) / fy, (f32(-1) * cx) / fx, (f32(-1) * cy) / fy
+        rx = np.broadcast_to((k00 * np.arange(W, dtype=f32) + k02)[None, :], (H, W)).reshape(-1)
+        ry = np.broadcast_to((k11 * np.arange(H, dtype=f32) + k12)[:, None], (H, W)).reshape(-1)
+        P = rx.size
+        live = np.ones(P, bool)                                  # no hit so far
+        prev = np.zeros(P, bool)
+        tp = np.zeros(P, f32)
+        dep, nor, pic = depth.reshape(-1), normal.reshape(-1, 3), (picture.reshape(-1, 4) if picture is not None else None)
+        top = [f32(nx - 2), f32(ny - 2), f32(nz - 2)]
+        for i in range(int(n)):
+            if not live.any():
+                break
+            s = near + f32(i) * step
+            d = [s * rx - t[0], s * ry - t[1], np.full(P, s - t[2], f32)]
+            g, b = [], []
+            valid = live.copy()
+            for r in range(3):
+                w = R[0, r] * d[0] + R[1, r] * d[1] + R[2, r] * d[2]
+                gr = (w - o[r]) / voxel - f32(0.5)
+                br = np.floor(gr)
+                valid &= np.isfinite(gr) & (br >= 0) & (br <= top[r])
+                g.append(gr)
+                b.append(br)
+            at = np.nonzero(valid)[0]
+            bi = [b[r][at].astype(np.int64) for r in range(3)]
+            base = bi[2] * sz + bi[1] * sy + bi[0]
+            ok = np.ones(at.size, bool)
+            for c in corner:
+                ok &= flat_w[base + c] >= min_weight
+            prev[live & ~valid] = False                          # outside the grid ...
+            prev[at[~ok]] = False                                # ... or next to a voxel that is not valid: the sample clears prev
+            at, base = at[ok], base[ok]
+            f = [g[r][at] - b[r][at] for r in range(3)]
+            T = [flat_t[base + c] for c in corner]
+            cz = [T[2 * q] + f[0] * (T[2 * q + 1] - T[2 * q]) for q in range(4)]
+            e = [cz[0] + f[1] * (cz[1] - cz[0]), cz[2] + f[1] * (cz[3] - cz[2])]
+            ti = e[0] + f[2] * (e[1] - e[0])
+            hit = prev[at] & (tp[at] > 0) & (ti <= 0)
+            ha = at[hit]
+            if ha.size:
+                sp = near + f32(i - 1) * step
+                th, tq = ti[hit], tp[ha]
+                dep[ha] = sp + step * (tq / (tq - th))
+                fh = [x[hit] for x in f]
+                X = [(T[2 * q + 1] - T[2 * q])[hit] for q in range(4)]
+                x0, x1 = X[0] + fh[1] * (X[1] - X[0]), X[2] + fh[1] * (X[3] - X[2])
+                gx = x0 + fh[2] * (x1 - x0)
+                y0, y1 = (cz[1] - cz[0])[hit], (cz[3] - cz[2])[hit]
+                gy = y0 + fh[2] * (y1 - y0)
+                gz = (e[1] - e[0])[hit]
+                ln = np.sqrt(gx * gx + gy * gy + gz * gz)
+                unit = (ln > 0) & (ln < np.inf)
+                for r in range(3):
+                    nor[ha, r] = np.where(unit, (R[r, 0] * gx + R[r, 1] * gy + R[r, 2] * gz) / ln, f32(0))
+                if pic is not None:
+                    near_c = base[hit] + (fh[0] >= f32(0.5)) * 1 + (fh[1] >= f32(0.5)) * sy + (fh[2] >= f32(0.5)) * sz
+                    pic[ha, :3] = flat_c[near_c, :3]
+                    pic[ha, 3] = 255
+                live[ha] = False
+            keep = at[~hit]
+            prev[keep] = True
+            tp[keep] = ti[~hit]
+    return depth, normal, picture

@@ -34,7 +34,12 @@ crossings as coloured points (the record and the PLY layout of --save-cloud), in
 the corner of the first voxel (default: the first camera at the middle of the near face), --trunc M the truncation distance (default 4 V),
 --min-weight N the number of observations a voxel needs (default 1).  --save-mesh adds `volume_mesh.ply`, the same surface as a triangle mesh
 (TsdfVolume.save_mesh: one vertex per grid cell the surface passes through, two triangles per crossing, coloured like the points).  All lengths are in the model's depth units: a monocular model's scale is
-not aligned.  The model needs a context one frame away."""
+not aligned.  The model needs a context one frame away.
+
+--render-volume (with --volume) looks at the model while it grows: after every frame's depth has gone in, the volume is rendered from that
+frame's own camera (PairPredictor.stream(..., render=...): ray casting on the device, TsdfVolume.render) and `<stem>_model.png` holds the colour
+picture, `<stem>_model_depth.png` the model's depth along every pixel's ray in the --save-depth format (0 where the ray finds no surface);
+--save-normals adds `<stem>_model_normal.png`, the surface normal in camera coordinates as (n * 0.5 + 0.5) * 255.  --min-weight applies."""
 import argparse
 import os
 import sys
@@ -69,6 +74,9 @@ def parse_args(argv=None):
                                                                                           "coordinates (default: the camera at the middle of the near face)")
     p.add_argument("--min-weight", type=float, default=1.0, help="with --volume: observations a voxel needs to count as surface (default 1)")
     p.add_argument("--save-mesh", action="store_true", help="with --volume: also write volume_mesh.ply, the surface as a triangle mesh")
+    p.add_argument("--render-volume", action="store_true", help="with --volume: also write <stem>_model.png and <stem>_model_depth.png, the volume seen "
+                                                                "from the frame's camera (colour, and depth * 255 as a 16-bit PNG)")
+    p.add_argument("--save-normals", action="store_true", help="with --render-volume: also write <stem>_model_normal.png, (normal * 0.5 + 0.5) * 255")
     p.add_argument("--cloud-step", type=int, default=1, help="the cloud takes every N-th pixel of every N-th row (default 1: all)")
     p.add_argument("--opts", default=[], nargs=argparse.REMAINDER, help="config overrides as KEY VALUE pairs, e.g. MODEL.WEIGHTS model.pth")
     args = p.parse_args(argv)
@@ -93,6 +101,10 @@ def parse_args(argv=None):
         p.error("--voxel, --trunc and --volume-origin need --volume NX NY NZ")
     elif args.save_mesh:
         p.error("--save-mesh needs --volume NX NY NZ")
+    elif args.render_volume:
+        p.error("--render-volume needs --volume NX NY NZ")
+    if args.save_normals and not args.render_volume:
+        p.error("--save-normals needs --render-volume")
     for flag in ("save_flow", "save_trajectory", "rigid_only", "stabilise", "volume"):
         if getattr(args, flag) not in (None, False) and not args.pairs:
             p.error(f"--{flag.replace('_', '-')} needs --pairs")
@@ -143,6 +155,20 @@ def trajectory_steps(results, offsets):
     return steps, start
 
 
+def model_depth_u16(depth):
+    """depth [H,W] float32 -> uint16 [H,W]: the fp32 product depth * 255, truncated and cut at 65535 -- the --save-depth format."""
+    import numpy as np
+    v = np.asarray(depth, dtype=np.float32) * np.float32(255)
+    return np.where(v >= 65535, 65535, np.where(v > 0, v, 0)).astype(np.uint16)
+
+
+def normal_picture(normal):
+    """normal [H,W,3] float32, unit vectors or zeros -> uint8 [H,W,3]: (n * 0.5 + 0.5) * 255, truncated; a miss is mid-grey."""
+    import numpy as np
+    v = (np.asarray(normal, dtype=np.float32) * np.float32(0.5) + np.float32(0.5)) * np.float32(255)
+    return np.clip(np.nan_to_num(v), 0, 255).astype(np.uint8)
+
+
 def run_pairs(args, cfg, files):
     import numpy as np
     from PIL import Image
@@ -165,8 +191,9 @@ def run_pairs(args, cfg, files):
     if args.volume is not None:
         from ..hip.volume import TsdfVolume
         volume = TsdfVolume(args.volume, args.voxel, origin=args.volume_origin, trunc=args.trunc, device=predictor.device, **depth_range)
+    render = dict(normals=args.save_normals, picture=True, min_weight=args.min_weight) if args.render_volume else None
     for res in predictor.stream((read_rgb(f) for f in files), K, rigid_only=args.rigid_only, temporal=temporal, want_u16=args.save_depth, cloud=cloud,
-                                volume=volume):
+                                volume=volume, render=render):
         stem = os.path.splitext(os.path.basename(files[res["index"]]))[0]
         Image.fromarray(res["canvas"]).save(os.path.join(args.output, stem + ".png"), format="PNG", compress_level=3)
         if args.save_flow:
@@ -178,6 +205,11 @@ def run_pairs(args, cfg, files):
             write_ply(os.path.join(args.output, stem + ".ply"), as_records(res["points"], res["count"])[0])
         if args.save_state:
             Image.fromarray(state_picture(res["temporal_state"])).save(os.path.join(args.output, stem + "_state.png"), format="PNG", compress_level=3)
+        if render is not None:
+            Image.fromarray(res["model_picture"][..., :3]).save(os.path.join(args.output, stem + "_model.png"), format="PNG", compress_level=3)
+            Image.fromarray(model_depth_u16(res["model_depth"])).save(os.path.join(args.output, stem + "_model_depth.png"), format="PNG", compress_level=3)
+            if args.save_normals:
+                Image.fromarray(normal_picture(res["model_normal"])).save(os.path.join(args.output, stem + "_model_normal.png"), format="PNG", compress_level=3)
         kept.append({"index": res["index"], "pose": res["pose"].copy(), "pose_next": res["pose_next"]})
     if not kept:
         raise SystemExit(f"--pairs: {len(files)} frame(s) are fewer than one window of the model (offsets {predictor.offsets})")
