@@ -920,6 +920,88 @@ int sde_tsdf_render(const float* tsdf, const float* weight, const uint8_t* rgba,
                     uint8_t* picture, sde_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Frame-to-model alignment: the camera tracked against the TSDF volume (csrc/align.hip; binding and host twins in hip/align.py).  ONE call of
+ * sde_frame_align is ONE Gauss-Newton iteration of a point-to-plane fit of the current frame's depth to the model that sde_tsdf_render shows
+ * from the PREDICTED pose C, together with the update of one depth scale.  No counterpart in the reference.
+ *
+ * state: SDE_ALIGN_STATE_WORDS (40) 4-byte words of DEVICE memory, 4-byte aligned:
+ *   words  0..15  D    [4,4] fp32 row-major: the current frame's camera coordinates -> the render camera's.  World -> corrected camera is D^-1 C.
+ *   words 16..31  Dinv [4,4] fp32 row-major: its rigid inverse [R^T | -R^T t].
+ *   word  32      s    fp32: the scale the frame's depth is multiplied by              (SDE_ALIGN_SCALE_AT)
+ *   word  33      fp32:  the last iteration's sum of r^2 over the pose inliers         (SDE_ALIGN_SUMSQ_AT)
+ *   word  34      int32: the last iteration's pose-inlier count                        (SDE_ALIGN_COUNT_AT)
+ *   word  35      int32: the last iteration's scale-inlier count                       (SDE_ALIGN_SCALE_COUNT_AT)
+ *   word  36      int32: the last iteration's status, SDE_ALIGN_OK / _TOO_FEW / _SINGULAR  (SDE_ALIGN_STATUS_AT)
+ *   words 37..39  reserved: written as 0 by the reset, never afterwards.
+ * sde_frame_align_reset: D = Dinv = I, s = 1, words 33..39 all bits zero.  One launch of one workgroup.
+ *
+ * sde_frame_align.  pred [ph,pw], ymap [H], xmap [W], K [3,3]: the contract of sde_tsdf_integrate.  model_depth [H,W] (z-depth, 0 = miss) and
+ * model_normal [H,W,3] (camera coordinates) are sde_tsdf_render's outputs.  mode: SDE_ALIGN_POSE | SDE_ALIGN_SCALE.  Two launches ordered on
+ * the stream.
+ *
+ * ACCUMULATE.  One thread per pixel, workgroups of 256 threads on a grid of ceil(W / 32) x ceil(H / 8): thread t of workgroup (bx, by) has
+ * wave = t / 64, lane = t % 64 and the pixel u = 32 bx + 8 wave + lane % 8, v = 8 by + lane / 8 (sde_tsdf_render's tile).  In fp32, in exactly
+ * this order, nothing fused, every division correctly rounded; D and s are the state's on entry:
+ *   1. kept iff u < W and v < H;   my = ymap[v];  mx = xmap[u];                         kept iff both >= 0;
+ *      d0 = pred[my * pw + mx];                                                         kept iff d0 is finite and min_depth < d0 <= max_depth;
+ *      d = s * d0;
+ *   2. with k00 = 1 / fx, k02 = (-1 * cx) / fx, k11 = 1 / fy, k12 = (-1 * cy) / fy:  rx(u) = k00 * (float)u + k02;  ry(v) = k11 * (float)v + k12;
+ *      p = (d * rx(u), d * ry(v), d);
+ *   3. q_r = ((D_r0 * p_x + D_r1 * p_y) + D_r2 * p_z) + D_r3  for r = x, y, z;           kept iff q_z is finite and > 0;
+ *   4. step 2 of sde_tsdf_integrate on q: X = (fx * q_x + cx * q_z) / (q_z + 1e-6f), Y likewise, rintf, |.| < 1e9f, 0 <= ix < W, 0 <= iy < H;
+ *   5. m = model_depth[iy * W + ix];                                                    kept iff m > 0;
+ *      n = model_normal[iy * W + ix];                                                   kept iff not (n_x == 0 and n_y == 0 and n_z == 0);
+ *   6. g = (m * rx(ix), m * ry(iy), m);   e = q - g;   r = (n_x * e_x + n_y * e_y) + n_z * e_z;
+ *   7. POSE INLIER iff |r| <= dist_tol * m (a NaN is none).  With c = (q_y n_z - q_z n_y, q_z n_x - q_x n_z, q_x n_y - q_y n_x) and
+ *      J = (c_x, c_y, c_z, n_x, n_y, n_z) the pixel's terms are
+ *        term[k] = J_i * J_j for i <= j, k = 0..20 in the order (0,0), (0,1), .. (0,5), (1,1), .. (5,5);   term[21 + i] = J_i * r;
+ *        term[27] = r * r;   term[28] = 1;
+ *   8. rho = m / q_z;   SCALE INLIER iff |rho - 1| <= scale_tol:   term[29] = rho;   term[30] = 1.   Step 8 does not depend on step 7.
+ *   Every term that is not set, term[31] and all terms of a pixel that is not kept are 0.
+ * The workgroup's 32 sums, each in this order: the 64 terms of a wave as a balanced binary tree over the lanes ((l0 + l1) + (l2 + l3)) + ...;
+ * then the four waves ((w0 + w1) + w2) + w3.  Row by * gridDim.x + bx of the slab [rows][32] in the workspace receives them.  Every workgroup
+ * writes its whole row: the workspace's contents on entry do not matter.
+ *
+ * FINISH, fp64 from here on until the stores.  Column k of the slab: S_g = the rows g, g + 32, g + 64, ... added in ascending order starting
+ * from 0.0, for g = 0..31; then the 32 S_g as a balanced binary tree (S_0 + S_1) + (S_2 + S_3) ...  The totals of columns 28 and 30 are the
+ * counts (exact).  Words 33, 34, 35 are written every time (word 33 = the total of column 27 rounded to fp32).  Then, in this order:
+ *   1. count < min_count: status SDE_ALIGN_TOO_FEW, nothing else is written.
+ *   2. with SDE_ALIGN_POSE: A = the symmetric 6 x 6 matrix of the totals 0..20, b_i = total[21 + i];  A_ii = A_ii * (1.0 + (double)damping).
+ *      LDL^T without pivoting, for j = 0..5:  d_j = A_jj - sum_{c<j} (L_jc * L_jc) * d_c;  for i > j:  L_ij = (A_ij - sum_{c<j} (L_ic * L_jc) * d_c) / d_j;
+ *      every sum subtracted term by term for ascending c.  y_i = -b_i - sum_{c<i} L_ic * y_c (ascending i);  z_i = y_i / d_i;
+ *      xi_i = z_i - sum_{c>i} L_ci * xi_c (descending i, ascending c).  A pivot d_j that is <= 0 or not finite, or a (float)xi_i that is not
+ *      finite: status SDE_ALIGN_SINGULAR, nothing else is written.
+ *   3. xi = (omega, v).  a = 0.5 * omega;  aa = (a_0 * a_0 + a_1 * a_1) + a_2 * a_2;  the Cayley rotation, each entry rounded to fp32 once:
+ *        R_ii = ((1.0 - aa) + 2.0 * (a_i * a_i)) / (1.0 + aa);     R_ij = (2.0 * (a_i * a_j) + 2.0 * x_ij) / (1.0 + aa)  with  x_01 = -a_2, x_02 = a_1,
+ *        x_10 = a_2, x_12 = -a_0, x_20 = -a_1, x_21 = a_0 (the second product is exact; a_i * a_j with the smaller index first).  T = [R | (float)v].
+ *   4. D <- T * D in fp32 in sde_pose_compose's order; Dinv_rc = D_cr, Dinv_r3 = -((D_0r * D_03 + D_1r * D_13) + D_2r * D_23) of the new D; the
+ *      bottom rows are not touched.
+ *   5. with SDE_ALIGN_SCALE and scale count >= min_count:  s <- s * (float)(total[29] / (double)scale count)   (one fp32 product).
+ *   6. status SDE_ALIGN_OK.
+ * Both launches: no atomics, no ticket, no workgroup waits for another, no allocation, no host synchronisation: legal under graph capture, the
+ * same bytes every run; nothing is written but the state and the workspace.  workspace: sde_frame_align_ws_bytes(H, W) bytes (0 for sizes the
+ * entry point refuses), 4-byte aligned.  Refused before any launch: H or W outside [1, 32768], ph or pw <= 0, a NULL pointer, a state off a
+ * 4-byte boundary, mode outside 1..3, dist_tol or scale_tol <= 0 (or a NaN), damping < 0 (or a NaN), min_count < 6, min_depth >= max_depth (or
+ * a NaN), a workspace that is NULL, misaligned or too small. */
+#define SDE_ALIGN_POSE 1
+#define SDE_ALIGN_SCALE 2
+#define SDE_ALIGN_OK 0
+#define SDE_ALIGN_TOO_FEW 1
+#define SDE_ALIGN_SINGULAR 2
+#define SDE_ALIGN_SUMS 32
+#define SDE_ALIGN_STATE_WORDS 40
+#define SDE_ALIGN_SCALE_AT 32
+#define SDE_ALIGN_SUMSQ_AT 33
+#define SDE_ALIGN_COUNT_AT 34
+#define SDE_ALIGN_SCALE_COUNT_AT 35
+#define SDE_ALIGN_STATUS_AT 36
+size_t sde_frame_align_ws_bytes(int H, int W);
+int sde_frame_align_reset(float* state, sde_stream_t stream);
+int sde_frame_align(const float* pred, int ph, int pw, const int* ymap, const int* xmap, int H, int W, const float* K, const float* model_depth,
+                    const float* model_normal, float min_depth, float max_depth, float dist_tol, float scale_tol, int min_count, float damping,
+                    int mode, float* state, void* workspace, size_t workspace_bytes, sde_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * MotionLearning loss stack (csrc/motion_loss.hip; autograd wrappers in hip/motion_loss.py).  fp32, planar NCHW, no host synchronisation.
  *
  * sde_view_synthesis_pp: detectron2/geometry/camera.py:L166-202 with a per-pixel translation t [B,3,H,W] and a 3x3 rotation R [B,3,3]; the

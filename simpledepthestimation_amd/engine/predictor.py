@@ -27,6 +27,7 @@ from ..hip import cloud as HC
 from ..hip import flow as HF
 from ..hip import present as HP
 from ..hip import temporal as HT
+from ..hip.align import AlignState, unpack_state
 
 IMAGE_STEPS = ("KBCrop", "CropTopTo", "Resize")       # the steps with a backward(): DatasetEvaluator.preprocess_chain keeps the same three
 KB_H, KB_W = 352, 1216
@@ -541,16 +542,50 @@ def render_arg(render, volume):
     return normals, picture, check_min_weight(render.get("min_weight", 1)), near, far, step
 
 
+TRACK_KEYS = ("schedule", "scale", "dist_tol", "scale_tol", "min_count", "damping", "min_weight", "near", "far", "step")
+
+
+def track_arg(track, volume):
+    """track=None -> None; else dict(schedule=None, scale=True, dist_tol=, scale_tol=, min_count=, damping=, min_weight=1, near=, far=, step=), the
+    arguments of hip.volume.TsdfVolume.track, checked against the volume -> (schedule, dist_tol, scale_tol, min_count, damping, min_weight, near,
+    far, step): part of the replay key.  scale=False takes the SCALE bit out of every iteration of the schedule (the depth keeps its scale)."""
+    if track is None:
+        return None
+    if volume is None:
+        raise ValueError("PairPredictor: track= aligns every frame with the volume the sequence is fused into, it needs volume=TsdfVolume(...)")
+    if not isinstance(track, dict) or set(track) - set(TRACK_KEYS):
+        raise ValueError(f"PairPredictor: track must be None or a dict with keys from {TRACK_KEYS}, got {track!r}")
+    from ..hip import align as AL
+    from ..hip.volume import check_min_weight, check_render
+    schedule = AL.DEFAULT_SCHEDULE if track.get("schedule") is None else tuple(track["schedule"])
+    kw = {k: AL.DEFAULTS[k] if track.get(k) is None else track[k] for k in ("dist_tol", "scale_tol", "min_count", "damping")}
+    checked = [AL.check_align(mode=m, min_depth=volume.min_depth, max_depth=volume.max_depth, **kw) for m in schedule]
+    if not bool(track.get("scale", True)):
+        checked = [c for c in checked if c[4] & AL.POSE]
+        schedule = tuple(AL.POSE for _ in checked)
+    else:
+        schedule = tuple(c[4] for c in checked)
+    if not schedule:
+        raise ValueError(f"PairPredictor: track's schedule must name at least one iteration (with scale=False: one with the POSE bit), got {track.get('schedule')!r}")
+    near, far, step = (float(np.float32(d if track.get(k) is None else track[k])) for k, d in (("near", volume.min_depth), ("far", volume.max_depth),
+                                                                                              ("step", volume.voxel)))
+    check_render((1, 1), near, far, step)
+    dist_tol, scale_tol, min_count, damping = checked[0][:4]
+    return schedule, dist_tol, scale_tol, min_count, damping, check_min_weight(track.get("min_weight", 1)), near, far, step
+
+
 class _VolumeState:
     """What the volume fusion keeps on the device from one window to the next, beside the temporal state: C, the world-to-camera pose of the
     window's target (the first target of a sequence is the world), and T, the step previous target -> this one that C is advanced by before the
     window is integrated -- the form _TemporalState keeps its pose in, the identity until a window has run (`started`, for a model that only
-    looks back and so brings the step into its own window along).  The graphs of both slots read and write these tensors."""
+    looks back and so brings the step into its own window along).  The graphs of both slots read and write these tensors.  `align` is the
+    hip.align.AlignState of track=: scratch that every window resets, made when the first tracked window of the size runs."""
 
     def __init__(self, device):
         self.eye = torch.eye(4, dtype=torch.float32, device=device)
         self.C, self.T, self.inv = self.eye.clone(), self.eye.clone(), self.eye.clone()
         self.started = torch.zeros((1,), dtype=torch.bool, device=device)
+        self.align = None
 
     def tensors(self):
         return [self.C, self.T, self.started]
@@ -601,7 +636,8 @@ class PairPredictor(_Predictor):
     `stream(..., volume=vol)` fuses the sequence into one TSDF volume (hip/volume.py): sde_pose_compose chains the world-to-camera pose from the
     model's step poses on the device and sde_tsdf_integrate averages every window's depth -- the one the pictures show -- into the caller's grid
     through it, inside the same graph.  With `render=dict(...)` as well, sde_tsdf_render then shows the volume from the window's own camera, and
-    the record holds the model's depth, normal and colour for the frame."""
+    the record holds the model's depth, normal and colour for the frame.  With `track=dict(...)` the chained pose is corrected against the model
+    before the window's depth goes in (hip/align.py: sde_frame_align, frame-to-model alignment of pose and depth scale)."""
     NAME = "PairPredictor"
 
     def __init__(self, cfg, model=None, chain=None, device="cuda", use_graph=None, vmax=None, gamma=0.8):
@@ -635,7 +671,7 @@ class PairPredictor(_Predictor):
             self._volume[key] = _VolumeState(self.device)
         return self._volume[key]
 
-    def _chain(self, plan, frames, K, K_src, present, rigid_only, max_flow, temporal=None, want_u16=False, cloud=None, volume=None, render=None):
+    def _chain(self, plan, frames, K, K_src, present, rigid_only, max_flow, temporal=None, want_u16=False, cloud=None, volume=None, render=None, track=None):
         N = 1 + self.n
         img, _ = self._aug.prep(frames, self._no_jitter(N), plan.h, plan.w, tabs=(plan.xtab, plan.ytab))
         nd = 2 if self.pose_use_depth else 1                   # frames the depth net sees
@@ -681,7 +717,17 @@ class PairPredictor(_Predictor):
                 vs.inv[:3, 3].copy_(-(Rt[:, 0] * t[0] + Rt[:, 1] * t[1] + Rt[:, 2] * t[2]))
                 vs.T.copy_(torch.where(vs.started, vs.inv, vs.eye))
             vol.compose(vs.T, vs.C)
-            vol.integrate(shown, ymap, xmap, K_src[:1], vs.C, frame=frames[:1])
+            fused = shown
+            if track is not None:                               # the predicted pose against the model: C <- D^-1 C, and the depth goes in times the scale
+                schedule, dist_tol, scale_tol, min_count, damping, min_weight, near, far, step = track
+                if vs.align is None or (vs.align.H, vs.align.W) != (plan.Hs, plan.Ws):
+                    vs.align = AlignState((plan.Hs, plan.Ws), self.device)
+                vol.track(shown, ymap, xmap, K_src[:1], vs.C, (plan.Hs, plan.Ws), schedule=schedule, dist_tol=dist_tol, scale_tol=scale_tol, min_count=min_count,
+                          damping=damping, min_weight=min_weight, near=near, far=far, step=step, state=vs.align)
+                vol.compose(vs.align.Dinv, vs.C)
+                fused = shown * vs.align.scale                  # a device scalar: the first window's empty volume leaves D = I and scale = 1 by itself
+                out["track_state"] = vs.align.state.clone()
+            vol.integrate(fused, ymap, xmap, K_src[:1], vs.C, frame=frames[:1])
             out["world_to_camera"] = vs.C.clone()               # the state moves on with the next window, on the other slot: this slot's copy
             if render is not None:                              # the model as this camera sees it, this window's depth included
                 normals, picture, min_weight, near, far, step = render
@@ -705,7 +751,7 @@ class PairPredictor(_Predictor):
             raise ValueError("PairPredictor: the flow needs intrinsics (the source-size K [3,3] of the frames)")
         return self._host_K("PairPredictor", intrinsics, 1)[0]          # one K for the whole window
 
-    def _run(self, slot, plan, intrinsics, K_host, present, rigid_only, max_flow, temporal=None, want_u16=False, cloud=None, volume=None, render=None):
+    def _run(self, slot, plan, intrinsics, K_host, present, rigid_only, max_flow, temporal=None, want_u16=False, cloud=None, volume=None, render=None, track=None):
         N = 1 + self.n
         K = self._device_copy(slot, "K", plan.intrinsics(intrinsics), N)
         K_src =self._device_copy(slot, "K_src", K_host, self.n)
@@ -722,11 +768,13 @@ class PairPredictor(_Predictor):
             key += (("volume",) + vol.params(),)
             if render is not None:
                 key += (("render",) + render,)
+            if track is not None:
+                key += (("track",) + track,)
             persistent = persistent + vs.tensors() + [t for t in (vol.tsdf, vol.weight, vol.rgba) if t is not None]
         return self._replay(slot, key, lambda: self._chain(plan, slot.frames, K, K_src, bool(present), bool(rigid_only), max_flow, temporal, bool(want_u16), cloud,
-                                                           volume, render), persistent=persistent)
+                                                           volume, render, track), persistent=persistent)
 
-    def predict(self, frames, intrinsics, present=True, rigid_only=False, max_flow=None, temporal=None, volume=None, render=None):
+    def predict(self, frames, intrinsics, present=True, rigid_only=False, max_flow=None, temporal=None, volume=None, render=None, track=None):
         """frames: the window, a list of 1 + n uint8 [H,W,3] RGB frames of one size -- the target, then the n context frames in the order the dataset
         emits `ctx_img` (self.offsets, ascending, e.g. the frames at -1 and +1).  intrinsics: the source-size K [3,3] of the frames.  Returns a
         dict of device tensors: `depth` [1,H,W], `canvas` [1,2H,W,3], `depth_net` [1,h,w] as DepthPredictor returns them for the target; `pose`
@@ -736,14 +784,16 @@ class PairPredictor(_Predictor):
         still returned).  max_flow: the flow length, in pixels, that reaches full saturation in `flow_canvas`; default 5 % of the frame's
         width -- a presentation constant, like gamma.  present=False skips the three pictures.  Translations, and with them the flow's share
         that comes from them, are up to the scale of the monocular depth.  No host synchronisation after the first call of a size.  predict keeps
-        nothing from call to call: temporal fusion and volume fusion are `stream`'s, and anything but temporal=None, volume=None, render=None is
-        refused."""
+        nothing from call to call: temporal fusion and volume fusion are `stream`'s, and anything but temporal=None, volume=None, render=None,
+        track=None is refused."""
         if temporal is not None:
             raise ValueError("PairPredictor.predict is stateless: temporal fusion needs the frames in order, use stream(..., temporal=...)")
         if volume is not None:
             raise ValueError("PairPredictor.predict is stateless: volume fusion chains the poses of frames in order, use stream(..., volume=...)")
         if render is not None:
             raise ValueError("PairPredictor.predict is stateless: render= shows the volume a sequence is fused into, use stream(..., volume=..., render=...)")
+        if track is not None:
+            raise ValueError("PairPredictor.predict is stateless: track= aligns frames with the volume a sequence is fused into, use stream(..., volume=..., track=...)")
         t = as_window(frames, self.n)
         K_host = self._source_intrinsics(intrinsics)
         plan = self.plan(t.shape[1], t.shape[2])
@@ -763,10 +813,13 @@ class PairPredictor(_Predictor):
             res["depth_u16"] = res["depth_u16"].view(np.uint16)
         j, inverted = self.next_context
         res["pose_next"] = invert_pose_np(res["pose"][j]) if inverted else res["pose"][j].copy()
+        if "track_state" in res:
+            u = unpack_state(res.pop("track_state"))
+            res.update(track_delta=u["D"], track_scale=u["scale"], track_count=u["count"], track_rms=u["rms"], track_status=u["status"])
         return res
 
     def stream(self, frames_iter, intrinsics, present=True, rigid_only=False, max_flow=None, temporal=None, want_u16=False, cloud=None, volume=None,
-               render=None):
+               render=None, track=None):
         """Generator over host frames of a sequence (uint8 [H,W,3] RGB, one at a time, one size).  Keeps a sliding window and yields, in order, one
         dict of host arrays per target frame that has all its context frames: the outputs of `predict` (`depth` [H,W], `canvas` [2H,W,3], `pose`,
         `flow`, `flow_valid`, `flow_canvas`, `motion`; with present=False `depth_net` instead of the pictures), `index`, the target's position in
@@ -796,11 +849,24 @@ class PairPredictor(_Predictor):
         TsdfVolume.render: the source-size intrinsics, the chained pose, the frame's size) inside the same graph.  Every record then holds
         `model_depth` [H,W] float32, the z-depth of the fused model's surface along every pixel's ray, 0 where there is none -- the depth that
         is consistent over the whole sequence -- and, unless switched off, `model_normal` [H,W,3] float32 in camera coordinates and
-        `model_picture` [H,W,4] uint8."""
+        `model_picture` [H,W,4] uint8.
+
+        track=dict(schedule=None, scale=True, dist_tol=, scale_tol=, min_count=, damping=, min_weight=1, near=, far=, step=) (with volume=; every
+        key optional, defaults in hip.align): frame-to-model tracking.  Before a window's depth goes in, the volume is rendered from the pose the
+        chain PREDICTS, the depth is aligned with that model (hip.volume.TsdfVolume.track: sde_frame_align, a point-to-plane Gauss-Newton
+        iteration per entry of `schedule`, which also fits one depth scale unless scale=False), the pose becomes D^-1 C on the device and the
+        depth is integrated -- and rendered, with render= -- times the scale; all inside the same graph, with no read-back: against an empty
+        volume (the first window) the kernels leave D = I and the scale at 1 by themselves.  `world_to_camera` is then the CORRECTED pose, and
+        every record also holds `track_delta` [4,4] (D: the frame's camera coordinates -> the predicted camera's), `track_scale`, `track_count`
+        (the last iteration's inliers), `track_rms` (their root-mean-square point-to-plane distance) and `track_status` (hip.align.OK, TOO_FEW or
+        SINGULAR, after which D and the scale are what the iterations before left).  The scale is fitted per window and starts at 1 every time;
+        `depth`, the pictures, the cloud and the flow keep the network's scale, and the pose network's next translation is NOT rescaled by it.
+        With track=None nothing changes: the same graphs, the same bytes."""
         K_host = self._source_intrinsics(intrinsics)
         fuse = temporal_args(temporal)
         volume = volume_arg(volume, self.device)
         render = render_arg(render, volume)
+        track = track_arg(track, volume)
         cloud, _ = DepthPredictor._cloud_args(cloud, K_host, 1)
         want_u16 = bool(want_u16 and present)
         if fuse is not None or volume is not None:
@@ -809,7 +875,8 @@ class PairPredictor(_Predictor):
                                  ("temporal_state", fuse is not None), ("pose", True), ("flow", True), ("flow_valid", True), ("flow_canvas", present),
                                  ("motion", True), ("depth_u16", want_u16), ("points", cloud is not None), ("count", cloud is not None),
                                  ("world_to_camera", volume is not None), ("model_depth", render is not None),
-                                 ("model_normal", render is not None and render[0]), ("model_picture", render is not None and render[1])) if on]
+                                 ("model_normal", render is not None and render[0]), ("model_picture", render is not None and render[1]),
+                                 ("track_state", track is not None)) if on]
         live, live_v = [], []                                  # the states this call has reset and is advancing
         lo, hi = min(self.offsets + (0,)), max(self.offsets + (0,))
         targets = []
@@ -844,10 +911,12 @@ class PairPredictor(_Predictor):
                     from ..hip.volume import check_render
                     check_render((plan.Hs, plan.Ws), render[3], render[4], render[5])
             if fuse is None:
-                return self._run(slot, plan, intrinsics, K_host, present, rigid_only, max_flow, want_u16=want_u16, cloud=cloud, volume=vol, render=render)
+                return self._run(slot, plan, intrinsics, K_host, present, rigid_only, max_flow, want_u16=want_u16, cloud=cloud, volume=vol, render=render,
+                                 track=track)
             st = self._temporal_state(plan)
             if not live or live[0] is not st:                  # the first window of this call, or frames of another size: an empty state
                 st.reset()
                 live[:] = [st]
-            return self._run(slot, plan, intrinsics, K_host, present, rigid_only, max_flow, temporal=fuse + (st,), want_u16=want_u16, cloud=cloud, volume=vol, render=render)
+            return self._run(slot, plan, intrinsics, K_host, present, rigid_only, max_flow, temporal=fuse + (st,), want_u16=want_u16, cloud=cloud, volume=vol, render=render,
+                             track=track)
         yield from self._pump(windows(), names, run, result)

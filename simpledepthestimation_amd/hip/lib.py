@@ -147,6 +147,10 @@ _PROTOS = {
     "sde_tsdf_mesh_ws_bytes": ([_I, _I, _I], c_size_t),
     "sde_tsdf_mesh": ([_P, _P, _P, _I, _I, _I, POINTER(c_float), _F, _F, _P, c_size_t, _P, ctypes.c_long, _P, ctypes.c_long, _P, _P], c_int),
     "sde_tsdf_render": ([_P, _P, _P, _I, _I, _I, POINTER(c_float), _F, _F, _P, _P, _I, _I, _F, _F, _I, _P, _P, _P, _P], c_int),
+    # frame-to-model alignment against the rendered volume (csrc/align.hip; binding and host twins in hip/align.py)
+    "sde_frame_align_ws_bytes": ([_I, _I], c_size_t),
+    "sde_frame_align_reset": ([_P, _P], c_int),
+    "sde_frame_align": ([_P, _I, _I, _P, _P, _I, _I, _P, _P, _P, _F, _F, _F, _F, _I, _F, _I, _P, _P, c_size_t, _P], c_int),
 }
 
 _lib = None

@@ -4,7 +4,8 @@ sde_tsdf_points; csrc/volume.hip).  `TsdfVolume` owns the three device arrays an
 which compare the two bit for bit.  Every frame's depth is averaged into the voxel grid through its world-to-camera pose; the zero crossings
 of the grid are the surface, handed out as the 16-byte records of hip.cloud (as_records and the PLY writer take them as they are), or connected
 into a triangle mesh by surface nets (sde_tsdf_mesh: `TsdfVolume.mesh`, `save_mesh`, the twin `mesh_host`, `write_mesh_ply` / `read_mesh_ply`), or
-seen from a camera pose by ray casting (sde_tsdf_render: `TsdfVolume.render`, the twin `render_host`)."""
+seen from a camera pose by ray casting (sde_tsdf_render: `TsdfVolume.render`, the twin `render_host`); `TsdfVolume.track` aligns a frame's depth
+with that view (hip/align.py: sde_frame_align)."""
 import ctypes
 import warnings
 
@@ -241,6 +242,38 @@ class TsdfVolume:
         L.check(L.lib().sde_tsdf_render(L.ptr(self.tsdf), L.ptr(self.weight), L.ptr(self.rgba), nx, ny, nz, self._origin, self.voxel, min_weight,
                                         L.ptr(K), L.ptr(C), H, W, near, step, n, L.ptr(depth), L.ptr(normal), L.ptr(pic), L.stream()), "sde_tsdf_render")
         return depth, normal, pic
+
+    def track(self, pred, ymap, xmap, K, C, size, schedule=None, dist_tol=None, scale_tol=None, min_count=None, damping=None, min_weight=1, near=None,
+              far=None, step=None, state=None):
+        """A frame's depth aligned with the volume (hip.align: sde_frame_align) -> the AlignState.  C [4,4] is the PREDICTED world -> camera pose
+        (the chain of `compose`), size = (H, W) = (ymap.numel(), xmap.numel()).  In order, on the current stream, with no host synchronisation:
+        the volume's depth and normals are rendered from C (near / far / step / min_weight as in `render`); the state is reset (D = I, scale = 1);
+        one `frame_align` runs per entry of `schedule` (a sequence of modes: align.POSE, align.SCALE or both; None: align.DEFAULT_SCHEDULE).
+        Afterwards state.D takes the frame's camera coordinates to those of the camera at C: world -> corrected camera is D^-1 C, which the
+        caller forms with `compose(state.Dinv, C)`; state.scale [1] is the factor the frame's depth is multiplied by.  An empty volume (every ray
+        misses) leaves D = I and scale = 1 with the status "too few": the host never looks.  dist_tol, scale_tol, min_count, damping: None takes
+        align.DEFAULTS.  state: an AlignState of this size to run in (its buffers are reused); None makes one."""
+        from . import align as AL
+        H, W = AL.check_size(size)
+        schedule = AL.DEFAULT_SCHEDULE if schedule is None else tuple(schedule)
+        if not schedule:
+            raise ValueError("TsdfVolume.track: schedule must name at least one iteration")
+        kw = {k: AL.DEFAULTS[k] if v is None else v for k, v in (("dist_tol", dist_tol), ("scale_tol", scale_tol), ("min_count", min_count), ("damping", damping))}
+        for mode in schedule:                                   # every argument error before the first launch
+            AL.check_align(mode=mode, min_depth=self.min_depth, max_depth=self.max_depth, **kw)
+        if state is None:
+            state = AL.AlignState((H, W), self.device)
+        if not isinstance(state, AL.AlignState) or (state.H, state.W) != (H, W) or state.device != self.device:
+            raise ValueError(f"TsdfVolume.track: state must be an AlignState of size {(H, W)} on {self.device}")
+        if torch.is_tensor(ymap) and torch.is_tensor(xmap) and (ymap.numel(), xmap.numel()) != (H, W):
+            raise ValueError(f"TsdfVolume.track: size {(H, W)} does not match the maps ({ymap.numel()}, {xmap.numel()})")
+        self.render(K, C, (H, W), near=near, far=far, step=step, min_weight=min_weight, normals=True, picture=False,
+                    out=(state.model_depth, state.model_normal, None))
+        state.reset()
+        for mode in schedule:
+            AL.frame_align(pred, ymap, xmap, K, state.model_depth, state.model_normal, state, mode=mode, min_depth=self.min_depth,
+                           max_depth=self.max_depth, **kw)
+        return state
 
     def save_mesh(self, path, min_weight=1, cap_vertices=None, cap_faces=None):
         """The mesh as a binary PLY (write_mesh_ply).  Synchronises.  When either cap was too small the mesh is taken once more with exactly the

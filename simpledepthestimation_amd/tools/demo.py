@@ -36,6 +36,11 @@ the corner of the first voxel (default: the first camera at the middle of the ne
 (TsdfVolume.save_mesh: one vertex per grid cell the surface passes through, two triangles per crossing, coloured like the points).  All lengths are in the model's depth units: a monocular model's scale is
 not aligned.  The model needs a context one frame away.
 
+--track-volume (with --volume) tracks the camera against the model: before a frame's depth goes in, the volume is rendered from the pose the
+chain predicts and the depth is aligned with it (PairPredictor.stream(..., track=...): TsdfVolume.track, sde_frame_align), which corrects the pose
+and fits one depth scale per frame (--no-track-scale: the pose alone).  `trajectory.txt` (--save-trajectory) then holds the CORRECTED
+camera-to-world poses, one line per target frame, the first target being the world.
+
 --render-volume (with --volume) looks at the model while it grows: after every frame's depth has gone in, the volume is rendered from that
 frame's own camera (PairPredictor.stream(..., render=...): ray casting on the device, TsdfVolume.render) and `<stem>_model.png` holds the colour
 picture, `<stem>_model_depth.png` the model's depth along every pixel's ray in the --save-depth format (0 where the ray finds no surface);
@@ -77,6 +82,9 @@ def parse_args(argv=None):
     p.add_argument("--render-volume", action="store_true", help="with --volume: also write <stem>_model.png and <stem>_model_depth.png, the volume seen "
                                                                 "from the frame's camera (colour, and depth * 255 as a 16-bit PNG)")
     p.add_argument("--save-normals", action="store_true", help="with --render-volume: also write <stem>_model_normal.png, (normal * 0.5 + 0.5) * 255")
+    p.add_argument("--track-volume", action="store_true", help="with --volume: align every frame with the volume before its depth goes in (frame-to-model "
+                                                               "tracking); trajectory.txt then holds the corrected poses")
+    p.add_argument("--no-track-scale", action="store_true", help="with --track-volume: fit the pose alone and leave the depth's scale as it is")
     p.add_argument("--cloud-step", type=int, default=1, help="the cloud takes every N-th pixel of every N-th row (default 1: all)")
     p.add_argument("--opts", default=[], nargs=argparse.REMAINDER, help="config overrides as KEY VALUE pairs, e.g. MODEL.WEIGHTS model.pth")
     args = p.parse_args(argv)
@@ -103,6 +111,10 @@ def parse_args(argv=None):
         p.error("--save-mesh needs --volume NX NY NZ")
     elif args.render_volume:
         p.error("--render-volume needs --volume NX NY NZ")
+    elif args.track_volume:
+        p.error("--track-volume needs --volume NX NY NZ")
+    if args.no_track_scale and not args.track_volume:
+        p.error("--no-track-scale needs --track-volume")
     if args.save_normals and not args.render_volume:
         p.error("--save-normals needs --render-volume")
     for flag in ("save_flow", "save_trajectory", "rigid_only", "stabilise", "volume"):
@@ -192,8 +204,9 @@ def run_pairs(args, cfg, files):
         from ..hip.volume import TsdfVolume
         volume = TsdfVolume(args.volume, args.voxel, origin=args.volume_origin, trunc=args.trunc, device=predictor.device, **depth_range)
     render = dict(normals=args.save_normals, picture=True, min_weight=args.min_weight) if args.render_volume else None
+    track = dict(scale=not args.no_track_scale, min_weight=args.min_weight) if args.track_volume else None
     for res in predictor.stream((read_rgb(f) for f in files), K, rigid_only=args.rigid_only, temporal=temporal, want_u16=args.save_depth, cloud=cloud,
-                                volume=volume, render=render):
+                                volume=volume, render=render, track=track):
         stem = os.path.splitext(os.path.basename(files[res["index"]]))[0]
         Image.fromarray(res["canvas"]).save(os.path.join(args.output, stem + ".png"), format="PNG", compress_level=3)
         if args.save_flow:
@@ -211,9 +224,14 @@ def run_pairs(args, cfg, files):
             if args.save_normals:
                 Image.fromarray(normal_picture(res["model_normal"])).save(os.path.join(args.output, stem + "_model_normal.png"), format="PNG", compress_level=3)
         kept.append({"index": res["index"], "pose": res["pose"].copy(), "pose_next": res["pose_next"]})
+        if track is not None:
+            kept[-1]["world_to_camera"] = res["world_to_camera"].copy()
     if not kept:
         raise SystemExit(f"--pairs: {len(files)} frame(s) are fewer than one window of the model (offsets {predictor.offsets})")
-    if args.save_trajectory:
+    if args.save_trajectory and track is not None:        # the corrected poses, one per target frame: the first target is the world
+        from ..geometry.pose_utils import invert_pose_np
+        write_kitti_poses(os.path.join(args.output, "trajectory.txt"), np.stack([invert_pose_np(r["world_to_camera"].astype(np.float64)) for r in kept]))
+    elif args.save_trajectory:
         steps, _ = trajectory_steps(kept, predictor.offsets)
         write_kitti_poses(os.path.join(args.output, "trajectory.txt"), accumulate_poses(np.stack(steps)))
     if volume is not None:
