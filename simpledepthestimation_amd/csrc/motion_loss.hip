@@ -471,6 +471,13 @@ __global__ void __launch_bounds__(PB_N) mc_fwd_kernel(const float* __restrict__ 
     if (threadIdx.x == 0) partial[(n * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = s;
 }
 
+// v / den^2.  By den * den wherever that square is a normal fp32 number (the operation order every recorded result has); by den twice where it is not:
+// with both rotations the identity, or both translations zero, den is the 1e-24f guard alone, its square is 0 in fp32 and v / (den * den) was 0 / 0.
+__device__ __forceinline__ float div_sq(float v, float den) {
+    const float d2 = den * den;
+    return d2 >= 1.17549435e-38f ? v / d2 : v / den / den;
+}
+
 // rotation part of one sample: r = mean((R1 R2 - I)^2) / (mean((R1 - I)^2) + mean((R2 - I)^2) + 1e-24); optionally its gradient * g
 __device__ __forceinline__ float mc_rot(const float* __restrict__ R1, const float* __restrict__ R2, float g, float* dR1, float* dR2) {
     float M[9], A[9], B[9], re = 0.f, a = 0.f, b = 0.f;
@@ -486,7 +493,7 @@ __device__ __forceinline__ float mc_rot(const float* __restrict__ R1, const floa
     re = re / 9.0f; a = a / 9.0f; b = b / 9.0f;
     const float den = a + b + 1e-24f;
     if (dR1) {
-        const float gm = g / den * (2.0f / 9.0f), gs = -g * re / (den * den) * (2.0f / 9.0f);
+        const float gm = g / den * (2.0f / 9.0f), gs = div_sq(-g * re, den) * (2.0f / 9.0f);
 #pragma unroll
         for (int i = 0; i < 3; ++i)
 #pragma unroll
@@ -529,7 +536,7 @@ __global__ void __launch_bounds__(PB_N) mc_bwd_kernel(const float* __restrict__ 
         McPix p;
         mc_pixel(grid, R, tA, tB, n, pix, H, W, p);
         const float g = (g_trans ? g_trans[0] : 0.f) * inv_pixels * mask[n * hw + pix];
-        const float dden = -g * p.E / (p.den * p.den);
+        const float dden = div_sq(-g * p.E, p.den);
         float de[3], ds[3];
 #pragma unroll
         for (int i = 0; i < 3; ++i) {

@@ -787,8 +787,10 @@ def make_cam(A, K, P, sx, sy):
     return {"k": k, "ki": ki, "kr": kr, "kt": kt}
 
 
-def project(A, cam, depth, dec=None):
-    """projection.h project + make_taps on every pixel.  dec: the discrete decisions (x0, y0, passx, passy) of the fp32 chain (required with V)."""
+def project(A, cam, depth, dec=None, eps=None):
+    """projection.h project + make_taps on every pixel.  dec: the discrete decisions (x0, y0, passx, passy) of the fp32 chain (required with V).
+    cam["kt"] may hold per-pixel values [B, h, w] (motion_loss.hip: set_kt).  eps: kEps as an A-value (default: the fp32 number itself, for references
+    that use that number; motion_bounds passes V.c(1e-6) since its reference holds the real 1e-6)."""
     B, _, h, w = depth.shape
     d = A.inp(depth[:, 0])
     fx, fy = A.inp(torch.arange(w).float().view(1, 1, w)), A.inp(torch.arange(h).float().view(1, h, 1))
@@ -796,12 +798,14 @@ def project(A, cam, depth, dec=None):
     ki, kr, kt = cam["ki"], cam["kr"], cam["kt"]
     p = [ki[3 * i + 2].fma(d, ki[3 * i + 1].fma(g1, ki[3 * i] * g0)) for i in range(3)]
     q = [kr[3 * i + 2].fma(p[2], kr[3 * i + 1].fma(p[1], kr[3 * i] * p[0])) + kt[i] for i in range(3)]
-    den = q[2] + A.k(EPS)
+    den = q[2] + (A.k(EPS) if eps is None else eps)
     X, Y = q[0] / den, q[1] / den
     out = {"p": p, "q": q, "X": X, "Y": Y, "den": den, "fx": fx, "fy": fy}
     for name, c, n in (("x", X, w), ("y", Y, h)):
         cs = c.maximum(0.0).minimum(A.k(n - 1))
-        i = ((cs.scale(2.0) / A.k(n - 1)) - 1.0 + 1.0) * A.k((n - 1) / 2.0)
+        gn = (cs.scale(2.0) / A.k(n - 1)) - 1.0                 # the normalised grid coordinate (store_grid)
+        i = (gn + 1.0) * A.k((n - 1) / 2.0)
+        out["g" + name] = gn
         if dec is None:
             i0 = torch.floor(i.val)
             ps = torch.isfinite(c.val) & (c.val >= 0) & (c.val <= n - 1)
