@@ -171,10 +171,104 @@ __global__ void __launch_bounds__(256) bn_apply_kernel(const T* __restrict__ y, 
 // channels (128 bytes of every row, 16-bit types) x a range of rows.  It first reduces the slab columns of ITS 64 channels -- every workgroup of
 // a strip redundantly, in the same fixed order, fp64: identical results everywhere -- into scale / shift held in LDS, then streams its rows.  The
 // workgroups of row range 0 also write bnp (for backward) and update the running statistics.  Saves the separate finalize launch (4.7 us + a kernel
-// boundary, 53 times per ResNet-50 forward pass) at the price of <= 100 KB of L2-resident re-reads per workgroup.
+// boundary, 53 times per ResNet-50 forward pass) at the price of rows x 512 B of L2-resident re-reads per workgroup (<= 128 KB at 256 slab rows; 46 KB
+// against 12 KB of payload for layer3's C = 1024, 96 KB against 48 KB for layer1's C = 256): the same sums about a thousand times per launch, in front
+// of the payload.  So nothing of it is left to wait alone: a thread issues its slab loads BNFA_SLAB_BATCH at a time before their first add (64 slab rows
+// per L2 round trip, the tail rows included: 90 rows are two trips, not five; 256 rows are still four), the first BNFA_U row passes of its payload are
+// requested directly behind the last of them -- vmcnt counts in issue order, so the wait in front of the adds leaves the payload loads outstanding --
+// and the row loop keeps BNFA_U (x 2 with a second tensor) loads per thread in flight.
+// Registers: 98 - 100 (84 without a residual) against 72 before, i.e. 4 (5) waves per SIMD against 7.  A launch has about 1024 workgroups of four waves,
+// four per compute unit, one wave per SIMD each: four waves per SIMD keep the whole grid resident, as seven did.  Batches of 16 slab loads (128 VGPRs,
+// spills at BNFA_U = 4) were slower in the step and on short slabs, where every slot is converted and added whether a row stands behind it or not
+// (profiles/bn_stream_ab.txt).
 constexpr int BNFA_MAX_ROWS = 256;
-template <typename T>
-__global__ void __launch_bounds__(256) bn_finalize_apply_kernel(const float* __restrict__ part, int rows, int C, float count, const float* __restrict__ gamma,
+constexpr int BNFA_MAX_C = 1 << 22;                      // the kernels' 32-bit offsets: 256 slab rows x 2 C floats, and 32 rows x C elements, stay below 2^31
+#ifndef SDE_BNFA_U
+#define SDE_BNFA_U 4
+#endif
+#ifndef SDE_BNFA_SLAB_BATCH
+#define SDE_BNFA_SLAB_BATCH 8
+#endif
+#ifndef SDE_BNFA_AHEAD
+#define SDE_BNFA_AHEAD 1
+#endif
+constexpr bool BNFA_AHEAD = SDE_BNFA_AHEAD;              // 0: the first block's loads behind the second barrier, as before (A/B)
+constexpr int BNFA_U = SDE_BNFA_U;                       // row passes (32 rows each) per block of the row loop = passes requested ahead of the slab reduce
+constexpr int BNFA_SLAB_BATCH = SDE_BNFA_SLAB_BATCH;     // slab loads (16 B) a thread issues before their first add; a multiple of 8
+
+// Column sums of a strip's 128 floats (sum, sum^2 interleaved; 64 channels from c0) over every slab row, into acc[row lane][128]: thread = (float4 tid & 31,
+// row lane tid >> 5) owns the slab rows rl, rl + 8, ...  The additions are, per thread, in ascending row order: of every complete group of eight rows the
+// even positions go to a[], the odd ones to b[]; the rows after the last complete group go to a[]; then a + b.  (The eight row lanes are summed by the
+// caller, in fp64, ascending.)  Loads come BNFA_SLAB_BATCH at a time; a slot past the thread's last row holds zeros, and x + 0.0 == x for every x a sum
+// that started at +0.0 can hold.  `ahead` is called once, behind the loads of the last batch and in front of its adds.
+struct BnfaSlab {
+    const float* src;                                    // uniform; the thread's part is a 32-bit offset (a slab has at most 256 rows): one register per load
+    int rows, ld, f4, rl, n;                             // slab rows, floats per slab row, float4 column, row lane, slab rows of this thread
+    double a[4] = {0, 0, 0, 0}, b[4] = {0, 0, 0, 0};
+    // unconditional (a load under a lane condition made hipcc drain vmcnt after every one): a slot past the thread's last row reads the last slab row again
+    __device__ __forceinline__ void load(int base, float4 (&v)[BNFA_SLAB_BATCH]) const {
+#pragma unroll
+        for (int i = 0; i < BNFA_SLAB_BATCH; ++i)
+            v[i] = *reinterpret_cast<const float4*>(src + ((unsigned)min(rl + 8 * (base + i), rows - 1) * (unsigned)ld + (unsigned)(f4 * 4)));
+    }
+    __device__ __forceinline__ void add(int base, const float4 (&v)[BNFA_SLAB_BATCH]) {
+#pragma unroll
+        for (int g = 0; g < BNFA_SLAB_BATCH; g += 8) {
+            if (base + g + 8 <= n) {                     // a complete group of eight: even positions to a[], odd ones to b[]
+#pragma unroll
+                for (int i = g; i < g + 8; i += 2) {
+                    a[0] += v[i].x; a[1] += v[i].y; a[2] += v[i].z; a[3] += v[i].w;
+                    b[0] += v[i + 1].x; b[1] += v[i + 1].y; b[2] += v[i + 1].z; b[3] += v[i + 1].w;
+                }
+            } else {                                     // the rows after the last complete group, all to a[]; an empty slot adds +0.0
+#pragma unroll
+                for (int i = g; i < g + 8; ++i) {
+                    unsigned m = base + i < n ? ~0u : 0u;            // masked as bits the compiler cannot see through: as a select, hipcc hoists the fp64
+                    asm volatile("" : "+v"(m));                      // conversions of both branches above them and holds 64 more registers
+                    a[0] += __uint_as_float(__float_as_uint(v[i].x) & m); a[1] += __uint_as_float(__float_as_uint(v[i].y) & m);
+                    a[2] += __uint_as_float(__float_as_uint(v[i].z) & m); a[3] += __uint_as_float(__float_as_uint(v[i].w) & m);
+                }
+            }
+        }
+    }
+};
+
+template <typename Ahead>
+__device__ __forceinline__ void bnfa_strip_colsum(const float* __restrict__ part, int rows, int C, int c0, double (*acc)[128], Ahead&& ahead) {
+    static_assert(BNFA_SLAB_BATCH % 8 == 0, "the a[] / b[] alternation is per group of eight");
+    BnfaSlab s;
+    s.src = part + (size_t)c0 * 2; s.rows = rows; s.ld = 2 * C; s.f4 = threadIdx.x & 31; s.rl = threadIdx.x >> 5;
+    s.n = (rows - s.rl + 7) >> 3;
+    const int nmax = (rows + 7) >> 3;                    // slab rows of row lane 0 (rows >= 1): the batches are the same for every thread
+    float4 v[BNFA_SLAB_BATCH];
+    int base = 0;
+    for (; base + BNFA_SLAB_BATCH < nmax; base += BNFA_SLAB_BATCH) { s.load(base, v); s.add(base, v); }
+    s.load(base, v);
+    ahead();
+    s.add(base, v);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) acc[s.rl][s.f4 * 4 + e] = s.a[e] + s.b[e];
+}
+
+// Rows lr, lr + 32, ... (BNFA_U of them) of a workgroup's nr rows, of one tensor or two, 16 bytes each at element lr * C + g behind the workgroup's
+// uniform base: issued here, unpacked at the use.  Unconditional, like the slab loads: a row past the range reads row nr - 1 again and is not used.
+// The offsets are 32-bit (one register per load): bnfa_grid keeps a workgroup's rows x C below 2^31 elements.
+template <typename T, bool TWO>
+struct BnfaRows {
+    uint4 p[BNFA_U], q[TWO ? BNFA_U : 1];
+    __device__ __forceinline__ void issue(const T* __restrict__ tp, const T* __restrict__ tq, int lr, int nr, int C, int g) {
+#pragma unroll
+        for (int i = 0; i < BNFA_U; ++i) {
+            const unsigned o = (unsigned)min(lr + 32 * i, nr - 1) * (unsigned)C + (unsigned)g;
+            p[i] = load_raw16(tp + o);
+            if (TWO) q[TWO ? i : 0] = load_raw16(tq + o);
+        }
+    }
+};
+
+// RES: with a residual (a run-time test would put the payload loads under a branch, and the waits behind it count for the worse path)
+template <typename T, bool RES>
+__global__ void __launch_bounds__(256, 4) bn_finalize_apply_kernel(const float* __restrict__ part, int rows, int C, float count, const float* __restrict__ gamma,
                                                                 const float* __restrict__ beta, float* __restrict__ rmean, float* __restrict__ rvar,
                                                                 float momentum, float eps, float* __restrict__ bnp, const T* __restrict__ y,
                                                                 const T* __restrict__ res, int relu, long M, long rows_per_wg, T* __restrict__ out) {
@@ -183,27 +277,16 @@ __global__ void __launch_bounds__(256) bn_finalize_apply_kernel(const float* __r
     __shared__ float ss[2][64];                          // scale, shift of the strip
     const int strip = blockIdx.x, c0 = strip * 64;
     const int tid = threadIdx.x;
-    {   // column sums of the strip's 128 floats (sum, sum^2 interleaved) of every slab row: thread = (float4 tid & 31, row lane tid >> 5), eight
-        // independent 16-byte loads per round trip (256 rows = 4 round trips)
-        const int f4 = tid & 31, rl = tid >> 5;
-        const float4* src = reinterpret_cast<const float4*>(part + (size_t)c0 * 2) + f4;
-        const size_t ld4 = (size_t)C / 2;                // float4 per slab row
-        double a[4] = {0, 0, 0, 0}, b[4] = {0, 0, 0, 0};
-        int r = rl;
-        for (; r + 56 < rows; r += 64) {
-            float4 v[8];
-#pragma unroll
-            for (int i = 0; i < 8; ++i) v[i] = src[(size_t)(r + 8 * i) * ld4];
-#pragma unroll
-            for (int i = 0; i < 8; i += 2) {
-                a[0] += v[i].x; a[1] += v[i].y; a[2] += v[i].z; a[3] += v[i].w;
-                b[0] += v[i + 1].x; b[1] += v[i + 1].y; b[2] += v[i + 1].z; b[3] += v[i + 1].w;
-            }
-        }
-        for (; r < rows; r += 8) { const float4 v = src[(size_t)r * ld4]; a[0] += v.x; a[1] += v.y; a[2] += v.z; a[3] += v.w; }
-#pragma unroll
-        for (int e = 0; e < 4; ++e) acc[rl][f4 * 4 + e] = a[e] + b[e];
-    }
+    const int g8 = tid & 7;                              // 16-byte group inside the strip
+    const long r0 = (long)blockIdx.y * rows_per_wg;
+    const int nr = (int)(min(M, r0 + rows_per_wg) - r0); // rows of this workgroup
+    int lr = tid >> 3;                                   // row lane (32 rows per pass)
+    y += r0 * C + c0; out += r0 * C + c0;
+    if (RES) res += r0 * C + c0;
+    float ga = 0.f, be = 0.f;
+    if (tid < 64) { ga = gamma[c0 + tid]; be = beta[c0 + tid]; }      // in front of the slab loads: their wait must not stand behind the payload's
+    BnfaRows<T, RES> ld;
+    bnfa_strip_colsum(part, rows, C, c0, acc, [&] { if (BNFA_AHEAD) ld.issue(y, res, lr, nr, C, g8 * V); });
     __syncthreads();
     if (tid < 64) {
         const int c = c0 + tid;
@@ -214,7 +297,7 @@ __global__ void __launch_bounds__(256) bn_finalize_apply_kernel(const float* __r
         double var = s2 / count - mean * mean;
         if (var < 0) var = 0;
         const float rstd = (float)(1.0 / sqrt(var + (double)eps));
-        const float sc = gamma[c] * rstd, sf = beta[c] - (float)mean * sc;
+        const float sc = ga * rstd, sf = be - (float)mean * sc;
         ss[0][tid] = sc; ss[1][tid] = sf;
         if (blockIdx.y == 0) {
             bnp[c] = (float)mean; bnp[C + c] = rstd; bnp[2 * C + c] = sc; bnp[3 * C + c] = sf;
@@ -226,24 +309,30 @@ __global__ void __launch_bounds__(256) bn_finalize_apply_kernel(const float* __r
         }
     }
     __syncthreads();
-    const int g8 = tid & 7, rl = tid >> 3;               // 16-byte group inside the strip, row lane (32 rows per pass)
     float sc[V], sf[V];
 #pragma unroll
     for (int e = 0; e < V; ++e) { sc[e] = ss[0][g8 * V + e]; sf[e] = ss[1][g8 * V + e]; }
-    const long r0 = (long)blockIdx.y * rows_per_wg, r1 = min(M, r0 + rows_per_wg);
-    for (long r = r0 + rl; r < r1; r += 32) {
-        const long off = r * C + c0 + g8 * V;
-        float v[V], rr[V];
-        load_vec<T>(y + off, v);
-        if (res) load_vec<T>(res + off, rr);
+    if (!BNFA_AHEAD) ld.issue(y, res, lr, nr, C, g8 * V);
+    for (;;) {                                           // blocks of BNFA_U passes, a block's loads issued before its first use; the first are on their way
 #pragma unroll
-        for (int e = 0; e < V; ++e) {
-            float t = fmaf(v[e], sc[e], sf[e]);          // (bn_bwd_reduce re-derives the ReLU mask from exactly this expression)
-            if (res) t += rr[e];
-            if (relu) t = fmaxf(t, 0.f);
-            v[e] = t;
+        for (int i = 0; i < BNFA_U; ++i) {
+            if (lr + 32 * i < nr) {
+                float v[V], rr[V];
+                unpack_vec<T>(ld.p[i], v);
+                if (RES) unpack_vec<T>(ld.q[RES ? i : 0], rr);
+#pragma unroll
+                for (int e = 0; e < V; ++e) {
+                    float t = fmaf(v[e], sc[e], sf[e]);  // (bn_bwd_reduce re-derives the ReLU mask from exactly this expression)
+                    if (RES) t += rr[e];
+                    if (relu) t = fmaxf(t, 0.f);
+                    v[e] = t;
+                }
+                store_vec<T>(out + ((unsigned)(lr + 32 * i) * (unsigned)C + (unsigned)(g8 * V)), v);
+            }
         }
-        store_vec<T>(out + off, v);
+        lr += 32 * BNFA_U;
+        if (lr >= nr) break;
+        ld.issue(y, res, lr, nr, C, g8 * V);
     }
 }
 
@@ -423,7 +512,7 @@ __global__ void __launch_bounds__(256) bn_bwd_apply_kernel(const T* __restrict__
 // twin of bn_finalize_apply_kernel: a workgroup owns a 64-channel strip x a range of rows, first reduces the slab columns (sum dz, sum dz * xhat) of its
 // own 64 channels -- every workgroup of a strip redundantly, same fixed order, fp64 -- then streams its rows; row range 0 also writes dgamma / dbeta.
 template <typename T>
-__global__ void __launch_bounds__(256) bn_bwd_finalize_apply_kernel(const float* __restrict__ part, int rows, int C, float count, float* __restrict__ dgamma,
+__global__ void __launch_bounds__(256, 4) bn_bwd_finalize_apply_kernel(const float* __restrict__ part, int rows, int C, float count, float* __restrict__ dgamma,
                                                                     float* __restrict__ dbeta, int accumulate, const T* __restrict__ dz_in,
                                                                     const T* __restrict__ y, const float* __restrict__ bnp, long M, long rows_per_wg,
                                                                     T* __restrict__ dy) {
@@ -431,26 +520,13 @@ __global__ void __launch_bounds__(256) bn_bwd_finalize_apply_kernel(const float*
     __shared__ double acc[8][128];
     __shared__ float cf[2][64];                          // mean(dz), mean(dz * xhat) of the strip
     const int c0 = blockIdx.x * 64, tid = threadIdx.x;
-    {
-        const int f4 = tid & 31, rl = tid >> 5;
-        const float4* src = reinterpret_cast<const float4*>(part + (size_t)c0 * 2) + f4;
-        const size_t ld4 = (size_t)C / 2;
-        double a[4] = {0, 0, 0, 0}, b[4] = {0, 0, 0, 0};
-        int r = rl;
-        for (; r + 56 < rows; r += 64) {
-            float4 v[8];
-#pragma unroll
-            for (int i = 0; i < 8; ++i) v[i] = src[(size_t)(r + 8 * i) * ld4];
-#pragma unroll
-            for (int i = 0; i < 8; i += 2) {
-                a[0] += v[i].x; a[1] += v[i].y; a[2] += v[i].z; a[3] += v[i].w;
-                b[0] += v[i + 1].x; b[1] += v[i + 1].y; b[2] += v[i + 1].z; b[3] += v[i + 1].w;
-            }
-        }
-        for (; r < rows; r += 8) { const float4 v = src[(size_t)r * ld4]; a[0] += v.x; a[1] += v.y; a[2] += v.z; a[3] += v.w; }
-#pragma unroll
-        for (int e = 0; e < 4; ++e) acc[rl][f4 * 4 + e] = a[e] + b[e];
-    }
+    const int g8 = tid & 7;
+    const long r0 = (long)blockIdx.y * rows_per_wg;
+    const int nr = (int)(min(M, r0 + rows_per_wg) - r0);
+    int lr = tid >> 3;
+    dz_in += r0 * C + c0; y += r0 * C + c0; dy += r0 * C + c0;
+    BnfaRows<T, true> ld;
+    bnfa_strip_colsum(part, rows, C, c0, acc, [&] { if (BNFA_AHEAD) ld.issue(dz_in, y, lr, nr, C, g8 * V); });
     __syncthreads();
     if (tid < 64) {
         const int c = c0 + tid;
@@ -464,25 +540,31 @@ __global__ void __launch_bounds__(256) bn_bwd_finalize_apply_kernel(const float*
         }
     }
     __syncthreads();
-    const int g8 = tid & 7, rl = tid >> 3;
     float mean[V], rstd[V], sc[V], k1[V], k2[V];
 #pragma unroll
     for (int e = 0; e < V; ++e) {
         const int c = c0 + g8 * V + e;
         mean[e] = bnp[c]; rstd[e] = bnp[C + c]; sc[e] = bnp[2 * C + c]; k1[e] = cf[0][g8 * V + e]; k2[e] = cf[1][g8 * V + e];
     }
-    const long r0 = (long)blockIdx.y * rows_per_wg, r1 = min(M, r0 + rows_per_wg);
-    for (long r = r0 + rl; r < r1; r += 32) {
-        const long off = r * C + c0 + g8 * V;
-        float d[V], yv[V], g[V];
-        load_vec<T>(dz_in + off, d);
-        load_vec<T>(y + off, yv);
+    if (!BNFA_AHEAD) ld.issue(dz_in, y, lr, nr, C, g8 * V);
+    for (;;) {                                           // blocks of BNFA_U passes, as in bn_finalize_apply_kernel
 #pragma unroll
-        for (int e = 0; e < V; ++e) {
-            const float xh = (yv[e] - mean[e]) * rstd[e];
-            g[e] = sc[e] * (d[e] - k1[e] - xh * k2[e]);
+        for (int i = 0; i < BNFA_U; ++i) {
+            if (lr + 32 * i < nr) {
+                float d[V], yv[V], g[V];
+                unpack_vec<T>(ld.p[i], d);
+                unpack_vec<T>(ld.q[i], yv);
+#pragma unroll
+                for (int e = 0; e < V; ++e) {
+                    const float xh = (yv[e] - mean[e]) * rstd[e];
+                    g[e] = sc[e] * (d[e] - k1[e] - xh * k2[e]);
+                }
+                store_vec<T>(dy + ((unsigned)(lr + 32 * i) * (unsigned)C + (unsigned)(g8 * V)), g);
+            }
         }
-        store_vec<T>(dy + off, g);
+        lr += 32 * BNFA_U;
+        if (lr >= nr) break;
+        ld.issue(dz_in, y, lr, nr, C, g8 * V);
     }
 }
 
@@ -1388,7 +1470,28 @@ int sde_bn_set_fuse(int on) {
     return old;
 }
 
-int sde_bn_finalize_apply_ok(int tiles, int C, int dtype) { return SDE_IS16(dtype) && C % 64 == 0 && tiles >= 1 && tiles <= BNFA_MAX_ROWS; }
+// Grid of the fused finalize + apply launches (forward and both backward entry points): strips x row ranges, about BNFA_TARGET_WGS workgroups, rows per
+// workgroup (*rpw) a multiple of the kernels' 32-row pass.  Every workgroup re-reduces its strip's slab columns, so fewer and longer workgroups re-read
+// less; 1024 stays: 512 and 768 were 0.02 ms per step ahead, less than the spread of the runs, and 256 was behind (profiles/bn_stream_ab.txt).
+// C <= BNFA_MAX_C (bnfa_ok): rows per workgroup are cut, and the ranges multiplied, so that rows x C stays below 2^31, the kernels' 32-bit offsets.
+#ifndef SDE_BNFA_TARGET_WGS
+#define SDE_BNFA_TARGET_WGS 1024
+#endif
+constexpr long BNFA_TARGET_WGS = SDE_BNFA_TARGET_WGS;
+static dim3 bnfa_grid(long M, int strips, long* rpw) {
+    long chunks = (BNFA_TARGET_WGS + strips - 1) / strips;
+    long r = (M + chunks - 1) / chunks;
+    r = (r + 31) / 32 * 32;
+    const long cap = ((1L << 31) - 1) / (strips * 64L) / 32 * 32;      // >= 480 rows for C <= BNFA_MAX_C
+    if (r > cap) r = cap;
+    chunks = (M + r - 1) / r;
+    *rpw = r;
+    return dim3((unsigned)strips, (unsigned)chunks);
+}
+
+static bool bnfa_ok(int rows, int C, int dtype) { return SDE_IS16(dtype) && C % 64 == 0 && C <= BNFA_MAX_C && rows >= 1 && rows <= BNFA_MAX_ROWS; }
+
+int sde_bn_finalize_apply_ok(int tiles, int C, int dtype) { return bnfa_ok(tiles, C, dtype); }
 
 int sde_bn_finalize_apply(const float* part, int tiles, int C, long count, const float* gamma, const float* beta, float* running_mean, float* running_var,
                           float momentum, float eps, float* bnp, const void* y, const void* residual, int relu, int dtype, void* out, sde_stream_t stream) {
@@ -1397,18 +1500,14 @@ int sde_bn_finalize_apply(const float* part, int tiles, int C, long count, const
                   BNFA_MAX_ROWS, tiles, C);
     const long M = count;
     const int strips = C / 64;
-    // enough workgroups to stream at full rate (>= ~1024), rows per workgroup a multiple of the 32-row pass
-    long chunks = (1024 + strips - 1) / strips;
-    long rpw = (M + chunks - 1) / chunks;
-    rpw = (rpw + 31) / 32 * 32;
-    if (rpw < 32) rpw = 32;
-    chunks = (M + rpw - 1) / rpw;
-    const dim3 grid((unsigned)strips, (unsigned)chunks);
+    long rpw;
+    const dim3 grid = bnfa_grid(M, strips, &rpw);
     hipStream_t s = (hipStream_t)stream;
     Types16::dispatch(dtype, [&](auto tag) {
         typedef typename decltype(tag)::type T;
-        hipLaunchKernelGGL(bn_finalize_apply_kernel<T>, grid, dim3(256), 0, s, part, tiles, C, (float)count, gamma, beta, running_mean, running_var, momentum, eps, bnp,
-                           (const T*)y, (const T*)residual, relu, M, rpw, (T*)out);
+        auto kernel = residual ? bn_finalize_apply_kernel<T, true> : bn_finalize_apply_kernel<T, false>;
+        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, part, tiles, C, (float)count, gamma, beta, running_mean, running_var, momentum, eps, bnp, (const T*)y,
+                           (const T*)residual, relu, M, rpw, (T*)out);
     });
     SDE_CHECK_LAUNCH("sde_bn_finalize_apply");
     return SDE_OK;
@@ -1478,13 +1577,10 @@ int sde_bn_bwd(const void* dout, const void* dout1, const void* dout2, const voi
     }
     SDE_CHECK_LAUNCH("sde_bn_bwd/reduce");
     const void* dz = gm ? gm : dout;
-    if (g_bn_fuse && SDE_IS16(dtype) && C % 64 == 0 && nblk <= BNFA_MAX_ROWS) {       // short slab: finalize + apply in one launch
+    if (g_bn_fuse && bnfa_ok(nblk, C, dtype)) {       // short slab: finalize + apply in one launch
         const int strips = C / 64;
-        long chunks = (1024 + strips - 1) / strips;
-        long rpw = (M + chunks - 1) / chunks;
-        rpw = (rpw + 31) / 32 * 32;
-        chunks = (M + rpw - 1) / rpw;
-        const dim3 grid((unsigned)strips, (unsigned)chunks);
+        long rpw;
+        const dim3 grid = bnfa_grid(M, strips, &rpw);
         Types16::dispatch(dtype, [&](auto tag) {
             typedef typename decltype(tag)::type T;
             hipLaunchKernelGGL(bn_bwd_finalize_apply_kernel<T>, grid, dim3(256), 0, s, part, nblk, C, (float)M, dgamma, dbeta, accumulate_params, (const T*)dz, (const T*)y, bnp,
@@ -1512,13 +1608,10 @@ int sde_bn_bwd_from_part(const float* part, int rows, const void* gm, const void
     const int V = sde_vec_elems(dtype);
     SDE_CHECK_ARG(part && gm && y && bnp && coef && dgamma && dbeta && dy && rows > 0 && M > 0 && C > 0 && C % V == 0, "sde_bn_bwd_from_part: bad argument");
     hipStream_t s = (hipStream_t)stream;
-    if (g_bn_fuse && SDE_IS16(dtype) && C % 64 == 0 && rows <= BNFA_MAX_ROWS) {       // short slab: finalize + apply in one launch
+    if (g_bn_fuse && bnfa_ok(rows, C, dtype)) {       // short slab: finalize + apply in one launch
         const int strips = C / 64;
-        long chunks = (1024 + strips - 1) / strips;
-        long rpw = (M + chunks - 1) / chunks;
-        rpw = (rpw + 31) / 32 * 32;
-        chunks = (M + rpw - 1) / rpw;
-        const dim3 grid((unsigned)strips, (unsigned)chunks);
+        long rpw;
+        const dim3 grid = bnfa_grid(M, strips, &rpw);
         Types16::dispatch(dtype, [&](auto tag) {
             typedef typename decltype(tag)::type T;
             hipLaunchKernelGGL(bn_bwd_finalize_apply_kernel<T>, grid, dim3(256), 0, s, part, rows, C, (float)M, dgamma, dbeta, accumulate_params, (const T*)gm, (const T*)y, bnp,

@@ -35,6 +35,24 @@ template <> __device__ __forceinline__ void load_vec<half_t>(const half_t* p, fl
 #pragma unroll
     for (int i = 0; i < 8; ++i) v[i] = (float)t[i];
 }
+// The same in two steps, for kernels that keep several loads in flight: load_raw16 only issues the load (4 registers, nothing waits), unpack_vec converts
+// at the point of use.  unpack_vec<T>(load_raw16(p), v) gives the floats of load_vec<T>(p, v).
+template <typename T> __device__ __forceinline__ uint4 load_raw16(const T* p) { return *reinterpret_cast<const uint4*>(p); }
+template <typename T> __device__ __forceinline__ void unpack_vec(const uint4& t, float* v);
+template <> __device__ __forceinline__ void unpack_vec<bf16_t>(const uint4& t, float* v) {
+    const uint32_t w[4] = {t.x, t.y, t.z, t.w};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        v[2 * i] = __uint_as_float(w[i] << 16);
+        v[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
+    }
+}
+template <> __device__ __forceinline__ void unpack_vec<half_t>(const uint4& t, float* v) {
+    typedef __attribute__((ext_vector_type(8))) _Float16 h8;
+    const h8 h = __builtin_bit_cast(h8, t);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) v[i] = (float)h[i];
+}
 template <typename T> __device__ __forceinline__ void store_vec(T* p, const float* v);
 template <> __device__ __forceinline__ void store_vec<float>(float* p, const float* v) {
     *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
