@@ -238,6 +238,11 @@ int sde_conv_dgrad_bnbwd(const sde_conv_desc* d, const void* w_packed, void* gm,
 int sde_conv_dgrad_bnbwd_res_rows(const sde_conv_desc* d, int Cout, int ldy);
 int sde_conv_dgrad_bnbwd_res(const sde_conv_desc* d, const void* w_packed, void* gm, int Cout, int ldy, const void* bn_y, const float* bnp, float* part,
                              const void* res_grad, const void* bn_out, sde_stream_t stream);
+/* The dispatcher's queries -- sde_conv_fwd_tiles_m (rows of the statistics slab), sde_conv_fwd_variant (the kernel: <BM><BN> register-staged tiles,
+ * 3128<BN> LDS-halo 3x3, 5<Cin><ldy> narrow-input halo, 7<BM><BN> persistent GEMM), sde_conv_fwd_ws_bytes, sde_conv_dgrad_bnbwd_rows / _res_rows,
+ * sde_conv_wgrad_variant and sde_conv_wgrad_splits -- read the one route the launch itself takes (csrc/conv.hip: route_fwd, route_wgrad).
+ * All of them answer 0 for a NULL descriptor or one the launch would refuse, with the reason in sde_last_error(); the launch then refuses the
+ * same descriptor with SDE_ERR_ARG, so a caller that sizes its buffers by a 0 never reaches a kernel. */
 int sde_conv_fwd_tiles_m(const sde_conv_desc* d, int ldy);
 int sde_conv_fwd_variant(const sde_conv_desc* d, int ldy);
 /* Tuning / test knob: the LDS-halo 3x3 kernel is used when a launch has at least this many workgroups (default 192; 0 = whenever it

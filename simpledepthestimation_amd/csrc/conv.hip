@@ -19,11 +19,17 @@
 //     partials for training-mode BatchNorm (deterministic: no atomics).
 //   * weight gradient: reduction over pixels with both operands read transposed out of LDS (ds_read_b64_tr_b16), split
 //     over pixel ranges into fp32 slabs that a second kernel sums in fixed order (bit-reproducible gradients).
+//
+// Host side (second half of the file): which kernel a GEMM takes -- the narrow-input halo kernel, the persistent LDS-DMA GEMM, the LDS-halo 3x3
+// kernel or the register-staged tiles of this file -- with its split-K factor, slab heights and BatchNorm-backward epilogue is decided in ONE
+// function, route_fwd; the launch and every query of include/sde_hip.h read its FwdRoute.  route_wgrad does the same for the weight gradient.
+// The sibling files' host interface is declared in conv_common.h; the storage-type dispatch is launch.h's SdeTypes.
 #include <type_traits>
 
 #include "vec16.h"      // VecOf
 #include "sde_hip.h"
 #include "conv_common.h"
+#include "launch.h"     // SdeTypes: the storage-type dispatch
 
 namespace {
 using namespace sdeconv;
@@ -463,7 +469,7 @@ __global__ void __launch_bounds__(256) splitk_finish_kernel(const float* __restr
 //   Per 64-channel block the (8+2)x(16+2) input pixels are staged in LDS ONCE; the nine filter taps are then nine shifted
 //   reads of that tile (address = base + tap offset), so the input crosses the vector-memory path 1.4x instead of 9x and the
 //   K loop carries no gather arithmetic at all -- only the small weight tiles stream per tap.  Same epilogue as igemm_kernel.
-//   Used for forward and data-gradient of every 3x3/1 layer whose output tiles well (see use_halo()).
+//   Used for forward and data-gradient of every 3x3/1 layer whose output tiles well (see halo_applicable()).
 // ------------------------------------------------------------------------------------------------------------------
 constexpr int HT_H = 8, HT_W = 16, HALO_W = HT_W + 2, HALO_PIX = (HT_H + 2) * HALO_W;   // 10 x 18 = 180 halo pixels
 // 128 B of channels + 32 B pad.  ds_read_b128 serves a wave in four groups of 16 lanes; a group of the fragment read holds all 16 pixel columns,
@@ -1353,25 +1359,16 @@ int launch_igemm(const IGemmP& p, hipStream_t s) {
     return 0;
 }
 
-// Tile choice (one place): returns BM*1000 + BN.  Small-N layers get narrow N tiles (the GEMM is then A-bandwidth bound);
-// layers whose 128x128 grid would not fill the 256 CUs fall back to 64x64 tiles.
-int pick_tile(long M, int N, int Ktot) {
+// Tile of the register-staged kernel (a rule of route_fwd): BM*1000 + BN.  Small-N layers get narrow N tiles (the GEMM is then A-bandwidth bound).
+int staged_tile(int N) {
     // Measured end to end in round 1 (Supervised R50, bs 12): 64x64 tiles for every N > 32 layer 10.10 ms/step, 128x64 10.28, 128x128 10.47 -- the
     // register-staged loop is latency-bound, not MFMA-bound (111 VGPRs / 32 KB LDS = 4 workgroups per CU vs 222 / 70 KB = 2), so occupancy wins
     // over operand reuse.  The wide instantiations were removed with their switches.
-    (void)M; (void)Ktot;
     if (N > 32) return 64064;
     if (N > 16) return 128032;
     return 128016;
 }
 
-// which specialisation of the gather a descriptor gets (bf16); fp32 (parity mode) keeps the run-time generic kernel
-int src_kind(const Gather& g) {
-    if (g.mode == SDE_SRC_UPCAT) return SRC_UPCAT_REFLECT;
-    if (g.mode == SDE_SRC_ZEROINS) return SRC_ZEROINS_ZERO;
-    if (g.KH == 1 && g.KW == 1 && g.pad == 0 && !g.reflect) return SRC_1X1;
-    return g.reflect ? SRC_PLAIN_REFLECT : SRC_PLAIN_ZERO;
-}
 bool one_tap_ok(const Gather& g, int group) {      // group = elements covered by one thread per stage
     return (g.Cin % group == 0) && (g.mode != SDE_SRC_UPCAT || g.C0 % group == 0);
 }
@@ -1391,26 +1388,24 @@ int dispatch_src(const IGemmP& p, hipStream_t s) {
     }
 }
 
-// ---- LDS-halo 3x3 kernel: when it applies and how it tiles (one place; sde_conv_fwd_tiles_m / _variant use it too)
+// ---- LDS-halo 3x3 kernel: when it applies and how it tiles (rules of route_fwd)
 int g_halo_min_blocks = 192;      // below this many workgroups the 64x64 generic tiles fill the chip better (sde_conv_set_halo_min_blocks)
 
-long halo_tiles(const Gather& g) { return (long)g.Bn * sde_cdiv(g.OH, HT_H) * sde_cdiv(g.OW, HT_W); }
+int halo_tiles(const Gather& g) { return (int)((long)g.Bn * sde_cdiv(g.OH, HT_H) * sde_cdiv(g.OW, HT_W)); }      // M tiles = rows of its slabs
 // N tile of the halo kernel: 64, or 32 / 16 for narrow outputs
-int halo_bn(const Gather& g, int ldy) {
-    (void)g;
+int halo_bn(int ldy) {
     return ldy > 32 ? 64 : (ldy > 16 ? 32 : 16);      // 64 wide at most: 3 waves / SIMD (measured 10.05 vs 10.10 ms/step against a 128-wide tile)
 }
-bool use_halo(const Gather& g, int dtype, int ldy) {
+bool halo_applicable(const Gather& g, int dtype, int ldy) {
     if (g_halo_min_blocks < 0 || !SDE_IS16(dtype) || g.KH != 3 || g.KW != 3 || g.stride != 1 || g.mode == SDE_SRC_ZEROINS) return false;
     if (g.mode == SDE_SRC_UPCAT && !g.reflect) return false;
     if (g.Cin % 8 || g.OH < HT_H || g.OW < HT_W) return false;
     if (sde_cdiv(g.Cin, 64) * 64 * 3 > g.Cin * 4) return false;     // the tile stages 64-channel blocks: narrow inputs (Cin < 48) waste MFMA and LDS
     const long tiles = (long)sde_cdiv(g.OH, HT_H) * sde_cdiv(g.OW, HT_W);
     if ((double)g.OH * g.OW < 0.75 * (double)tiles * HT_H * HT_W) return false;         // ragged tiling: the generic kernel wastes less
-    if (halo_tiles(g) * sde_cdiv(ldy, halo_bn(g, ldy)) < g_halo_min_blocks) return false; // too few workgroups: prefer the 64x64 generic tiles
+    if ((long)halo_tiles(g) * sde_cdiv(ldy, halo_bn(ldy)) < g_halo_min_blocks) return false; // too few workgroups: prefer the 64x64 generic tiles
     return true;
 }
-int halo_tiles_m(const Gather& g) { return (int)halo_tiles(g); }
 
 template <typename T, int BN, int WM, int WN, int SRC>
 int launch_halo(const IGemmP& p, hipStream_t s) {
@@ -1422,7 +1417,7 @@ int launch_halo(const IGemmP& p, hipStream_t s) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&halo3_kernel<T, BN, WM, WN, SRC>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
         attr_done = true;
     }
-    dim3 grid(halo_tiles_m(p.g) * sde_cdiv(p.ldy, BN));
+    dim3 grid(halo_tiles(p.g) * sde_cdiv(p.ldy, BN));
     hipLaunchKernelGGL((halo3_kernel<T, BN, WM, WN, SRC>), grid, dim3(NTHREADS), lds, s, p);
     return 0;
 }
@@ -1431,9 +1426,10 @@ int dispatch_halo_src(const IGemmP& p, hipStream_t s) {
     if (p.g.mode == SDE_SRC_UPCAT) return launch_halo<T, BN, WM, WN, SRC_UPCAT_REFLECT>(p, s);
     return p.g.reflect ? launch_halo<T, BN, WM, WN, SRC_PLAIN_REFLECT>(p, s) : launch_halo<T, BN, WM, WN, SRC_PLAIN_ZERO>(p, s);
 }
+// `tile` below is the route's (route_fwd): the launch templates do not ask the rules again
 template <typename T>
-int dispatch_halo(const IGemmP& p, hipStream_t s) {
-    switch (halo_bn(p.g, p.ldy)) {
+int dispatch_halo(const IGemmP& p, int tile, hipStream_t s) {
+    switch (tile % 1000) {
         case 64: return dispatch_halo_src<T, 64, 2, 2>(p, s);
         case 32: return dispatch_halo_src<T, 32, 4, 1>(p, s);
         default: return dispatch_halo_src<T, 16, 4, 1>(p, s);
@@ -1441,8 +1437,8 @@ int dispatch_halo(const IGemmP& p, hipStream_t s) {
 }
 
 template <typename T>
-int dispatch_igemm(const IGemmP& p, hipStream_t s) {
-    switch (pick_tile(p.g.M, p.ldy, p.g.Ktot)) {
+int dispatch_igemm(const IGemmP& p, int tile, hipStream_t s) {
+    switch (tile) {
         case 128032: return dispatch_src<T, 128, 32, 4, 1>(p, s);
         case 128016: return dispatch_src<T, 128, 16, 4, 1>(p, s);
         default: return dispatch_src<T, 64, 64, 2, 2>(p, s);
@@ -1516,52 +1512,63 @@ int fill_gather(const sde_conv_desc* d, Gather& g, const char* who) {
 
 }  // namespace
 
-// persistent LDS-DMA GEMM (pgemm.hip)
-namespace sdeconv {
-bool pgemm_applicable(const Gather& g, int dtype, int ldy);
-bool pgemm_bnbwd_ok(const Gather& g, int dtype, int ldy, int Cout, int depth);
-int pgemm_tile(const Gather& g, int ldy);
-int pgemm_run(const IGemmP& p, int dtype, int depth, hipStream_t s);
-int pgemm_stats_rows(const Gather& g, int ldy, int depth, bool bnbwd = false);
-// narrow-input 3x3 layers at high resolution (conv_halo_small.hip)
-bool chalo_applicable(const Gather& g, int dtype, int ldy);
-int chalo_run(const IGemmP& p, int dtype, hipStream_t s);
-// weight gradient on LDS-DMA for 64-channel-multiple layers (wgrad_dma.hip)
-bool wgrad_dma_applicable(const Gather& g, int dtype, int Cout, int ldd);
-int wgrad_dma_run(const Gather& g, int dtype, const void* dy, int Cout, int ldd, float* slab, int splits, int rows_per_split, hipStream_t s);
-int wgrad_dma_lds_bytes(int ring);
-extern int g_wgrad_dma_ring;
-int pgemm_lds_bytes(int depth);
-extern int g_pgemm_per_cu;
-int whalo_lds_bytes(int NB, int CO16);
-// halo weight gradient of the small-channel 3x3 layers (wgrad_halo.hip)
-bool whalo_applicable(const Gather& g, int dtype, int Cout, int ldd);
-int whalo_splits(const Gather& g, int Cout);
-int whalo_run(const Gather& g, int dtype, const void* dy, int Cout, int ldd, float* slab, int splits, hipStream_t s);
-extern int g_pgemm_force_tile;
-}
 namespace {
 // Dispatcher options: the ONLY process-wide state of the convolution engine (sde_conv_set_option; every former SDE_* environment switch of
-// this file either became one of these or was deleted with the code path it selected).
+// this file either became one of these or was deleted with the code path it selected).  The sibling files keep theirs beside the code they
+// steer (conv_common.h declares them); kOptions below is the one writer of all of them.
 int g_use_pgemm = 1;        // SDE_OPT_PGEMM
 int g_pgemm_depth = 3;      // SDE_OPT_PGEMM_DEPTH: ring stages (3: 48 KB -> 3 workgroups per CU; measured better than 4 on every layer)
 int g_pgemm_3x3 = 0;        // SDE_OPT_PGEMM_3X3: also take the layers the LDS-halo 3x3 kernel would get
 int g_splitk = 1;           // SDE_OPT_SPLITK
-long g_wgrad_blocks = 256;  // SDE_OPT_WGRAD_BLOCKS
-bool use_pgemm(const Gather& g, int dtype, int ldy) {
-    if (!g_use_pgemm || !pgemm_applicable(g, dtype, ldy)) return false;
-    return g_pgemm_3x3 || !use_halo(g, dtype, ldy);
-}
-}
+int g_wgrad_blocks = 256;   // SDE_OPT_WGRAD_BLOCKS
+int g_wgrad_halo = 1;       // SDE_OPT_WGRAD_HALO
+int g_conv_small = 1;       // SDE_OPT_CONV_SMALL
+int g_wgrad_dma = 1;        // SDE_OPT_WGRAD_DMA
+int g_bnbwd_fuse = 1;       // SDE_OPT_BNBWD_FUSE
 
-extern "C" {
+// {key, slot, validator or null, message of a refused value (may print the value)}
+const struct { int key; int* slot; bool (*ok)(int); const char* msg; } kOptions[] = {
+    {SDE_OPT_PGEMM, &g_use_pgemm, nullptr, nullptr},
+    {SDE_OPT_PGEMM_DEPTH, &g_pgemm_depth, [](int v) { return v == 3 || v == 4; }, "sde_conv_set_option: ring depth must be 3 or 4"},
+    {SDE_OPT_PGEMM_3X3, &g_pgemm_3x3, nullptr, nullptr},
+    {SDE_OPT_PGEMM_TILE, &g_pgemm_force_tile, [](int v) { return v == 0 || v == 64064 || v == 128064 || v == 128128; }, "sde_conv_set_option: bad tile %d"},
+    {SDE_OPT_SPLITK, &g_splitk, nullptr, nullptr},
+    {SDE_OPT_WGRAD_BLOCKS, &g_wgrad_blocks, [](int v) { return v >= 1 && v <= 65536; }, "sde_conv_set_option: bad workgroup target %d"},
+    {SDE_OPT_WGRAD_HALO, &g_wgrad_halo, nullptr, nullptr},
+    {SDE_OPT_CONV_SMALL, &g_conv_small, nullptr, nullptr},
+    {SDE_OPT_WGRAD_DMA, &g_wgrad_dma, nullptr, nullptr},
+    {SDE_OPT_BNBWD_FUSE, &g_bnbwd_fuse, nullptr, nullptr},
+    {SDE_OPT_CU_RESERVE, &g_cu_reserve, [](int v) { return v >= 0 && v <= 128 && v % 8 == 0; }, "sde_conv_set_option: CU reserve must be a multiple of 8 in [0, 128], got %d"},
+    {SDE_OPT_WGRAD_DMA_RING, &g_wgrad_dma_ring, [](int v) { return wgrad_dma_lds_bytes(v) > 0; }, "sde_conv_set_option: bad weight-gradient ring %d"},
+    {SDE_OPT_PGEMM_PER_CU, &g_pgemm_per_cu, [](int v) { return v >= 2 && v <= 4; }, "sde_conv_set_option: workgroups per CU must be 2, 3 or 4, got %d"},
+};
 
-// Split-K factor of a forward / data-gradient GEMM: layers whose 64x64 tiling leaves most of the 256 CUs x 4 workgroup slots empty while
-// the K loop is long (layer4 and the first decoder levels: M = 1440 ... 5760 pixels) cut K into up to 8 ranges.
-static int pick_ksplit(const Gather& g, int dtype, int ldy) {
-    const bool pg = use_pgemm(g, dtype, ldy);
+// storage types of the kernels in this file, in the order their kernels have always been emitted (launch.h)
+typedef SdeTypes<bf16_t, half_t, float> Types;      // register-staged GEMMs, split-K finish, weight packing
+typedef SdeTypes<bf16_t, half_t> Types16;           // LDS-halo 3x3 kernel
+
+// ------------------------------------------------------------------------------------------------------------------
+// The route of a forward / data-gradient GEMM, decided ONCE: the launch (conv_fwd_impl, dgrad_bnbwd_impl) and every query Python sizes its
+// buffers by (sde_conv_fwd_variant / _tiles_m / _ws_bytes, sde_conv_dgrad_bnbwd[_res]_rows) read the same FwdRoute, so a rule cannot be edited
+// in one of them and not the others.  A new kernel adds one branch to route_fwd and one case to launch_route.
+// ------------------------------------------------------------------------------------------------------------------
+enum { K_STAGED = 0, K_HALO = 3000000, K_CHALO = 5000000, K_PGEMM = 7000000 };      // = the leading digit of sde_conv_fwd_variant
+struct FwdRoute {
+    int kernel;      // K_*
+    int tile;        // BM*1000 + BN of that kernel (halo: 128*1000 + its N tile; chalo: Cin*1000 + ldy, the key of its instantiation)
+    int ksplit;      // 1, or the K ranges when a workspace is available
+    int stats_rows;  // rows of the statistics slab this launch writes
+    int bnbwd;       // 0 | K_PGEMM | K_HALO: the BatchNorm-backward epilogue exists for this layer
+    int bnbwd_rows;  // rows of its partial slab
+};
+
+// Split-K factor of a GEMM a workspace is available for: layers whose 64x64 tiling leaves most of the 256 CUs x 4 workgroup slots empty while
+// the K loop is long (layer4 and the first decoder levels: M = 1440 ... 5760 pixels) cut K into up to 8 ranges.  Only the 64x64 tiles of the
+// persistent and the register-staged kernel have the split form (the halo kernel's tile is 128 rows).
+int split_rule(const Gather& g, int dtype, int ldy, int kernel, int tile) {
+    const bool pg = kernel == K_PGEMM;
     if (!g_splitk || ldy % 4) return 1;
-    if (pg ? (pgemm_tile(g, ldy) != 64064 || g.mode == SDE_SRC_ZEROINS) : (use_halo(g, dtype, ldy) || pick_tile(g.M, ldy, g.Ktot) != 64064)) return 1;
+    if (tile != 64064 || (pg && g.mode == SDE_SRC_ZEROINS)) return 1;
     const long tiles = (long)sde_cdiv(g.M, 64) * sde_cdiv(ldy, 64);
     const int nk = sde_cdiv(g.Ktot, SDE_IS16(dtype) ? 64 : 32);
     // register-staged kernel (4 workgroups per CU, pipeline drained per tile): split below 384 tiles towards 768 workgroups (measured 10.12 ->
@@ -1579,8 +1586,85 @@ static int pick_ksplit(const Gather& g, int dtype, int ldy) {
     return S < 2 ? 1 : (int)S;
 }
 
-int g_conv_small = 1;       // SDE_OPT_CONV_SMALL
-static bool use_chalo(const Gather& g, int dtype, int ldy) { return g_conv_small && sdeconv::chalo_applicable(g, dtype, ldy); }
+// Cout matters to the bnbwd fields alone (the queries that do not ask for them pass 0).
+FwdRoute route_fwd(const Gather& g, int dtype, int Cout, int ldy, bool want_stats, bool have_ws) {
+    FwdRoute r = {};
+    const bool halo = halo_applicable(g, dtype, ldy);
+    if (g_use_pgemm && pgemm_applicable(g, dtype, ldy) && (g_pgemm_3x3 || !halo)) {
+        r.kernel = K_PGEMM; r.tile = pgemm_tile(g, ldy);
+        r.stats_rows = pgemm_stats_rows(g, ldy, g_pgemm_depth);      // (a split layer: one row per 64 rows -- conv_fwd_impl checks that this is the same number)
+    } else if (halo) {
+        r.kernel = K_HALO; r.tile = 128000 + halo_bn(ldy);
+        r.stats_rows = halo_tiles(g);
+    } else {
+        r.kernel = K_STAGED; r.tile = staged_tile(ldy);
+        r.stats_rows = sde_cdiv(g.M, r.tile / 1000);
+    }
+    const int split = split_rule(g, dtype, ldy, r.kernel, r.tile);
+    r.ksplit = have_ws ? split : 1;
+    const bool chalo = g_conv_small && chalo_applicable(g, dtype, ldy);
+    // BatchNorm-backward epilogue: the persistent GEMM's and the halo kernel's 64-wide form have one.  A layer the split rule cuts or chalo takes has none,
+    // whether or not this launch gets a workspace or writes statistics: those layers' data gradient goes the unfused way (sde_conv_fwd_ws + sde_bn_bwd).
+    if (g_bnbwd_fuse && SDE_IS16(dtype) && ldy == Cout && Cout % 64 == 0 && g.mode == SDE_SRC_PLAIN && g.stride == 1 && !g.reflect && split == 1 && !chalo) {
+        if (r.kernel == K_PGEMM && pgemm_bnbwd_ok(g, dtype, ldy, Cout, g_pgemm_depth)) { r.bnbwd = K_PGEMM; r.bnbwd_rows = pgemm_stats_rows(g, ldy, g_pgemm_depth, true); }
+        else if (r.kernel == K_HALO && r.tile == 128064) { r.bnbwd = K_HALO; r.bnbwd_rows = halo_tiles(g); }
+    }
+    // the narrow-input halo kernel writes no statistics and has no split form
+    if (chalo && !want_stats && r.ksplit == 1) { r.kernel = K_CHALO; r.tile = g.Cin * 1000 + ldy; }
+    return r;
+}
+
+// (fill_gather has refused every dtype outside Types, and the halo route is 16-bit by its predicate)
+void launch_route(int kernel, int tile, const IGemmP& p, int dtype, hipStream_t s) {
+    switch (kernel) {
+        case K_CHALO: chalo_run(p, dtype, s); break;
+        case K_PGEMM: pgemm_run(p, dtype, g_pgemm_depth, s); break;      // (takes its tile from pgemm_tile itself, 64x64 for the fused form)
+        case K_HALO: Types16::dispatch(dtype, [&](auto tag) { dispatch_halo<typename decltype(tag)::type>(p, tile, s); }); break;
+        default: Types::dispatch(dtype, [&](auto tag) { dispatch_igemm<typename decltype(tag)::type>(p, tile, s); }); break;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// The route of a weight-gradient GEMM, likewise: wgrad_partial, sde_conv_wgrad_variant and sde_conv_wgrad_splits read it.
+// ------------------------------------------------------------------------------------------------------------------
+struct WgradRoute {
+    int kind;        // SDE_WGRAD_*_KERNEL
+    int splits;      // fp32 slabs (pixel ranges) the layer asks for; the halo kernel accepts no other count
+};
+int wgrad_br(int dtype) { return SDE_IS16(dtype) ? WGTraits<bf16_t>::BR : WGTraits<float>::BR; }      // pixels per stage
+// pixels of one range when the caller cuts M into `splits` (the staged and the LDS-DMA kernel take any count >= 1): whole stages
+int wgrad_rows_per_split(int M, int splits, int dtype) { return sde_cdiv(sde_cdiv(M, splits), wgrad_br(dtype)) * wgrad_br(dtype); }
+
+WgradRoute route_wgrad(const Gather& g, int dtype, int Cout, int ldd) {
+    WgradRoute r;
+    r.kind = g_wgrad_halo && whalo_applicable(g, dtype, Cout, ldd) ? SDE_WGRAD_HALO_KERNEL
+           : g_wgrad_dma && wgrad_dma_applicable(g, dtype, Cout, ldd) ? SDE_WGRAD_DMA_KERNEL : SDE_WGRAD_STAGED_KERNEL;
+    if (r.kind == SDE_WGRAD_HALO_KERNEL) { r.splits = whalo_splits(g, Cout); return r; }
+    const long M = g.M, tiles = (long)sde_cdiv(Cout, wgrad_bmg(Cout)) * sde_cdiv(g.Ktot, 128);
+    long tgt = g_wgrad_blocks;                  // default 256 = one workgroup per CU (sde_conv_set_option(SDE_OPT_WGRAD_BLOCKS, n))
+    // a network's first layer (image input: <= 16 padded channels, huge M, a handful of output tiles) has no data gradient beside it and runs last
+    // in backward with nothing else on the GPU: two workgroups per CU hide its gather latency (7x7 stem: 74 -> 51 us; the one-per-CU default is
+    // the better choice only where the GEMM shares the GPU with the data-gradient chain)
+    // (a fixed target, not a multiple of the option: with PackNet's 1024 the 5x5 first layer ran 2048 workgroups and took 1.9 ms instead of 0.3)
+    if (g.Cin <= 16 && M >= 65536 && tiles <= 8) tgt = 2 * sde_persistent_cus();
+    long want = (tgt + tiles - 1) / tiles;                  // default 256 (one workgroup per CU): measured best end to end -- every extra split is another fp32 slab through HBM
+    const long max_by_rows = (M + 4 * wgrad_br(dtype) - 1) / (4 * wgrad_br(dtype));   // at least 4 stages per split
+    if (want > max_by_rows) want = max_by_rows;
+    const long max_by_mem = (256L << 20) / ((long)Cout * g.Ktot * 4);   // slab <= 256 MiB
+    if (want > max_by_mem) want = max_by_mem;
+    r.splits = want < 1 ? 1 : (int)want;
+    return r;
+}
+
+// One prologue for every query: false -- the query then answers 0, with the reason in sde_last_error -- for a null descriptor or one fill_gather
+// refuses.  (The launch the caller sizes its buffers for refuses the same descriptor with the same reason.)
+bool query_gather(const sde_conv_desc* d, Gather& g, const char* who) {
+    if (!d) { sde_set_error("%s: null descriptor", who); return false; }
+    return fill_gather(d, g, who) == SDE_OK;
+}
+}  // namespace
+
+extern "C" {
 
 static int conv_fwd_impl(const sde_conv_desc* d, const void* w_packed, const float* bias, int act, void* y, int Cout, int ldy, float* stats,
                          float* ws, size_t ws_bytes, sde_stream_t stream) {
@@ -1594,29 +1678,24 @@ static int conv_fwd_impl(const sde_conv_desc* d, const void* w_packed, const flo
     p.ksplit = 1; p.ws = nullptr;
     p.no_kfull = 0;
     p.bn_y = nullptr; p.bnp = nullptr; p.bn_gb = nullptr; p.bn_out = nullptr;
-    const int S = ws ? pick_ksplit(p.g, d->dtype, ldy) : 1;
-    if (S > 1) {
-        SDE_CHECK_ARG(ws_bytes >= (size_t)S * p.g.M * ldy * sizeof(float), "sde_conv_fwd_ws: workspace too small (%zu bytes)", ws_bytes);
-        p.ksplit = S; p.ws = ws;
+    const FwdRoute r = route_fwd(p.g, d->dtype, Cout, ldy, stats != nullptr, ws != nullptr);
+    if (r.ksplit > 1) {
+        SDE_CHECK_ARG(ws_bytes >= (size_t)r.ksplit * p.g.M * ldy * sizeof(float), "sde_conv_fwd_ws: workspace too small (%zu bytes)", ws_bytes);
+        p.ksplit = r.ksplit; p.ws = ws;
     }
-    if (!stats && p.ksplit == 1 && use_chalo(p.g, d->dtype, ldy)) {
-        sdeconv::chalo_run(p, d->dtype, (hipStream_t)stream);
-    } else if (use_pgemm(p.g, d->dtype, ldy)) {
-        SDE_CHECK_ARG((p.ksplit - 1) * sde_cdiv(p.g.Ktot / 64, p.ksplit) < p.g.Ktot / 64, "sde_conv_fwd: empty K split");
-        // sde_conv_fwd_tiles_m does not know whether a workspace will be passed: a split layer's statistics slab has one row per 64 rows
-        SDE_CHECK_ARG(p.ksplit == 1 || sdeconv::pgemm_stats_rows(p.g, ldy, g_pgemm_depth) == sde_cdiv(p.g.M, 64), "sde_conv_fwd: split-K layer with per-workgroup statistics");
-        sdeconv::pgemm_run(p, d->dtype, g_pgemm_depth, (hipStream_t)stream);
-    } else if (use_halo(p.g, d->dtype, ldy)) {
-        if (d->dtype == SDE_BF16) dispatch_halo<bf16_t>(p, (hipStream_t)stream); else dispatch_halo<half_t>(p, (hipStream_t)stream);
-    } else if (d->dtype == SDE_BF16) dispatch_igemm<bf16_t>(p, (hipStream_t)stream);
-    else if (d->dtype == SDE_F16) dispatch_igemm<half_t>(p, (hipStream_t)stream);
-    else dispatch_igemm<float>(p, (hipStream_t)stream);
+    if (r.kernel == K_PGEMM) {
+        SDE_CHECK_ARG((r.ksplit - 1) * sde_cdiv(p.g.Ktot / 64, r.ksplit) < p.g.Ktot / 64, "sde_conv_fwd: empty K split");
+        // the route's slab height does not depend on a workspace being passed: a split layer's finish kernel writes one row per 64 rows
+        SDE_CHECK_ARG(r.ksplit == 1 || r.stats_rows == sde_cdiv(p.g.M, 64), "sde_conv_fwd: split-K layer with per-workgroup statistics");
+    }
+    launch_route(r.kernel, r.tile, p, d->dtype, (hipStream_t)stream);
     SDE_CHECK_LAUNCH("sde_conv_fwd");
-    if (S > 1) {
+    if (r.ksplit > 1) {
         const unsigned nb = (unsigned)(sde_cdiv(p.g.M, 64) * sde_cdiv(ldy, 64));
-        if (d->dtype == SDE_BF16) hipLaunchKernelGGL(splitk_finish_kernel<bf16_t>, dim3(nb), dim3(256), 0, (hipStream_t)stream, ws, S, p.g.M, ldy, Cout, bias, act, (bf16_t*)y, stats);
-        else if (d->dtype == SDE_F16) hipLaunchKernelGGL(splitk_finish_kernel<half_t>, dim3(nb), dim3(256), 0, (hipStream_t)stream, ws, S, p.g.M, ldy, Cout, bias, act, (half_t*)y, stats);
-        else hipLaunchKernelGGL(splitk_finish_kernel<float>, dim3(nb), dim3(256), 0, (hipStream_t)stream, ws, S, p.g.M, ldy, Cout, bias, act, (float*)y, stats);
+        Types::dispatch(d->dtype, [&](auto tag) {
+            typedef typename decltype(tag)::type T;
+            hipLaunchKernelGGL(splitk_finish_kernel<T>, dim3(nb), dim3(256), 0, (hipStream_t)stream, ws, r.ksplit, p.g.M, ldy, Cout, bias, act, (T*)y, stats);
+        });
         SDE_CHECK_LAUNCH("sde_conv_fwd/splitk_finish");
     }
     return SDE_OK;
@@ -1627,57 +1706,40 @@ int sde_conv_fwd(const sde_conv_desc* d, const void* w_packed, const float* bias
     return conv_fwd_impl(d, w_packed, bias, act, y, Cout, ldy, stats, nullptr, 0, stream);
 }
 
-size_t sde_conv_fwd_ws_bytes(const sde_conv_desc* d, int ldy) {
-    Gather g;
-    if (!d || fill_gather(d, g, "sde_conv_fwd_ws_bytes") != SDE_OK) return 0;
-    const int S = pick_ksplit(g, d->dtype, ldy);
-    return S > 1 ? (size_t)S * g.M * ldy * sizeof(float) : 0;
-}
-
 int sde_conv_fwd_ws(const sde_conv_desc* d, const void* w_packed, const float* bias, int act, void* y, int Cout, int ldy, float* stats, void* ws,
                     size_t ws_bytes, sde_stream_t stream) {
     return conv_fwd_impl(d, w_packed, bias, act, y, Cout, ldy, stats, (float*)ws, ws_bytes, stream);
 }
 
-static int gather_of(const sde_conv_desc* d, Gather& g) { return fill_gather(d, g, "sde_conv_fwd_tiles_m"); }
+// ---- the queries: each is one field of the route (0 for a descriptor the launch would refuse: query_gather)
+size_t sde_conv_fwd_ws_bytes(const sde_conv_desc* d, int ldy) {
+    Gather g;
+    if (!query_gather(d, g, "sde_conv_fwd_ws_bytes")) return 0;
+    const int S = route_fwd(g, d->dtype, 0, ldy, false, true).ksplit;
+    return S > 1 ? (size_t)S * g.M * ldy * sizeof(float) : 0;
+}
 
-int g_bnbwd_fuse = 1;       // SDE_OPT_BNBWD_FUSE
+int sde_conv_fwd_variant(const sde_conv_desc* d, int ldy) {
+    // 5<Cin><ldy>: narrow-input halo kernel, 7<BM><BN>: persistent LDS-DMA GEMM, 3128<BN>: LDS-halo 3x3 kernel, <BM><BN>: register-staged tiles.
+    // The kernel of a launch WITHOUT statistics and without a workspace: a layer that asks for statistics never takes chalo, and one the split rule
+    // cuts (sde_conv_fwd_ws_bytes > 0) runs the split form of the base kernel when it is given the workspace -- callers pin the split beside this.
+    Gather g;
+    if (!query_gather(d, g, "sde_conv_fwd_variant")) return 0;
+    const FwdRoute r = route_fwd(g, d->dtype, 0, ldy, false, false);
+    return r.kernel + r.tile;
+}
 
-// 1 = persistent GEMM, 2 = LDS-halo 3x3 kernel, 0 = this layer's data gradient runs on a kernel without the BatchNorm-backward epilogue
-static int bnbwd_kind(const Gather& g, int dtype, int ldy, int Cout) {
-    if (!g_bnbwd_fuse || !SDE_IS16(dtype) || ldy != Cout || Cout % 64 || g.mode != SDE_SRC_PLAIN || g.stride != 1 || g.reflect) return 0;
-    if (pick_ksplit(g, dtype, ldy) != 1) return 0;
-    if (use_chalo(g, dtype, ldy)) return 0;
-    if (use_pgemm(g, dtype, ldy)) return sdeconv::pgemm_bnbwd_ok(g, dtype, ldy, Cout, g_pgemm_depth) ? 1 : 0;
-    if (use_halo(g, dtype, ldy)) return halo_bn(g, ldy) == 64 ? 2 : 0;
-    return 0;
+int sde_conv_fwd_tiles_m(const sde_conv_desc* d, int ldy) {
+    // number of M tiles the dispatcher will use (= rows of the BN-statistics slab)
+    Gather g;
+    if (!query_gather(d, g, "sde_conv_fwd_tiles_m")) return 0;
+    return route_fwd(g, d->dtype, 0, ldy, true, false).stats_rows;
 }
 
 int sde_conv_dgrad_bnbwd_rows(const sde_conv_desc* d, int Cout, int ldy) {
     Gather g;
-    if (!d || fill_gather(d, g, "sde_conv_dgrad_bnbwd_rows") != SDE_OK) return 0;
-    const int kind = bnbwd_kind(g, d->dtype, ldy, Cout);
-    if (kind == 1) return sdeconv::pgemm_stats_rows(g, ldy, g_pgemm_depth, true);
-    if (kind == 2) return halo_tiles_m(g);
-    return 0;
-}
-
-int sde_conv_dgrad_bnbwd(const sde_conv_desc* d, const void* w_packed, void* gm, int Cout, int ldy, const void* bn_y, const float* bnp, float* part,
-                         sde_stream_t stream) {
-    SDE_CHECK_ARG(d && w_packed && gm && bn_y && bnp && part, "sde_conv_dgrad_bnbwd: null pointer");
-    IGemmP p;
-    int rc = fill_gather(d, p.g, "sde_conv_dgrad_bnbwd");
-    if (rc) return rc;
-    const int kind = bnbwd_kind(p.g, d->dtype, ldy, Cout);
-    SDE_CHECK_ARG(kind != 0, "sde_conv_dgrad_bnbwd: this layer has no fused form (ask sde_conv_dgrad_bnbwd_rows first)");
-    p.w = w_packed; p.bias = nullptr; p.y = gm; p.stats = part; p.Cout = Cout; p.ldy = ldy; p.act = SDE_ACT_NONE;
-    p.ksplit = 1; p.ws = nullptr; p.no_kfull = 0;
-    p.bn_y = bn_y; p.bnp = bnp; p.bn_gb = nullptr; p.bn_out = nullptr;
-    if (kind == 1) sdeconv::pgemm_run(p, d->dtype, g_pgemm_depth, (hipStream_t)stream);
-    else if (d->dtype == SDE_BF16) dispatch_halo<bf16_t>(p, (hipStream_t)stream);
-    else dispatch_halo<half_t>(p, (hipStream_t)stream);
-    SDE_CHECK_LAUNCH("sde_conv_dgrad_bnbwd");
-    return SDE_OK;
+    if (!query_gather(d, g, "sde_conv_dgrad_bnbwd_rows")) return 0;
+    return route_fwd(g, d->dtype, Cout, ldy, true, false).bnbwd_rows;
 }
 
 // The same for a BatchNorm followed by "+ identity, ReLU" whose output has a second consumer (torchvision's Bottleneck: conv1 of the next block and that
@@ -1685,84 +1747,51 @@ int sde_conv_dgrad_bnbwd(const sde_conv_desc* d, const void* w_packed, void* gm,
 // The persistent GEMM and the LDS-halo 3x3 kernel (BasicBlock's conv1) carry this form.
 int sde_conv_dgrad_bnbwd_res_rows(const sde_conv_desc* d, int Cout, int ldy) {
     Gather g;
-    if (!d || fill_gather(d, g, "sde_conv_dgrad_bnbwd_res_rows") != SDE_OK) return 0;
-    const int kind = bnbwd_kind(g, d->dtype, ldy, Cout);
-    return kind == 1 ? sdeconv::pgemm_stats_rows(g, ldy, g_pgemm_depth, true) : kind == 2 ? halo_tiles_m(g) : 0;
+    if (!query_gather(d, g, "sde_conv_dgrad_bnbwd_res_rows")) return 0;
+    return route_fwd(g, d->dtype, Cout, ldy, true, false).bnbwd_rows;
+}
+
+// one body for both fused data gradients: the residual form passes res_grad / bn_out, the plain one nulls
+static int dgrad_bnbwd_impl(const char* who, const sde_conv_desc* d, const void* w_packed, void* gm, int Cout, int ldy, const void* bn_y, const float* bnp,
+                            float* part, const void* res_grad, const void* bn_out, sde_stream_t stream) {
+    IGemmP p;
+    int rc = fill_gather(d, p.g, who);
+    if (rc) return rc;
+    const FwdRoute r = route_fwd(p.g, d->dtype, Cout, ldy, true, false);
+    SDE_CHECK_ARG(r.bnbwd != 0, "%s: this layer has no fused form (ask %s_rows first)", who, who);
+    p.w = w_packed; p.bias = nullptr; p.y = gm; p.stats = part; p.Cout = Cout; p.ldy = ldy; p.act = SDE_ACT_NONE;
+    p.ksplit = 1; p.ws = nullptr; p.no_kfull = 0;
+    p.bn_y = bn_y; p.bnp = bnp; p.bn_gb = res_grad; p.bn_out = bn_out;
+    // r.bnbwd is r.kernel where it is not 0, so r.tile is that kernel's: the halo form's 128064; pgemm_run ignores it
+    launch_route(r.bnbwd, r.tile, p, d->dtype, (hipStream_t)stream);
+    SDE_CHECK_LAUNCH(who);
+    return SDE_OK;
+}
+
+int sde_conv_dgrad_bnbwd(const sde_conv_desc* d, const void* w_packed, void* gm, int Cout, int ldy, const void* bn_y, const float* bnp, float* part,
+                         sde_stream_t stream) {
+    SDE_CHECK_ARG(d && w_packed && gm && bn_y && bnp && part, "sde_conv_dgrad_bnbwd: null pointer");
+    return dgrad_bnbwd_impl("sde_conv_dgrad_bnbwd", d, w_packed, gm, Cout, ldy, bn_y, bnp, part, nullptr, nullptr, stream);
 }
 
 int sde_conv_dgrad_bnbwd_res(const sde_conv_desc* d, const void* w_packed, void* gm, int Cout, int ldy, const void* bn_y, const float* bnp, float* part,
                              const void* res_grad, const void* bn_out, sde_stream_t stream) {
     SDE_CHECK_ARG(d && w_packed && gm && bn_y && bnp && part && res_grad && bn_out, "sde_conv_dgrad_bnbwd_res: null pointer");
-    IGemmP p;
-    int rc = fill_gather(d, p.g, "sde_conv_dgrad_bnbwd_res");
-    if (rc) return rc;
-    const int kind = bnbwd_kind(p.g, d->dtype, ldy, Cout);
-    SDE_CHECK_ARG(kind != 0, "sde_conv_dgrad_bnbwd_res: this layer has no fused form (ask sde_conv_dgrad_bnbwd_res_rows first)");
-    p.w = w_packed; p.bias = nullptr; p.y = gm; p.stats = part; p.Cout = Cout; p.ldy = ldy; p.act = SDE_ACT_NONE;
-    p.ksplit = 1; p.ws = nullptr; p.no_kfull = 0;
-    p.bn_y = bn_y; p.bnp = bnp; p.bn_gb = res_grad; p.bn_out = bn_out;
-    if (kind == 1) sdeconv::pgemm_run(p, d->dtype, g_pgemm_depth, (hipStream_t)stream);
-    else if (d->dtype == SDE_BF16) dispatch_halo<bf16_t>(p, (hipStream_t)stream);
-    else dispatch_halo<half_t>(p, (hipStream_t)stream);
-    SDE_CHECK_LAUNCH("sde_conv_dgrad_bnbwd_res");
-    return SDE_OK;
-}
-
-int sde_conv_fwd_variant(const sde_conv_desc* d, int ldy) {
-    Gather g;
-    if (gather_of(d, g) == SDE_OK && use_chalo(g, d->dtype, ldy)) return 5000000 + g.Cin * 1000 + ldy;            // 5<Cin><ldy>: narrow-input halo kernel (without BN statistics)
-    if (gather_of(d, g) == SDE_OK && use_pgemm(g, d->dtype, ldy)) return 7000000 + pgemm_tile(g, ldy);   // 7<BM><BN>: persistent LDS-DMA GEMM
-    if (gather_of(d, g) == SDE_OK && use_halo(g, d->dtype, ldy)) return 3128000 + halo_bn(g, ldy);      // 3128<BN>: LDS-halo 3x3 kernel
-    return pick_tile((long)d->Bn * d->OH * d->OW, ldy, d->KH * d->KW * (d->C0 + d->C1));
-}
-
-int sde_conv_fwd_tiles_m(const sde_conv_desc* d, int ldy) {
-    // number of M tiles the dispatcher will use (= rows of the BN-statistics slab)
-    Gather g;
-    if (gather_of(d, g) == SDE_OK && use_pgemm(g, d->dtype, ldy)) return sdeconv::pgemm_stats_rows(g, ldy, g_pgemm_depth);
-    if (gather_of(d, g) == SDE_OK && use_halo(g, d->dtype, ldy)) return halo_tiles_m(g);
-    const long M = (long)d->Bn * d->OH * d->OW;
-    return sde_cdiv(M, pick_tile(M, ldy, d->KH * d->KW * (d->C0 + d->C1)) / 1000);
-}
-
-int g_wgrad_halo = 1;       // SDE_OPT_WGRAD_HALO
-int g_wgrad_dma = 1;        // SDE_OPT_WGRAD_DMA
-static bool use_whalo(const Gather& g, int dtype, int Cout, int ldd) { return g_wgrad_halo && sdeconv::whalo_applicable(g, dtype, Cout, ldd); }
-// which weight-gradient GEMM a layer takes (one place: wgrad_partial and sde_conv_wgrad_variant)
-static int wgrad_kind(const Gather& g, int dtype, int Cout, int ldd) {
-    if (use_whalo(g, dtype, Cout, ldd)) return SDE_WGRAD_HALO_KERNEL;
-    if (g_wgrad_dma && sdeconv::wgrad_dma_applicable(g, dtype, Cout, ldd)) return SDE_WGRAD_DMA_KERNEL;
-    return SDE_WGRAD_STAGED_KERNEL;
+    return dgrad_bnbwd_impl("sde_conv_dgrad_bnbwd_res", d, w_packed, gm, Cout, ldy, bn_y, bnp, part, res_grad, bn_out, stream);
 }
 
 int sde_conv_wgrad_variant(const sde_conv_desc* d, int Cout, int ldd) {
     Gather g;
-    if (!d || fill_gather(d, g, "sde_conv_wgrad_variant") != SDE_OK) return 0;
-    return wgrad_kind(g, d->dtype, Cout, ldd);
+    if (!query_gather(d, g, "sde_conv_wgrad_variant")) return 0;
+    return route_wgrad(g, d->dtype, Cout, ldd).kind;
 }
 
 int sde_conv_wgrad_splits(const sde_conv_desc* d, int Cout) {
-    {
-        Gather g;
-        if (fill_gather(d, g, "sde_conv_wgrad_splits") == SDE_OK && use_whalo(g, d->dtype, Cout, 8)) return sdeconv::whalo_splits(g, Cout);
-    }
-    const long M = (long)d->Bn * d->OH * d->OW;
-    const int Ktot = d->KH * d->KW * (d->C0 + d->C1);
-    const long tiles = (long)sde_cdiv(Cout, wgrad_bmg(Cout)) * sde_cdiv(Ktot, 128);
-    const int BR = SDE_IS16(d->dtype) ? 64 : 32;
-    long tgt = g_wgrad_blocks;                  // default 256 = one workgroup per CU (sde_conv_set_option(SDE_OPT_WGRAD_BLOCKS, n))
-    // a network's first layer (image input: <= 16 padded channels, huge M, a handful of output tiles) has no data gradient beside it and runs last
-    // in backward with nothing else on the GPU: two workgroups per CU hide its gather latency (7x7 stem: 74 -> 51 us; the one-per-CU default is
-    // the better choice only where the GEMM shares the GPU with the data-gradient chain)
-    // (a fixed target, not a multiple of the option: with PackNet's 1024 the 5x5 first layer ran 2048 workgroups and took 1.9 ms instead of 0.3)
-    if (d->C0 + d->C1 <= 16 && M >= 65536 && tiles <= 8) tgt = 2 * sdeconv::sde_persistent_cus();
-    long want = (tgt + tiles - 1) / tiles;                  // default 256 (one workgroup per CU): measured best end to end -- every extra split is another fp32 slab through HBM
-    const long max_by_rows = (M + 4 * BR - 1) / (4 * BR);   // at least 4 stages per split
-    if (want > max_by_rows) want = max_by_rows;
-    const long max_by_mem = (256L << 20) / ((long)Cout * Ktot * 4);   // slab <= 256 MiB
-    if (want > max_by_mem) want = max_by_mem;
-    if (want < 1) want = 1;
-    return (int)want;
+    Gather g;
+    if (!query_gather(d, g, "sde_conv_wgrad_splits")) return 0;
+    // This query has no ldd parameter and has always asked the halo predicate with ldd = 8 (any multiple of 8 passes its alignment test; its 2 GiB test then
+    // sees M * 8 * 2 bytes, not the launch's M * ldd * 2).  Kept, so that its answers do not move; the split count of the other kernels does not read ldd.
+    return route_wgrad(g, d->dtype, Cout, 8).splits;
 }
 
 // The GEMM: `splits` fp32 slabs [Cout][Ktot].
@@ -1773,31 +1802,26 @@ static int wgrad_partial(const sde_conv_desc* d, const void* dy, int Cout, int l
     const int V = SDE_IS16(d->dtype) ? 8 : 4;
     SDE_CHECK_ARG(Cout > 0 && ldd >= Cout && ldd % V == 0, "sde_conv_wgrad: bad Cout=%d ldd=%d", Cout, ldd);
     SDE_CHECK_ARG(splits >= 1, "sde_conv_wgrad: bad splits=%d", splits);
-    const int kind = wgrad_kind(p.g, d->dtype, Cout, ldd);
-    if (kind == SDE_WGRAD_HALO_KERNEL) {
-        SDE_CHECK_ARG(splits == sdeconv::whalo_splits(p.g, Cout), "sde_conv_wgrad: splits=%d, this layer needs sde_conv_wgrad_splits() = %d", splits,
-                      sdeconv::whalo_splits(p.g, Cout));
-        sdeconv::whalo_run(p.g, d->dtype, dy, Cout, ldd, slab, splits, s);
+    const WgradRoute r = route_wgrad(p.g, d->dtype, Cout, ldd);
+    const int rps = wgrad_rows_per_split(p.g.M, splits, d->dtype);
+    if (r.kind == SDE_WGRAD_HALO_KERNEL) {
+        SDE_CHECK_ARG(splits == r.splits, "sde_conv_wgrad: splits=%d, this layer needs sde_conv_wgrad_splits() = %d", splits, r.splits);
+        whalo_run(p.g, d->dtype, dy, Cout, ldd, slab, splits, s);
         SDE_CHECK_LAUNCH("sde_conv_wgrad (halo)");
         g = p.g;
         return SDE_OK;
     }
-    const int BR = SDE_IS16(d->dtype) ? 64 : 32;
-    int rps = sde_cdiv(p.g.M, splits);
-    rps = sde_cdiv(rps, BR) * BR;
     SDE_CHECK_ARG((long)rps * splits >= p.g.M, "sde_conv_wgrad: split arithmetic");
     // 1x1 layers 11-16 us against 14-21 us for the register-staged kernel, 3x3 layers 22-26 us against 27-30 us (profiles/README.md item 16)
-    if (kind == SDE_WGRAD_DMA_KERNEL) {
-        sdeconv::wgrad_dma_run(p.g, d->dtype, dy, Cout, ldd, slab, splits, rps, s);
+    if (r.kind == SDE_WGRAD_DMA_KERNEL) {
+        wgrad_dma_run(p.g, d->dtype, dy, Cout, ldd, slab, splits, rps, s);
         SDE_CHECK_LAUNCH("sde_conv_wgrad (LDS-DMA)");
         g = p.g;
         return SDE_OK;
     }
     p.dy = dy; p.slab = slab; p.Cout = Cout; p.ldd = ldd; p.rows_per_split = rps;
     p.single_buf = SDE_IS16(d->dtype) ? 1 : 0;      // one LDS stage buffer for the 16-bit tiles: 3 workgroups per CU, measured -0.7 % step time
-    if (d->dtype == SDE_BF16) dispatch_wgrad<bf16_t>(p, splits, s);
-    else if (d->dtype == SDE_F16) dispatch_wgrad<half_t>(p, splits, s);
-    else dispatch_wgrad<float>(p, splits, s);
+    Types::dispatch(d->dtype, [&](auto tag) { dispatch_wgrad<typename decltype(tag)::type>(p, splits, s); });
     SDE_CHECK_LAUNCH("sde_conv_wgrad");
     g = p.g;
     return SDE_OK;
@@ -1893,43 +1917,37 @@ int sde_pack_weight(const float* w, void* out, int dtype, int Cout, int Cin, int
     const size_t total = for_dgrad ? (size_t)Cin_pad * KH * KW * Cout_pad : (size_t)Cout_pad * KH * KW * Cin_pad;
     const int nb = (int)((total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256);
     if (for_dgrad) {
-        if (dtype == SDE_BF16) hipLaunchKernelGGL(pack_w_dgrad_kernel<bf16_t>, dim3(nb), dim3(256), 0, s, w, (bf16_t*)out, Cout, Cin, KH, KW, Cout_pad, Cin_pad);
-        else if (dtype == SDE_F16) hipLaunchKernelGGL(pack_w_dgrad_kernel<half_t>, dim3(nb), dim3(256), 0, s, w, (half_t*)out, Cout, Cin, KH, KW, Cout_pad, Cin_pad);
-        else hipLaunchKernelGGL(pack_w_dgrad_kernel<float>, dim3(nb), dim3(256), 0, s, w, (float*)out, Cout, Cin, KH, KW, Cout_pad, Cin_pad);
+        Types::dispatch(dtype, [&](auto tag) {
+            typedef typename decltype(tag)::type T;
+            hipLaunchKernelGGL(pack_w_dgrad_kernel<T>, dim3(nb), dim3(256), 0, s, w, (T*)out, Cout, Cin, KH, KW, Cout_pad, Cin_pad);
+        });
     } else {
-        if (dtype == SDE_BF16) hipLaunchKernelGGL(pack_w_fwd_kernel<bf16_t>, dim3(nb), dim3(256), 0, s, w, (bf16_t*)out, Cout, Cin, KH, KW, Cin_pad, Cout_pad);
-        else if (dtype == SDE_F16) hipLaunchKernelGGL(pack_w_fwd_kernel<half_t>, dim3(nb), dim3(256), 0, s, w, (half_t*)out, Cout, Cin, KH, KW, Cin_pad, Cout_pad);
-        else hipLaunchKernelGGL(pack_w_fwd_kernel<float>, dim3(nb), dim3(256), 0, s, w, (float*)out, Cout, Cin, KH, KW, Cin_pad, Cout_pad);
+        Types::dispatch(dtype, [&](auto tag) {
+            typedef typename decltype(tag)::type T;
+            hipLaunchKernelGGL(pack_w_fwd_kernel<T>, dim3(nb), dim3(256), 0, s, w, (T*)out, Cout, Cin, KH, KW, Cin_pad, Cout_pad);
+        });
     }
     SDE_CHECK_LAUNCH("sde_pack_weight");
     return SDE_OK;
 }
 
 int sde_conv_set_option(int key, int value) {
-    if (key == SDE_OPT_WGRAD_BLOCKS) {
-        SDE_CHECK_ARG(value >= 1 && value <= 65536, "sde_conv_set_option: bad workgroup target %d", value);
-        const int old = (int)g_wgrad_blocks;
-        g_wgrad_blocks = value;
+    for (const auto& o : kOptions) {
+        if (o.key != key) continue;
+        if (o.ok && !o.ok(value)) { sde_set_error(o.msg, value); return SDE_ERR_ARG; }
+        const int old = *o.slot;
+        *o.slot = value;
         return old;
     }
-    int* slot = key == SDE_OPT_WGRAD_DMA_RING ? &sdeconv::g_wgrad_dma_ring : key == SDE_OPT_PGEMM_PER_CU ? &sdeconv::g_pgemm_per_cu : key == SDE_OPT_PGEMM ? &g_use_pgemm : key == SDE_OPT_PGEMM_DEPTH ? &g_pgemm_depth : key == SDE_OPT_PGEMM_3X3 ? &g_pgemm_3x3 :
-                key == SDE_OPT_PGEMM_TILE ? &sdeconv::g_pgemm_force_tile : key == SDE_OPT_SPLITK ? &g_splitk : key == SDE_OPT_WGRAD_HALO ? &g_wgrad_halo : key == SDE_OPT_CONV_SMALL ? &g_conv_small : key == SDE_OPT_WGRAD_DMA ? &g_wgrad_dma : key == SDE_OPT_BNBWD_FUSE ? &g_bnbwd_fuse : key == SDE_OPT_CU_RESERVE ? &sdeconv::g_cu_reserve : nullptr;
-    SDE_CHECK_ARG(slot, "sde_conv_set_option: unknown key %d", key);
-    SDE_CHECK_ARG(key != SDE_OPT_CU_RESERVE || (value >= 0 && value <= 128 && value % 8 == 0), "sde_conv_set_option: CU reserve must be a multiple of 8 in [0, 128], got %d", value);
-    SDE_CHECK_ARG(key != SDE_OPT_PGEMM_DEPTH || value == 3 || value == 4, "sde_conv_set_option: ring depth must be 3 or 4");
-    SDE_CHECK_ARG(key != SDE_OPT_WGRAD_DMA_RING || sdeconv::wgrad_dma_lds_bytes(value) > 0, "sde_conv_set_option: bad weight-gradient ring %d", value);
-    SDE_CHECK_ARG(key != SDE_OPT_PGEMM_PER_CU || (value >= 2 && value <= 4), "sde_conv_set_option: workgroups per CU must be 2, 3 or 4, got %d", value);
-    SDE_CHECK_ARG(key != SDE_OPT_PGEMM_TILE || value == 0 || value == 64064 || value == 128064 || value == 128128, "sde_conv_set_option: bad tile %d", value);
-    const int old = *slot;
-    *slot = value;
-    return old;
+    sde_set_error("sde_conv_set_option: unknown key %d", key);
+    return SDE_ERR_ARG;
 }
 
 int sde_kernel_lds_bytes(int kind, int variant) {
     switch (kind) {
-        case SDE_KERNEL_PGEMM: return variant == 3 || variant == 4 ? sdeconv::pgemm_lds_bytes(variant) : -1;
-        case SDE_KERNEL_WGRAD_DMA: return sdeconv::wgrad_dma_lds_bytes(variant);
-        case SDE_KERNEL_WGRAD_HALO: return sdeconv::whalo_lds_bytes(variant / 10, variant % 10);
+        case SDE_KERNEL_PGEMM: return variant == 3 || variant == 4 ? pgemm_lds_bytes(variant) : -1;
+        case SDE_KERNEL_WGRAD_DMA: return wgrad_dma_lds_bytes(variant);
+        case SDE_KERNEL_WGRAD_HALO: return whalo_lds_bytes(variant / 10, variant % 10);
         case SDE_KERNEL_WGRAD_STAGED: return variant == 0 ? 4 * WGTraits<bf16_t>::BR * 288 / 2 : -1;      // 16-bit tiles, one stage buffer (wgrad_partial: single_buf)
         case SDE_KERNEL_WGRAD_SUM: return variant == 0 ? 3 * 64 * (int)sizeof(float4) : -1;
         case SDE_KERNEL_WGRAD_REDUCE: return variant == 0 ? WREDUCE_LDS_FLOATS * (int)sizeof(float) : -1;
@@ -1951,9 +1969,9 @@ int sde_pack_item_blocks(int Cout_pad, int Cin_pad, int KH, int KW) {
 int sde_pack_weights_batched(const sde_pack_item* items_dev, int n, long total_blocks, int dtype, sde_stream_t stream) {
     SDE_CHECK_ARG(items_dev && n > 0 && total_blocks > 0 && total_blocks < 0x7fffffffL, "sde_pack_weights_batched: bad argument");
     SDE_CHECK_ARG(SDE_DTYPE_OK(dtype), "sde_pack_weights_batched: bad dtype");
-    if (dtype == SDE_BF16) hipLaunchKernelGGL(pack_batched_kernel<bf16_t>, dim3((unsigned)total_blocks), dim3(256), 0, (hipStream_t)stream, items_dev, n);
-    else if (dtype == SDE_F16) hipLaunchKernelGGL(pack_batched_kernel<half_t>, dim3((unsigned)total_blocks), dim3(256), 0, (hipStream_t)stream, items_dev, n);
-    else hipLaunchKernelGGL(pack_batched_kernel<float>, dim3((unsigned)total_blocks), dim3(256), 0, (hipStream_t)stream, items_dev, n);
+    Types::dispatch(dtype, [&](auto tag) {
+        hipLaunchKernelGGL(pack_batched_kernel<typename decltype(tag)::type>, dim3((unsigned)total_blocks), dim3(256), 0, (hipStream_t)stream, items_dev, n);
+    });
     SDE_CHECK_LAUNCH("sde_pack_weights_batched");
     return SDE_OK;
 }

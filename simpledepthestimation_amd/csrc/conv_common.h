@@ -1,4 +1,7 @@
-// Shared pieces of the convolution engine (conv.hip, pgemm.hip): gather description, XCD-aware tile order, buffer-resource helpers.
+// Shared pieces of the convolution engine (conv.hip and its sibling files pgemm.hip, conv_halo_small.hip, wgrad_dma.hip, wgrad_halo.hip):
+//   * device side: gather description, XCD-aware tile order, buffer-resource helpers, source kinds;
+//   * host side (end of the file): the interface between conv.hip's dispatcher and the sibling files, declared ONCE -- every definition and
+//     every call sees these declarations, so the two sides cannot drift apart.
 #pragma once
 #include "common.h"
 #include "sde_hip.h"
@@ -84,5 +87,39 @@ __device__ __forceinline__ uint4 buf_load16(__amdgpu_buffer_rsrc_t r, unsigned o
 // Source kinds.  bf16 kernels are specialised on the kind (straight-line loop bodies: with the kind decided at run time the
 // loop breaks into ~70 basic blocks per 32 MFMAs and nothing overlaps); SRC_RUNTIME keeps one generic fp32 instantiation.
 constexpr int SRC_RUNTIME = -1, SRC_PLAIN_ZERO = 0, SRC_PLAIN_REFLECT = 1, SRC_UPCAT_REFLECT = 2, SRC_ZEROINS_ZERO = 3, SRC_1X1 = 4;
+// which specialisation of the gather a descriptor gets (16-bit kernels; fp32, parity mode, keeps the run-time generic kernel)
+inline int src_kind(const Gather& g) {
+    if (g.mode == SDE_SRC_UPCAT) return SRC_UPCAT_REFLECT;
+    if (g.mode == SDE_SRC_ZEROINS) return SRC_ZEROINS_ZERO;
+    if (g.KH == 1 && g.KW == 1 && g.pad == 0 && !g.reflect) return SRC_1X1;
+    return g.reflect ? SRC_PLAIN_REFLECT : SRC_PLAIN_ZERO;
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// Host interface of the sibling files.  conv.hip decides the route (route_fwd / route_wgrad) from the *_applicable predicates and the tile /
+// row / split queries below and launches through *_run; the g_* globals are the dispatcher options that live beside the code they steer
+// (sde_conv_set_option's table in conv.hip is their only writer).
+// ------------------------------------------------------------------------------------------------------------------
+// persistent LDS-DMA GEMM (pgemm.hip)
+bool pgemm_applicable(const Gather& g, int dtype, int ldy);
+bool pgemm_bnbwd_ok(const Gather& g, int dtype, int ldy, int Cout, int depth);
+int pgemm_tile(const Gather& g, int ldy);
+int pgemm_run(const IGemmP& p, int dtype, int depth, hipStream_t s);
+int pgemm_stats_rows(const Gather& g, int ldy, int depth, bool bnbwd = false);
+int pgemm_lds_bytes(int depth);
+extern int g_pgemm_per_cu, g_pgemm_force_tile;
+// narrow-input 3x3 layers at high resolution (conv_halo_small.hip)
+bool chalo_applicable(const Gather& g, int dtype, int ldy);
+int chalo_run(const IGemmP& p, int dtype, hipStream_t s);
+// weight gradient on LDS-DMA for 64-channel-multiple layers (wgrad_dma.hip)
+bool wgrad_dma_applicable(const Gather& g, int dtype, int Cout, int ldd);
+int wgrad_dma_run(const Gather& g, int dtype, const void* dy, int Cout, int ldd, float* slab, int splits, int rows_per_split, hipStream_t s);
+int wgrad_dma_lds_bytes(int ring);
+extern int g_wgrad_dma_ring;
+// halo weight gradient of the small-channel 3x3 layers (wgrad_halo.hip)
+bool whalo_applicable(const Gather& g, int dtype, int Cout, int ldd);
+int whalo_splits(const Gather& g, int Cout);
+int whalo_run(const Gather& g, int dtype, const void* dy, int Cout, int ldd, float* slab, int splits, hipStream_t s);
+int whalo_lds_bytes(int NB, int CO16);
 
 }  // namespace sdeconv

@@ -755,13 +755,6 @@ bool pgemm_applicable(const Gather& g, int dtype, int ldy) {
     return true;
 }
 
-int pgemm_src_kind(const Gather& g) {
-    if (g.mode == SDE_SRC_UPCAT) return SRC_UPCAT_REFLECT;
-    if (g.mode == SDE_SRC_ZEROINS) return SRC_ZEROINS_ZERO;
-    if (g.KH == 1 && g.KW == 1 && g.pad == 0 && !g.reflect) return SRC_1X1;
-    return g.reflect ? SRC_PLAIN_REFLECT : SRC_PLAIN_ZERO;
-}
-
 // Tile choice (one place): BM*1000 + BN.  64x64 with a 3-stage ring (four waves, three workgroups per CU) everywhere.  Round 3 built eight-wave
 // workgroups for the 128-row tiles (128x64: 4 x 2 waves, two workgroups per CU; 128x128: 2 x 4 waves, one per CU) -- the round-2 forms kept four waves,
 // 236 VGPRs, and lost 5-40 %.  Stand-alone (profiles/r03l_gemm_microbench.txt, every forward / data-gradient shape of the ResNet-50 workload) 128x64 is
@@ -793,7 +786,7 @@ static int pg_depth(int tile, int depth) { return tile != 64064 || depth == 3 ? 
 // k x k stride-1 sources, full 64-channel output tiles.
 bool pgemm_bnbwd_ok(const Gather& g, int dtype, int ldy, int Cout, int depth) {
     if (!pgemm_applicable(g, dtype, ldy) || depth != 3 || (g_pgemm_force_tile && g_pgemm_force_tile != 64064)) return false;      // (the fused epilogue exists for 64x64 tiles: pgemm_run takes them for such a launch whatever pgemm_tile says)
-    const int src = pgemm_src_kind(g);
+    const int src = src_kind(g);
     return (src == SRC_1X1 || src == SRC_PLAIN_ZERO) && g.stride == 1 && Cout % 64 == 0 && ldy == Cout;
 }
 
@@ -815,7 +808,7 @@ int pgemm_run(const IGemmP& p, int dtype, int depth, hipStream_t s) {
     q.total = q.tiles_mn * p.ksplit;
     q.nk_total = p.g.Ktot / 64;
     q.nk_per = sde_cdiv(q.nk_total, p.ksplit);
-    const int src = pgemm_src_kind(p.g);
+    const int src = src_kind(p.g);
     q.zero_siblings = 0;
     q.stats_acc = p.stats && pg_stats_acc(q.tiles_n, q.tiles_mn, p.ksplit, src, BM, BN, pg_depth(tile, depth)) ? 1 : 0;
     for (int c = 0; c < 4; ++c) q.cls_end[c] = 0;
@@ -839,7 +832,7 @@ int pgemm_stats_rows(const Gather& g, int ldy, int depth, bool bnbwd) {
     const int BM = tile / 1000, BN = tile % 1000;
     depth = pg_depth(tile, depth);
     const int tiles_n = sde_cdiv(ldy, BN), tiles_mn = sde_cdiv(g.M, BM) * tiles_n;
-    if (pg_stats_acc(tiles_n, tiles_mn, 1, pgemm_src_kind(g), BM, BN, depth)) return pg_grid_max(BM, BN, depth) / tiles_n;
+    if (pg_stats_acc(tiles_n, tiles_mn, 1, src_kind(g), BM, BN, depth)) return pg_grid_max(BM, BN, depth) / tiles_n;
     return sde_cdiv(g.M, BM);
 }
 

@@ -723,7 +723,7 @@ def test_full_size_conv_properties(NN):
 
 
 HALO_CASES = [
-    # name, B, H, W, Cin, Cout, reflect, bias, act; "halo_*" run on the LDS-halo kernel (asserted), "staged_*" do not: use_halo refuses inputs narrower
+    # name, B, H, W, Cin, Cout, reflect, bias, act; "halo_*" run on the LDS-halo kernel (asserted), "staged_*" do not: halo_applicable refuses inputs narrower
     # than 48 channels, so these two run on the register-staged 128x16 tile (also rows of tests/conv_variant_table.py, under that variant)
     ("halo_64_64_zero", 2, 16, 32, 64, 64, False, False, 0),
     ("halo_128_128_zero", 2, 16, 32, 128, 128, False, False, 0),
@@ -856,7 +856,7 @@ def halo_batchnorm_stats_case(NN, Cin, variant):
 
 
 def test_conv_halo_batchnorm_stats(NN, force_halo):
-    """BatchNorm statistics from the convolution's epilogue over ragged tiles.  (32 input channels are too narrow for the halo kernel -- use_halo --
+    """BatchNorm statistics from the convolution's epilogue over ragged tiles.  (32 input channels are too narrow for the halo kernel -- halo_applicable --
     so this case has always run on the register-staged 64x64 tile; the next test is the halo kernel's.)"""
     halo_batchnorm_stats_case(NN, 32, 64064)
 
